@@ -7,7 +7,10 @@ when the timed region starts; the decoded arenas stay in HBM. Batches rotate thr
 Infinity Cache so steps do not re-read cached input. The driver's `--steps 20` is therefore 200 decodes (the timed region
 of round 1 was 20 decodes, 1.6 ms).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline. `--full` adds everything else the line reports: the roofline
+leg, the side legs (`--legs`), the CPU baseline. `--dump-outputs DIR` writes what the last timed batch decoded as DIR/<name>.npy.
 
 N > 1 is launched by the driver under torch.distributed.run (one rank per GPU). Each rank decodes its own contiguous,
 commit-aligned shard of the stream (weak scaling: `--inner` batches per rank per step); the collective of the path is an
@@ -15,7 +18,7 @@ all-gather of a 64-byte header per rank per batch (RCCL over xGMI) that gives ev
 `--workload cfg4` is BASELINE configs[3]: ONE 8 GiB stream cut into N commit-aligned shards, device-side boundary scan,
 control-frame broadcast, header all-gather and (`--gather-arenas`) the padded arena all-gather.
 
-Rank 0 prints ONE JSON line. Beside the headline it carries one object per other BASELINE config, each with its own
+Rank 0 prints ONE JSON line. With --full, beside the headline it carries one object per other BASELINE config, each with its own
 algorithmic bytes and kernel times: `cfg3` (mixed I/U/D, TEXT / NUMERIC), `cfg5` (Relation / DDL messages in the stream,
 default flags: the control path), `copy` (table-copy rows), `no_sidecar` (record-boundary scan on the device first), `default_flags` (the headline workload
 without the caller's no-control assertion: the optimistic control path), `handoff` (columns / RowBinary / protobuf of a decoded
@@ -124,7 +127,7 @@ class Pipeline:
         self.bytes = self.frames = self.out_bytes = self.events = 0
         self.k = 0
 
-    def _retire(self):
+    def _retire(self, keep=False):
         b, nbytes, nfr = self.inflight.pop(0)
         rc = b.sync()
         v = b.view()
@@ -134,6 +137,8 @@ class Pipeline:
         self.events += v.n_events
         self.bytes += nbytes
         self.frames += nfr
+        if keep:
+            return b
         b.close()
 
     def issue(self, hdr_ptr=None):
@@ -146,9 +151,37 @@ class Pipeline:
             b.header_to_device(hdr_ptr)
         self.inflight.append((b, nbytes, nfr))
 
-    def drain(self):
+    def drain(self, keep_last=False):
+        """Retire every batch in flight; keep_last: the last one stays open and is returned (the caller closes it)."""
+        last = None
         while self.inflight:
-            self._retire()
+            last = self._retire(keep=keep_last and len(self.inflight) == 1)
+        return last
+
+
+DUMP_SEED = 0xE7102
+DUMP_MAX_ELEMS = 1 << 19   # per array: ten arrays of float64 stay within 40 MiB
+
+
+def dump_outputs(batch, outdir):
+    """What a caller of the timed path receives for one batch (the arena of etlg_batch_view: event header columns, fixed row arena,
+    heap), downloaded and written as DIR/<name>.npy in float64 (every value exact), plus `counts.npy` (n_events, n_frames, fixed
+    bytes, heap bytes, payload bytes). An array the batch has nothing in (the heap of a fixed-width workload) is not written: its
+    length 0 is in `counts.npy`. An array longer than DUMP_MAX_ELEMS is written as a fixed sample of its positions (seeded, sorted):
+    the same positions for the same arguments, so two builds compare element for element."""
+    import numpy as np
+    hb = batch.host()
+    os.makedirs(outdir, exist_ok=True)
+    counts = [hb.n_events, hb.n_frames, len(hb.fixed), len(hb.heap), *hb.payload_bytes]
+    np.save(os.path.join(outdir, "counts.npy"), np.array(counts, dtype=np.float64))
+    for name in hb.ARRAYS:
+        a = getattr(hb, name)
+        if not len(a):
+            continue
+        if len(a) > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), DUMP_MAX_ELEMS, replace=False))]
+        assert int(a.max()) < (1 << 53), name   # float64 holds it exactly
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(np.float64))
 
 
 def kernel_table(prof):
@@ -1001,12 +1034,14 @@ def main():
     ap.add_argument("--batch-mib", type=int, default=64)
     ap.add_argument("--pool", type=int, default=6, help="distinct batches resident in HBM (rotated)")
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg3", "cfg4"])
-    ap.add_argument("--legs", default="cfg1,cfg3,cfg5,wide70,copy,no_sidecar,handoff,default_flags,cfg2_mixed,pcie,cfg4", help="extra legs on rank 0 (comma separated; empty = none)")
-    ap.add_argument("--cfg4-leg", action="store_true", help="add the cfg4 leg to a cfg2 / cfg3 run")
+    ap.add_argument("--full", action="store_true", help="beside the headline: roofline leg, the side legs (--legs), CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed batch decoded to DIR/<name>.npy")
+    ap.add_argument("--legs", default="cfg1,cfg3,cfg5,wide70,copy,no_sidecar,handoff,default_flags,cfg2_mixed,pcie,cfg4", help="--full: extra legs on rank 0 (comma separated; empty = none)")
+    ap.add_argument("--cfg4-leg", action="store_true", help="--full: add the cfg4 leg to a cfg2 / cfg3 run")
     ap.add_argument("--cfg4-gib", type=int, default=8)
     ap.add_argument("--cfg4-seg-mib", type=int, default=1024)
     ap.add_argument("--gather-arenas", action="store_true", help="cfg4: also all-gather the arenas (padded) to every rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-cores CPU leg (0 = the cores available, at most 64; 1 = skip)")
     ap.add_argument("--cpu-threads-seconds", type=float, default=6.0)
@@ -1015,6 +1050,8 @@ def main():
     ap.add_argument("--prime", type=int, default=WINDOW + 2, help="decodes that grow the arena pool before warm-up (profiling runs under rocprofv3 --pmc use 2)")
     ap.add_argument("--gather-every", type=int, default=4, help="N > 1: batches per header all-gather (their 64-byte headers travel together)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "cfg4":
+        ap.error("--dump-outputs: the cfg2 / cfg3 workloads")
     legs = [x for x in args.legs.split(",") if x]
     if args.no_scan_leg and "no_sidecar" in legs:
         legs.remove("no_sidecar")
@@ -1111,7 +1148,7 @@ def main():
             hg.batch_done(nwarm + k)
     if gather:
         hg.flush(nbatches)
-    p.drain()
+    last = p.drain(keep_last=bool(args.dump_outputs))
     ta = time.perf_counter()
     if gather:
         hg.wait()
@@ -1134,11 +1171,15 @@ def main():
         assert args.no_check or not lay["any_error"]
     else:
         all_bytes, all_frames = my_bytes, my_frames
+    if last is not None:
+        if rank == 0:
+            dump_outputs(last, args.dump_outputs)
+        last.close()
 
     # ---- roofline leg: HIP-event timing of every kernel over a fresh run of 4 x inner batches (rank 0)
     roof = None
     paths = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # Consecutive ASYNC batches run side by side on the library's two decode streams, so the per-launch HIP-event durations of
         # the chain overlap (their sum exceeds the wall clock). `roofline` is therefore priced on the kernel timed ALONE — the same
         # chain kept on one stream (profile mode 2: what `ETLG_OVERLAP=0 rocprofv3 --kernel-trace --stats` shows, profiles/) — and
@@ -1176,6 +1217,7 @@ def main():
                                "launch_interval_us": round(interval_us, 2),
                                "effective_GBps": round(alg_bytes / (interval_us * 1e-6) / 1e9, 1),
                                "effective_frac": round(alg_bytes / (interval_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4)}
+    if rank == 0:
         paths = {**dec.debug_paths(), **dec.debug_rows()}
 
     extra = {}
@@ -1185,8 +1227,9 @@ def main():
         t = time.perf_counter()
         print(f"[bench] {name}: {t - _leg_t[0]:.1f} s", file=sys.stderr, flush=True)
         _leg_t[0] = t
-    _leg_done("headline + roofline leg")
-    if rank == 0:
+    if args.full:
+        _leg_done("headline + roofline leg")
+    if rank == 0 and args.full:
         extra["deferred_cells"] = deferred_cells(dec, items[0])
         if "no_sidecar" in legs and args.workload == "cfg2":
             extra["no_sidecar"] = leg_no_sidecar(local_rank, items, 160, check)
@@ -1224,13 +1267,13 @@ def main():
         if "pcie" in legs:
             extra["pcie"] = leg_pcie(local_rank, dev, cap, 24)
             _leg_done("pcie")
-    if (args.cfg4_leg or "cfg4" in legs) and world == 1 and args.workload != "cfg4":
+    if args.full and (args.cfg4_leg or "cfg4" in legs) and world == 1 and args.workload != "cfg4":
         extra["cfg4"] = leg_cfg4(local_rank, dev, 1, 0, args.cfg4_gib if args.cfg4_leg else 2, args.cfg4_seg_mib, False, None)   # the default line: 2 GiB of the 64 GiB stream on this one GPU
         _leg_done("cfg4")
 
     # ---- CPU baseline leg (rank 0, N == 1 only): the oracle on the same host cores
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle
         o = oracle.Oracle(mode=oracle.MODE_FULL)
         w.register(o)

@@ -4,6 +4,7 @@ timestamp:8 xid:4; 'C' flags:1 commit_lsn:8 end_lsn:8 timestamp:8: the layouts o
 parser, which the reference decodes through, crates/etl/src/replication/apply.rs:2037-2125). This file pins the two constants to the
 frames the test suite and the oracle agree on; what a stream does to break the assumption is the GPU tier's business
 (tests/test_gpu_fixed_plan.py::test_prepass_*)."""
+import os
 import re
 
 import numpy as np
@@ -20,8 +21,9 @@ def _frame_len(msg):
 def test_begin_and_commit_frames_have_the_lengths_the_pre_pass_assumes():
     assert _frame_len(W.begin(0x5000, ts=7, xid=9)) == 51
     assert _frame_len(W.commit(0x5000, 0x5008, ts=7, flags=0)) == 56
-    src = open("etl_amd/csrc/plan.hip").read()
-    body_off = int(re.search(r"constexpr uint32_t kBodyOff = (\d+);", open("etl_amd/csrc/codec.hip.h").read()).group(1))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "etl_amd", "csrc", "plan.hip")).read()
+    body_off = int(re.search(r"constexpr uint32_t kBodyOff = (\d+);", open(os.path.join(root, "etl_amd", "csrc", "codec.hip.h")).read()).group(1))
     m = re.search(r"kPreBeginLen = kBodyOff \+ (\d+)u, kPreCommitLen = kBodyOff \+ (\d+)u", src)
     assert m and body_off + int(m.group(1)) == 51 and body_off + int(m.group(2)) == 56
 

@@ -156,7 +156,20 @@ def test_other_sources_use_only_bound_symbols():
     assert os.path.exists(os.path.join(CRATE, "Cargo.toml")) and os.path.exists(os.path.join(CRATE, "build.rs"))
 
 
-REF = "/root/reference"
+# What the last two checks need of the reference checkout the shim targets, recorded from it (it is not part of this repository):
+# the item names every module the shim names declares or re-exports, the exported macros, and a digest of every line of the two files
+# the patches change. `python -m tests.test_rust_shim <reference checkout>` records them again.
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_rust_shim.json")
+PATCHES = (("apply_rs.diff", "crates/etl/src/replication/apply.rs"), ("table_copy_rs.diff", "crates/etl/src/postgres/stream/table_copy.rs"))
+
+
+def _crate_src(crate):
+    return "crates/" + ("etl" if crate == "etl" else "etl-postgres") + "/src"
+
+
+def _line_digest(line):
+    import hashlib
+    return hashlib.sha256(line.strip().encode()).hexdigest()[:16]
 
 
 def _etl_paths():
@@ -176,42 +189,70 @@ def _etl_paths():
     return sorted(out)
 
 
-def test_every_reference_path_the_shim_names_exists():
-    """grep-level check against the checkout the shim targets (it cannot be compiled here): each `etl::module::Item` resolves to a
-    module file of crates/etl (or crates/etl-postgres) that declares or re-exports an item of that name."""
-    import pytest
-    if not os.path.isdir(REF):
-        pytest.skip("the reference checkout is only present in the build container")
-    paths = _etl_paths()
-    assert len(paths) >= 15, paths
-    for crate, mod, item in paths:
-        root = os.path.join(REF, "crates", "etl" if crate == "etl" else "etl-postgres", "src")
-        if not mod:   # exported macros
+def record_fixture(ref):
+    """The fixture, read from a checkout of the reference at `ref`."""
+    names = {}
+    for crate, mod, _ in _etl_paths():
+        root = os.path.join(ref, _crate_src(crate))
+        entry = names.setdefault(_crate_src(crate), {"macros": [], "modules": {}})
+        if not mod:
             text = "".join(open(os.path.join(dp, fn)).read() for dp, _, fns in os.walk(root) for fn in fns if fn.endswith(".rs"))
-            assert re.search(r"macro_rules!\s+" + item + r"\b", text), (crate, item)
+            entry["macros"] = sorted(set(re.findall(r"macro_rules!\s+([A-Za-z_0-9]+)", text)))
             continue
         rel = mod.replace("::", "/")
-        cands = [os.path.join(root, rel + ".rs"), os.path.join(root, rel, "mod.rs")]
-        files = [c for c in cands if os.path.exists(c)]
-        assert files, (crate, mod, item, "no such module")
+        files = [c for c in (os.path.join(root, rel + ".rs"), os.path.join(root, rel, "mod.rs")) if os.path.exists(c)]
+        if not files:
+            continue
         text = open(files[0]).read()
         if os.path.isdir(os.path.join(root, rel)):   # a module directory: the item may live in a child it re-exports
             text += "".join(open(os.path.join(root, rel, fn)).read() for fn in os.listdir(os.path.join(root, rel)) if fn.endswith(".rs"))
-        assert re.search(r"\b(struct|enum|trait|type|fn|const|static|mod)\s+" + item + r"\b|pub use [^;]*\b" + item + r"\b", text), (crate, mod, item)
+        declared = set(re.findall(r"\b(?:struct|enum|trait|type|fn|const|static|mod)\s+([A-Za-z_0-9]+)", text))
+        for use in re.findall(r"pub use [^;]*", text):
+            declared |= set(re.findall(r"[A-Za-z_][A-Za-z_0-9]*", use[len("pub use "):]))
+        entry["modules"][mod] = sorted(declared)
+    lines = {target: sorted({_line_digest(l) for l in open(os.path.join(ref, target)).read().split("\n") if l.strip()})
+             for _, target in PATCHES}
+    return {"names": names, "line_sha256_16": lines}
+
+
+def _fixture():
+    import json
+    return json.load(open(FIXTURE))
+
+
+def test_every_reference_path_the_shim_names_exists():
+    """grep-level check against the checkout the shim targets (it cannot be compiled here): each `etl::module::Item` resolves to a
+    module file of crates/etl (or crates/etl-postgres) that declares or re-exports an item of that name."""
+    names = _fixture()["names"]
+    paths = _etl_paths()
+    assert len(paths) >= 15, paths
+    for crate, mod, item in paths:
+        entry = names[_crate_src(crate)]
+        if not mod:   # exported macros
+            assert item in entry["macros"], (crate, item)
+            continue
+        assert mod in entry["modules"], (crate, mod, item, "no such module")
+        assert item in entry["modules"][mod], (crate, mod, item)
 
 
 def test_the_patch_quotes_the_reference():
-    """patches/*.diff: their context lines (the ones without +/-) are lines of the reference file they patch."""
-    import pytest
-    if not os.path.isdir(REF):
-        pytest.skip("the reference checkout is only present in the build container")
-    for name, target in (("apply_rs.diff", "crates/etl/src/replication/apply.rs"), ("table_copy_rs.diff", "crates/etl/src/postgres/stream/table_copy.rs")):
-        ref = open(os.path.join(REF, target)).read()
+    """patches/*.diff: their context lines (the ones without +/-) and hunk headers are lines of the reference file they patch."""
+    lines = _fixture()["line_sha256_16"]
+    for name, target in PATCHES:
+        ref = set(lines[target])
         patch = open(os.path.join(CRATE, "patches", name)).read()
         body = patch[patch.index("--- a/" + target):]
         ctx = [l[1:].strip() for l in body.split("\n") if l.startswith(" ") and l.strip()]
         assert len(ctx) >= 8, name
         for l in ctx:
-            assert l in ref, (name, l)
+            assert _line_digest(l) in ref, (name, l)
         for hunk in re.findall(r"^@@ (.+)$", body, flags=re.M):
-            assert hunk.strip().split("(")[0] in ref, (name, hunk)
+            assert _line_digest(hunk) in ref, (name, hunk)
+
+
+if __name__ == "__main__":
+    import json
+    import sys
+    with open(FIXTURE, "w") as f:
+        json.dump(record_fixture(sys.argv[1]), f, indent=0, sort_keys=True)
+        f.write("\n")

@@ -4,8 +4,10 @@ and the parity test files run against that build in a subprocess. TEST INFRASTRU
 contains the emulator (etl_amd/native.py refuses to load it outside this run), and the emulator models neither
 timing nor memory ordering nor races between waves: the -m gpu suite on an MI355X stays the gate."""
 import os
+import queue
 import subprocess
 import sys
+import threading
 
 import pytest
 
@@ -65,8 +67,10 @@ def _pytest_job(args, timeout, order=None, grid=None, streams=None):
     return dict(cmd=[sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider"] + args, timeout=timeout, order=order, drop=None, grid=grid, streams=streams)
 
 
-# Every emulated run of this file is a subprocess of its own (the parity files pick the library up from the environment); they are all
-# started when the first of them is asked for and run side by side — the suite's wall time is the longest of them, not their sum.
+# Every emulated run of this file is a subprocess of its own (the parity files pick the library up from the environment). They run side
+# by side, at most one per CPU this process may use, the longest first: each run is single-threaded, and its time limit (also the
+# emulator's watchdog, ETLG_SIMT_WATCHDOG) counts from its own start, so a box with few CPUs makes the suite longer, not the runs
+# time out. The suite's wall time is about the sum of the runs over the CPUs.
 _JOBS = {
     "scenarios": _pytest_job(["tests/test_gpu_parity.py", "-k", "scenario_parity or temporal_matrix or wider_than_16 or type_matrix"], 900),
     "shim_twin": _pytest_job(["tests/test_shim_twin.py"], 600),
@@ -93,22 +97,92 @@ _JOBS = {
 }
 
 
+def _cpus():
+    """CPUs this process may use: its affinity mask, within the cgroup's CPU quota when there is one and within MAX_JOBS when the
+    environment sets that budget."""
+    n = len(os.sched_getaffinity(0))
+    for path in ("/sys/fs/cgroup/cpu.max", "/sys/fs/cgroup/cpu/cpu.cfs_quota_us"):
+        try:
+            vals = open(path).read().split()
+            if path.endswith("cpu.max"):
+                quota, period = vals
+            else:
+                quota, period = vals[0], open("/sys/fs/cgroup/cpu/cpu.cfs_period_us").read().split()[0]
+            if quota not in ("max", "-1"):
+                n = min(n, max(1, int(quota) // int(period)))
+        except (OSError, ValueError):
+            pass
+    if os.environ.get("MAX_JOBS", "").isdigit():
+        n = min(n, int(os.environ["MAX_JOBS"]))
+    return max(1, n)
+
+
+# the longest runs first (alone, on one CPU each: scenarios 310 s, lazy_streams 245, shard_async 187, resident_reverse 138, then 80 s and
+# less): the suite ends soon after its longest run
+_ORDER = ["scenarios", "lazy_streams", "shard_async", "resident_reverse", "plans", "copy_scan", "lane_order", "other_compiler",
+          "round6_lazy_streams", "shim_twin", "resident_shuffle", "plans_shuffled", "finish_pass", "hand_off", "long_chains", "copy_fuzz",
+          "cell_fuzz"]
+assert sorted(_ORDER) == sorted(_JOBS)
+
+
+class _EmuJobs:
+    """The emulated runs of _JOBS, started in _ORDER by _cpus() workers; result(name) waits for one of them."""
+
+    def __init__(self, simt_lib):
+        self.simt_lib = simt_lib
+        self.results = {}
+        self.done = {name: threading.Event() for name in _JOBS}
+        self.running = {}
+        self.stop = False
+        self.queue = queue.Queue()
+        for name in _ORDER:
+            self.queue.put(name)
+        self.workers = [threading.Thread(target=self._work, daemon=True) for _ in range(min(_cpus(), len(_ORDER)))]
+        for t in self.workers:
+            t.start()
+
+    def _work(self):
+        while not self.stop:
+            try:
+                name = self.queue.get_nowait()
+            except queue.Empty:
+                return
+            j = _JOBS[name]
+            env = _emu_env(self.simt_lib, j["timeout"], j["order"], grid=j.get("grid"), streams=j.get("streams")) if j["drop"] is None else _emu_env(self.simt_lib, j["timeout"], j["order"], j["drop"])
+            pr = subprocess.Popen(j["cmd"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env)
+            self.running[name] = pr
+            try:
+                out, err = pr.communicate(timeout=j["timeout"] + 120)
+            except subprocess.TimeoutExpired:
+                pr.kill()
+                out, err = pr.communicate()
+                err += f"\n(killed after {j['timeout'] + 120} s)"
+            self.results[name] = (pr.returncode, out, err)
+            self.done[name].set()
+
+    def result(self, name):
+        self.done[name].wait()
+        return self.results[name]
+
+    def close(self):
+        self.stop = True
+        for pr in list(self.running.values()):
+            if pr.poll() is None:
+                pr.kill()
+        for t in self.workers:
+            t.join()
+
+
 @pytest.fixture(scope="module")
 def emu_jobs(simt_lib):
-    procs = {}
-    for name, j in _JOBS.items():
-        env = _emu_env(simt_lib, j["timeout"], j["order"], grid=j.get("grid"), streams=j.get("streams")) if j["drop"] is None else _emu_env(simt_lib, j["timeout"], j["order"], j["drop"])
-        procs[name] = subprocess.Popen(j["cmd"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env)
-    yield procs
-    for pr in procs.values():
-        if pr.poll() is None:
-            pr.kill()
+    jobs = _EmuJobs(simt_lib)
+    yield jobs
+    jobs.close()
 
 
 def _result(emu_jobs, name):
     """(return code, stdout, stderr) of one of the emulated runs."""
-    out, err = emu_jobs[name].communicate(timeout=_JOBS[name]["timeout"] + 120)
-    return emu_jobs[name].returncode, out, err
+    return emu_jobs.result(name)
 
 
 def _passed(emu_jobs, name):

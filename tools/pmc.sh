@@ -1,7 +1,7 @@
 # PMC counter passes for the dominant kernel: bash tools/pmc.sh [cfg2|cfg3] ; results -> gpurun_out/pmc_<wl>_*.csv
 WL=${1:-cfg2}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-B="python bench.py --workload $WL --steps 4 --warmup 1 --no-cpu-baseline --no-check"
+B="python bench.py --full --workload $WL --steps 4 --warmup 1 --no-cpu-baseline --no-check"
 i=0
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \
            "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA" \

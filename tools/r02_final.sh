@@ -8,9 +8,9 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 bash tools/traffic.sh cfg2 > $O/traffic_cfg2.log 2>&1; bash tools/traffic.sh cfg3 > $O/traffic_cfg3.log 2>&1
 cp gpurun_out/traffic_cfg2.json gpurun_out/traffic_cfg3.json $O/ 2>/dev/null
 cp gpurun_out/traffic_cfg2.json gpurun_out/traffic_cfg3.json profiles/ 2>/dev/null   # bench.py reads them from profiles/
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
 for wl in cfg2 cfg3; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -o p -- python bench.py --workload $wl --steps 6 --warmup 1 --legs= --no-cpu-baseline > $O/bench_${wl}_under_rocprof.json 2> $O/prof_$wl.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -o p -- python bench.py --full --workload $wl --steps 6 --warmup 1 --legs= --no-cpu-baseline > $O/bench_${wl}_under_rocprof.json 2> $O/prof_$wl.err
   f=$(ls $O/prof_$wl/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && { cp $f $O/${wl}_kernel_stats.csv; head -4 $f; }
   t=$(ls $O/prof_$wl/*kernel_trace.csv 2>/dev/null | head -1); [ -n "$t" ] && head -40 $t > $O/${wl}_kernel_trace_head.csv
   rm -rf $O/prof_$wl

@@ -2,7 +2,7 @@
 # hardware counters of the fixed-width path (k_plan behind k_plan_pre) on cfg2: separate rocprofv3 --pmc passes over a short bench command,
 # averages per launch and kernel -> gpurun_out/r04aw_cfg2_k_plan_counters.json
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-B="python bench.py --workload cfg2 --steps 1 --warmup 1 --inner 4 --prime 2 --legs= --no-cpu-baseline"
+B="python bench.py --full --workload cfg2 --steps 1 --warmup 1 --inner 4 --prime 2 --legs= --no-cpu-baseline"
 O=gpurun_out/r04aw; rm -rf $O; mkdir -p $O
 i=0
 for set in "VALUBusy SALUBusy MemUnitStalled LDSBankConflict" \
@@ -22,7 +22,7 @@ for f in glob.glob(sys.argv[1] + "/p*/*counter_collection.csv"):
         k = k.split("etlg::")[1].split("(")[0]
         agg[k][r["Counter_Name"]] += float(r["Counter_Value"]); n[(k, r["Counter_Name"])] += 1
 out = {k: {c: round(v / n[(k, c)], 2) for c, v in d.items()} for k, d in agg.items()}
-out["how"] = "rocprofv3 --pmc, four separate passes over `ETLG_OVERLAP=0 python bench.py --workload cfg2 --steps 1 --warmup 1 --inner 4 --prime 2 --legs= --no-cpu-baseline` (tools/r04_counters.sh); averages per launch"
+out["how"] = "rocprofv3 --pmc, four separate passes over `ETLG_OVERLAP=0 python bench.py --full --workload cfg2 --steps 1 --warmup 1 --inner 4 --prime 2 --legs= --no-cpu-baseline` (tools/r04_counters.sh); averages per launch"
 json.dump(out, open("gpurun_out/r04aw_cfg2_k_plan_counters.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
 PY

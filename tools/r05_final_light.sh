@@ -7,4 +7,4 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export PYTHONPATH=$PWD
 ( time timeout 600 python -m pytest tests -m gpu -q -x ) > $O/tests.log 2>&1 < /dev/null; tail -n 4 $O/tests.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 < /dev/null; tail -n 1 $O/smoke.log
-( time timeout 600 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null ); tail -c 300 $O/bench.json
+( time timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null ); tail -c 300 $O/bench.json

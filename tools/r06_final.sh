@@ -19,9 +19,9 @@ for wl in cfg5 wide70 copy copy_clean; do
 done
 TRAFFIC_KERNEL=k_bounds_local bash tools/traffic.sh scan python tools/one_kernel.py nosidecar 4 > $O/traffic_scan.log 2>&1
 cp gpurun_out/traffic_scan.json $O/ 2>/dev/null; cp gpurun_out/traffic_scan.json profiles/ 2>/dev/null
-( time timeout 900 python bench.py > $O/bench.json 2> $O/bench.err ); tail -c 300 $O/bench.json
+( time timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err ); tail -c 300 $O/bench.json
 for wl in cfg2 cfg3; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -o p -- python bench.py --workload $wl --steps 6 --warmup 1 --inner 100 --legs= --no-cpu-baseline > $O/bench_${wl}_under_rocprof.json 2> $O/prof_$wl.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -o p -- python bench.py --full --workload $wl --steps 6 --warmup 1 --inner 100 --legs= --no-cpu-baseline > $O/bench_${wl}_under_rocprof.json 2> $O/prof_$wl.err
   f=$(ls $O/prof_$wl/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && { cp $f $O/${wl}_kernel_stats.csv; head -n 4 $f | cut -c1-200; }
   t=$(ls $O/prof_$wl/*kernel_trace.csv 2>/dev/null | head -1); [ -n "$t" ] && head -n 40 $t > $O/${wl}_kernel_trace_head.csv
   rm -rf $O/prof_$wl

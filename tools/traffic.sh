@@ -5,7 +5,7 @@
 # The file names the kernel sources it was taken with (sources_sha); bench.py quotes it only while that hash is the build's.
 WL=${1:-cfg2}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-B="python bench.py --workload $WL --steps 1 --warmup 1 --inner 4 --prime 2 --legs= --no-cpu-baseline"
+B="python bench.py --full --workload $WL --steps 1 --warmup 1 --inner 4 --prime 2 --legs= --no-cpu-baseline"
 if [ $# -gt 1 ]; then shift; B="$*"; fi
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c --output-format csv -d gpurun_out/traffic_${WL}_$c -o p -- $B > gpurun_out/traffic_${WL}_$c.log 2>&1
