@@ -12,6 +12,7 @@
 // finishes it from the arena (row_event names the event). Integer / byte work, HBM-bound: no MFMA.
 #include "codec.hip.h"
 #include "float_slow.h"
+#include "float_json.h"
 #include <type_traits>
 
 namespace etlg {
@@ -1517,8 +1518,257 @@ DEV uint32_t pb_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
   return 0;
 }
 
+// ---- Snowflake NDJSON rows (serialize_row, crates/etl-destinations/src/snowflake/encoding.rs:57-72; CellSerializer /
+// ArrayCellSerializer :94-280): one serde_json compact map per row, `"<col>":<value>` in column order, then "_cdc_operation" and
+// "_cdc_sequence_number" = OffsetToken::new (snowflake/streaming/offset_token.rs:21-23), then '\n'. Every column is written as its key
+// (escaped once by the host: RbJob.nd_keys), its value and a ',' — the trailing CDC pair always follows, so the bytes are serde_json's.
+// Rows: Insert, the new row of a full Update, the old row of a Delete — only the identity columns for a key image (core.rs:345-438,
+// :572-608). Errors are the sink's Error::Encoding (non-finite floats, numeric NaN / Infinity); the host turns the codes into them.
+enum : uint32_t { ND_E_FLOAT_NAN = 7, ND_E_FLOAT_INF = 8, ND_E_FLOAT_NINF = 9, ND_E_NUM_NAN = 10, ND_E_NUM_INF = 11 };
+
+// serde_json's escape table (format_escaped_str): '"' '\\' and the bytes below 0x20 are escaped, everything else is raw
+DEV uint32_t nd_esc_extra(uint32_t c) {
+  if (c == '"' || c == '\\' || c == 8u || c == 12u || c == '\n' || c == '\r' || c == '\t') return 1;
+  return c < 0x20u ? 5u : 0u;
+}
+template <class S> DEV void nd_esc_put(S& s, uint32_t c) {
+  if (c >= 0x20u && c != '"' && c != '\\') { s.put((u8)c); return; }
+  s.put('\\');
+  switch (c) {
+    case '"': s.put('"'); break;
+    case '\\': s.put('\\'); break;
+    case 8u: s.put('b'); break;
+    case 12u: s.put('f'); break;
+    case '\n': s.put('n'); break;
+    case '\r': s.put('r'); break;
+    case '\t': s.put('t'); break;
+    default: s.put('u'); s.put('0'); s.put('0'); s.put((u8)('0' + (c >> 4))); { const uint32_t l = c & 15u; s.put((u8)(l < 10 ? '0' + l : 'a' + l - 10)); } break;
+  }
+}
+// bit 7 of some byte set <=> one of the eight bytes is below 0x20, '"' or '\\' (the has-less / has-zero tests: exact for "any")
+DEV uint64_t nd_swar_esc(uint64_t w) {
+  const uint64_t L = 0x0101010101010101ull, q = w ^ (0x22u * L), b = w ^ (0x5Cu * L);
+  return (((w - 0x20u * L) & ~w) | ((q - L) & ~q) | ((b - L) & ~b)) & (0x80u * L);
+}
+// a JSON string of n bytes: the count pass tests eight bytes at a time and looks at single bytes only in a word that has something to
+// escape; the byte pass copies 16-byte pieces that have nothing and escapes byte by byte only inside a piece that has
+template <class S> DEV void nd_str(S& s, const u8* p, uint32_t n) {
+  s.put('"');
+  uint32_t k = 0;
+  if constexpr (std::is_same<S, RbCount>::value) {
+    uint32_t extra = 0;
+    for (; k + 8u <= n; k += 8u) {
+      uint64_t w; __builtin_memcpy(&w, p + k, 8);
+      if (nd_swar_esc(w)) for (uint32_t b = 0; b < 8u; b++) extra += nd_esc_extra(p[k + b]);
+    }
+    for (; k < n; k++) extra += nd_esc_extra(p[k]);
+    s.zeros(n + extra);
+  } else {
+    for (; k + 16u <= n; k += 16u) {
+      uint64_t v[2]; __builtin_memcpy(v, p + k, 16);
+      if (!(nd_swar_esc(v[0]) | nd_swar_esc(v[1]))) { s.append(v[0], 8); s.append(v[1], 8); }
+      else for (uint32_t b = 0; b < 16u; b++) nd_esc_put(s, p[k + b]);
+    }
+    for (; k < n; k++) nd_esc_put(s, p[k]);
+  }
+  s.put('"');
+}
+template <class S> DEV void nd_lit(S& s, const char* t) { while (*t) s.put((u8)*t++); }
+template <class S> DEV void nd_u64(S& s, uint64_t v) {
+  u8 d[20];
+  uint32_t n = 0;
+  if (v >> 32) { do { d[n++] = (u8)('0' + v % 10u); v /= 10u; } while (v >> 32); }
+  uint32_t x = (uint32_t)v;
+  do { d[n++] = (u8)('0' + x % 10u); x /= 10u; } while (x);
+  while (n) s.put(d[--n]);
+}
+template <class S> DEV void nd_i64(S& s, int64_t v) { if (v < 0) { s.put('-'); nd_u64(s, 0ull - (uint64_t)v); } else nd_u64(s, (uint64_t)v); }
+template <class S> DEV uint32_t nd_numeric(S& s, const u8* ent) {   // serialize_pg_numeric (:147-159)
+  if (ent[0] == ETLG_NUM_NAN) return ND_E_NUM_NAN;
+  if (ent[0] != ETLG_NUM_VALUE) return ND_E_NUM_INF;
+  s.put('"'); numeric_str(s, ent); s.put('"');
+  return 0;
+}
+template <class S> DEV uint32_t nd_float(S& s, uint64_t bits, bool is32) {   // reject_non_finite (:162-169), then ryu (float_json.h)
+  const uint32_t eb = is32 ? 23u : 52u, emax = is32 ? 0xFFu : 0x7FFu;
+  if (((uint32_t)(bits >> eb) & emax) == emax) {
+    if (bits & ((1ull << eb) - 1u)) return ND_E_FLOAT_NAN;
+    return (bits >> (is32 ? 31 : 63)) & 1u ? ND_E_FLOAT_NINF : ND_E_FLOAT_INF;
+  }
+  (void)float_json(s, bits, is32);
+  return 0;
+}
+// One non-null value of class `cls` whose slot words start at `slot` (a row's slot, an element's words from the walk or from a typed
+// array); `heap`: where a numeric's entry / a text's bytes are (the arena's heap, or the walk's scratch for numeric elements).
+template <class S>
+DEV uint32_t nd_value(S& s, uint32_t cls, const u8* slot, const u8* heap) {
+  const uint32_t w0 = ld32a(slot);
+  switch (cls) {
+    case ETLG_TC_BOOL: nd_lit(s, w0 ? "true" : "false"); return 0;
+    case ETLG_TC_I16: case ETLG_TC_I32: nd_i64(s, (int32_t)w0); return 0;
+    case ETLG_TC_U32: nd_u64(s, w0); return 0;
+    case ETLG_TC_I64: nd_i64(s, (int64_t)(((uint64_t)ld32a(slot + 4) << 32) | w0)); return 0;
+    case ETLG_TC_F32: return nd_float(s, w0, true);
+    case ETLG_TC_F64: return nd_float(s, ((uint64_t)ld32a(slot + 4) << 32) | w0, false);
+    case ETLG_TC_NUMERIC: return nd_numeric(s, heap + w0);
+    case ETLG_TC_DATE: s.put('"'); pb_date(s, (int32_t)w0); s.put('"'); return 0;                                   // DATE_FORMAT
+    case ETLG_TC_TIME: s.put('"'); time_str(s, w0, ld32a(slot + 4)); s.put('"'); return 0;                         // TIME_FORMAT
+    case ETLG_TC_TIMESTAMP: case ETLG_TC_TIMESTAMPTZ:                                                                // TIMESTAMP_FORMAT / TIMESTAMPTZ_FORMAT_HH_MM
+      s.put('"'); pb_date(s, (int32_t)w0); s.put(' '); time_str(s, ld32a(slot + 4), ld32a(slot + 8));
+      if (cls == ETLG_TC_TIMESTAMPTZ) nd_lit(s, "+00:00");
+      s.put('"'); return 0;
+    case ETLG_TC_TIMETZ: s.put('"'); timetz_str(s, slot); s.put('"'); return 0;                                    // PgTimeTz Display
+    case ETLG_TC_UUID:
+      s.put('"');
+      for (int k = 0; k < 16; k++) {
+        const uint32_t b = slot[k], h = b >> 4, l = b & 15;
+        if (k == 4 || k == 6 || k == 8 || k == 10) s.put('-');
+        s.put((u8)(h < 10 ? '0' + h : 'a' + h - 10)); s.put((u8)(l < 10 ? '0' + l : 'a' + l - 10));
+      }
+      s.put('"'); return 0;
+    case ETLG_TC_STRING: nd_str(s, heap + w0, ld32a(slot + 4)); return 0;
+    case ETLG_TC_BYTEA: s.put('"'); s.hex(heap + w0, ld32a(slot + 4)); s.put('"'); return 0;                       // HexDisplay
+    default: return RB_E_HOST_CELL;
+  }
+}
+// An array cell that is still its source literal (DEFERRED): a JSON array, NULL elements `null`, every element by the scalar rules
+// (ArrayCellSerializer :186-224). Returns 0, the first element's error, RB_E_JSON (a json[] element that is not JSON) or RB_E_HOST_CELL
+// (a literal the walkers do not take apart, a json element beyond json_display's limits or longer than kJsonElemMax).
+template <bool JS, class S>
+DEV uint32_t nd_array(S& s, uint32_t elem, const u8* txt, uint32_t tn) {
+  uint32_t cnt = 0, k = 0;
+  if (elem == ETLG_TC_JSON) {   // json[] / jsonb[]: every element's Value, embedded (ArrayCell::Json)
+    if (!JS) return RB_E_HOST_CELL;
+    u8 tmp[kJsonElemMax];
+    bool too_long = false, bad_json = false, limit = false;
+    if (arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t ulen) {
+          if (is_null) return;
+          if (ulen > kJsonElemMax) { too_long = true; return; }
+          uint32_t q = 0;
+          arr_unescape(txt, p0, p1, [&](u8 c) { tmp[q++] = c; });
+          if (std::is_same<S, RbCount>::value && !json_valid(tmp, ulen)) { bad_json = true; return; }
+          JsCount c;
+          if (json_display(c, tmp, ulen, false)) limit = true;
+        })) too_long = true;
+    if (too_long) return RB_E_HOST_CELL;
+    if (bad_json) return RB_E_JSON;
+    if (limit) return RB_E_HOST_CELL;
+    s.put('[');
+    (void)arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t ulen) {
+      if (k++) s.put(',');
+      if (is_null) { nd_lit(s, "null"); return; }
+      uint32_t q = 0;
+      arr_unescape(txt, p0, p1, [&](u8 c) { tmp[q++] = c; });
+      if constexpr (std::is_same<S, RbCount>::value) { JsCount c; (void)json_display(c, tmp, ulen, false); s.zeros(c.n); }
+      else (void)json_display(s, tmp, ulen, false);
+    });
+    s.put(']');
+    return 0;
+  }
+  if (elem == ETLG_TC_STRING || elem == ETLG_TC_BYTEA) {   // the unescaped text as a JSON string; bytea: the hex digits of its "\x.." text
+    bool bad = false;
+    if (arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t ulen) {
+          if (elem == ETLG_TC_BYTEA && !is_null && arr_bytea_len(txt, p0, p1, ulen) == ~0u) bad = true;
+        }) || bad) return RB_E_HOST_CELL;
+    s.put('[');
+    (void)arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t) {
+      if (k++) s.put(',');
+      if (is_null) { nd_lit(s, "null"); return; }
+      s.put('"');
+      if (elem == ETLG_TC_STRING) arr_unescape(txt, p0, p1, [&](u8 c) { nd_esc_put(s, c); });
+      else { uint32_t q = 0; arr_unescape(txt, p0, p1, [&](u8 c) { if (q++ >= 2) s.put((u8)(c - 'A' < 6u ? c | 0x20 : c)); }); }
+      s.put('"');
+    });
+    s.put(']');
+    return 0;
+  }
+  auto none = [](uint32_t) -> u8* { return nullptr; };
+  if (arr_walk<false>(txt, tn, elem, cnt, [](uint32_t, bool, const uint32_t*, const u8*) {}, none)) return RB_E_HOST_CELL;
+  uint32_t ee = 0;
+  s.put('[');
+  (void)arr_walk<false>(txt, tn, elem, cnt, [&](uint32_t, bool is_null, const uint32_t* w, const u8* scratch) {
+    if (k++) s.put(',');
+    if (is_null) { nd_lit(s, "null"); return; }
+    const uint32_t e1 = nd_value(s, elem, (const u8*)w, scratch);
+    if (e1 && !ee) ee = e1;
+  }, none);
+  s.put(']');
+  return ee;
+}
+// A typed array (ETLG_F_FINISH_CELLS: a VALUE cell whose slot holds an etlg_array_hdr entry) from its header — never as text.
+template <class S>
+DEV uint32_t nd_typed_array(S& s, const u8* h) {
+  const uint32_t n = ld32a(h), elem = h[4], eb = h[5];
+  const uint32_t* valid = (const uint32_t*)(h + 8);
+  const u8* body = h + 8 + 4u * ((n + 31u) / 32u);
+  const uint32_t* end = (const uint32_t*)body;
+  const u8* data = body + 4u * n;
+  uint32_t ee = 0;
+  s.put('[');
+  for (uint32_t k = 0; k < n; k++) {
+    if (k) s.put(',');
+    if (!((valid[k >> 5] >> (k & 31u)) & 1u)) { nd_lit(s, "null"); continue; }
+    uint32_t e1 = 0;
+    if (eb) e1 = nd_value(s, elem, body + (size_t)k * eb, nullptr);
+    else {
+      const uint32_t a = k ? end[k - 1] : 0u, b = end[k];
+      if (elem == ETLG_TC_STRING) nd_str(s, data + a, b - a);
+      else if (elem == ETLG_TC_BYTEA) { s.put('"'); s.hex(data + a, b - a); s.put('"'); }
+      else if (elem == ETLG_TC_NUMERIC) e1 = nd_numeric(s, data + a);
+      else e1 = RB_E_HOST_CELL;
+    }
+    if (e1 && !ee) ee = e1;
+  }
+  s.put(']');
+  return ee;
+}
+
+template <bool JS, class S, class M>
+DEV uint32_t nd_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_hi, M&& mark) {   // 0, or column << 8 | code
+  const uint64_t base = j.row_base[r], ev = j.row_event[r];
+  const uint32_t kind = j.ev_kind[ev];
+  // a Delete with a key image: the identity columns only, keyed by their names (identity_column_schemas, core.rs:412-426)
+  const bool keyrow = kind == 'D' && (j.ev_flags[ev] & 3u) == ETLG_OLD_KEY;
+  uint32_t err0 = 0;
+  if (c_lo == 0) s.put('{');
+  for (uint32_t i = c_lo; i < c_hi; i++) {
+    mark(i);
+    const uint32_t cd = j.cols[i], cls = cd & 0xFF;
+    uint32_t off = cd >> 16, sti = i;
+    if (keyrow) {
+      const uint32_t kc = j.kcols[i];
+      if (!(kc & 1u)) continue;
+      off = kc >> 16; sti = (kc >> 8) & 0xFFu;
+    }
+    const uint32_t a = j.nd_key_off[i];
+    s.bytes(j.nd_keys + a, j.nd_key_off[i + 1] - a);
+    const uint32_t st = (j.fixed[base + sti / 4] >> (2 * (sti % 4))) & 3u;
+    const u8* slot = j.fixed + base + off;
+    uint32_t e = 0;
+    if (st == ETLG_CELL_NULL) nd_lit(s, "null");
+    else if (cls == ETLG_TC_ARRAY && st == ETLG_CELL_VALUE) e = nd_typed_array(s, j.heap + ld32a(slot));
+    else if (cls == ETLG_TC_ARRAY && st == ETLG_CELL_DEFERRED) e = nd_array<JS>(s, (cd >> 9) & 0x7Fu, j.heap + ld32a(slot), ld32a(slot + 4));
+    else if (cls == ETLG_TC_JSON && st == ETLG_CELL_DEFERRED) e = JS ? rb_json(s, j.heap + ld32a(slot), ld32a(slot + 4), false, [](uint32_t) {}) : RB_E_HOST_CELL;   // Cell::Json: the Value itself
+    else if (st != ETLG_CELL_VALUE) e = RB_E_HOST_CELL;
+    else e = nd_value(s, cls, slot, j.heap);
+    if (e == RB_E_JSON) return (i << 8) | e;   // the reference's decode error: before anything the sink would report
+    if (e && !err0) err0 = (i << 8) | e;
+    s.put(',');
+  }
+  if (err0) return err0;
+  if (c_hi != j.n_cols) return 0;
+  nd_lit(s, "\"_cdc_operation\":\"");
+  nd_lit(s, kind == 'I' ? "insert" : kind == 'U' ? "update" : "delete");
+  nd_lit(s, "\",\"_cdc_sequence_number\":\"");
+  const uint64_t lsn = j.nd_zero_token ? 0ull : j.ev_commit[ev], ord = j.nd_zero_token ? 0ull : j.ev_ord[ev];
+  pb_hex16(s, lsn); s.put('/'); pb_hex16(s, ord);
+  nd_lit(s, "\"}\n");
+  return 0;
+}
+
 // JS: the table has a json column (kernels of their own, as for the Arrow columns)
-template <bool JS>
+// ND: the Snowflake NDJSON instantiation (nd_row), so the RowBinary / protobuf kernels carry no third arm
+template <bool JS, bool ND = false>
 __global__ __launch_bounds__(256) void k_rb_lens(RbJob j, unsigned long long* blk) {
   __shared__ uint64_t lds_sum[4];
   const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1529,7 +1779,9 @@ __global__ __launch_bounds__(256) void k_rb_lens(RbJob j, unsigned long long* bl
     auto mark = [&](uint32_t i) {
       while (next < j.qparts && i == rb_part_col(j, next)) { j.part_off[(uint64_t)(next - 1) * j.n_rows + r] = c.n; next++; }
     };
-    const uint32_t e = j.format ? pb_row<JS>(j, r, c, 0, j.n_cols, mark) : rb_row<JS>(j, r, c, 0, j.n_cols, mark);
+    uint32_t e;
+    if constexpr (ND) e = nd_row<JS>(j, r, c, 0, j.n_cols, mark);
+    else e = j.format ? pb_row<JS>(j, r, c, 0, j.n_cols, mark) : rb_row<JS>(j, r, c, 0, j.n_cols, mark);
     // first failing row in event order, rows with a date out of range before all others (bit 62 clear)
     // (and a json cell that is not JSON before those: the reference's decode fails before any sink sees a row)
     if (e) {
@@ -1554,7 +1806,7 @@ DEV uint32_t rb_rows_per_block(uint32_t parts) { return parts == 1 ? 256u : part
 // fits kRbLds, the lanes build it in LDS and the whole workgroup stores it in 16-byte pieces; a piece that does not fit (rows of more
 // than ~500 bytes on average) is written directly as before.
 constexpr uint32_t kRbLds = 32 * 1024;
-template <bool JS>
+template <bool JS, bool ND = false>
 __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   __shared__ uint4 img[kRbLds / 16 + 2];
   const uint32_t rpb = rb_rows_per_block(j.parts), part = threadIdx.x / rpb;
@@ -1571,7 +1823,8 @@ __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   if (!staged) {
     if (active) {
       RbWrite w(j.out + j.offsets[r] + po);
-      if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
+      if constexpr (ND) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
+      else if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
       w.finish();
     }
     return;
@@ -1582,7 +1835,8 @@ __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   if (active) {
     const uint32_t o = pad + (uint32_t)((uint64_t)j.offsets[r] - g0) + po;
     RbLdsWrite w((uint32_t*)img + (o >> 2), o & 3u);
-    if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
+    if constexpr (ND) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
+    else if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
     w.finish();
   }
   __syncthreads();
@@ -1898,13 +2152,16 @@ void etlg_k_rowbinary(const void* jv, unsigned long long* blk, int64_t* offsets,
   const RbJob j = *(const RbJob*)jv;
   if (!j.n_rows) return;
   const uint32_t nb = (uint32_t)((j.n_rows + 255) / 256);
+  const bool nd = j.format == 2;   // (Snowflake NDJSON: kernels of their own)
   if (step == 0) {
-    if (j.has_json) hipLaunchKernelGGL(k_rb_lens<true>, dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL(k_rb_lens<false>, dim3(nb), dim3(256), 0, st, j, blk);
+    if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, true>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, true>), dim3(nb), dim3(256), 0, st, j, blk); }
+    else if (j.has_json) hipLaunchKernelGGL(k_rb_lens<true>, dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL(k_rb_lens<false>, dim3(nb), dim3(256), 0, st, j, blk);
     hipLaunchKernelGGL(k_col_len_scan, dim3(1), dim3(256), 0, st, blk, nb);
     hipLaunchKernelGGL(k_col_offsets, dim3(nb), dim3(256), 0, st, (const uint32_t*)j.lens, j.n_rows, (const unsigned long long*)blk, offsets, tot);
   } else {
     const uint32_t rpb = j.parts == 1 ? 256u : j.parts == 2 ? 128u : 64u, nbw = (uint32_t)((j.n_rows + rpb - 1) / rpb);
-    if (j.has_json) hipLaunchKernelGGL(k_rb_rows<true>, dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL(k_rb_rows<false>, dim3(nbw), dim3(256), 0, st, j);
+    if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, true>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, true>), dim3(nbw), dim3(256), 0, st, j); }
+    else if (j.has_json) hipLaunchKernelGGL(k_rb_rows<true>, dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL(k_rb_rows<false>, dim3(nbw), dim3(256), 0, st, j);
   }
 }
 

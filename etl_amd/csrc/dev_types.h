@@ -280,7 +280,7 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   uint64_t n_rows;
   uint32_t n_cols, engine;         // engine: 0 MergeTree, 1 ReplacingMergeTree
   uint32_t cdc_nullable;           // bit 0 / 1: the first / second trailing CDC column is Nullable() in the destination
-  uint32_t format;                 // 0 ClickHouse RowBinary, 1 BigQuery protobuf (Insert rows, prost wire format)
+  uint32_t format;                 // 0 ClickHouse RowBinary, 1 BigQuery protobuf (prost wire format), 2 Snowflake NDJSON
   const uint32_t* cols;            // per replicated column: cls | nullable << 8 | off_full << 16
   const uint32_t* kcols;           // per replicated column, for key images: identity | source nullable << 1 | primary key << 2 | key_index << 8 | off_key << 16
   const uint8_t* ev_flags;
@@ -289,6 +289,10 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   uint32_t has_json;               // the table has a json / jsonb column: the kernels that carry json_display
   uint32_t qparts, parts;          // the counting pass notes where the row's qparts pieces begin (4; 2 / 1 for narrow tables); the byte pass writes a row with parts lanes (1, 2, 4 <= qparts)
   uint32_t* part_off;              // [(qparts - 1) x n_rows]: where pieces 1 .. of a row begin, in bytes from the row's start
+  // format 2 (Snowflake NDJSON, nd_row): the escaped `"name":` key of every column (key_off: n_cols + 1 byte offsets into keys), and
+  // whether the batch is a table copy (every row's sequence number is the zero token)
+  const uint8_t* nd_keys; const uint32_t* nd_key_off;
+  uint32_t nd_zero_token;
 };
 
 

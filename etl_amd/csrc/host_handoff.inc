@@ -451,8 +451,9 @@ void etlg_columns_free(etlg_columns* cs) {
   delete cs;
 }
 
+struct NdKeys { std::vector<uint32_t> off; std::string bytes; };   // format 2: the escaped `"name":` of every column, back to back
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
-                            uint32_t flags, uint32_t format, etlg_rowbinary** out);
+                            uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd = nullptr);
 
 int32_t etlg_batch_rowbinary(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
                              uint32_t flags, etlg_rowbinary** out) {
@@ -465,9 +466,40 @@ int32_t etlg_batch_protobuf(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t f
   return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags, 1u, out);
 }
 
-// format 0: ClickHouse RowBinary (Insert / Update / Delete rows + the engine's CDC columns); 1: BigQuery protobuf (Insert rows)
+// Snowflake NDJSON (snowflake/encoding.rs:57-72): the column names are escaped here once — serde_json's table (format_escaped_str) — and
+// go up with the column words as the `"name":` keys of nd_row.
+int32_t etlg_batch_ndjson(etlg_ctx* c, etlg_batch* b, int32_t slot, const char* col_names, uint32_t n_names, uint32_t flags, etlg_rowbinary** out) {
+  if (!c || !b || !out || b->ctx != c || (n_names && !col_names)) return ETLG_InvalidArgument;
+  *out = nullptr;
+  if (slot < 0 || (size_t)slot >= c->slots.size()) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (n_names != c->slots[(size_t)slot]->desc.n_cols) return lib_error(c, ETLG_InvalidArgument, "Snowflake row width mismatch: one column name per replicated column");
+  NdKeys k;
+  const char* p = col_names;
+  for (uint32_t i = 0; i < n_names; i++) {
+    k.off.push_back((uint32_t)k.bytes.size());
+    k.bytes.push_back('"');
+    for (; *p; p++) {
+      const unsigned char ch = (unsigned char)*p;
+      static const char hexd[] = "0123456789abcdef";
+      if (ch == '"' || ch == '\\') { k.bytes.push_back('\\'); k.bytes.push_back((char)ch); }
+      else if (ch == 8) k.bytes += "\\b";
+      else if (ch == 12) k.bytes += "\\f";
+      else if (ch == '\n') k.bytes += "\\n";
+      else if (ch == '\r') k.bytes += "\\r";
+      else if (ch == '\t') k.bytes += "\\t";
+      else if (ch < 0x20) { k.bytes += "\\u00"; k.bytes.push_back(hexd[ch >> 4]); k.bytes.push_back(hexd[ch & 15]); }
+      else k.bytes.push_back((char)ch);
+    }
+    p++;
+    k.bytes += "\":";
+  }
+  k.off.push_back((uint32_t)k.bytes.size());
+  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, 2u, out, &k);
+}
+
+// format 0: ClickHouse RowBinary (Insert / Update / Delete rows + the engine's CDC columns); 1: BigQuery protobuf; 2: Snowflake NDJSON
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
-                            uint32_t flags, uint32_t format, etlg_rowbinary** out) {
+                            uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd) {
   *out = nullptr;
   if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }   // an ASYNC batch that ended in a decode error: the caller gets that error (fail-fast, as the reference), not a hand-off of the prefix
   if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, "etlg_batch_rowbinary needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
@@ -520,7 +552,8 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   const uint64_t nr_cap = format ? 2 * ne : ne;   // BigQuery: an update that changes the primary key is two rows
   const uint32_t nblk = (uint32_t)((ne + 255) / 256);
   // block S (freed on return): block counts | host-row counter | error word | column words | row_base
-  const size_t o_cnt = al((size_t)(nblk + 1) * 4), o_cols = o_cnt + 64, o_base = o_cols + al((size_t)nc * 8 + 8), s_bytes = o_base + al(nr_cap * 8) + 64;
+  const size_t nd_bytes = nd ? (size_t)(nc + 1) * 4 + nd->bytes.size() : 0;   // (format 2: the keys' offsets and bytes behind the column words)
+  const size_t o_cnt = al((size_t)(nblk + 1) * 4), o_cols = o_cnt + 64, o_base = o_cols + al((size_t)nc * 8 + 8 + nd_bytes), s_bytes = o_base + al(nr_cap * 8) + 64;
   rb->m.ctx = c; rb->m.ctx_gen = c->gen;
   ScratchBlk sblk{c};
   HIPCHK(c, blk_take(c, s_bytes, false, &sblk.p, &sblk.cap));
@@ -529,7 +562,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   // pinned staging: [host rows = 0 | error word = ~0 | total | pad to 64 | column words] goes up in one copy (S + o_cnt .. lies the same
   // way); [row count] and [host rows | error word | total] come back in one copy each. (From / to pageable memory every one of these
   // small copies was a stop of its own.)
-  const size_t up_bytes = 64 + (size_t)nc * 8, hand_bytes = al(up_bytes) + 64;
+  const size_t up_bytes = 64 + (size_t)nc * 8 + nd_bytes, hand_bytes = al(up_bytes) + 64;
   if (c->h_hand_cap < hand_bytes) {
     if (c->h_hand) { HIPCHK(c, hipStreamSynchronize(s)); (void)hipHostFree(c->h_hand); c->h_hand = nullptr; c->h_hand_cap = 0; }
     HIPCHK(c, hipHostMalloc((void**)&c->h_hand, hand_bytes + 4096, hipHostMallocDefault));
@@ -539,6 +572,10 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     unsigned long long* up = (unsigned long long*)c->h_hand;
     up[0] = 0ull; up[1] = ~0ull; up[2] = 0ull;
     if (nc) memcpy(c->h_hand + 64, cols.data(), (size_t)nc * 8);
+    if (nd) {
+      memcpy(c->h_hand + 64 + (size_t)nc * 8, nd->off.data(), (size_t)(nc + 1) * 4);
+      if (!nd->bytes.empty()) memcpy(c->h_hand + 64 + (size_t)nc * 12 + 4, nd->bytes.data(), nd->bytes.size());
+    }
     HIPCHK(c, hipMemcpyAsync(S + o_cnt, c->h_hand, up_bytes, hipMemcpyHostToDevice, s));
   }
   volatile unsigned long long* down = (volatile unsigned long long*)(c->h_hand + al(up_bytes));   // [0] row count, [1..3] host rows, error word, total
@@ -557,10 +594,12 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     // clickhouse/core.rs:1359-1427). Such Updates are not encoded here: they are left to the host (n_host_rows), which raises
     // the reference's SourceReplicaIdentityError when it meets the first of them.
     const bool upd_ok = format != 0 || engine != ETLG_CH_REPLACING_MERGE_TREE || sh.identity_type == 1 || sh.identity_type == 2;
-    q.n_events = ne; q.slot = (uint32_t)slot; q.kinds = format ? 1u : ((upd_ok ? 7u : 5u) | (key_ok ? 8u : 0u)); q.host_rows = (unsigned long long*)(S + o_cnt);
+    // Snowflake: inserts, full updates, deletes with a full old row or a key image (core.rs:345-438, snowflake_update_row /
+    // snowflake_delete_row :572-608); partial updates and deletes without an old row stay with the host (SourceReplicaIdentityError)
+    q.n_events = ne; q.slot = (uint32_t)slot; q.kinds = format == 2 ? 15u : format ? 1u : ((upd_ok ? 7u : 5u) | (key_ok ? 8u : 0u)); q.host_rows = (unsigned long long*)(S + o_cnt);
     q.row_full = sh.desc.row_bytes_full; q.row_key = sh.desc.row_bytes_key;
     q.blk = (uint32_t*)S; q.nblocks = nblk; q.row_event = (uint64_t*)A; q.row_base = (uint64_t*)(S + o_base);
-    if (format) {  // BigQuery: inserts, updates (one or two rows) and deletes (bigquery/core.rs:978-1036); the events the reference refuses stay with the host
+    if (format == 1) {  // BigQuery: inserts, updates (one or two rows) and deletes (bigquery/core.rs:978-1036); the events the reference refuses stay with the host
       q.pb = 1; q.n_cols = nc; q.identity_pk = sh.identity_type == 1 ? 1u : 0u; q.pk_comparable = pk_comparable ? 1u : 0u;
       q.fixed = bv.fixed; q.heap = bv.heap; q.cols = (const uint32_t*)(S + o_cols); q.kcols = (const uint32_t*)(S + o_cols) + nc;
     }
@@ -581,6 +620,11 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   for (uint32_t i = 0; i < nc; i++) if (sh.cols[i].type_class == ETLG_TC_JSON || (sh.cols[i].type_class == ETLG_TC_ARRAY && (uint32_t)etlg_array_elem_class(sh.cols[i].type_oid) == ETLG_TC_JSON)) j.has_json = 1;
   j.qparts = nc >= 4 ? 4u : nc >= 2 ? 2u : 1u; j.parts = 1;
   j.part_off = (uint32_t*)(A + o_part);
+  if (nd) {
+    j.kcols = (const uint32_t*)(S + o_cols) + nc;
+    j.nd_key_off = (const uint32_t*)(S + o_cols + (size_t)nc * 8); j.nd_keys = S + o_cols + (size_t)nc * 12 + 4;
+    j.nd_zero_token = b->copy.active ? 1u : 0u;   // a table-copy batch (etlg_copy_decode): Insert rows under OffsetToken::zero (core.rs:683-699)
+  }
   int64_t total = 0;
   if (n) {
     etlg_k_rowbinary(&j, (unsigned long long*)(A + o_scan), (int64_t*)(A + o_off), (unsigned long long*)(S + o_cnt) + 2, 0, s);
@@ -601,6 +645,16 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
       blk_give(c, c->gen, rb->m.d_a, rb->m.cap_a, false); rb->m.d_a = nullptr;
       *out = rb.release();
       return ETLG_OK;
+    }
+    if (code >= 7 && code <= 11) {  // Error::Encoding of the serde message (snowflake/encoding.rs:162-180, error.rs:25-26, 52)
+      const int32_t k = lib_error(c, ETLG_InvalidData, "Snowflake encoding error");
+      static const char* const what[] = {"Snowflake does not support NaN/Infinity float values: NaN", "Snowflake does not support NaN/Infinity float values: inf",
+                                         "Snowflake does not support NaN/Infinity float values: -inf", "Snowflake NUMBER does not support NaN",
+                                         "Snowflake NUMBER does not support Infinity"};
+      c->err_detail = std::string("Encoding error: ") + what[code - 7];
+      c->err.detail = c->err_detail.c_str();
+      c->err.frame_index = (int64_t)ev;
+      return k;
     }
     if (code == 4 || code == 6) {  // BigQueryTableRow::try_from_tagged_cells (bigquery/encoding.rs:37-45) around validate_numeric_for_bigquery (validation.rs:20-35) / reject_nulls (:127-141): the wrapper keeps the kind
       const int32_t k = lib_error(c, code == 6 ? ETLG_NullValuesNotSupportedInArrayInDestination : ETLG_UnsupportedValueInDestination, "Cell validation failed for BigQuery compatibility");

@@ -109,6 +109,18 @@ class Batch:
             raise self.dec.last_error()
         return RowBinary(self.dec, out)
 
+    def ndjson(self, slot, names, on_device=False):
+        """Snowflake NDJSON lines (one per row, each ending in '\\n') of schema slot `slot`, encoded on the device (etlg_batch_ndjson).
+        `names`: the slot's replicated column names (str or bytes) in slot order. Raises EtlError for the sink's encoding errors and
+        ETLG_E_JSON; `RowBinary.status == abi.RB_NEEDS_HOST` when a cell has no device encoding."""
+        raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        blob = b"".join(n + b"\0" for n in raw)
+        out = C.c_void_p()
+        rc = self.dec.L.etlg_batch_ndjson(self.dec.h, self.h, slot, blob, len(raw), abi.F_OUTPUT_ON_DEVICE if on_device else 0, C.byref(out))
+        if rc != abi.OK or not out:
+            raise self.dec.last_error()
+        return RowBinary(self.dec, out)
+
     def close(self):
         if self.h:
             self.dec.L.etlg_batch_free(self.h)

@@ -778,6 +778,29 @@ int32_t etlg_batch_rowbinary(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_sl
  * etlg_batch_rowbinary), DEFERRED cells and json cells beyond json_display's limits return ETLG_RB_NEEDS_HOST.
  * The result is an etlg_rowbinary (same view; n_rows can exceed the number of events). */
 int32_t etlg_batch_protobuf(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, uint32_t flags, etlg_rowbinary** out);
+/* Snowflake Snowpipe Streaming rows for ONE schema slot: the NDJSON line serialize_row writes for every row the sink builds
+ * (crates/etl-destinations/src/snowflake/encoding.rs:57-72; core.rs:345-438), in event order, at most one row per event, each line
+ * serde_json's compact map followed by '\n':
+ *   {"<col>":<value>,...,"_cdc_operation":"insert|update|delete","_cdc_sequence_number":"<commit_lsn:016x>/<tx_ordinal:016x>"}
+ *   Insert -> every replicated column ("insert"); Update with a full new row -> the new row ("update"); Delete with a full old row ->
+ *   every replicated column, with a key image -> the identity columns only, keyed by their names ("delete"). A partial Update and a
+ *   Delete without an old row are left out and counted in n_host_rows (the host raises SourceReplicaIdentityError, :572-608).
+ *   A table-copy batch (etlg_copy_decode) gives "insert" rows under the zero token 0000000000000000/0000000000000000 (:683-699).
+ * col_names: the slot's replicated column names in slot order, each NUL-terminated, back to back; n_names must be the slot's n_cols
+ * (ETLG_InvalidArgument otherwise). Keys and text values are escaped like serde_json (\" \\ \b \f \n \r \t, \u00xx for the other
+ * bytes below 0x20, everything else raw). Values (CellSerializer :94-140): NULL null; bool; integers in decimal; float4 / float8 in
+ * ryu's shortest form (serde_json serialize_f32 / _f64); numeric, date (%Y-%m-%d), time (%H:%M:%S%.f), timestamp, timestamptz
+ * (%Y-%m-%d %H:%M:%S%.f+00:00), timetz, uuid (hyphenated lower case) and bytea (lower-case hex) as JSON strings; json / jsonb the value
+ * itself, embedded; text-like cells JSON strings; arrays JSON arrays of the same (a NULL element is null).
+ * A float that is NaN / +-inf, a numeric NaN / +-Infinity (cell or element) fails the call like Error::Encoding: ETLG_InvalidData,
+ * description "Snowflake encoding error", detail "Encoding error: Snowflake does not support NaN/Infinity float values: NaN" (inf, -inf) /
+ * "Encoding error: Snowflake NUMBER does not support NaN" / "... Infinity", frame_index = the event. A json cell or element that is not
+ * one JSON value fails it with ETLG_E_JSON before anything else. Otherwise the first row in event order (its first column, an array's
+ * first element) that fails or that the device cannot encode decides: DEFERRED cells, literals the array walkers do not take apart and
+ * json beyond json_display's limits give status ETLG_RB_NEEDS_HOST (host_event / host_column). Typed array cells of a batch finished
+ * with ETLG_F_FINISH_CELLS are written from their etlg_array_hdr. Flags: ETLG_F_OUTPUT_ON_DEVICE. Every row's bytes include its '\n'. */
+int32_t etlg_batch_ndjson(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const char* col_names, uint32_t n_names, uint32_t flags,
+                          etlg_rowbinary** out);
 int32_t etlg_rowbinary_view_get(const etlg_rowbinary* rb, etlg_rowbinary_view* out);
 void etlg_rowbinary_free(etlg_rowbinary* rb);
 
