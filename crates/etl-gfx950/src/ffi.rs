@@ -272,6 +272,8 @@ pub const ETLG_CH_MERGE_TREE: i32 = 0;
 pub const ETLG_CH_REPLACING_MERGE_TREE: i32 = 1;
 pub const ETLG_RB_OK: u32 = 0;
 pub const ETLG_RB_NEEDS_HOST: u32 = 3;
+pub const ETLG_DL_TUPLES: i32 = 0;
+pub const ETLG_DL_PREDICATES: i32 = 1;
 
 #[repr(C)]
 pub struct etlg_kernel_stat {
@@ -405,6 +407,16 @@ extern "C" {
         ctx: *mut etlg_ctx,
         batch: *mut etlg_batch,
         schema_slot: i32,
+        col_names: *const c_char,
+        n_names: u32,
+        flags: u32,
+        out: *mut *mut etlg_rowbinary,
+    ) -> i32;
+    pub fn etlg_batch_duckdb(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        schema_slot: i32,
+        what: i32,
         col_names: *const c_char,
         n_names: u32,
         flags: u32,

@@ -13,6 +13,7 @@
 #include "codec.hip.h"
 #include "float_slow.h"
 #include "float_json.h"
+#include "float_display.h"
 #include <type_traits>
 
 namespace etlg {
@@ -86,15 +87,40 @@ DEV uint32_t pb_selected(const ColSel& s, uint64_t i, unsigned long long* bases)
   return 1;
 }
 
+// ---- DuckLake: what an event becomes for the tuples (dl 1) and for the predicates (dl 2; 3: a table-copy batch, every row):
+// 0 nothing, 1 a row (base: the image, | kPbKey when it has the key layout), 2 an event the host has to take (n_host_rows).
+// Insert -> a tuple; Update -> the new row's tuple unless it is partial, and the predicate of the old image — without one, of the
+// new row's identity columns (TableMutation::Replace) unless that row is partial (key_row_from_updated_partial_row); Delete -> the
+// predicate of the old image, which it must carry ("DuckLake delete requires an old row image").
+DEV uint32_t dl_selected(const ColSel& s, uint64_t i, unsigned long long& base) {
+  if (i >= s.n_events || s.ev_slot[i] != s.slot) return 0;
+  const uint32_t k = s.ev_kind[i], fl = s.ev_flags[i], ok = fl & 3u;
+  const bool partial = (fl & ETLG_FLAG_PARTIAL) != 0;
+  base = s.ev_body[i];
+  if (k == 'I') return s.dl != 2u ? 1u : 0u;
+  if (k != 'U' && k != 'D') return 0;
+  if (s.dl == 1u) {
+    if (k == 'D') return 0;
+    if (partial) return 2;
+    base += ok == ETLG_OLD_FULL ? s.row_full : ok == ETLG_OLD_KEY ? s.row_key : 0u;
+    return 1;
+  }
+  if (!s.dl_ident) return 2;   // "DuckLake delete requires a replica identity"
+  if (ok == ETLG_OLD_FULL) return 1;
+  if (ok == ETLG_OLD_KEY) { base |= kPbKey; return 1; }
+  return k == 'U' && !partial ? 1u : 2u;
+}
+
 __global__ __launch_bounds__(256) void k_col_count(ColSel s) {
   __shared__ uint32_t lds[8];
   uint64_t base;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   unsigned long long pbb[2];
-  const uint32_t sel = s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
+  const uint32_t dls = s.dl ? dl_selected(s, i, pbb[0]) : 0u;
+  const uint32_t sel = s.dl ? (dls == 1u ? 1u : 0u) : s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
   if (s.host_rows) {  // row events of the slot that are not handed off
-    bool left = false;
-    if (!sel && i < s.n_events && s.ev_slot[i] == s.slot) { const uint32_t k = s.ev_kind[i]; left = k == 'I' || k == 'U' || k == 'D'; }
+    bool left = dls == 2u;
+    if (!s.dl && !sel && i < s.n_events && s.ev_slot[i] == s.slot) { const uint32_t k = s.ev_kind[i]; left = k == 'I' || k == 'U' || k == 'D'; }
     const unsigned long long m = __ballot(left);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(s.host_rows, (unsigned long long)__builtin_popcountll(m));
   }
@@ -123,11 +149,11 @@ __global__ __launch_bounds__(256) void k_col_rows(ColSel s) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   uint64_t base = 0;
   unsigned long long pbb[2] = {0, 0};
-  const uint32_t sel = s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
+  const uint32_t sel = s.dl ? (dl_selected(s, i, pbb[0]) == 1u ? 1u : 0u) : s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
   const uint32_t inc = block_scan_incl<0>(sel, lds, nullptr);
   if (sel) {
     const uint32_t r = s.blk[blockIdx.x] + inc - sel;
-    s.row_event[r] = i; s.row_base[r] = s.pb ? pbb[0] : base;
+    s.row_event[r] = i; s.row_base[r] = (s.pb || s.dl) ? pbb[0] : base;
     if (sel == 2) { s.row_event[r + 1] = i; s.row_base[r + 1] = pbb[1]; }
   }
 }
@@ -728,8 +754,8 @@ struct RbWriterT : B {
     for (; k + 8u <= len; k += 8u) { uint64_t v; __builtin_memcpy(&v, s + k, 8); append(v, 8); }
     if (k < len) { uint64_t v = 0; for (uint32_t b = 0; k + b < len; b++) v |= (uint64_t)s[k + b] << (8u * b); append(v, len - k); }
   }
-  DEV void hex(const u8* s, uint32_t len) {   // bytes_to_hex, lowercase (:176-185)
-    auto h1 = [](uint32_t d) -> uint64_t { return d < 10 ? '0' + d : 'a' + d - 10; };
+  DEV void hex(const u8* s, uint32_t len, uint32_t alpha = 'a') {   // bytes_to_hex, lowercase (:176-185); alpha 'A': upper case
+    auto h1 = [alpha](uint32_t d) -> uint64_t { return d < 10 ? '0' + d : alpha + d - 10; };
     uint32_t k = 0;
     for (; k + 4u <= len; k += 4u) {   // four bytes -> eight digits
       uint64_t v = 0;
@@ -1097,8 +1123,9 @@ struct RbCount {
   DEV void put32(uint32_t) { n += 4; }
   DEV void put64(uint64_t) { n += 8; }
   DEV void zeros(uint32_t k) { n += k; }
+  DEV void append(uint64_t, uint32_t k) { n += k; }
   DEV void bytes(const u8*, uint32_t len) { n += len; }
-  DEV void hex(const u8*, uint32_t len) { n += 2 * len; }
+  DEV void hex(const u8*, uint32_t len, uint32_t = 'a') { n += 2 * len; }
 };
 
 template <class S>
@@ -1766,9 +1793,271 @@ DEV uint32_t nd_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
   return 0;
 }
 
+// ---- DuckLake SQL literals (cell_to_sql_literal, crates/etl-destinations/src/ducklake/encoding.rs:366-612): the text every row the
+// DuckLake sink writes goes through — `(lit, lit, ...)` per upserted row (table_row_to_sql_literal_ref, hashed into the batch identity
+// and inserted as VALUES text) and `"col" = lit AND "col" IS NULL` per row image it deletes / matches by (delete_predicate_from_row,
+// batches.rs:1229-1316). RbJob.dl_what says which: 0 tuples, 1 predicates over the identity columns, 2 predicates over the primary-key
+// columns (a table-copy batch). Records carry no separator; the sink itself has no encoding error on this path.
+//
+// quote_literal is pg_escape 0.1.1, RESTATED FROM THE CRATE'S DOCUMENTATION (its source is not vendored with the reference and no
+// reference test pins more than the plain arm): `'` is doubled; a text that holds a backslash has every backslash doubled and the
+// literal is prefixed with " E" (a\b -> " E'a\\b'"); otherwise plain '...'. The quote doubling and the backslash arm are UNPINNED. The
+// rule itself is the next three functions — which bytes are doubled, what opens the literal, how a byte is written — and dl_quote is
+// the one function that applies it to a text (tests/ducklake_literals.py quote_literal is its twin); a json cell's Display and an array
+// element's unescaped characters, which are not contiguous, go through the same three from DlQCount / DlQSink.
+// The prefix must be known before the first byte, so both passes run over the text twice.
+DEV bool dl_q_special(uint32_t c) { return c == '\'' || c == '\\'; }
+template <class S> DEV void dl_q_open(S& s, bool backslash) { if (backslash) { s.put(' '); s.put('E'); } s.put('\''); }
+template <class S> DEV void dl_q_put(S& s, uint32_t c) { const bool twice = dl_q_special(c); s.append(twice ? c | (c << 8) : c, twice ? 2u : 1u); }   // (one append: c, or c c)
+struct DlQCount { uint32_t n = 0, extra = 0, bs = 0; DEV void put(u8 c) { n++; extra += dl_q_special(c) ? 1u : 0u; bs += c == '\\' ? 1u : 0u; } };
+template <class S> struct DlQSink { S& s; DEV void put(u8 c) { dl_q_put(s, c); } };
+// (an array element's unescaped characters s0[p0 .. p1): a call of its own, so that the lambda that writes an element replays it once)
+DEV_NOINLINE DlQCount arr_q_count(const u8* s0, uint32_t p0, uint32_t p1) {
+  DlQCount c;
+  arr_unescape(s0, p0, p1, [&](u8 ch) { c.put(ch); });
+  return c;
+}
+// a contiguous text: eight bytes at a time for a byte to double (as nd_str does), then the copy in 16-byte pieces that hold none
+template <class S>
+DEV void dl_quote(S& s, const u8* text, uint32_t n) {
+  auto swar = [](uint64_t w) {   // bit 7 of some byte set <=> one of the eight bytes is '\'' or '\\' (has-zero: exact for "any")
+    const uint64_t L = 0x0101010101010101ull, q = w ^ (0x27u * L), b = w ^ (0x5Cu * L);
+    return (((q - L) & ~q) | ((b - L) & ~b)) & (0x80u * L);
+  };
+  DlQCount c;
+  uint32_t k = 0;
+  for (; k + 8u <= n; k += 8u) {
+    uint64_t w; __builtin_memcpy(&w, text + k, 8);
+    if (swar(w)) for (uint32_t b = 0; b < 8u; b++) c.put(text[k + b]);
+  }
+  for (; k < n; k++) c.put(text[k]);
+  dl_q_open(s, c.bs != 0);
+  if constexpr (std::is_same<S, RbCount>::value) s.zeros(n + c.extra);
+  else if (!c.extra) s.bytes(text, n);
+  else {
+    for (k = 0; k + 16u <= n; k += 16u) {
+      uint64_t v[2]; __builtin_memcpy(v, text + k, 16);
+      if (!(swar(v[0]) | swar(v[1]))) { s.append(v[0], 8); s.append(v[1], 8); }
+      else for (uint32_t b = 0; b < 16u; b++) dl_q_put(s, text[k + b]);
+    }
+    for (; k < n; k++) dl_q_put(s, text[k]);
+  }
+  s.put('\'');
+}
+// CAST(<quote_literal(j.to_string())> AS JSON) (:415). The text is checked in the counting pass only, as rb_json does.
+template <class S> DEV uint32_t dl_json(S& s, const u8* t, uint32_t tn, bool check) {
+  if (check && std::is_same<S, RbCount>::value && !json_valid(t, tn)) return RB_E_JSON;
+  DlQCount c;
+  if (json_display(c, t, tn, false)) return RB_E_HOST_CELL;
+  nd_lit(s, "CAST(");
+  dl_q_open(s, c.bs != 0);
+  if constexpr (std::is_same<S, RbCount>::value) s.zeros(c.n + c.extra);
+  else { DlQSink<S> k{s}; (void)json_display(k, t, tn, false); }
+  s.put('\'');
+  nd_lit(s, " AS JSON)");
+  return 0;
+}
+// from_hex('<UPPER-case hex>'): encode_hex, {byte:02X} (:615-617)
+template <class S> DEV void dl_bytea(S& s, const u8* p, uint32_t n) { nd_lit(s, "from_hex('"); s.hex(p, n, 'A'); nd_lit(s, "')"); }
+// float_literal (:588-612): the three CASTs, else `value.to_string()` of the f64 (a float4 widened first) — float_display.h
+template <class S> DEV void dl_float(S& s, uint64_t bits, bool is32) {
+  const uint64_t b = is32 ? f32_widen_bits((uint32_t)bits) : bits;
+  if (((b >> 52) & 0x7FFu) == 0x7FFu) {
+    nd_lit(s, (b & ((1ull << 52) - 1u)) ? "CAST('NaN' AS " : (b >> 63) ? "CAST('-Infinity' AS " : "CAST('Infinity' AS ");
+    nd_lit(s, is32 ? "FLOAT)" : "DOUBLE)");
+    return;
+  }
+  (void)float_display(s, b);
+}
+// %H:%M:%S%.6f — always six fraction digits (a leap second is nanos >= 10^9 on second 59, printed as :60)
+template <class S> DEV void dl_time(S& s, uint32_t secs, uint32_t nanos) {
+  const uint32_t leap = nanos >= 1000000000u ? 1u : 0u;
+  nanos -= leap * 1000000000u;
+  put_2d(s, secs / 3600); s.put(':'); put_2d(s, secs / 60 % 60); s.put(':'); put_2d(s, secs % 60 + leap);
+  s.put('.');
+  const uint32_t us = nanos / 1000u;
+  for (uint32_t div = 100000u; div; div /= 10) s.put((u8)('0' + us / div % 10));
+}
+// numeric / timetz Display through quote_literal: their texts hold neither a quote nor a backslash, so the plain arm
+template <class S> DEV void dl_numeric(S& s, const u8* ent) { s.put('\''); numeric_str(s, ent); s.put('\''); }
+// One non-null value of class `cls` (nd_value's arguments)
+template <class S>
+DEV uint32_t dl_value(S& s, uint32_t cls, const u8* slot, const u8* heap) {
+  const uint32_t w0 = ld32a(slot);
+  switch (cls) {
+    case ETLG_TC_BOOL: nd_lit(s, w0 ? "TRUE" : "FALSE"); return 0;
+    case ETLG_TC_I16: case ETLG_TC_I32: nd_i64(s, (int32_t)w0); return 0;
+    case ETLG_TC_U32: nd_u64(s, w0); return 0;
+    case ETLG_TC_I64: nd_i64(s, (int64_t)(((uint64_t)ld32a(slot + 4) << 32) | w0)); return 0;
+    case ETLG_TC_F32: dl_float(s, w0, true); return 0;
+    case ETLG_TC_F64: dl_float(s, ((uint64_t)ld32a(slot + 4) << 32) | w0, false); return 0;
+    case ETLG_TC_NUMERIC: dl_numeric(s, heap + w0); return 0;
+    case ETLG_TC_DATE: nd_lit(s, "DATE '"); pb_date(s, (int32_t)w0); s.put('\''); return 0;
+    case ETLG_TC_TIME: nd_lit(s, "TIME '"); dl_time(s, w0, ld32a(slot + 4)); s.put('\''); return 0;
+    case ETLG_TC_TIMESTAMP: case ETLG_TC_TIMESTAMPTZ:
+      nd_lit(s, cls == ETLG_TC_TIMESTAMPTZ ? "TIMESTAMPTZ '" : "TIMESTAMP '");
+      pb_date(s, (int32_t)w0); s.put(' '); dl_time(s, ld32a(slot + 4), ld32a(slot + 8));
+      if (cls == ETLG_TC_TIMESTAMPTZ) nd_lit(s, "+00:00");   // %:z of a DateTime<Utc>
+      s.put('\''); return 0;
+    case ETLG_TC_TIMETZ: s.put('\''); timetz_str(s, slot); s.put('\''); return 0;
+    case ETLG_TC_UUID:
+      nd_lit(s, "CAST('");
+      for (int k = 0; k < 16; k++) {
+        const uint32_t b = slot[k], h = b >> 4, l = b & 15;
+        if (k == 4 || k == 6 || k == 8 || k == 10) s.put('-');
+        s.put((u8)(h < 10 ? '0' + h : 'a' + h - 10)); s.put((u8)(l < 10 ? '0' + l : 'a' + l - 10));
+      }
+      nd_lit(s, "' AS UUID)"); return 0;
+    case ETLG_TC_STRING: dl_quote(s, heap + w0, ld32a(slot + 4)); return 0;
+    case ETLG_TC_BYTEA: dl_bytea(s, heap + w0, ld32a(slot + 4)); return 0;
+    default: return RB_E_HOST_CELL;
+  }
+}
+// An array cell that is still its source literal (DEFERRED): `[e, e, NULL]`, elements by the scalar rules (array_cell_to_sql_literal
+// :470-585). Returns as nd_array does.
+template <bool JS, class S>
+DEV uint32_t dl_array(S& s, uint32_t elem, const u8* txt, uint32_t tn) {
+  uint32_t cnt = 0, k = 0;
+  if (elem == ETLG_TC_JSON) {
+    if (!JS) return RB_E_HOST_CELL;
+    u8 tmp[kJsonElemMax];
+    bool too_long = false, bad_json = false, limit = false;
+    if (arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t ulen) {
+          if (is_null) return;
+          if (ulen > kJsonElemMax) { too_long = true; return; }
+          uint32_t q = 0;
+          arr_unescape(txt, p0, p1, [&](u8 c) { tmp[q++] = c; });
+          if (std::is_same<S, RbCount>::value && !json_valid(tmp, ulen)) { bad_json = true; return; }
+          JsCount c;
+          if (json_display(c, tmp, ulen, false)) limit = true;
+        })) too_long = true;
+    if (too_long) return RB_E_HOST_CELL;
+    if (bad_json) return RB_E_JSON;
+    if (limit) return RB_E_HOST_CELL;
+    s.put('[');
+    (void)arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t ulen) {
+      if (k++) { s.put(','); s.put(' '); }
+      if (is_null) { nd_lit(s, "NULL"); return; }
+      uint32_t q = 0;
+      arr_unescape(txt, p0, p1, [&](u8 c) { tmp[q++] = c; });
+      (void)dl_json(s, tmp, ulen, false);
+    });
+    s.put(']');
+    return 0;
+  }
+  if (elem == ETLG_TC_STRING || elem == ETLG_TC_BYTEA) {
+    bool bad = false;
+    if (arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t ulen) {
+          if (elem == ETLG_TC_BYTEA && !is_null && arr_bytea_len(txt, p0, p1, ulen) == ~0u) bad = true;
+        }) || bad) return RB_E_HOST_CELL;
+    s.put('[');
+    (void)arr_spans(txt, tn, cnt, [&](uint32_t, bool is_null, uint32_t p0, uint32_t p1, uint32_t) {
+      if (k++) { s.put(','); s.put(' '); }
+      if (is_null) { nd_lit(s, "NULL"); return; }
+      if (elem == ETLG_TC_STRING) {
+        const DlQCount c = arr_q_count(txt, p0, p1);
+        dl_q_open(s, c.bs != 0);
+        if constexpr (std::is_same<S, RbCount>::value) s.zeros(c.n + c.extra);
+        else arr_unescape(txt, p0, p1, [&](u8 ch) { dl_q_put(s, ch); });
+        s.put('\'');
+      }
+      else {   // the hex digits of the element's "\x.." text, in upper case
+        nd_lit(s, "from_hex('");
+        uint32_t q = 0;
+        arr_unescape(txt, p0, p1, [&](u8 c) { if (q++ >= 2) s.put((u8)(c - 'a' < 6u ? c & ~0x20u : c)); });
+        nd_lit(s, "')");
+      }
+    });
+    s.put(']');
+    return 0;
+  }
+  auto none = [](uint32_t) -> u8* { return nullptr; };
+  if (arr_walk<false>(txt, tn, elem, cnt, [](uint32_t, bool, const uint32_t*, const u8*) {}, none)) return RB_E_HOST_CELL;
+  uint32_t ee = 0;
+  s.put('[');
+  (void)arr_walk<false>(txt, tn, elem, cnt, [&](uint32_t, bool is_null, const uint32_t* w, const u8* scratch) {
+    if (k++) { s.put(','); s.put(' '); }
+    if (is_null) { nd_lit(s, "NULL"); return; }
+    const uint32_t e1 = dl_value(s, elem, (const u8*)w, scratch);
+    if (e1 && !ee) ee = e1;
+  }, none);
+  s.put(']');
+  return ee;
+}
+// A typed array (ETLG_F_FINISH_CELLS) from its etlg_array_hdr, as nd_typed_array
+template <class S>
+DEV uint32_t dl_typed_array(S& s, const u8* h) {
+  const uint32_t n = ld32a(h), elem = h[4], eb = h[5];
+  const uint32_t* valid = (const uint32_t*)(h + 8);
+  const u8* body = h + 8 + 4u * ((n + 31u) / 32u);
+  const uint32_t* end = (const uint32_t*)body;
+  const u8* data = body + 4u * n;
+  uint32_t ee = 0;
+  s.put('[');
+  for (uint32_t k = 0; k < n; k++) {
+    if (k) { s.put(','); s.put(' '); }
+    if (!((valid[k >> 5] >> (k & 31u)) & 1u)) { nd_lit(s, "NULL"); continue; }
+    uint32_t e1 = 0;
+    if (eb) e1 = dl_value(s, elem, body + (size_t)k * eb, nullptr);
+    else {
+      const uint32_t a = k ? end[k - 1] : 0u, b = end[k];
+      if (elem == ETLG_TC_STRING) dl_quote(s, data + a, b - a);
+      else if (elem == ETLG_TC_BYTEA) dl_bytea(s, data + a, b - a);
+      else if (elem == ETLG_TC_NUMERIC) dl_numeric(s, data + a);
+      else e1 = RB_E_HOST_CELL;
+    }
+    if (e1 && !ee) ee = e1;
+  }
+  s.put(']');
+  return ee;
+}
+
+template <bool JS, class S, class M>
+DEV uint32_t dl_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_hi, M&& mark) {   // 0, or column << 8 | code
+  const uint64_t rb = j.row_base[r], base = rb & kPbBase;
+  const bool pred = j.dl_what != 0, keyrow = (rb & kPbKey) != 0;   // keyrow: the image has the key layout (the identity cells only)
+  const uint32_t kbit = j.dl_what == 2 ? 4u : 1u;                   // which columns a predicate takes: identity / primary key
+  bool first = true;                                                // no predicate column in front of this lane's columns?
+  if (pred) for (uint32_t i = 0; i < c_lo; i++) if (j.kcols[i] & kbit) first = false;
+  uint32_t err0 = 0;
+  if (!pred && c_lo == 0) s.put('(');
+  for (uint32_t i = c_lo; i < c_hi; i++) {
+    mark(i);
+    const uint32_t cd = j.cols[i], cls = cd & 0xFF;
+    uint32_t off = cd >> 16, sti = i;
+    if (pred) {
+      const uint32_t kc = j.kcols[i];
+      if (!(kc & kbit)) continue;
+      if (keyrow) { off = kc >> 16; sti = (kc >> 8) & 0xFFu; }
+      if (!first) nd_lit(s, " AND ");
+      first = false;
+      const uint32_t a = j.nd_key_off[i];
+      s.bytes(j.nd_keys + a, j.nd_key_off[i + 1] - a);   // the quoted identifier
+    } else if (i) { s.put(','); s.put(' '); }
+    const uint32_t st = (j.fixed[base + sti / 4] >> (2 * (sti % 4))) & 3u;
+    const u8* slot = j.fixed + base + off;
+    uint32_t e = 0;
+    if (st == ETLG_CELL_NULL) nd_lit(s, pred ? " IS NULL" : "NULL");
+    else {
+      if (pred) nd_lit(s, " = ");
+      if (cls == ETLG_TC_ARRAY && st == ETLG_CELL_VALUE) e = dl_typed_array(s, j.heap + ld32a(slot));
+      else if (cls == ETLG_TC_ARRAY && st == ETLG_CELL_DEFERRED) e = dl_array<JS>(s, (cd >> 9) & 0x7Fu, j.heap + ld32a(slot), ld32a(slot + 4));
+      else if (cls == ETLG_TC_JSON && st == ETLG_CELL_DEFERRED) e = JS ? dl_json(s, j.heap + ld32a(slot), ld32a(slot + 4), true) : RB_E_HOST_CELL;
+      else if (st != ETLG_CELL_VALUE) e = RB_E_HOST_CELL;
+      else e = dl_value(s, cls, slot, j.heap);
+    }
+    if (e == RB_E_JSON) return (i << 8) | e;   // the reference's decode error: before anything else
+    if (e && !err0) err0 = (i << 8) | e;
+  }
+  if (err0) return err0;
+  if (!pred && c_hi == j.n_cols) s.put(')');
+  return 0;
+}
+
 // JS: the table has a json column (kernels of their own, as for the Arrow columns)
-// ND: the Snowflake NDJSON instantiation (nd_row), so the RowBinary / protobuf kernels carry no third arm
-template <bool JS, bool ND = false>
+// ND: 1 the Snowflake NDJSON instantiation (nd_row), 2 the DuckLake literal one (dl_row), so the RowBinary / protobuf kernels carry
+// no third arm
+template <bool JS, int ND = 0>
 __global__ __launch_bounds__(256) void k_rb_lens(RbJob j, unsigned long long* blk) {
   __shared__ uint64_t lds_sum[4];
   const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1780,7 +2069,8 @@ __global__ __launch_bounds__(256) void k_rb_lens(RbJob j, unsigned long long* bl
       while (next < j.qparts && i == rb_part_col(j, next)) { j.part_off[(uint64_t)(next - 1) * j.n_rows + r] = c.n; next++; }
     };
     uint32_t e;
-    if constexpr (ND) e = nd_row<JS>(j, r, c, 0, j.n_cols, mark);
+    if constexpr (ND == 2) e = dl_row<JS>(j, r, c, 0, j.n_cols, mark);
+    else if constexpr (ND == 1) e = nd_row<JS>(j, r, c, 0, j.n_cols, mark);
     else e = j.format ? pb_row<JS>(j, r, c, 0, j.n_cols, mark) : rb_row<JS>(j, r, c, 0, j.n_cols, mark);
     // first failing row in event order, rows with a date out of range before all others (bit 62 clear)
     // (and a json cell that is not JSON before those: the reference's decode fails before any sink sees a row)
@@ -1806,7 +2096,7 @@ DEV uint32_t rb_rows_per_block(uint32_t parts) { return parts == 1 ? 256u : part
 // fits kRbLds, the lanes build it in LDS and the whole workgroup stores it in 16-byte pieces; a piece that does not fit (rows of more
 // than ~500 bytes on average) is written directly as before.
 constexpr uint32_t kRbLds = 32 * 1024;
-template <bool JS, bool ND = false>
+template <bool JS, int ND = 0>
 __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   __shared__ uint4 img[kRbLds / 16 + 2];
   const uint32_t rpb = rb_rows_per_block(j.parts), part = threadIdx.x / rpb;
@@ -1823,7 +2113,8 @@ __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   if (!staged) {
     if (active) {
       RbWrite w(j.out + j.offsets[r] + po);
-      if constexpr (ND) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
+      if constexpr (ND == 2) (void)dl_row<JS>(j, r, w, c_lo, c_hi, none);
+      else if constexpr (ND == 1) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
       else if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
       w.finish();
     }
@@ -1835,7 +2126,8 @@ __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   if (active) {
     const uint32_t o = pad + (uint32_t)((uint64_t)j.offsets[r] - g0) + po;
     RbLdsWrite w((uint32_t*)img + (o >> 2), o & 3u);
-    if constexpr (ND) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
+    if constexpr (ND == 2) (void)dl_row<JS>(j, r, w, c_lo, c_hi, none);
+    else if constexpr (ND == 1) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
     else if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
     w.finish();
   }
@@ -2152,15 +2444,17 @@ void etlg_k_rowbinary(const void* jv, unsigned long long* blk, int64_t* offsets,
   const RbJob j = *(const RbJob*)jv;
   if (!j.n_rows) return;
   const uint32_t nb = (uint32_t)((j.n_rows + 255) / 256);
-  const bool nd = j.format == 2;   // (Snowflake NDJSON: kernels of their own)
+  const bool nd = j.format == 2, dl = j.format == 3;   // (Snowflake NDJSON, DuckLake literals: kernels of their own)
   if (step == 0) {
-    if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, true>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, true>), dim3(nb), dim3(256), 0, st, j, blk); }
+    if (dl) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, 2>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, 2>), dim3(nb), dim3(256), 0, st, j, blk); }
+    else if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, 1>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, 1>), dim3(nb), dim3(256), 0, st, j, blk); }
     else if (j.has_json) hipLaunchKernelGGL(k_rb_lens<true>, dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL(k_rb_lens<false>, dim3(nb), dim3(256), 0, st, j, blk);
     hipLaunchKernelGGL(k_col_len_scan, dim3(1), dim3(256), 0, st, blk, nb);
     hipLaunchKernelGGL(k_col_offsets, dim3(nb), dim3(256), 0, st, (const uint32_t*)j.lens, j.n_rows, (const unsigned long long*)blk, offsets, tot);
   } else {
     const uint32_t rpb = j.parts == 1 ? 256u : j.parts == 2 ? 128u : 64u, nbw = (uint32_t)((j.n_rows + rpb - 1) / rpb);
-    if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, true>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, true>), dim3(nbw), dim3(256), 0, st, j); }
+    if (dl) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, 2>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, 2>), dim3(nbw), dim3(256), 0, st, j); }
+    else if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, 1>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, 1>), dim3(nbw), dim3(256), 0, st, j); }
     else if (j.has_json) hipLaunchKernelGGL(k_rb_rows<true>, dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL(k_rb_rows<false>, dim3(nbw), dim3(256), 0, st, j);
   }
 }

@@ -233,6 +233,10 @@ struct ColSel {            // which events are rows of the hand-off
   const uint8_t* fixed; const uint8_t* heap;
   const uint32_t* cols;    // per replicated column: cls | .. | off_full << 16 (RbJob.cols)
   const uint32_t* kcols;   // identity | source nullable << 1 | primary key << 2 | key_index << 8 | off_key << 16 (RbJob.kcols)
+  // DuckLake rows (dl != 0; ducklake/core.rs:1824-1945, batches.rs:1128-1226): 1 the tuples the sink upserts, 2 the predicates it deletes /
+  // matches by (a row's base carries kPbKey when the image has the key layout), 3 the predicates of a table-copy batch (every row).
+  // dl_ident: the slot has identity columns (without them every predicate candidate of a WAL batch stays with the host)
+  uint32_t dl, dl_ident;
 };
 constexpr unsigned long long kPbDelete = 1ull << 63, kPbKey = 1ull << 62, kPbSecond = 1ull << 61, kPbBase = (1ull << 61) - 1;
 
@@ -280,7 +284,7 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   uint64_t n_rows;
   uint32_t n_cols, engine;         // engine: 0 MergeTree, 1 ReplacingMergeTree
   uint32_t cdc_nullable;           // bit 0 / 1: the first / second trailing CDC column is Nullable() in the destination
-  uint32_t format;                 // 0 ClickHouse RowBinary, 1 BigQuery protobuf (prost wire format), 2 Snowflake NDJSON
+  uint32_t format;                 // 0 ClickHouse RowBinary, 1 BigQuery protobuf (prost wire format), 2 Snowflake NDJSON, 3 DuckLake SQL literals
   const uint32_t* cols;            // per replicated column: cls | nullable << 8 | off_full << 16
   const uint32_t* kcols;           // per replicated column, for key images: identity | source nullable << 1 | primary key << 2 | key_index << 8 | off_key << 16
   const uint8_t* ev_flags;
@@ -293,6 +297,9 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   // whether the batch is a table copy (every row's sequence number is the zero token)
   const uint8_t* nd_keys; const uint32_t* nd_key_off;
   uint32_t nd_zero_token;
+  // format 3 (DuckLake, dl_row): nd_keys are the quoted identifiers; 0 tuples, 1 predicates over the identity columns, 2 predicates
+  // over the primary-key columns (a table-copy batch)
+  uint32_t dl_what;
 };
 
 

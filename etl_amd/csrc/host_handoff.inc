@@ -453,7 +453,7 @@ void etlg_columns_free(etlg_columns* cs) {
 
 struct NdKeys { std::vector<uint32_t> off; std::string bytes; };   // format 2: the escaped `"name":` of every column, back to back
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
-                            uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd = nullptr);
+                            uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd = nullptr, uint32_t dl_what = 0u);
 
 int32_t etlg_batch_rowbinary(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
                              uint32_t flags, etlg_rowbinary** out) {
@@ -497,9 +497,33 @@ int32_t etlg_batch_ndjson(etlg_ctx* c, etlg_batch* b, int32_t slot, const char* 
   return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, 2u, out, &k);
 }
 
-// format 0: ClickHouse RowBinary (Insert / Update / Delete rows + the engine's CDC columns); 1: BigQuery protobuf; 2: Snowflake NDJSON
+// DuckLake SQL literals (ducklake/encoding.rs:366-612, batches.rs:1229-1316): the column names are quoted here once, as
+// quote_double_identifier does (ducklake/sql.rs:10-12: '"' doubled, nothing else changed), and go up with the column words like the
+// NDJSON keys; dl_row puts ` = <literal>` / ` IS NULL` behind them.
+int32_t etlg_batch_duckdb(etlg_ctx* c, etlg_batch* b, int32_t slot, int32_t what, const char* col_names, uint32_t n_names, uint32_t flags,
+                          etlg_rowbinary** out) {
+  if (!c || !b || !out || b->ctx != c || (n_names && !col_names)) return ETLG_InvalidArgument;
+  *out = nullptr;
+  if ((uint32_t)what != ETLG_DL_TUPLES && (uint32_t)what != ETLG_DL_PREDICATES) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_duckdb: what must be ETLG_DL_TUPLES or ETLG_DL_PREDICATES");
+  if (slot < 0 || (size_t)slot >= c->slots.size()) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (n_names != c->slots[(size_t)slot]->desc.n_cols) return lib_error(c, ETLG_InvalidArgument, "DuckLake row width mismatch: one column name per replicated column");
+  NdKeys k;
+  const char* p = col_names;
+  for (uint32_t i = 0; i < n_names; i++) {
+    k.off.push_back((uint32_t)k.bytes.size());
+    k.bytes.push_back('"');
+    for (; *p; p++) { if (*p == '"') k.bytes.push_back('"'); k.bytes.push_back(*p); }
+    p++;
+    k.bytes.push_back('"');
+  }
+  k.off.push_back((uint32_t)k.bytes.size());
+  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, 3u, out, &k, (uint32_t)what);
+}
+
+// format 0: ClickHouse RowBinary (Insert / Update / Delete rows + the engine's CDC columns); 1: BigQuery protobuf; 2: Snowflake NDJSON;
+// 3: DuckLake SQL literals (dl_what: ETLG_DL_TUPLES / ETLG_DL_PREDICATES)
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
-                            uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd) {
+                            uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd, uint32_t dl_what) {
   *out = nullptr;
   if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }   // an ASYNC batch that ended in a decode error: the caller gets that error (fail-fast, as the reference), not a hand-off of the prefix
   if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, "etlg_batch_rowbinary needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
@@ -538,6 +562,8 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
       const ColPlan lp = list_plan(elem);
       host_class = lp.kind != ETLG_AK_LIST && elem != ETLG_TC_JSON;   // (text-like / numeric / timetz / bytea / json elements are written on the device too)
     }
+    // (DuckLake predicates look at the key columns only: the identity columns, for a table-copy batch the primary-key ones)
+    if (format == 3 && dl_what == ETLG_DL_PREDICATES && !(b->copy.active ? sh.pk[i] != 0 : sh.cols[i].identity != 0)) host_class = false;
     if (host_class) {
       rb->v.status = ETLG_RB_NEEDS_HOST; rb->v.host_column = i;
       *out = rb.release();
@@ -599,6 +625,10 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     q.n_events = ne; q.slot = (uint32_t)slot; q.kinds = format == 2 ? 15u : format ? 1u : ((upd_ok ? 7u : 5u) | (key_ok ? 8u : 0u)); q.host_rows = (unsigned long long*)(S + o_cnt);
     q.row_full = sh.desc.row_bytes_full; q.row_key = sh.desc.row_bytes_key;
     q.blk = (uint32_t*)S; q.nblocks = nblk; q.row_event = (uint64_t*)A; q.row_base = (uint64_t*)(S + o_base);
+    if (format == 3) {  // DuckLake: dl_selected (ducklake/core.rs:1824-1945, batches.rs:1128-1226)
+      q.dl = dl_what == ETLG_DL_TUPLES ? 1u : b->copy.active ? 3u : 2u;
+      q.dl_ident = sh.desc.n_ident != 0 ? 1u : 0u;
+    }
     if (format == 1) {  // BigQuery: inserts, updates (one or two rows) and deletes (bigquery/core.rs:978-1036); the events the reference refuses stay with the host
       q.pb = 1; q.n_cols = nc; q.identity_pk = sh.identity_type == 1 ? 1u : 0u; q.pk_comparable = pk_comparable ? 1u : 0u;
       q.fixed = bv.fixed; q.heap = bv.heap; q.cols = (const uint32_t*)(S + o_cols); q.kcols = (const uint32_t*)(S + o_cols) + nc;
@@ -624,6 +654,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     j.kcols = (const uint32_t*)(S + o_cols) + nc;
     j.nd_key_off = (const uint32_t*)(S + o_cols + (size_t)nc * 8); j.nd_keys = S + o_cols + (size_t)nc * 12 + 4;
     j.nd_zero_token = b->copy.active ? 1u : 0u;   // a table-copy batch (etlg_copy_decode): Insert rows under OffsetToken::zero (core.rs:683-699)
+    j.dl_what = dl_what == ETLG_DL_TUPLES ? 0u : b->copy.active ? 2u : 1u;   // (format 3; a copied row's predicate is over the primary key: delete_predicate_from_copy_row)
   }
   int64_t total = 0;
   if (n) {

@@ -121,6 +121,19 @@ class Batch:
             raise self.dec.last_error()
         return RowBinary(self.dec, out)
 
+    def duckdb(self, slot, names, what=abi.DL_TUPLES, on_device=False):
+        """DuckLake SQL literals of schema slot `slot`, encoded on the device (etlg_batch_duckdb): `what=abi.DL_TUPLES` one
+        "(lit, lit, ...)" per row the sink upserts, `abi.DL_PREDICATES` one `"col" = lit AND ...` per row image it deletes / matches
+        by; no separator between records. `names` as for ndjson(). Raises EtlError for ETLG_E_JSON and bad arguments;
+        `RowBinary.status == abi.RB_NEEDS_HOST` when a cell has no device encoding."""
+        raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        blob = b"".join(n + b"\0" for n in raw)
+        out = C.c_void_p()
+        rc = self.dec.L.etlg_batch_duckdb(self.dec.h, self.h, slot, what, blob, len(raw), abi.F_OUTPUT_ON_DEVICE if on_device else 0, C.byref(out))
+        if rc != abi.OK or not out:
+            raise self.dec.last_error()
+        return RowBinary(self.dec, out)
+
     def close(self):
         if self.h:
             self.dec.L.etlg_batch_free(self.h)

@@ -801,6 +801,41 @@ int32_t etlg_batch_protobuf(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slo
  * with ETLG_F_FINISH_CELLS are written from their etlg_array_hdr. Flags: ETLG_F_OUTPUT_ON_DEVICE. Every row's bytes include its '\n'. */
 int32_t etlg_batch_ndjson(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const char* col_names, uint32_t n_names, uint32_t flags,
                           etlg_rowbinary** out);
+/* DuckLake SQL literals for ONE schema slot: the text cell_to_sql_literal writes (crates/etl-destinations/src/ducklake/encoding.rs:
+ * 366-612), which every row the DuckLake sink writes goes through. `what` picks the records, in event order, at most one per event per
+ * call, with NO separator or terminator between them (row_offsets cut them):
+ *   ETLG_DL_TUPLES      one "(lit, lit, ...)" per row the sink upserts (table_row_to_sql_literal_ref: hashed into the batch identity,
+ *                       inserted as VALUES text): Insert -> the row; Update with a full new row -> the new row; a table-copy batch
+ *                       (etlg_copy_decode) -> every row. A partial Update is counted in n_host_rows; Deletes give nothing.
+ *   ETLG_DL_PREDICATES  one `"col" = lit AND "col" IS NULL` per row image the sink deletes / matches by (delete_predicate_from_row,
+ *                       batches.rs:1229-1316): Update / Delete -> from the old image (a full image: the cells at the identity columns'
+ *                       positions; a key image: its cells), identity columns in slot order; an Update without an old image -> from the
+ *                       new row's identity columns (TableMutation::Replace) unless that row is partial; a partial Update without an old
+ *                       image and a Delete without one are counted in n_host_rows; Inserts give nothing. A table-copy batch -> every
+ *                       row, over the PRIMARY-KEY columns (etlg_col.primary_key). A NULL key cell is `"col" IS NULL`. A slot without
+ *                       identity columns: every Update / Delete is counted in n_host_rows (the host raises "DuckLake delete requires a
+ *                       replica identity"); a copy batch without primary-key columns gives empty records.
+ * col_names: as for etlg_batch_ndjson (n_names must be the slot's n_cols, ETLG_InvalidArgument otherwise; so is an unknown `what`).
+ * Names are quoted like quote_double_identifier (ducklake/sql.rs:10-12): '"' doubled, nothing else changed.
+ * Values: NULL; TRUE / FALSE; integers in decimal; float8 as Rust's f64 Display (shortest digits, positional, never an exponent: 1,
+ * -0, 0.1, 1e21 as 1 and 21 zeros; up to 327 bytes), float4 widened first (0.1f32 -> 0.10000000149011612), NaN / +-inf as
+ * CAST('NaN' AS DOUBLE) / CAST('Infinity' AS DOUBLE) / CAST('-Infinity' AS DOUBLE) (AS FLOAT for float4) — values, not errors;
+ * text-like cells, numeric and timetz Display through quote_literal; DATE '%Y-%m-%d'; TIME '%H:%M:%S%.6f';
+ * TIMESTAMP '%Y-%m-%d %H:%M:%S%.6f'; TIMESTAMPTZ '...%.6f+00:00'; CAST('<hyphenated lower-case uuid>' AS UUID);
+ * CAST(<quote_literal(serde_json Display)> AS JSON); from_hex('<UPPER-case hex>'); arrays [e, e, NULL] of the same ("[]" when empty),
+ * from the source literal or from the etlg_array_hdr ETLG_F_FINISH_CELLS leaves.
+ * quote_literal is pg_escape 0.1.1, RESTATED FROM THE CRATE'S DOCUMENTATION — its source is not vendored with the reference and the
+ * reference's tests pin only the plain arm ('alice'): a ' is doubled; a text that holds a backslash has every backslash doubled and is
+ * prefixed with a space and E (a\b -> " E'a\\b'" in C notation); otherwise plain '...'. The quote doubling and the backslash arm are
+ * UNPINNED (one function on each side: dl_quote in columns.hip, quote_literal in tests/ducklake_literals.py).
+ * Errors: a json cell or element that is not one JSON value fails the call with ETLG_E_JSON at its event before anything else; the sink
+ * has no encoding error on this path. A DEFERRED scalar, an array literal the walkers do not take apart and json beyond json_display's
+ * limits give status ETLG_RB_NEEDS_HOST with the first such event and column in event order; for ETLG_DL_PREDICATES only the key
+ * columns are looked at. Flags: ETLG_F_OUTPUT_ON_DEVICE. The result is an etlg_rowbinary (same view). */
+#define ETLG_DL_TUPLES 0u
+#define ETLG_DL_PREDICATES 1u
+int32_t etlg_batch_duckdb(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, int32_t what, const char* col_names, uint32_t n_names,
+                          uint32_t flags, etlg_rowbinary** out);
 int32_t etlg_rowbinary_view_get(const etlg_rowbinary* rb, etlg_rowbinary_view* out);
 void etlg_rowbinary_free(etlg_rowbinary* rb);
 
