@@ -92,6 +92,7 @@ pub const ETLG_F_OUTPUT_ON_DEVICE: u32 = 1 << 1;
 pub const ETLG_F_NO_CONTROL: u32 = 1 << 2;
 pub const ETLG_F_ASYNC: u32 = 1 << 3;
 pub const ETLG_F_FINISH_CELLS: u32 = 1 << 4;
+pub const ETLG_F_CHECK_CELLS: u32 = 1 << 5;
 pub const ETLG_FINISH_ARRAYS: u32 = 1;
 pub const ETLG_FINISH_FLOATS: u32 = 2;
 

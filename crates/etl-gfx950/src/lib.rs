@@ -53,6 +53,7 @@ fn kind_of(k: i32) -> ErrorKind {
 
 pub struct GpuDecoder {
     ctx: *mut etlg_ctx,
+    check_cells: bool,
 }
 
 // One context per apply-loop stream, used from one task at a time (`&mut self`), like the loop's own state.
@@ -67,7 +68,7 @@ impl GpuDecoder {
             return Err(etl_error!(ErrorKind::ConfigError, "MI355X decode context could not be created", why));
         }
         debug_assert_eq!(unsafe { etlg_abi_version() }, ETLG_ABI_VERSION);
-        Ok(Self { ctx })
+        Ok(Self { ctx, check_cells: false })
     }
 
     fn last_error(&self) -> EtlError {
@@ -114,6 +115,14 @@ impl GpuDecoder {
         unsafe { etlg_ctx_set_worker(self.ctx, kind, id, bootstrap_snapshot_lsn) };
     }
 
+    /// `ETLG_F_CHECK_CELLS` for every batch `decode_async` enqueues (default off: the crate behaves as before). With it a json /
+    /// jsonb cell that is not one JSON value and an array literal the reference rejects are decode errors at their frame, like every
+    /// other cell error — which is what makes `finish`'s "events BEFORE the failing frame" promise hold for json and array errors.
+    /// Without it such a cell comes back as deferred text, `materialize::events` finds it, and the whole batch's events are lost.
+    pub fn set_check_cells(&mut self, on: bool) {
+        self.check_cells = on;
+    }
+
     /// The raw context, for `StagingBatcher::new` (its buffers are pinned through the context's device).
     pub fn raw(&self) -> *mut etlg_ctx {
         self.ctx
@@ -126,7 +135,7 @@ impl GpuDecoder {
     pub fn decode_async(&mut self, staged: StagedBatch) -> Result<InFlight, (StagedBatch, EtlError)> {
         let mut batch = ptr::null_mut();
         // (ETLG_F_FINISH_CELLS: arrays arrive typed and floats exact — materialize.rs then parses no array text on the host)
-        let flags = ETLG_F_ASYNC | ETLG_F_OUTPUT_ON_DEVICE | ETLG_F_FINISH_CELLS | if staged.control_free { ETLG_F_NO_CONTROL } else { 0 };
+        let flags = ETLG_F_ASYNC | ETLG_F_OUTPUT_ON_DEVICE | ETLG_F_FINISH_CELLS | if staged.control_free { ETLG_F_NO_CONTROL } else { 0 } | if self.check_cells { ETLG_F_CHECK_CELLS } else { 0 };
         let rc = unsafe { etlg_decode(self.ctx, staged.frames_ptr(), staged.len, staged.offsets_ptr(), staged.nframes, flags, &mut batch) };
         if batch.is_null() {
             let _ = rc;

@@ -55,6 +55,7 @@ F_OUTPUT_ON_DEVICE = 1 << 1
 F_NO_CONTROL = 1 << 2
 F_ASYNC = 1 << 3
 F_FINISH_CELLS = 1 << 4
+F_CHECK_CELLS = 1 << 5   # json / array cells the reference rejects are decode errors at their frame (include/etlg.h)
 FINISH_ARRAYS, FINISH_FLOATS = 1, 2
 
 OLD_NONE, OLD_FULL, OLD_KEY, FLAG_PARTIAL = 0, 1, 2, 4

@@ -3,6 +3,7 @@
 libetlg_synth.so (synthetic WAL generator, plain g++)."""
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -17,7 +18,7 @@ SOURCES = ["kernels.hip", "fused.hip", "cells.hip", "rows.hip", "plan.hip", "sca
 OPT = {"fused.hip": "-Os", "cells.hip": "-Os"}
 DEFS = {}   # no per-source feature flags: one code path per kernel
 # what every object depends on beside its own source (the shared headers); host.cpp also on its parts
-COMMON = ["../build.py", "dev_types.h", "codec.hip.h", "lookback.hip.h", "utf8_swar.h", "float_fast.h", "float_slow.h", "pow5_table.h", "float_json.h", "ryu_table.h", "float_display.h", os.path.join("..", "..", "include", "etlg.h")]
+COMMON = ["../build.py", "dev_types.h", "codec.hip.h", "cellparse.hip.h", "check.hip.h", "lookback.hip.h", "utf8_swar.h", "float_fast.h", "float_slow.h", "pow5_table.h", "float_json.h", "ryu_table.h", "float_display.h", os.path.join("..", "..", "include", "etlg.h")]
 EXTRA = {"fused.hip": ["fixed_tile.hip.h"], "host.cpp": ["host_state.h", "host_control.inc", "host_handoff.inc", "host_orchestrate.inc"]}
 DEPS = SOURCES + COMMON + [d for v in EXTRA.values() for d in v]   # (the library as a whole)
 
@@ -33,8 +34,9 @@ def build_native(force=False, verbose=False):
     deps = [os.path.join(CSRC, d) for d in DEPS]
     if not force and not _stale(LIB, deps):
         return LIB
-    objs = []
-    for src in SOURCES:
+    objs = [os.path.join(CSRC, os.path.splitext(src)[0] + ".o") for src in SOURCES]
+
+    def compile_one(src):
         obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
         if force or _stale(obj, [os.path.join(CSRC, d) for d in [src] + COMMON + EXTRA.get(src, [])]):
             cmd = [HIPCC, "--offload-arch=gfx950", OPT.get(src, "-O3"), "-std=c++17", "-fPIC", "-Wall",
@@ -44,7 +46,12 @@ def build_native(force=False, verbose=False):
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
-        objs.append(obj)
+
+    # the sources are independent translation units: compiled side by side, the longest (columns.hip: most of the build's time) first,
+    # so that the build takes as long as that one source instead of the sum of all
+    jobs = max(1, min(len(SOURCES), int(os.environ.get("MAX_JOBS", "0") or 0) or (os.cpu_count() or 1), 16))
+    with ThreadPoolExecutor(jobs) as ex:
+        list(ex.map(compile_one, sorted(SOURCES, key=lambda s: s != "columns.hip")))
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd))

@@ -1376,6 +1376,13 @@ DEV uint32_t get_state(const u8* row, uint32_t i) { return (((const uint32_t*)ro
 // A single body (one inlined copy of the value codec) serves all three.
 enum : uint32_t { ROW_FULL = 0, ROW_KEY = 1, ROW_UPDATE = 2 };
 
+// CHECK (ETLG_F_CHECK_CELLS, the multi-pass kernels only: kernels.hip): a json / jsonb / array cell is validated where it is deferred,
+// behind its UTF-8 check, with the code parse_cell_from_postgres_text would raise (cell_text_error, cellparse.hip.h). A compile-time
+// choice: the single-pass kernels instantiate CHECK = false and carry no trace of it.
+DEV_NOINLINE uint32_t cell_text_error(uint32_t cls, uint32_t elem, const u8* s, uint32_t n);
+// element class per DevCol, stored directly behind the DevCol records in GLOBAL memory (build_side_inputs, host_orchestrate.inc)
+DEV const u8* chk_elem_table(const DecParams& p) { return (const u8*)(p.cols + p.n_cols); }
+template <bool CHECK = false>
 DEV uint32_t write_row(const DecParams& p, const DevSlot& s, uint32_t mode, const u8* tuple, uint32_t ncells, u8* row,
                        uint32_t old_kind, const u8* old_row, uint32_t& hcur, bool& partial, bool over = false) {
   bool dense = false;
@@ -1428,6 +1435,12 @@ DEV uint32_t write_row(const DecParams& p, const DevSlot& s, uint32_t mode, cons
     } else if (t == 't') {
       const uint32_t err = decode_text_cell(col.cls, d, len, slot, p.heap, hcur, st, over);
       if (err) return err;
+      if constexpr (CHECK) {
+        if (class_always_deferred(col.cls)) {
+          const uint32_t ce = cell_text_error(col.cls, chk_elem_table(p)[s.cols_base + ci], d, len);
+          if (ce && ce < 0x100u) return ce;   // (0x100, ARR_HOST: a lane cannot decide — the cell stays DEFERRED, include/etlg.h)
+        }
+      }
     } else {
       return ETLG_E_BINARY_FORMAT;
     }
@@ -1606,6 +1619,7 @@ DEV void txn_check_frame(const DecParams& p, const FrameView& v, const TxnCtx& t
 // Decodes one emitting frame into the arena at (ev_idx, fx_off, hp_off).
 // `pu` (optional): the same parameters with GLOBAL side-table pointers, enabling the
 // wave-uniform INSERT path; `over`: the frame bytes may be over-read by up to 7 bytes.
+template <bool CHECK = false>
 DEV void write_frame(const DecParams& p, const FrameView& v, const TxnCtx& tx, const RowMsg& m, int row_slot,
                      uint64_t ev_idx, uint64_t fx_off, uint64_t hp_off, const DecParams* pu = nullptr, bool over = false) {
   const uint32_t f = v.f, tag = v.tag;
@@ -1669,7 +1683,7 @@ DEV void write_frame(const DecParams& p, const FrameView& v, const TxnCtx& tx, c
           const bool is_new = img == 1;
           const uint32_t mode = is_new ? (tag == 'U' ? (uint32_t)ROW_UPDATE : (uint32_t)ROW_FULL)
                                        : (m.old_kind == ETLG_OLD_KEY ? (uint32_t)ROW_KEY : (uint32_t)ROW_FULL);
-          err = write_row(p, s, mode, is_new ? m.new_t : m.old_t, is_new ? m.new_n : m.old_n,
+          err = write_row<CHECK>(p, s, mode, is_new ? m.new_t : m.old_t, is_new ? m.new_n : m.old_n,
                           is_new ? body + old_sz : body, m.old_kind, body, hcur, partial, over);
         }
       }

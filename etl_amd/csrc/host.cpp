@@ -42,7 +42,18 @@ void launch_raw(etlg_ctx* c, int which, const DecParams& p) {
   else if (which == kCells) etlg_k_launch_cells(&p, &c->fq, c->stream);
   else if (which == kCopyCells) etlg_k_launch_copy_cells(&p, &c->fq, c->stream);
   else if (which == kRows) etlg_k_launch_rows(&p, &c->fq, c->stream);
+  else if (which == kWriteChk) etlg_k_launch(7, &p, c->stream);
   else etlg_k_launch(which, &p, c->stream);
+}
+
+// ETLG_F_CHECK_CELLS behind a single-pass kernel: k_chk_cells over the arena it wrote, unless no slot the batch can decode against has
+// a json / jsonb / array column (the side inputs know: SideSet::chk_any). The event count is read on the device; p.nframes bounds it.
+void launch_chk_cells(etlg_ctx* c, const etlg_batch* b) {
+  if (!b->check_cells || !b->side || !b->side->chk_any || !b->params.nframes) return;
+  ProfRec r; r.which = kChkCells;
+  if (c->prof) { (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b); (void)hipEventRecord(r.a, c->stream); }
+  etlg_k_launch_chk_cells(&b->params, b->side->chk_maxc, b->params.nframes, c->stream);
+  if (c->prof) { (void)hipEventRecord(r.b, c->stream); c->prof_recs.push_back(r); }
 }
 
 void launch(etlg_ctx* c, int which, const DecParams& p) {
@@ -106,7 +117,7 @@ void launch_multipass(etlg_ctx* c, const DecParams& p, bool classify_done) {
   if (!classify_done) { if (p.nframes) launch(c, 0, p); launch(c, 1, p); }
   if (p.nframes) launch(c, 3, p);
   launch(c, 4, p);
-  if (p.nframes) launch(c, 5, p);
+  if (p.nframes) launch(c, (p.flags & 64u) ? kWriteChk : 5, p);   // (flags bit 6: ETLG_F_CHECK_CELLS)
   launch(c, 6, p);
   if (c->mp_tail) { (void)hipEventRecord(c->mp_tail, c->stream); c->mp_tail_set = true; }   // a pre-pass that runs ahead waits for it (shared scratch)
 }
@@ -498,7 +509,7 @@ int32_t etlg_ctx_profile_read(etlg_ctx* c, etlg_kernel_stat* out, uint32_t cap, 
   }
   c->prof_recs.clear();
   uint32_t k = 0;
-  for (int i = 0; i < kProfSlots && k < cap; i++) { out[k].name = i == kPlan ? "k_plan" : i == kPlanPre ? "k_plan_pre" : i == kFused ? "k_fused" : i == kCells ? "k_cells" : i == kBounds ? "k_bounds" : i == kCopy ? "k_copy_frames" : i == kCopyCells ? "k_copy_cells" : i == kRows ? "k_rows" : etlg_k_name(i); out[k].launches = c->prof_n[i]; out[k].total_ms = c->prof_ms[i]; k++; }
+  for (int i = 0; i < kProfSlots && k < cap; i++) { out[k].name = i == kPlan ? "k_plan" : i == kPlanPre ? "k_plan_pre" : i == kFused ? "k_fused" : i == kCells ? "k_cells" : i == kBounds ? "k_bounds" : i == kCopy ? "k_copy_frames" : i == kCopyCells ? "k_copy_cells" : i == kRows ? "k_rows" : i == kWriteChk ? "k_write_chk" : i == kChkCells ? "k_chk_cells" : etlg_k_name(i); out[k].launches = c->prof_n[i]; out[k].total_ms = c->prof_ms[i]; k++; }
   *n = k;
   return ETLG_OK;
 }
@@ -862,7 +873,7 @@ int32_t etlg_copy_decode(etlg_ctx* c, int32_t schema_slot, const uint8_t* buf, s
   const bool sv_in = c->in_txn; const uint64_t sv_lsn = c->final_lsn, sv_ord = c->next_ord;
   c->in_txn = true; c->final_lsn = 0; c->next_ord = 0;
   c->copy = j;
-  const uint32_t dflags = (flags & (ETLG_F_OUTPUT_ON_DEVICE | ETLG_F_FINISH_CELLS)) | ETLG_F_INPUT_ON_DEVICE | ETLG_F_NO_CONTROL | (j.async ? (uint32_t)ETLG_F_ASYNC : 0u);
+  const uint32_t dflags = (flags & (ETLG_F_OUTPUT_ON_DEVICE | ETLG_F_FINISH_CELLS | ETLG_F_CHECK_CELLS)) | ETLG_F_INPUT_ON_DEVICE | ETLG_F_NO_CONTROL | (j.async ? (uint32_t)ETLG_F_ASYNC : 0u);
   const int32_t rc = j.direct ? etlg_decode(c, j.d_rows, len, j.d_row_offs, nrows, dflags, out)
                               : etlg_decode(c, j.d_out, (size_t)syn_len, j.d_out_offs, nrows, dflags, out);
   j.stage_blk = c->copy.stage_blk; j.h2d_done = c->copy.h2d_done;   // (nullptr once the batch has adopted them: etlg_decode)
@@ -969,6 +980,7 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
   BatchGuard guard{b};
   b->user_no_ctrl = no_ctrl; b->out_dev = out_dev; b->in_dev = in_dev; b->scan = scan; b->len = len;
   b->finish_what = (flags & ETLG_F_FINISH_CELLS) ? (uint32_t)(ETLG_FINISH_ARRAYS | ETLG_FINISH_FLOATS) : 0u;
+  b->check_cells = (flags & ETLG_F_CHECK_CELLS) != 0;
   b->stage_blk = stage_blk; b->stage_cap = stage_cap; b->h2d_done = h2d_done;   // the batch owns them from here (etlg_batch_free)
   stage_blk = nullptr; h2d_done = nullptr;
   if (c->copy.active && c->copy.stage_blk) {   // an ASYNC table-copy batch whose rows were staged by etlg_copy_decode: likewise
@@ -1170,6 +1182,7 @@ int32_t decode_tail(etlg_ctx* c, etlg_batch* b, size_t nframes, bool async, etlg
   p.nframes = nf; p.nblocks = (nf + kBlock - 1) / kBlock; p.in_len = len;
   p.worker_kind = (uint32_t)c->worker; p.sync_table = c->sync_table;
   p.flags = c->fused_dbg & 0xF00u;  // profiling ablations (results are wrong)
+  if (b->check_cells) p.flags |= 64u;   // ETLG_F_CHECK_CELLS: the multi-pass kernels validate json / array cells (k_write_chk)
   p.copy_slot = -1;
   if (c->copy.active) { p.flags |= 2u; p.copy_slot = c->copy.slot; b->copy = c->copy; }
   p.host_err_frame = 0xFFFFFFFFu;

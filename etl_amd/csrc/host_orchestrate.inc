@@ -172,8 +172,23 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
     ss->o_epochs = al(tv.size() * sizeof(DevTable) + 16);
     ss->o_slots = ss->o_epochs + al(ev.size() * sizeof(DevEpoch) + 16);
     ss->o_cols = ss->o_slots + al(ds.size() * sizeof(DevSlot) + 16);
-    ss->o_ptabs = ss->o_cols + al(dc.size() * sizeof(DevCol) + 16);
+    ss->o_ptabs = ss->o_cols + al(dc.size() * (sizeof(DevCol) + 1) + 16);   // (the records, then one element-class byte per record)
     ss->o_pcols = ss->o_ptabs + al(pt.size() * sizeof(PlanTab) + 16);
+    // ETLG_F_CHECK_CELLS: the element class of every array column, in DevCol order (build_slots pushes no column for a dead slot),
+    // stored directly behind the DevCol records (chk_elem_table, codec.hip.h)
+    std::vector<uint8_t> ce;
+    ss->chk_any = false; ss->chk_maxc = 0;
+    for (int32_t li : live) {
+      if (li < 0 || (size_t)li >= c->slots.size()) continue;
+      const SlotHost& sh = *c->slots[(size_t)li];
+      bool any = false;
+      for (const etlg_slot_col& sc : sh.cols) {
+        ce.push_back(sc.type_class == ETLG_TC_ARRAY ? (uint8_t)etlg_array_elem_class(sc.type_oid) : (uint8_t)0);
+        any |= sc.type_class == ETLG_TC_ARRAY || sc.type_class == ETLG_TC_JSON;
+      }
+      if (any) { ss->chk_any = true; ss->chk_maxc = std::max<uint32_t>(ss->chk_maxc, sh.desc.n_cols); }
+    }
+    if (ce.size() != dc.size()) return lib_error(c, ETLG_InvalidState, "side inputs: element classes and columns differ in number");
     const size_t total = ss->o_pcols + al(pc.size() * 4 + 16);
     if (total > ss->h_cap) {
       if (ss->h) (void)hipHostFree(ss->h);
@@ -189,6 +204,7 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
     if (!dc.empty()) memcpy(ss->h + ss->o_cols, dc.data(), dc.size() * sizeof(DevCol));
     if (!pt.empty()) memcpy(ss->h + ss->o_ptabs, pt.data(), pt.size() * sizeof(PlanTab));
     if (!pc.empty()) memcpy(ss->h + ss->o_pcols, pc.data(), pc.size() * 4);
+    if (!ce.empty()) memcpy(ss->h + ss->o_cols + dc.size() * sizeof(DevCol), ce.data(), ce.size());
     HIPCHK(c, hipMemcpyAsync(ss->dev.p, ss->h, total, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(ss->ready, s));
     ss->synced = 1u << (s == c->stream2 && c->stream2 ? 1 : 0);
@@ -509,6 +525,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
         if (const char* ov = getenv("ETLG_ROWS_LDS")) q.lds_bytes = (uint32_t)atoi(ov);   // (experiments)
         if (getenv("ETLG_ROWS_TRACE")) fprintf(stderr, "[rows] cf %u maxc %u maxh %u lds %u (static %llu) side %u tables %llu need %llu (window min %llu, avg frame %llu) -> %d workgroups per CU by the runtime's count, %llu planned\n", cf, widest, maxh, q.lds_bytes, (unsigned long long)stat, q.side_bytes, (unsigned long long)tabb, (unsigned long long)need, (unsigned long long)c->rows_win_min, (unsigned long long)avg, etlg_k_rows_occupancy(q.lds_bytes), (unsigned long long)wgs);
         launch(c, kRows, p);
+        launch_chk_cells(c, b);
         b->used_fused = true; b->used_cells = false; b->used_rows = true;
         return ETLG_OK;
       }
@@ -545,6 +562,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
   q.d_clear = (unsigned long long*)doth; q.clear_words = (uint32_t)(dbytes / 8);
   q.copy_rel = direct ? b->copy.rel_id : 0u;
   launch(c, direct ? kCopyCells : use_cells ? kCells : kFused, p);
+  launch_chk_cells(c, b);
   b->used_fused = true;
   b->used_cells = use_cells;
   return ETLG_OK;

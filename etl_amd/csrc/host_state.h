@@ -84,6 +84,7 @@ extern "C" uint32_t etlg_k_rows_max_heap_cols(void);
 extern "C" uint32_t etlg_k_cells_lds_floor(uint32_t maxc);
 extern "C" uint32_t etlg_k_cells_static_lds(uint32_t maxc);
 extern "C" uint32_t etlg_k_copy_cells_static_lds(uint32_t maxc);
+extern "C" void etlg_k_launch_chk_cells(const DecParams* p, uint32_t maxc, uint32_t ev_bound, hipStream_t s);
 
 constexpr int kFused = 7;  // profiling slot of the fused kernel
 constexpr int kCells = 8;  // ... of the column-parallel kernel (cells.hip)
@@ -93,7 +94,9 @@ constexpr int kPlan = 11;  // ... of the fixed-width plan (plan.hip)
 constexpr int kCopyCells = 12;  // ... of the table-copy rows -> arena kernel (cells.hip, k_cells<.., COPYK>)
 constexpr int kPlanPre = 13;    // ... of the plan's sidecar pre-pass (plan.hip, k_plan_pre)
 constexpr int kRows = 14;       // ... of the row-synchronous kernel (rows.hip)
-constexpr int kProfSlots = 15;
+constexpr int kWriteChk = 15;   // ... of k_write with ETLG_F_CHECK_CELLS (kernels.hip, k_write_chk)
+constexpr int kChkCells = 16;   // ... of the cell check behind a single-pass kernel (check.hip.h, k_chk_cells)
+constexpr int kProfSlots = 17;
 
 namespace {
 
@@ -261,6 +264,8 @@ struct SideSet {
   DevBuf dev;
   uint8_t* h = nullptr; size_t h_cap = 0;
   size_t o_tables = 0, o_epochs = 0, o_slots = 0, o_cols = 0, o_ptabs = 0, o_pcols = 0;
+  bool chk_any = false;   // a live slot has a json / jsonb / array column (ETLG_F_CHECK_CELLS has something to look at)
+  uint32_t chk_maxc = 0;  // ... and the widest such slot, in columns
   uint32_t n_slots = 0, n_cols = 0;
   int users = 0;
   hipEvent_t ready = nullptr;   // recorded behind the upload
@@ -442,6 +447,7 @@ struct etlg_batch {
   bool deferred = false;        // ASYNC without a sidecar: scan in flight, decode not enqueued yet (etlg_ctx::deferred)
   const uint8_t* d_in_ptr = nullptr; const uint32_t* user_offs = nullptr;
   DevBuf* scan_offs = nullptr;  // ASYNC without a sidecar: the batch's own offsets (from the context's pool)
+  bool check_cells = false;     // ETLG_F_CHECK_CELLS: json / array cells the reference rejects are decode errors at their frame
   uint32_t finish_what = 0;     // ETLG_F_FINISH_CELLS: the ETLG_FINISH_* bits finish_batch applies before the batch is handed over
   bool scan_chained = false;    // ... and its decode (the fixed-width plan) was enqueued BEHIND the scan, with the frame count read on the device (DecParams.nframes_dev)
   uint32_t* d_scan_res = nullptr;   // the scan's result words, behind the batch's offsets

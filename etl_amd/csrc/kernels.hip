@@ -23,6 +23,7 @@
 // Integer / byte work only: no MFMA. All inter-workgroup data flows through
 // kernel boundaries (no in-kernel hand-offs), so there are no spin waits.
 #include "codec.hip.h"
+#include "cellparse.hip.h"   // ETLG_F_CHECK_CELLS: k_write_chk validates json / array cells where it defers them
 
 namespace etlg {
 
@@ -201,7 +202,8 @@ __global__ __launch_bounds__(kBlock) void k_scan_out(DecParams p) {
   if (threadIdx.x == 0) { p.blk_ev[p.nblocks] = (uint32_t)run_ev; p.blk_fixed[p.nblocks] = run_fx; p.blk_heap[p.nblocks] = run_hp; }
 }
 
-__global__ __launch_bounds__(kBlock) void k_write(DecParams p) {
+template <bool CHECK>
+DEV void write_body(const DecParams& p) {
   __shared__ uint32_t lds[8];
   __shared__ uint64_t lds64[4];
   const uint32_t f = blockIdx.x * kBlock + threadIdx.x;
@@ -221,8 +223,12 @@ __global__ __launch_bounds__(kBlock) void k_write(DecParams p) {
   FrameView v{f, tag, p.in + p.offs[f], p.in + p.offs[f + 1]};
   RowMsg m;
   (void)frame_structure(v, m);
-  write_frame(p, v, tx, m, -1, ev_idx, fx_off, hp_off);
+  write_frame<CHECK>(p, v, tx, m, -1, ev_idx, fx_off, hp_off);
 }
+__global__ __launch_bounds__(kBlock) void k_write(DecParams p) { write_body<false>(p); }
+// ETLG_F_CHECK_CELLS: the same pass with the json / array cells validated where they are deferred (write_row<true>, codec.hip.h), so
+// that a cell the reference rejects ends the batch at its frame, in the reference's order (old image before new image, column order)
+__global__ __launch_bounds__(kBlock) void k_write_chk(DecParams p) { write_body<true>(p); }
 
 // --------------------------------------------------------------- k_finalize
 // Single workgroup. Cuts the batch at the first failing frame, computes the
@@ -341,7 +347,7 @@ extern "C" {
 
 using namespace etlg;
 
-// which: 0 classify, 1 scan_txn, 2 ctrl_list, 3 size, 4 scan_out, 5 write, 6 finalize
+// which: 0 classify, 1 scan_txn, 2 ctrl_list, 3 size, 4 scan_out, 5 write, 6 finalize, 7 write with ETLG_F_CHECK_CELLS
 void etlg_k_launch(int which, const DecParams* p, hipStream_t s) {
   switch (which) {
     case 0: hipLaunchKernelGGL(k_classify, dim3(p->nblocks), dim3(kBlock), 0, s, *p); break;
@@ -351,6 +357,7 @@ void etlg_k_launch(int which, const DecParams* p, hipStream_t s) {
     case 4: hipLaunchKernelGGL(k_scan_out, dim3(1), dim3(kBlock), 0, s, *p); break;
     case 5: hipLaunchKernelGGL(k_write, dim3(p->nblocks), dim3(kBlock), 0, s, *p); break;
     case 6: hipLaunchKernelGGL(k_finalize, dim3(1), dim3(kBlock), 0, s, *p); break;
+    case 7: hipLaunchKernelGGL(k_write_chk, dim3(p->nblocks), dim3(kBlock), 0, s, *p); break;
     default: break;
   }
 }
@@ -394,8 +401,8 @@ void etlg_k_ctl_gather(const uint8_t* in, const uint32_t* offs, const uint32_t* 
 }
 
 const char* etlg_k_name(int which) {
-  static const char* names[] = {"k_classify", "k_scan_txn", "k_ctrl_list", "k_size", "k_scan_out", "k_write", "k_finalize"};
-  return which >= 0 && which < 7 ? names[which] : "?";
+  static const char* names[] = {"k_classify", "k_scan_txn", "k_ctrl_list", "k_size", "k_scan_out", "k_write", "k_finalize", "k_write_chk"};
+  return which >= 0 && which < 8 ? names[which] : "?";
 }
 
 }  // extern "C"

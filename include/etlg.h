@@ -284,10 +284,16 @@ enum {
                                         not touch buf / frame_offsets until the batch is synced (two staging buffers in
                                         rotation: fill one while the other is in flight). Without a sidecar a host-input
                                         batch is decoded synchronously, as before */
-  ETLG_F_FINISH_CELLS = 1u << 4      /* round 6: run etlg_batch_finish_cells(ETLG_FINISH_ARRAYS | ETLG_FINISH_FLOATS) on the batch
+  ETLG_F_FINISH_CELLS = 1u << 4,     /* round 6: run etlg_batch_finish_cells(ETLG_FINISH_ARRAYS | ETLG_FINISH_FLOATS) on the batch
                                         before it is handed over (an ASYNC batch: when it is synced; a host-output batch: before
                                         the download): array cells come back TYPED (etlg_array_hdr entries) and no float cell
                                         comes back DEFERRED. Also honoured by etlg_copy_decode */
+  ETLG_F_CHECK_CELLS = 1u << 5       /* json / jsonb cells that are not one JSON value and array literals the reference rejects are
+                                        decode errors AT THEIR FRAME, as in the reference (parse_cell_from_postgres_text validates
+                                        while it decodes the frame, codec/text.rs:126-134, 163-312; the apply loop stops there,
+                                        apply.rs:2475-2481), instead of DEFERRED text whose error the next reader of the cell finds.
+                                        The contract is with the DEFERRED rules below. etlg_decode and etlg_copy_decode, every
+                                        combination of the other flags. Without it nothing changes */
 };
 
 /* Pinned (page-locked) host memory for the staging buffers of a host that feeds etlg_decode with ETLG_F_ASYNC: what the
@@ -445,6 +451,31 @@ enum {
  *    DEFERRED. The rule is etl_amd/csrc/float_fast.h; the oracle evaluates the same header for the
  *    DECISION and glibc strtod / strtof for the value. Malformed text is the reference's
  *    "Float parsing failed". */
+
+/* ---- ETLG_F_CHECK_CELLS: the errors of DEFERRED json / array text, raised by the decode.
+ *
+ *  1. The first frame (table copy: row) that holds, in a row image the reference parses, a json / jsonb cell that is not one JSON
+ *     value (serde_json::from_str: ETLG_E_JSON) or an array literal the reference rejects — ETLG_E_ARRAY_DIMS / _MULTIDIM / _SHORT /
+ *     _BRACES / _QUOTE / _ESCAPE, an element its type's parser refuses (that parser's own code: ETLG_E_INT, ETLG_E_BOOL,
+ *     ETLG_E_DATETIME ...), ETLG_E_BYTEA for a bytea[] element, ETLG_E_JSON for a json[] / jsonb[] element — ends the batch exactly
+ *     like any other decode error: the same etlg_error (kind, code, description, frame_index), n_frames = that frame, every event
+ *     before it in the arena, the carried transaction state as of that frame, control-plane effects of later frames rolled back.
+ *  2. The order is the reference's. Between frames the earliest frame wins, whatever the kind of error. Inside a frame the old image
+ *     is read before the new one and cells in column order: an invalid json in column 1 beats a malformed int4 in column 3 of the
+ *     same row, and the other way round; invalid UTF-8 inside a json cell is ETLG_E_UTF8 (str::from_utf8 precedes the type switch).
+ *     Inside an array literal an element is parsed where it ends, so a bad element beats a shape error behind it. Cells the
+ *     reference never parses raise nothing: frames should_apply_changes skips, the non-identity positions of a full-width key
+ *     tuple, unchanged-toast ('u') cells that take the old image's value.
+ *  3. What a lane of the device cannot decide is NOT an error and stays DEFERRED as without the flag: an array literal with a
+ *     non-text element of more than 40 characters (the reference accepts any number of leading zeros), a json[] / jsonb[] element
+ *     of more than 256 unescaped bytes. These are the only cells of a batch that came back ETLG_OK under the flag whose host parse
+ *     can still fail.
+ *  4. Valid cells stay DEFERRED source text: the flag changes no byte of an error-free batch's arena. With ETLG_F_FINISH_CELLS as
+ *     well, the finish pass runs on the (possibly cut) batch as it does after any other error.
+ *  5. Cost: one more kernel (k_chk_cells) behind the single-pass decode kernel of a batch that can decode against a schema with a
+ *     json / jsonb / array column, none otherwise; no host stop, an ASYNC call returns as fast as without the flag. A batch that
+ *     holds such a cell is decoded a second time by the multi-pass kernels (like a batch with any other error), which find the
+ *     exact cut. */
 
 /* ---- the finish pass (round 6): typed arrays and exact floats in the arena itself.
  *
