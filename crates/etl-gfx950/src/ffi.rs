@@ -247,6 +247,14 @@ pub struct etlg_array_hdr {
 }
 
 #[repr(C)]
+pub struct etlg_changelog_info {
+    pub n_host_rows: u64,
+    pub host_event: u64,
+    pub host_reason: u32,
+    pub n_data_cols: u32,
+}
+
+#[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
     pub arrays_typed: u64,
@@ -269,6 +277,9 @@ pub const ETLG_ROWS_INSERT: u32 = 1;
 pub const ETLG_ROWS_UPDATE: u32 = 2;
 pub const ETLG_ROWS_PARSE_ARRAYS: u32 = 4;
 pub const ETLG_ROWS_FORMAT_JSON: u32 = 8;
+pub const ETLG_ICE_PARTIAL_UPDATE: u32 = 1;
+pub const ETLG_ICE_KEY_ONLY_DELETE: u32 = 2;
+pub const ETLG_ICE_DELETE_WITHOUT_OLD_ROW: u32 = 3;
 pub const ETLG_CH_MERGE_TREE: i32 = 0;
 pub const ETLG_CH_REPLACING_MERGE_TREE: i32 = 1;
 pub const ETLG_RB_OK: u32 = 0;
@@ -393,6 +404,8 @@ extern "C" {
     pub fn etlg_batch_columns(ctx: *mut etlg_ctx, batch: *mut etlg_batch, schema_slot: i32, row_kinds: u32, flags: u32, out: *mut *mut etlg_columns) -> i32;
     pub fn etlg_columns_view_get(cols: *const etlg_columns, out: *mut etlg_columns_view) -> i32;
     pub fn etlg_columns_free(cols: *mut etlg_columns);
+    pub fn etlg_batch_iceberg(ctx: *mut etlg_ctx, batch: *mut etlg_batch, schema_slot: i32, opts: u32, flags: u32, out: *mut *mut etlg_columns) -> i32;
+    pub fn etlg_columns_changelog_get(cols: *const etlg_columns, out: *mut etlg_changelog_info) -> i32;
     pub fn etlg_batch_rowbinary(
         ctx: *mut etlg_ctx,
         batch: *mut etlg_batch,

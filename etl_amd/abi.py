@@ -114,6 +114,10 @@ class ColumnsView(C.Structure):   # etlg_columns_view
                 ("row_event", C.c_void_p)]
 
 
+class ChangelogInfo(C.Structure):   # etlg_changelog_info
+    _fields_ = [("n_host_rows", C.c_uint64), ("host_event", C.c_uint64), ("host_reason", C.c_uint32), ("n_data_cols", C.c_uint32)]
+
+
 class RowBinaryView(C.Structure):   # etlg_rowbinary_view
     _fields_ = [("n_rows", C.c_uint64), ("n_bytes", C.c_uint64), ("n_host_rows", C.c_uint64), ("status", C.c_uint32),
                 ("on_device", C.c_uint32), ("host_event", C.c_uint64), ("host_column", C.c_uint32), ("_pad", C.c_uint32),
@@ -137,6 +141,8 @@ DL_TUPLES, DL_PREDICATES = 0, 1
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)
 AK_NONE = 255
 ROWS_INSERT, ROWS_UPDATE, ROWS_PARSE_ARRAYS, ROWS_FORMAT_JSON = 1, 2, 4, 8
+ICE_PARTIAL_UPDATE, ICE_KEY_ONLY_DELETE, ICE_DELETE_WITHOUT_OLD_ROW = 1, 2, 3
+NO_EVENT = (1 << 64) - 1   # etlg_changelog_info.host_event: no refused event
 
 
 class KernelStat(C.Structure):

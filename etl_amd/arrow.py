@@ -154,6 +154,17 @@ def columns_to_record_batch(cols, names=None, columns=None, on_text="raise"):
     return pa.RecordBatch.from_arrays(arrays, schema=pa.schema(fields))
 
 
+def changelog_to_record_batch(cols, names, cdc_names=("cdc_operation", "sequence_number"), columns=None, on_text="raise"):
+    """pyarrow.RecordBatch over the buffers `Batch.iceberg(slot, ...)` built on the device: the slot's replicated columns under
+    `names`, as columns_to_record_batch wraps them, followed by the two non-nullable LargeUtf8 CDC columns under `cdc_names` (the
+    Iceberg sink picks names that do not clash with the table's: find_unique_column_name, iceberg/core.rs:685-)."""
+    assert cols.changelog is not None, "not a Batch.iceberg() result"
+    nd = int(cols.changelog.n_data_cols)
+    assert len(names) == nd and len(cdc_names) == 2 and cols.view.n_cols == nd + 2
+    pick = None if columns is None else list(columns) + [nd, nd + 1]
+    return columns_to_record_batch(cols, names=list(names) + list(cdc_names), columns=pick, on_text=on_text)
+
+
 def _display_strings(hb, fx, so, valid, tc):
     import struct
     from .view import numeric_to_string, timetz_to_string

@@ -113,6 +113,16 @@ DEV uint32_t dl_selected(const ColSel& s, uint64_t i, unsigned long long& base) 
   return k == 'U' && !partial ? 1u : 2u;
 }
 
+// Iceberg changelog: why the sink refuses a row event of the slot that col_selected (kinds 7) left out (iceberg_update_row / iceberg_delete_row,
+// crates/etl-destinations/src/iceberg/core.rs:636-680); 0: not a row event of the slot
+DEV uint32_t ice_refused(const ColSel& s, uint64_t i) {
+  if (i >= s.n_events || s.ev_slot[i] != s.slot) return 0u;
+  const uint32_t k = s.ev_kind[i], fl = s.ev_flags[i];
+  if (k == 'U') return (fl & ETLG_FLAG_PARTIAL) ? ETLG_ICE_PARTIAL_UPDATE : 0u;
+  if (k == 'D') return (fl & 3u) == ETLG_OLD_FULL ? 0u : (fl & 3u) == ETLG_OLD_KEY ? ETLG_ICE_KEY_ONLY_DELETE : ETLG_ICE_DELETE_WITHOUT_OLD_ROW;
+  return 0u;
+}
+
 __global__ __launch_bounds__(256) void k_col_count(ColSel s) {
   __shared__ uint32_t lds[8];
   uint64_t base;
@@ -125,6 +135,14 @@ __global__ __launch_bounds__(256) void k_col_count(ColSel s) {
     if (!s.dl && !sel && i < s.n_events && s.ev_slot[i] == s.slot) { const uint32_t k = s.ev_kind[i]; left = k == 'I' || k == 'U' || k == 'D'; }
     const unsigned long long m = __ballot(left);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(s.host_rows, (unsigned long long)__builtin_popcountll(m));
+  }
+  if (s.ice) {  // the refused events of the slot: their count, and the first of them with its reason (the lanes of a wave hold ascending events)
+    const uint32_t why = sel ? 0u : ice_refused(s, i);
+    const unsigned long long m = __ballot(why != 0u);
+    if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) {
+      atomicAdd(s.ice, (unsigned long long)__builtin_popcountll(m));
+      atomicMin(s.ice + 3, (unsigned long long)((i << 8) | why));
+    }
   }
   uint32_t tot;
   block_scan_incl<0>(sel, lds, &tot);
@@ -157,6 +175,64 @@ __global__ __launch_bounds__(256) void k_col_rows(ColSel s) {
     const uint32_t r = s.blk[blockIdx.x] + inc - sel;
     s.row_event[r] = i; s.row_base[r] = (s.pb || s.dl) ? pbb[0] : base;
     if (sel == 2) { s.row_event[r + 1] = i; s.row_base[r + 1] = pbb[1]; }
+  }
+}
+
+// ---- Iceberg changelog: the two trailing CDC columns of every row (iceberg/core.rs:62-85, 268-291), both non-nullable LargeUtf8 of a
+// fixed width: cdc_operation "INSERT" | "UPDATE" | "DELETE" (6 bytes), sequence_number `{commit_lsn:016x}/{tx_ordinal:016x}` (33 bytes;
+// crates/etl/src/event.rs:346-351). Every output is a function of its byte position, so the launch is cut by bytes, not by rows: a
+// workgroup writes 4096 consecutive bytes of one value stream, a lane one aligned 16-byte piece of it (a uint4 store, consecutive lanes
+// to consecutive addresses; the piece that holds the stream's end is filled with zeros — the buffers are sized up to 16). The rows a
+// workgroup's bytes belong to (<= 126 / 684) are gathered once into LDS through row_event, which ascends: near-coalesced loads. The
+// remaining workgroups write the offsets (8-byte stores, lane-linear) and the bitmaps (validity all ones, deferred all zeros).
+constexpr uint32_t kCdcSeq = 33, kCdcOp = 6, kCdcTile = 4096;
+__global__ __launch_bounds__(256) void k_col_cdc(CdcJob j) {
+  __shared__ unsigned long long s_lsn[kCdcTile / kCdcSeq + 2], s_ord[kCdcTile / kCdcSeq + 2];
+  __shared__ uint8_t s_kind[kCdcTile / kCdcOp + 2];
+  uint32_t bx = blockIdx.x;
+  const uint64_t n = j.n_rows;
+  if (bx < j.nb_seq + j.nb_op) {
+    const bool seq = bx < j.nb_seq;
+    const uint32_t w = seq ? kCdcSeq : kCdcOp;
+    if (!seq) bx -= j.nb_seq;
+    const uint64_t b0 = (uint64_t)bx * kCdcTile, total = n * w, r0 = b0 / w;
+    const uint64_t rl = (b0 + kCdcTile - 1) / w;
+    const uint32_t nr = (uint32_t)((rl < n ? rl : n - 1) - r0 + 1);
+    for (uint32_t t = threadIdx.x; t < nr; t += 256) {
+      const uint64_t ev = j.row_event[r0 + t];
+      if (seq) { s_lsn[t] = j.zero_token ? 0ull : j.ev_commit[ev]; s_ord[t] = j.zero_token ? 0ull : j.ev_ord[ev]; }
+      else s_kind[t] = j.ev_kind[ev];
+    }
+    __syncthreads();
+    const uint64_t p0 = b0 + (uint64_t)threadIdx.x * 16;
+    if (p0 >= total) return;
+    uint32_t lr = (uint32_t)(p0 / w - r0), k = (uint32_t)(p0 % w);
+    uint32_t out[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t q = 0; q < 16; q++) {
+      uint32_t ch = 0u;
+      if (p0 + q < total) {
+        if (seq) {
+          const unsigned long long v = k < 16u ? s_lsn[lr] : s_ord[lr];
+          const uint32_t nib = (uint32_t)(v >> ((((k < 16u ? 15u : 32u) - k) * 4u) & 63u)) & 15u;   // digit k of the LSN, digit k - 17 of the ordinal (k == 16 is the '/')
+          ch = k == 16u ? (uint32_t)'/' : nib < 10u ? '0' + nib : 'a' + (nib - 10u);
+        } else {
+          const uint32_t kd = s_kind[lr];
+          const unsigned long long word = kd == 'U' ? 0x455441445055ull : kd == 'D' ? 0x4554454c4544ull : 0x545245534e49ull;   // "UPDATE" / "DELETE" / "INSERT", first byte lowest
+          ch = (uint32_t)(word >> (8u * k)) & 0xFFu;
+        }
+      }
+      out[q >> 2] |= ch << (8u * (q & 3u));
+      if (++k == w) { k = 0u; lr++; }
+    }
+    *(uint4*)((seq ? j.seq_values : j.op_values) + p0) = make_uint4(out[0], out[1], out[2], out[3]);
+    return;
+  }
+  bx -= j.nb_seq + j.nb_op;
+  const uint64_t t = (uint64_t)bx * 256 + threadIdx.x;
+  if (t <= n) { j.op_offsets[t] = (int64_t)(t * kCdcOp); j.seq_offsets[t] = (int64_t)(t * kCdcSeq); }
+  if (t < (n + 63) / 64) {
+    const unsigned long long m = (t == n / 64) ? (1ull << (n & 63)) - 1ull : ~0ull;   // (t == n / 64 only when n is no multiple of 64)
+    j.op_validity[t] = m; j.seq_validity[t] = m; j.op_deferred[t] = 0ull; j.seq_deferred[t] = 0ull;
   }
 }
 
@@ -2111,6 +2187,15 @@ void etlg_k_col_select(const void* selv, hipStream_t st) {
   hipLaunchKernelGGL(k_col_count, dim3(s.nblocks), dim3(256), 0, st, s);
   hipLaunchKernelGGL(k_col_scan, dim3(1), dim3(256), 0, st, s.blk, s.nblocks);
   hipLaunchKernelGGL(k_col_rows, dim3(s.nblocks), dim3(256), 0, st, s);
+}
+
+// both CDC columns of a changelog batch in one launch (the job's nb_seq / nb_op are filled in here)
+void etlg_k_col_cdc(const void* jv, hipStream_t st) {
+  CdcJob j = *(const CdcJob*)jv;
+  if (!j.n_rows) return;
+  j.nb_seq = (uint32_t)((j.n_rows * kCdcSeq + kCdcTile - 1) / kCdcTile);
+  j.nb_op = (uint32_t)((j.n_rows * kCdcOp + kCdcTile - 1) / kCdcTile);
+  hipLaunchKernelGGL(k_col_cdc, dim3(j.nb_seq + j.nb_op + (uint32_t)((j.n_rows + 256) / 256)), dim3(256), 0, st, j);
 }
 
 void etlg_k_col_fixed(const void* jv, hipStream_t st) {

@@ -239,6 +239,9 @@ struct ColSel {            // which events are rows of the hand-off
   // matches by (a row's base carries kPbKey when the image has the key layout), 3 the predicates of a table-copy batch (every row).
   // dl_ident: the slot has identity columns (without them every predicate candidate of a WAL batch stays with the host)
   uint32_t dl, dl_ident;
+  // Iceberg changelog (etlg_batch_iceberg; kinds = 7): the Update / Delete events of the slot the sink refuses are counted in ice[0],
+  // and ice[3] takes the minimum of (event << 8 | ETLG_ICE_*) over them, in the counting launch (k_col_count). Null: not asked for
+  unsigned long long* ice;
 };
 constexpr unsigned long long kPbDelete = 1ull << 63, kPbKey = 1ull << 62, kPbSecond = 1ull << 61, kPbBase = (1ull << 61) - 1;
 
@@ -253,6 +256,17 @@ struct ColJob {
   uint32_t elem_cls, _pad;
   uint32_t* child_validity; unsigned long long* child_nulls; unsigned long long* err;
   uint32_t* child_lens; const int64_t* child_offsets;   // lists of strings: byte length / start of every element
+};
+
+struct CdcJob {            // the two trailing CDC columns of an Iceberg changelog batch (k_col_cdc): cdc_operation, sequence_number
+  const uint64_t* row_event; const uint8_t* ev_kind; const uint64_t* ev_commit; const uint64_t* ev_ord;
+  uint64_t n_rows;
+  uint32_t zero_token;     // a table-copy batch: every sequence number is generate_sequence_number(0, 0)
+  uint32_t nb_seq, nb_op;  // workgroups of the launch that write sequence / operation bytes (4096 each); the rest write offsets and bitmaps
+  uint32_t _pad;
+  uint8_t* op_values; uint8_t* seq_values;   // 6 / 33 bytes per row; 16-byte aligned, sized up to a multiple of 16 (whole uint4 stores)
+  int64_t* op_offsets; int64_t* seq_offsets; // n_rows + 1 each
+  unsigned long long* op_validity; unsigned long long* seq_validity; unsigned long long* op_deferred; unsigned long long* seq_deferred;
 };
 
 struct HintJob {           // Event::size_hint per event (k_size_hints)

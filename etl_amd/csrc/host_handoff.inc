@@ -48,12 +48,15 @@ ColPlan col_plan(uint32_t cls) {
 }  // namespace
 }  // extern "C++"
 
-int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t row_kinds, uint32_t flags, etlg_columns** out) {
-  if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
+// The builder behind etlg_batch_columns and etlg_batch_iceberg. sel_kinds: ColSel.kinds (bit 0 inserts, 1 new rows of non-partial
+// updates, 2 full old rows of deletes); changelog: the Iceberg sink's rows — the refused events are counted in the selection's own
+// launches and read back with the row count, and the two CDC columns are written behind the data columns by one more launch
+// (etlg_k_col_cdc), so both calls stop for the device equally often.
+static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t sel_kinds, uint32_t row_kinds, uint32_t flags, bool changelog, etlg_columns** out) {
   *out = nullptr;
   if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }   // an ASYNC batch that ended in a decode error: the caller gets that error (fail-fast, as the reference), not a hand-off of the prefix
-  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, "etlg_batch_columns needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
-  if (slot < 0 || (size_t)slot >= c->slots.size() || !(row_kinds & 3u)) return ETLG_InvalidArgument;
+  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, changelog ? "etlg_batch_iceberg needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)" : "etlg_batch_columns needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
+  if (slot < 0 || (size_t)slot >= c->slots.size() || !sel_kinds) return ETLG_InvalidArgument;
   const bool parse_arrays = (row_kinds & ETLG_ROWS_PARSE_ARRAYS) != 0;
   const bool format_json = (row_kinds & ETLG_ROWS_FORMAT_JSON) != 0;
   const SlotHost& sh = *c->slots[(size_t)slot];
@@ -64,9 +67,22 @@ int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t ro
   const uint64_t ne = bv.n_events;
   const uint32_t nblk = (uint32_t)((ne + 255) / 256);
   // ---- 1. which events are rows (count -> scan -> scatter); row_event / row_base are sized for every event
-  HIPCHK(c, c->d_colsel.ensure(al((size_t)(nblk + 1) * 4) + 64));
+  const size_t o_ice = al((size_t)(nblk + 1) * 4);   // changelog: {refused events, -, -, min(event << 8 | reason)} behind the block counts
+  HIPCHK(c, c->d_colsel.ensure(o_ice + 64));
   uint32_t* d_blk = (uint32_t*)c->d_colsel.p;
   cs->m.ctx = c; cs->m.ctx_gen = c->gen;
+  cs->changelog = changelog; cs->ci.host_event = ~0ull; cs->ci.n_data_cols = sh.desc.n_cols;
+  // pinned {0, 0, 0, ~0} records: the initial values of the columns' counters (and of the changelog's refusal words) go up as an
+  // asynchronous copy (a pageable source made it a synchronisation)
+  auto cnt_init = [&](size_t want) -> int32_t {
+    if (c->h_cnt_init_cols >= want) return ETLG_OK;
+    if (c->h_cnt_init) { HIPCHK(c, hipStreamSynchronize(s)); (void)hipHostFree(c->h_cnt_init); c->h_cnt_init = nullptr; c->h_cnt_init_cols = 0; }
+    const size_t cap = want + 64;
+    HIPCHK(c, hipHostMalloc((void**)&c->h_cnt_init, cap * 32, hipHostMallocDefault));
+    for (size_t i = 0; i < cap; i++) { c->h_cnt_init[4 * i] = c->h_cnt_init[4 * i + 1] = c->h_cnt_init[4 * i + 2] = 0ull; c->h_cnt_init[4 * i + 3] = ~0ull; }
+    c->h_cnt_init_cols = cap;
+    return ETLG_OK;
+  };
   ScratchBlk rows_blk{c};
   if (ne) HIPCHK(c, blk_take(c, al(ne * 8) * 2, false, &rows_blk.p, &rows_blk.cap));
   void* d_rows = rows_blk.p;
@@ -76,12 +92,26 @@ int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t ro
   if (ne) {
     ColSel q{};
     q.ev_kind = bv.ev_kind; q.ev_flags = bv.ev_flags; q.ev_slot = bv.ev_schema_slot; q.ev_body = bv.ev_body_off;
-    q.n_events = ne; q.slot = (uint32_t)slot; q.kinds = row_kinds & 3u;
+    q.n_events = ne; q.slot = (uint32_t)slot; q.kinds = sel_kinds;
     q.row_full = sh.desc.row_bytes_full; q.row_key = sh.desc.row_bytes_key;
     q.blk = d_blk; q.nblocks = nblk; q.row_event = d_row_event; q.row_base = d_row_base;
+    unsigned long long back[(64 + 32) / 8] = {0};   // the row count; changelog: ... up to the refusal words, which ride the same copy
+    const size_t back_bytes = changelog ? o_ice + 32 - (size_t)nblk * 4 : 4;
+    if (changelog) {
+      { const int32_t rc = cnt_init(1); if (rc != ETLG_OK) return rc; }
+      q.ice = (unsigned long long*)((uint8_t*)d_blk + o_ice);
+      HIPCHK(c, hipMemcpyAsync(q.ice, c->h_cnt_init, 32, hipMemcpyHostToDevice, s));
+    }
     etlg_k_col_select(&q, s);
-    HIPCHK(c, hipMemcpyAsync(&n_rows32, d_blk + nblk, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(back, d_blk + nblk, back_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    memcpy(&n_rows32, back, 4);
+    if (changelog) {
+      unsigned long long ice[4];
+      memcpy(ice, (const uint8_t*)back + (back_bytes - 32), 32);
+      cs->ci.n_host_rows = ice[0];
+      if (ice[3] != ~0ull) { cs->ci.host_event = ice[3] >> 8; cs->ci.host_reason = (uint32_t)(ice[3] & 0xFFu); }
+    }
   }
   const uint64_t n = n_rows32;
   // ---- 2. block A: row_event | per column {validity, deferred, values or (lens, offsets)} | counters
@@ -101,6 +131,13 @@ int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t ro
     if (l.pl.var) { l.offsets = off; off += al((n + 1) * 8); l.lens = off; off += al(n * 4); }
     else { l.values = off; off += l.pl.kind == ETLG_AK_BOOLEAN ? bm : al(n * l.pl.vbytes); }
   }
+  // changelog: the two CDC columns — per column validity, deferred, offsets, values (fixed-width strings: sized here, in block A)
+  const uint32_t cdc_w[2] = {6u, 33u};
+  size_t cdc_validity[2] = {0, 0}, cdc_deferred[2] = {0, 0}, cdc_offsets[2] = {0, 0}, cdc_values[2] = {0, 0};
+  if (changelog) for (int k = 0; k < 2; k++) {
+    cdc_validity[k] = off; off += bm; cdc_deferred[k] = off; off += bm;
+    cdc_offsets[k] = off; off += al((n + 1) * 8); cdc_values[k] = off; off += al(n * cdc_w[k]);
+  }
   const size_t o_cnt = off; off += al((size_t)nc * 32);   // per column: nulls, deferred, child nulls, first list error
   const size_t o_tot = off; off += al((size_t)nc * 8);    // per var-len column: the bytes behind its offsets (one read-back for all)
   const uint32_t nrb = (uint32_t)((n + 255) / 256);
@@ -109,17 +146,25 @@ int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t ro
   const size_t a_bytes = off + 64;
   HIPCHK(c, blk_take(c, a_bytes, false, &cs->m.d_a, &cs->m.cap_a));
   uint8_t* A = (uint8_t*)cs->m.d_a;
-  if (nc) {   // the counters' initial values from pinned memory (the copy is asynchronous; a pageable source made it a synchronisation)
-    if (c->h_cnt_init_cols < nc) {
-      if (c->h_cnt_init) { HIPCHK(c, hipStreamSynchronize(s)); (void)hipHostFree(c->h_cnt_init); c->h_cnt_init = nullptr; c->h_cnt_init_cols = 0; }
-      const size_t cap = (size_t)nc + 64;
-      HIPCHK(c, hipHostMalloc((void**)&c->h_cnt_init, cap * 32, hipHostMallocDefault));
-      for (size_t i = 0; i < cap; i++) { c->h_cnt_init[4 * i] = c->h_cnt_init[4 * i + 1] = c->h_cnt_init[4 * i + 2] = 0ull; c->h_cnt_init[4 * i + 3] = ~0ull; }
-      c->h_cnt_init_cols = cap;
-    }
+  if (nc) {   // the counters' initial values
+    { const int32_t rc = cnt_init(nc); if (rc != ETLG_OK) return rc; }
     HIPCHK(c, hipMemcpyAsync(A + o_cnt, c->h_cnt_init, (size_t)nc * 32, hipMemcpyHostToDevice, s));
   }
   if (n) HIPCHK(c, hipMemcpyAsync(A, d_row_event, n * 8, hipMemcpyDeviceToDevice, s));
+  if (changelog) {
+    if (n) {
+      CdcJob cj{};
+      cj.row_event = d_row_event; cj.ev_kind = bv.ev_kind; cj.ev_commit = bv.ev_commit_lsn; cj.ev_ord = bv.ev_tx_ordinal;
+      cj.n_rows = n; cj.zero_token = b->copy.active ? 1u : 0u;   // a table-copy batch (etlg_copy_decode), told as etlg_batch_ndjson tells it
+      cj.op_values = A + cdc_values[0]; cj.seq_values = A + cdc_values[1];
+      cj.op_offsets = (int64_t*)(A + cdc_offsets[0]); cj.seq_offsets = (int64_t*)(A + cdc_offsets[1]);
+      cj.op_validity = (unsigned long long*)(A + cdc_validity[0]); cj.seq_validity = (unsigned long long*)(A + cdc_validity[1]);
+      cj.op_deferred = (unsigned long long*)(A + cdc_deferred[0]); cj.seq_deferred = (unsigned long long*)(A + cdc_deferred[1]);
+      etlg_k_col_cdc(&cj, s);
+    } else {
+      for (int k = 0; k < 2; k++) HIPCHK(c, hipMemsetAsync(A + cdc_offsets[k], 0, 8, s));
+    }
+  }
   std::vector<ColJob> jobs(nc);
   std::vector<int64_t> var_total(nc, 0);
   std::vector<uint32_t> fixed_ids, var_ids;   // columns whose kernels travel in packs (list columns keep launches of their own)
@@ -266,7 +311,14 @@ int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t ro
     blk_give(c, c->gen, cs->m.d_a, cs->m.cap_a, false); blk_give(c, c->gen, cs->m.d_b, cs->m.cap_b, false); blk_give(c, c->gen, cs->m.d_c, cs->m.cap_c, false);
     cs->m.d_a = cs->m.d_b = cs->m.d_c = nullptr;
   }
-  cs->cols.resize(nc);
+  cs->cols.resize(nc + (changelog ? 2u : 0u));
+  if (changelog) for (uint32_t t = 0; t < 2; t++) {
+    etlg_column& k = cs->cols[nc + t];
+    k = etlg_column{};
+    k.type_class = ETLG_TC_STRING; k.arrow_kind = ETLG_AK_LARGE_UTF8;
+    k.validity = base_a + cdc_validity[t]; k.deferred = base_a + cdc_deferred[t];
+    k.offsets = (const int64_t*)(base_a + cdc_offsets[t]); k.values = base_a + cdc_values[t]; k.values_bytes = n * cdc_w[t];
+  }
   for (uint32_t i = 0; i < nc; i++) {
     etlg_column& k = cs->cols[i];
     const Lay& l = lay[i];
@@ -286,9 +338,27 @@ int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t ro
     }
     if (!l.pl.var) { k.values = base_a + l.values; k.values_bytes = l.pl.kind == ETLG_AK_BOOLEAN ? ((n + 63) / 64) * 8 : n * l.pl.vbytes; }
   }
-  cs->v.n_rows = n; cs->v.n_cols = nc; cs->v.on_device = on_dev ? 1u : 0u; cs->v.cols = cs->cols.data();
+  cs->v.n_rows = n; cs->v.n_cols = (uint32_t)cs->cols.size(); cs->v.on_device = on_dev ? 1u : 0u; cs->v.cols = cs->cols.data();
   cs->v.row_event = (const uint64_t*)base_a;
   *out = cs.release();
+  return ETLG_OK;
+}
+
+int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t row_kinds, uint32_t flags, etlg_columns** out) {
+  if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
+  return build_columns(c, b, slot, row_kinds & 3u, row_kinds, flags, false, out);
+}
+
+int32_t etlg_batch_iceberg(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t opts, uint32_t flags, etlg_columns** out) {
+  if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
+  *out = nullptr;
+  if (opts & ~(ETLG_ROWS_PARSE_ARRAYS | ETLG_ROWS_FORMAT_JSON)) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_iceberg: opts takes ETLG_ROWS_PARSE_ARRAYS | ETLG_ROWS_FORMAT_JSON only (the row kinds are fixed)");
+  return build_columns(c, b, slot, 7u, opts, flags, true, out);
+}
+
+int32_t etlg_columns_changelog_get(const etlg_columns* cs, etlg_changelog_info* out) {
+  if (!cs || !out || !cs->changelog) return ETLG_InvalidArgument;
+  *out = cs->ci;
   return ETLG_OK;
 }
 

@@ -56,6 +56,7 @@ extern "C" void etlg_k_launch_plan(const DecParams* p, const void* q, hipStream_
 extern "C" void etlg_k_launch_plan_pre(const DecParams* p, const void* q, hipStream_t s);
 extern "C" int etlg_k_plan_set_lds(void);
 extern "C" void etlg_k_col_select(const void* sel, hipStream_t s);
+extern "C" void etlg_k_col_cdc(const void* job, hipStream_t s);
 extern "C" void etlg_k_col_fixed(const void* job, hipStream_t s);
 extern "C" uint32_t etlg_k_col_pack_max(void);
 extern "C" void etlg_k_col_fixed_pack(const void* jobs, uint32_t n, hipStream_t s);
@@ -498,10 +499,12 @@ struct HandoffBlocks {  // two device blocks (+ one pinned block when downloaded
   void* d_a = nullptr; void* d_b = nullptr; void* d_c = nullptr; uint8_t* h = nullptr;
   size_t cap_a = 0, cap_b = 0, cap_c = 0, cap_h = 0;
 };
-struct etlg_columns {  // etlg_batch_columns
+struct etlg_columns {  // etlg_batch_columns, etlg_batch_iceberg
   etlg_columns_view v{};
   std::vector<etlg_column> cols;
   HandoffBlocks m;
+  bool changelog = false;          // built by etlg_batch_iceberg: `ci` is valid (etlg_columns_changelog_get)
+  etlg_changelog_info ci{};
 };
 
 struct etlg_rowbinary {

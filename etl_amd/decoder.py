@@ -73,6 +73,22 @@ class Batch:
             raise self.dec.last_error()
         return Columns(self.dec, out)
 
+    def iceberg(self, slot, parse_arrays=False, format_json=False, on_device=False):
+        """The Iceberg sink's changelog rows of schema slot `slot` (etlg_batch_iceberg): Insert -> the row, Update -> the new row,
+        Delete -> the full old row, as the column buffers of columns() followed by the two CDC columns cdc_operation and
+        sequence_number. Returns a `Columns` whose `.changelog` (abi.ChangelogInfo) counts the events the sink refuses (partial
+        updates, deletes without a full old row) and names the first of them: the caller raises the sink's error for it."""
+        opts = (abi.ROWS_PARSE_ARRAYS if parse_arrays else 0) | (abi.ROWS_FORMAT_JSON if format_json else 0)
+        out = C.c_void_p()
+        rc = self.dec.L.etlg_batch_iceberg(self.dec.h, self.h, slot, opts, abi.F_OUTPUT_ON_DEVICE if on_device else 0, C.byref(out))
+        if rc != abi.OK or not out:
+            raise self.dec.last_error()
+        cols = Columns(self.dec, out)
+        cols.changelog = abi.ChangelogInfo()
+        rc = self.dec.L.etlg_columns_changelog_get(out, C.byref(cols.changelog))
+        assert rc == abi.OK, rc
+        return cols
+
     def finish_cells(self, what=abi.FINISH_ARRAYS | abi.FINISH_FLOATS):
         """Typed arrays / exact floats in the arena, on the device (etlg_batch_finish_cells). Returns abi.FinishStats."""
         st = abi.FinishStats()
@@ -151,6 +167,7 @@ class Columns:
 
     def __init__(self, dec, handle):
         self.dec, self.h = dec, handle
+        self.changelog = None   # abi.ChangelogInfo of a Batch.iceberg() result
         self.view = abi.ColumnsView()
         dec.L.etlg_columns_view_get(handle, C.byref(self.view))
 

@@ -734,6 +734,42 @@ int32_t etlg_columns_view_get(const etlg_columns* cols, etlg_columns_view* out);
 /* Returns the buffers to the context's pool (no device synchronisation): work the caller enqueued on them must be complete. */
 void etlg_columns_free(etlg_columns* cols);
 
+/* The Iceberg sink's changelog rows for ONE schema slot of a decoded batch, as the Arrow column buffers of etlg_batch_columns plus the
+ * two trailing CDC columns (crates/etl-destinations/src/iceberg/core.rs:300-416, write_table_rows :268-291): in event order, at most
+ * one row per event,
+ *   Insert -> the row; Update -> the full new row; Delete -> the full OLD row,
+ * and behind the slot's replicated columns two non-nullable ETLG_AK_LARGE_UTF8 columns (type_class ETLG_TC_STRING, null_count 0,
+ * validity all ones) of fixed-width values:
+ *   cols[n_data_cols]      cdc_operation   "INSERT" | "UPDATE" | "DELETE" (IcebergOperationType Display, core.rs:77-85): offsets[i] = 6 i
+ *   cols[n_data_cols + 1]  sequence_number `{commit_lsn:016x}/{tx_ordinal:016x}` of the row's event, lower-case hex (event_sequence_key()
+ *                          .to_string(), crates/etl/src/event.rs:346-351): offsets[i] = 33 i
+ * The events the sink refuses with SourceReplicaIdentityError (iceberg_update_row / iceberg_delete_row, core.rs:636-680) are not among
+ * the rows: a partial Update, a Delete that carries only the key, a Delete without an old image. They are counted (n_host_rows) and the
+ * first of them in event order is named with its reason; the other rows are still built, as in the other hand-offs. The reference fails
+ * the WHOLE write_events call at the first refused event across ALL tables (the `?` at core.rs:332-350): the host takes the minimum
+ * host_event over the slots it hands off and raises the error text of core.rs:642-678. Column NAMES (find_unique_column_name,
+ * core.rs:685-), Relation events and Truncates stay on the host.
+ * A table-copy batch (etlg_copy_decode): every row is kept, the operation is "INSERT" and the sequence number is
+ * generate_sequence_number(0, 0) = "0000000000000000/0000000000000000" (event.rs:370-375).
+ * opts: ETLG_ROWS_PARSE_ARRAYS | ETLG_ROWS_FORMAT_JSON, as for etlg_batch_columns; the row kinds are fixed, any other bit is
+ * ETLG_InvalidArgument. Batch requirements, flags and the reports of malformed array literals / json cells (first row in event order,
+ * then first column, over the rows selected here) as for etlg_batch_columns. An unchanged-toast cell cannot occur: partial rows are not
+ * selected, and a Delete's full old row is decoded through convert_tuple_to_row, which accepts no unchanged-toast cell
+ * (codec/event.rs:552). The result is read with etlg_columns_view_get (n_cols = the slot's columns + 2) and freed with
+ * etlg_columns_free; the call synchronises with the device exactly as often as etlg_batch_columns does for the same slot and options. */
+#define ETLG_ICE_PARTIAL_UPDATE 1u
+#define ETLG_ICE_KEY_ONLY_DELETE 2u
+#define ETLG_ICE_DELETE_WITHOUT_OLD_ROW 3u
+typedef struct etlg_changelog_info {
+  uint64_t n_host_rows;  /* Update / Delete events of the slot the sink refuses; they are not among the rows */
+  uint64_t host_event;   /* the first of them in event order, ~0 = none */
+  uint32_t host_reason;  /* ETLG_ICE_* of host_event, 0 = none */
+  uint32_t n_data_cols;  /* cols[0..n_data_cols) = the slot's replicated columns; [n_data_cols] cdc_operation, [+1] sequence_number */
+} etlg_changelog_info;
+int32_t etlg_batch_iceberg(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, uint32_t opts, uint32_t flags, etlg_columns** out);
+/* ETLG_InvalidArgument for an object that etlg_batch_columns built. */
+int32_t etlg_columns_changelog_get(const etlg_columns* cols, etlg_changelog_info* out);
+
 /* ClickHouse RowBinary rows for ONE schema slot of a decoded batch, encoded on the device: what
  * cell_to_clickhouse_value + encode_to_row_binary (crates/etl-destinations/src/clickhouse/encoding.rs:58-83,
  * :188-283) and append_cdc_columns (clickhouse/core.rs:96-114) produce for the rows core.rs:1078-1127 collects:
