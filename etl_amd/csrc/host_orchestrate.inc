@@ -400,7 +400,8 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
     q.n_tabs = c->n_plan_tabs; q.tabs = (const PlanTab*)((const uint8_t*)b->side->dev.p + b->side->o_ptabs); q.cols = (const uint32_t*)((const uint8_t*)b->side->dev.p + b->side->o_pcols);
     q.dbg = c->plan_dbg;
     q.max_row_dw = (c->plan_max_row + 3) / 4;
-    const size_t per = 2 * ((size_t)q.ntiles + ((size_t)q.ntiles + 63) / 64);   // pairs: {agg, lsn}[ntiles] | {agg, lsn}[ngroups]
+    const size_t gtiles = std::min<size_t>(64, (size_t)1 << etlg_k_plan_pre_group_log());   // (the look-back's groups are 64 tiles, the pre-pass's are what plan.hip makes them)
+    const size_t per = 2 * ((size_t)q.ntiles + ((size_t)q.ntiles + gtiles - 1) / gtiles);   // pairs: {agg, lsn}[ntiles] | {agg, lsn}[ngroups]
     // the sidecar pre-pass (k_plan_pre, plan.hip) leaves every tile's prefix in memory: the decode kernel
     // then has no look-back. Needs one row size for all planned tables (a frame is priced by its length alone).
     const bool pre = c->plan_pre != 0 && c->plan_uniform_dw != 0;

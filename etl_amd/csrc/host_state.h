@@ -54,6 +54,7 @@ extern "C" void etlg_k_launch_copy(const uint8_t* rows, const uint32_t* row_offs
 extern "C" void etlg_k_launch_cells(const DecParams* p, const void* q, hipStream_t s);
 extern "C" void etlg_k_launch_plan(const DecParams* p, const void* q, hipStream_t s);
 extern "C" void etlg_k_launch_plan_pre(const DecParams* p, const void* q, hipStream_t s);
+extern "C" uint32_t etlg_k_plan_pre_group_log(void);
 extern "C" int etlg_k_plan_set_lds(void);
 extern "C" void etlg_k_col_select(const void* sel, hipStream_t s);
 extern "C" void etlg_k_col_cdc(const void* job, hipStream_t s);

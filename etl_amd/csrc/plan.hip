@@ -150,8 +150,11 @@ DEV int plan_find(const PlanParams& q, uint32_t rel_u) {
 // prefix holds no mark patches it in afterwards (plan_resolve) — so only the first tiles of a batch depend on the batch before
 // it, and consecutive ASYNC batches can run side by side (DecParams.flags bit 4, host.cpp "two streams").
 constexpr uint32_t kPreBeginLen = kBodyOff + 20u, kPreCommitLen = kBodyOff + 25u;   // CopyData + XLogData head + tag, then lsn:8 ts:8 xid:4 (Begin) / flags:1 lsn:8 end:8 ts:8 (Commit): 51 and 56 bytes
-constexpr int kPreTilesPerWave = 16, kPreWaves = 16;   // the pre-pass: tiles a wave takes, waves of a workgroup
-constexpr uint32_t kPreGroupLog = 8;                   // ... tiles per group = kPreTilesPerWave * kPreWaves = 1 << kPreGroupLog
+constexpr int kPreTilesPerWave = 8, kPreWaves = 8;     // the pre-pass: tiles a wave takes, waves of a workgroup (two per SIMD: placeable in the wave slots a CU full of k_plan leaves free)
+constexpr uint32_t pre_log2(uint32_t v) { return v <= 1u ? 0u : 1u + pre_log2(v >> 1); }
+constexpr uint32_t kPreGroupLog = pre_log2(kPreTilesPerWave * kPreWaves);   // ... tiles per group = kPreTilesPerWave * kPreWaves = 1 << kPreGroupLog
+static_assert((1u << kPreGroupLog) == (uint32_t)(kPreTilesPerWave * kPreWaves), "a group of the pre-pass is a power of two of tiles");
+static_assert(kPreTilesPerWave <= 32 && kPreWaves <= 8, "cand_m / short_m are 32-bit masks; at most two waves per SIMD");
 constexpr uint32_t kPlanMaxPolls = 1u << 15;   // bounded spin (tens of milliseconds): a give-up sends the batch to the generic kernels
 
 struct PlanPre2 { unsigned long long a0 = 0, l0 = 0, a1 = 0, l1 = 0; bool valid = false; };
@@ -513,7 +516,7 @@ DEV void plan_late_carry(DecParams& p, uint32_t* failp) {
 // Finish, part 1: everything that LOADS — the look-back's answer, with it the open Begin's LSN — and the transaction context. A wave
 // runs this for both of its tiles before it stores anything: memory operations of a wave return in order, so a descriptor load issued
 // behind a tile's row / header stores waits for those stores to be acknowledged first.
-// The two words the sidecar pre-pass left for a tile — its prefix inside its group of 256 (kPreGroupLog), the group's prefix — through scalar loads
+// The two words the sidecar pre-pass left for a tile — its prefix inside its group of 1 << kPreGroupLog tiles, the group's prefix — through scalar loads
 // (one address per wave; written by the kernels before this one on the stream), requested before the tile's bytes are.
 struct PlanPreWords { unsigned long long g0 = 0, g1 = 0, t0 = 0, t1 = 0; };
 DEV PlanPreWords plan_pre_load(const PlanParams& q, uint32_t tile) {
@@ -777,8 +780,13 @@ DEV void plan_kernel(DecParams& p, const PlanParams& q_in, u8* smem) {
 // decode streams): its cost leaves the chain's critical path. The decode kernel verifies what the pre-pass assumed frame by frame
 // (plan_local): a stream that breaks it — a Begin with trailing bytes, a row of another table size, anything that is not B / C / I —
 // gives the batch up to the generic kernels exactly like today.
-// k_plan_pre: one workgroup of sixteen waves per GROUP of 256 tiles, a wave takes 16 consecutive tiles (lane = frame, tile after tile; the
-// offsets of all 16 are requested before the first is looked at). Leaves desc[tile] = the tile's exclusive prefix INSIDE its group and,
+// k_plan_pre: one workgroup of eight waves per GROUP of 64 tiles (kPreGroupLog) — two waves per SIMD, so that a workgroup fits into the
+// wave slots a CU full of decode tiles leaves free (LDS admits 21 of those on 32 slots: 2, 3, 3, 3 slots free per SIMD) and the
+// pre-pass of batch k + 2 starts beside the decode of batch k + 1 the moment batch k is over; 146 workgroups on cfg2's 64 MiB, spread
+// over the chip. (Sixteen-wave workgroups were 37 and could not be placed before the decode beside them had no workgroup left to
+// dispatch. Four waves of 8 tiles are 291 groups, five trips of the last group's scan instead of three: +1 % on the bench where
+// eight waves give +6 % — profiles/r07_plan_pre_ahead.md.) A wave takes 8 consecutive tiles (lane = frame, tile after tile; the offsets of all 8
+// are requested before the first is looked at: 54 VGPRs; 16 tiles need 102). Leaves desc[tile] = the tile's exclusive prefix INSIDE its group and,
 // behind them, gdesc[group] = the exclusive prefix of the group: every workgroup stores its group's
 // aggregate (16-byte word, this launch's status tag in both halves) and takes a ticket; the LAST one to arrive turns the aggregates
 // into exclusive prefixes in place — one wave, 64 groups per trip, the fold carried from trip to trip, a word that has not landed yet
@@ -797,7 +805,7 @@ __global__ __launch_bounds__(kPreWaves * 64) void k_plan_pre(DecParams p, PlanPa
     const uint64_t f = (uint64_t)(t0 + (uint32_t)i) * 64u + lane;
     o[i] = p.offs[f < p.nframes ? f : p.nframes];
   }
-  // the frames of a Begin's or a Commit's length: their tag byte and the eight bytes behind it, all 16 tiles' requests in flight at once
+  // the frames of a Begin's or a Commit's length: their tag byte and the eight bytes behind it, all of the wave's tiles' requests in flight at once
   // (one round trip; a wave meets a handful of such frames, and waiting for each tile's on its own was most of this kernel)
   uint32_t cand_m = 0;          // bit i: this lane's frame of tile i is such a frame
   uint32_t short_m = 0;         // bit i: ... is shorter than a row frame can be
@@ -827,9 +835,19 @@ __global__ __launch_bounds__(kPreWaves * 64) void k_plan_pre(DecParams p, PlanPa
     const uint64_t lsn = lsnv[i];
     const bool isB = cand && flen == kPreBeginLen && tag == 'B', isC = cand && flen == kPreCommitLen && tag == 'C';
     const bool isDel = ((short_m >> i) & 1u) || (cand && tag == 'D' && flen <= q.pre_key_max);   // (pre_key_max 0: never)
-    const uint32_t fixed_dw = !live ? 0u : isB ? 2u : isC ? 4u : isDel ? q.pre_key_dw : q.pre_row_dw;
-    const uint32_t mark = isB ? ((((uint32_t)f + 1u) << 1) | 1u) : isC ? (((uint32_t)f + 1u) << 1) : 0u;
-    const uint32_t tot_mark = wave_last(wave_scan_max(mark)), tot_fx = wave_last(wave_scan_add(fixed_dw));
+    // the tile's totals are a sum and a max, not scans: three ballots and their population counts give the dwords, the highest Begin /
+    // Commit lane gives the mark (marks grow with the frame index) — scalar work where two six-step DPP ladders were
+    const unsigned long long mB = __ballot(isB), mC = __ballot(isC), mD = __ballot(live && isDel && !isB && !isC);
+    const uint64_t base = (uint64_t)tile * 64u;
+    const uint32_t nlive = base >= p.nframes ? 0u : (p.nframes - base < 64u ? (uint32_t)(p.nframes - base) : 64u);
+    const uint32_t nB = (uint32_t)__builtin_popcountll(mB), nC = (uint32_t)__builtin_popcountll(mC), nD = (uint32_t)__builtin_popcountll(mD);
+    const uint32_t tot_fx = 2u * nB + 4u * nC + q.pre_key_dw * nD + q.pre_row_dw * (nlive - nB - nC - nD);
+    const unsigned long long mBC = mB | mC;
+    uint32_t tot_mark = 0;
+    if (mBC) {
+      const uint32_t h = 63u - (uint32_t)__builtin_clzll(mBC);
+      tot_mark = ((((uint32_t)base + h) + 1u) << 1) | (uint32_t)((mB >> h) & 1ull);
+    }
     uint64_t tile_lsn = 0;
     if (tot_mark & 1u) {
       const int src = (int)((tot_mark >> 1) - 1u - tile * 64u);
@@ -841,14 +859,9 @@ __global__ __launch_bounds__(kPreWaves * 64) void k_plan_pre(DecParams p, PlanPa
   }
   if (lane == 0) { s_wagg[wave][0] = fold_agg(run); s_wagg[wave][1] = fold_lsn(run); }
   __syncthreads();
-  // the waves of this group in front of this one: every wave scans the sixteen aggregates (lane = wave) and reads its own prefix off
-  const PlanFold winc = fold_scan(lane < (uint32_t)kPreWaves ? fold_of(s_wagg[lane][0], s_wagg[lane][1]) : fold_id());
+  // the waves of this group in front of this one: a handful of aggregates, folded in order (uniform reads of LDS)
   PlanFold before = fold_id();
-  if (wave) {
-    const int src = (int)wave - 1;
-    before = PlanFold{(uint32_t)__builtin_amdgcn_readlane((int)winc.fx, src), (uint32_t)__builtin_amdgcn_readlane((int)winc.mk, src),
-                      (uint32_t)__builtin_amdgcn_readlane((int)winc.l0, src), (uint32_t)__builtin_amdgcn_readlane((int)winc.l1, src)};
-  }
+  for (uint32_t w = 0; w < wave; w++) before = fold_f(before, fold_of(s_wagg[w][0], s_wagg[w][1]));
   if (lane < (uint32_t)kPreTilesPerWave && t0 + lane < q.ntiles) {
     const PlanFold r = fold_f(before, keep);
     unsigned long long* d = q.pre_out + 2 * (size_t)(t0 + lane);
@@ -925,6 +938,8 @@ void etlg_k_launch_plan(const DecParams* p, const void* qv, hipStream_t s) {
     else hipLaunchKernelGGL(k_plan2<8>, dim3((q->ntiles + 1) / 2), dim3(64), q->lds_bytes, s, *p, *q);
   } else hipLaunchKernelGGL(k_plan, dim3(q->ntiles), dim3(64), q->lds_bytes, s, *p, *q);
 }
+
+uint32_t etlg_k_plan_pre_group_log(void) { return kPreGroupLog; }   // tiles per group of the pre-pass, log 2: the host sizes the prefix buffers by it
 
 int etlg_k_plan_set_lds(void) {
   const int a = hipFuncSetAttribute((const void*)k_plan, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess ? 0 : 1;
