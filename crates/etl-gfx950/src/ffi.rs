@@ -286,6 +286,7 @@ pub const ETLG_RB_OK: u32 = 0;
 pub const ETLG_RB_NEEDS_HOST: u32 = 3;
 pub const ETLG_DL_TUPLES: i32 = 0;
 pub const ETLG_DL_PREDICATES: i32 = 1;
+pub const ETLG_DL_UPDATES: i32 = 3;
 
 #[repr(C)]
 pub struct etlg_kernel_stat {
@@ -437,6 +438,7 @@ extern "C" {
         out: *mut *mut etlg_rowbinary,
     ) -> i32;
     pub fn etlg_rowbinary_view_get(rb: *const etlg_rowbinary, out: *mut etlg_rowbinary_view) -> i32;
+    pub fn etlg_rowbinary_col_ends_get(rb: *const etlg_rowbinary, col_ends: *mut *const u32) -> i32;
     pub fn etlg_rowbinary_free(rb: *mut etlg_rowbinary);
     pub fn etlg_batch_size_hints(ctx: *mut etlg_ctx, batch: *mut etlg_batch, model: *const etlg_size_model, flags: u32, out: *mut u64) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;

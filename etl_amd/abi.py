@@ -136,7 +136,7 @@ class FinishStats(C.Structure):   # etlg_finish_stats
 SIZE_HINT_INCOMPLETE = 1 << 63
 CH_MERGE_TREE, CH_REPLACING_MERGE_TREE = 0, 1
 RB_OK, RB_NEEDS_HOST = 0, 3
-DL_TUPLES, DL_PREDICATES = 0, 1
+DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)
 AK_NONE = 255

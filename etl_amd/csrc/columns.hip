@@ -89,16 +89,38 @@ DEV uint32_t pb_selected(const ColSel& s, uint64_t i, unsigned long long* bases)
   return 1;
 }
 
-// ---- DuckLake: what an event becomes for the tuples (dl 1) and for the predicates (dl 2; 3: a table-copy batch, every row):
-// 0 nothing, 1 a row (base: the image, | kPbKey when it has the key layout), 2 an event the host has to take (n_host_rows).
+// ---- DuckLake: what an event becomes for the tuples (dl 1), for the predicates (dl 2; 3: a table-copy batch, every row) and for the
+// partial Updates (dl 4):
+// 0 nothing, 1 a row (bases[0]: the image, | kPbKey when it has the key layout), 2 an event the host has to take (n_host_rows),
+// 3 two rows (dl 4 only).
 // Insert -> a tuple; Update -> the new row's tuple unless it is partial, and the predicate of the old image — without one, of the
 // new row's identity columns (TableMutation::Replace) unless that row is partial (key_row_from_updated_partial_row); Delete -> the
 // predicate of the old image, which it must carry ("DuckLake delete requires an old row image").
-DEV uint32_t dl_selected(const ColSel& s, uint64_t i, unsigned long long& base) {
+// dl 4, a partial Update only (ducklake/core.rs:1846-1913, batches.rs:1179-1190): the SET clause of the partial new row (bases[0]) and
+// the predicate of the mutation's delete_row (bases[1], | kPbSecond): the old image, else the partial row's own identity cells. The
+// host takes the event when the slot has no identity columns, when no old image came and an identity cell is MISSING (core.rs:896-905)
+// and when no cell is present at all (batches.rs:1337).
+DEV uint32_t dl_selected(const ColSel& s, uint64_t i, unsigned long long* bases) {
   if (i >= s.n_events || s.ev_slot[i] != s.slot) return 0;
   const uint32_t k = s.ev_kind[i], fl = s.ev_flags[i], ok = fl & 3u;
   const bool partial = (fl & ETLG_FLAG_PARTIAL) != 0;
+  unsigned long long& base = bases[0];
   base = s.ev_body[i];
+  if (s.dl == 4u) {
+    if (k != 'U' || !partial) return 0;
+    if (!s.dl_ident) return 2;   // "DuckLake update requires a replica identity"
+    const uint64_t oldb = base, newb = oldb + (ok == ETLG_OLD_FULL ? s.row_full : ok == ETLG_OLD_KEY ? s.row_key : 0u);
+    bool any = false, key_missing = false;
+    for (uint32_t c = 0; c < s.n_cols; c++) {
+      const uint32_t st = (s.fixed[newb + c / 4] >> (2 * (c % 4))) & 3u;
+      if (st != ETLG_CELL_MISSING) any = true;
+      else if (s.kcols[c] & 1u) key_missing = true;
+    }
+    if (!any || (ok == ETLG_OLD_NONE && key_missing)) return 2;
+    bases[0] = newb;
+    bases[1] = (ok == ETLG_OLD_NONE ? newb : ok == ETLG_OLD_KEY ? oldb | kPbKey : oldb) | kPbSecond;
+    return 3;
+  }
   if (k == 'I') return s.dl != 2u ? 1u : 0u;
   if (k != 'U' && k != 'D') return 0;
   if (s.dl == 1u) {
@@ -112,6 +134,7 @@ DEV uint32_t dl_selected(const ColSel& s, uint64_t i, unsigned long long& base) 
   if (ok == ETLG_OLD_KEY) { base |= kPbKey; return 1; }
   return k == 'U' && !partial ? 1u : 2u;
 }
+DEV uint32_t dl_rows(uint32_t dls) { return dls == 1u ? 1u : dls == 3u ? 2u : 0u; }
 
 // Iceberg changelog: why the sink refuses a row event of the slot that col_selected (kinds 7) left out (iceberg_update_row / iceberg_delete_row,
 // crates/etl-destinations/src/iceberg/core.rs:636-680); 0: not a row event of the slot
@@ -128,8 +151,8 @@ __global__ __launch_bounds__(256) void k_col_count(ColSel s) {
   uint64_t base;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   unsigned long long pbb[2];
-  const uint32_t dls = s.dl ? dl_selected(s, i, pbb[0]) : 0u;
-  const uint32_t sel = s.dl ? (dls == 1u ? 1u : 0u) : s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
+  const uint32_t dls = s.dl ? dl_selected(s, i, pbb) : 0u;
+  const uint32_t sel = s.dl ? dl_rows(dls) : s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
   if (s.host_rows) {  // row events of the slot that are not handed off
     bool left = dls == 2u;
     if (!s.dl && !sel && i < s.n_events && s.ev_slot[i] == s.slot) { const uint32_t k = s.ev_kind[i]; left = k == 'I' || k == 'U' || k == 'D'; }
@@ -169,7 +192,7 @@ __global__ __launch_bounds__(256) void k_col_rows(ColSel s) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   uint64_t base = 0;
   unsigned long long pbb[2] = {0, 0};
-  const uint32_t sel = s.dl ? (dl_selected(s, i, pbb[0]) == 1u ? 1u : 0u) : s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
+  const uint32_t sel = s.dl ? dl_rows(dl_selected(s, i, pbb)) : s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
   const uint32_t inc = block_scan_incl<0>(sel, lds, nullptr);
   if (sel) {
     const uint32_t r = s.blk[blockIdx.x] + inc - sel;
@@ -1835,15 +1858,20 @@ DEV uint32_t dl_typed_array(S& s, const u8* h) {
   return ee;
 }
 
-template <bool JS, class S, class M>
+// UPD: ETLG_DL_UPDATES (dl_what 3, an instantiation of its own so that the tuples and the predicates compile as they did without it): the
+// SET clause of a partial new row (update_assignments_from_partial_row joined by ", ": every cell that is not MISSING), and behind it — the
+// row marked kPbSecond — the predicate of the same event
+template <bool JS, bool UPD = false, class S, class M>
 DEV uint32_t dl_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_hi, M&& mark) {   // 0, or column << 8 | code
   const uint64_t rb = j.row_base[r], base = rb & kPbBase;
-  const bool pred = j.dl_what != 0, keyrow = (rb & kPbKey) != 0;   // keyrow: the image has the key layout (the identity cells only)
+  const bool set = UPD && !(rb & kPbSecond);
+  const bool pred = j.dl_what != 0 && !set, keyrow = (rb & kPbKey) != 0;   // keyrow: the image has the key layout (the identity cells only)
   const uint32_t kbit = j.dl_what == 2 ? 4u : 1u;                   // which columns a predicate takes: identity / primary key
-  bool first = true;                                                // no predicate column in front of this lane's columns?
+  bool first = true;                                                // no predicate / present column in front of this lane's columns?
   if (pred) for (uint32_t i = 0; i < c_lo; i++) if (j.kcols[i] & kbit) first = false;
+  if constexpr (UPD) { if (set) for (uint32_t i = 0; i < c_lo; i++) if (((j.fixed[base + i / 4] >> (2 * (i % 4))) & 3u) != ETLG_CELL_MISSING) first = false; }
   uint32_t err0 = 0;
-  if (!pred && c_lo == 0) s.put('(');
+  if (!pred && !set && c_lo == 0) s.put('(');
   for (uint32_t i = c_lo; i < c_hi; i++) {
     mark(i);
     const uint32_t cd = j.cols[i], cls = cd & 0xFF;
@@ -1856,8 +1884,18 @@ DEV uint32_t dl_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
       first = false;
       const uint32_t a = j.nd_key_off[i];
       s.bytes(j.nd_keys + a, j.nd_key_off[i + 1] - a);   // the quoted identifier
-    } else if (i) { s.put(','); s.put(' '); }
+    } else if (!set && i) { s.put(','); s.put(' '); }
     const uint32_t st = (j.fixed[base + sti / 4] >> (2 * (sti % 4))) & 3u;
+    if constexpr (UPD) {
+      if (set) {
+        if (st == ETLG_CELL_MISSING) continue;
+        if (!first) { s.put(','); s.put(' '); }
+        first = false;
+        const uint32_t a = j.nd_key_off[i];
+        s.bytes(j.nd_keys + a, j.nd_key_off[i + 1] - a);
+        nd_lit(s, " = ");   // (a NULL cell: `"c" = NULL`, cell_to_sql_literal_ref(Cell::Null))
+      }
+    }
     const u8* slot = j.fixed + base + off;
     uint32_t e = 0;
     if (st == ETLG_CELL_NULL) nd_lit(s, pred ? " IS NULL" : "NULL");
@@ -1873,13 +1911,13 @@ DEV uint32_t dl_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
     if (e && !err0) err0 = (i << 8) | e;
   }
   if (err0) return err0;
-  if (!pred && c_hi == j.n_cols) s.put(')');
+  if (!pred && !set && c_hi == j.n_cols) s.put(')');
   return 0;
 }
 
 // JS: the table has a json column (kernels of their own, as for the Arrow columns)
-// ND: 1 the Snowflake NDJSON instantiation (nd_row), 2 the DuckLake literal one (dl_row), so the RowBinary / protobuf kernels carry
-// no third arm
+// ND: 1 the Snowflake NDJSON instantiation (nd_row), 2 the DuckLake literal one (dl_row), 3 the DuckLake partial Updates (dl_row with the
+// assignments arm, and col_ends from the counting pass), so the RowBinary / protobuf kernels carry no third arm
 template <bool JS, int ND = 0>
 __global__ __launch_bounds__(256) void k_rb_lens(RbJob j, unsigned long long* blk) {
   __shared__ uint64_t lds_sum[4];
@@ -1890,9 +1928,11 @@ __global__ __launch_bounds__(256) void k_rb_lens(RbJob j, unsigned long long* bl
     uint32_t next = 1;
     auto mark = [&](uint32_t i) {
       while (next < j.qparts && i == rb_part_col(j, next)) { j.part_off[(uint64_t)(next - 1) * j.n_rows + r] = c.n; next++; }
+      if constexpr (ND == 3) { if (i) j.col_ends[r * j.n_cols + i - 1] = c.n; }   // (ETLG_DL_UPDATES: column i - 1 is done)
     };
     uint32_t e;
-    if constexpr (ND == 2) e = dl_row<JS>(j, r, c, 0, j.n_cols, mark);
+    if constexpr (ND == 3) { e = dl_row<JS, true>(j, r, c, 0, j.n_cols, mark); if (j.n_cols) j.col_ends[(r + 1) * j.n_cols - 1] = c.n; }
+    else if constexpr (ND == 2) e = dl_row<JS>(j, r, c, 0, j.n_cols, mark);
     else if constexpr (ND == 1) e = nd_row<JS>(j, r, c, 0, j.n_cols, mark);
     else e = j.format ? pb_row<JS>(j, r, c, 0, j.n_cols, mark) : rb_row<JS>(j, r, c, 0, j.n_cols, mark);
     // first failing row in event order, rows with a date out of range before all others (bit 62 clear)
@@ -1936,7 +1976,8 @@ __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   if (!staged) {
     if (active) {
       RbWrite w(j.out + j.offsets[r] + po);
-      if constexpr (ND == 2) (void)dl_row<JS>(j, r, w, c_lo, c_hi, none);
+      if constexpr (ND == 3) (void)dl_row<JS, true>(j, r, w, c_lo, c_hi, none);
+      else if constexpr (ND == 2) (void)dl_row<JS>(j, r, w, c_lo, c_hi, none);
       else if constexpr (ND == 1) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
       else if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
       w.finish();
@@ -1949,7 +1990,8 @@ __global__ __launch_bounds__(256) void k_rb_rows(RbJob j) {
   if (active) {
     const uint32_t o = pad + (uint32_t)((uint64_t)j.offsets[r] - g0) + po;
     RbLdsWrite w((uint32_t*)img + (o >> 2), o & 3u);
-    if constexpr (ND == 2) (void)dl_row<JS>(j, r, w, c_lo, c_hi, none);
+    if constexpr (ND == 3) (void)dl_row<JS, true>(j, r, w, c_lo, c_hi, none);
+    else if constexpr (ND == 2) (void)dl_row<JS>(j, r, w, c_lo, c_hi, none);
     else if constexpr (ND == 1) (void)nd_row<JS>(j, r, w, c_lo, c_hi, none);
     else if (j.format) (void)pb_row<JS>(j, r, w, c_lo, c_hi, none); else (void)rb_row<JS>(j, r, w, c_lo, c_hi, none);
     w.finish();
@@ -2276,16 +2318,18 @@ void etlg_k_rowbinary(const void* jv, unsigned long long* blk, int64_t* offsets,
   const RbJob j = *(const RbJob*)jv;
   if (!j.n_rows) return;
   const uint32_t nb = (uint32_t)((j.n_rows + 255) / 256);
-  const bool nd = j.format == 2, dl = j.format == 3;   // (Snowflake NDJSON, DuckLake literals: kernels of their own)
+  const bool nd = j.format == 2, dl = j.format == 3 && j.dl_what != 3u, du = j.format == 3 && j.dl_what == 3u;   // (Snowflake NDJSON, DuckLake literals, DuckLake partial Updates: kernels of their own)
   if (step == 0) {
-    if (dl) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, 2>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, 2>), dim3(nb), dim3(256), 0, st, j, blk); }
+    if (du) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, 3>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, 3>), dim3(nb), dim3(256), 0, st, j, blk); }
+    else if (dl) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, 2>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, 2>), dim3(nb), dim3(256), 0, st, j, blk); }
     else if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_lens<true, 1>), dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL((k_rb_lens<false, 1>), dim3(nb), dim3(256), 0, st, j, blk); }
     else if (j.has_json) hipLaunchKernelGGL(k_rb_lens<true>, dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL(k_rb_lens<false>, dim3(nb), dim3(256), 0, st, j, blk);
     hipLaunchKernelGGL(k_col_len_scan, dim3(1), dim3(256), 0, st, blk, nb);
     hipLaunchKernelGGL(k_col_offsets, dim3(nb), dim3(256), 0, st, (const uint32_t*)j.lens, j.n_rows, (const unsigned long long*)blk, offsets, tot);
   } else {
     const uint32_t rpb = j.parts == 1 ? 256u : j.parts == 2 ? 128u : 64u, nbw = (uint32_t)((j.n_rows + rpb - 1) / rpb);
-    if (dl) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, 2>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, 2>), dim3(nbw), dim3(256), 0, st, j); }
+    if (du) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, 3>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, 3>), dim3(nbw), dim3(256), 0, st, j); }
+    else if (dl) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, 2>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, 2>), dim3(nbw), dim3(256), 0, st, j); }
     else if (nd) { if (j.has_json) hipLaunchKernelGGL((k_rb_rows<true, 1>), dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL((k_rb_rows<false, 1>), dim3(nbw), dim3(256), 0, st, j); }
     else if (j.has_json) hipLaunchKernelGGL(k_rb_rows<true>, dim3(nbw), dim3(256), 0, st, j); else hipLaunchKernelGGL(k_rb_rows<false>, dim3(nbw), dim3(256), 0, st, j);
   }

@@ -236,7 +236,10 @@ struct ColSel {            // which events are rows of the hand-off
   const uint32_t* cols;    // per replicated column: cls | .. | off_full << 16 (RbJob.cols)
   const uint32_t* kcols;   // identity | source nullable << 1 | primary key << 2 | key_index << 8 | off_key << 16 (RbJob.kcols)
   // DuckLake rows (dl != 0; ducklake/core.rs:1824-1945, batches.rs:1128-1226): 1 the tuples the sink upserts, 2 the predicates it deletes /
-  // matches by (a row's base carries kPbKey when the image has the key layout), 3 the predicates of a table-copy batch (every row).
+  // matches by (a row's base carries kPbKey when the image has the key layout), 3 the predicates of a table-copy batch (every row),
+  // 4 the partial Updates (ETLG_DL_UPDATES): two rows per event, the SET clause of the partial new row, then the predicate of the
+  // old image — without one, of the new row itself (kPbSecond marks the predicate row). That arm reads the new row's cell states
+  // through fixed / kcols / n_cols above.
   // dl_ident: the slot has identity columns (without them every predicate candidate of a WAL batch stays with the host)
   uint32_t dl, dl_ident;
   // Iceberg changelog (etlg_batch_iceberg; kinds = 7): the Update / Delete events of the slot the sink refuses are counted in ice[0],
@@ -314,8 +317,11 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   const uint8_t* nd_keys; const uint32_t* nd_key_off;
   uint32_t nd_zero_token;
   // format 3 (DuckLake, dl_row): nd_keys are the quoted identifiers; 0 tuples, 1 predicates over the identity columns, 2 predicates
-  // over the primary-key columns (a table-copy batch)
+  // over the primary-key columns (a table-copy batch), 3 partial Updates: a row whose base carries kPbSecond is a predicate over the
+  // identity columns, any other row the SET clause `"c" = lit, ...` of the cells that are not MISSING
   uint32_t dl_what;
+  // col_ends (dl_what 3, else null): [n_rows x n_cols] bytes of a record written once a column is done, from the counting pass
+  uint32_t* col_ends;
 };
 
 

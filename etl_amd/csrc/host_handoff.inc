@@ -574,7 +574,7 @@ int32_t etlg_batch_duckdb(etlg_ctx* c, etlg_batch* b, int32_t slot, int32_t what
                           etlg_rowbinary** out) {
   if (!c || !b || !out || b->ctx != c || (n_names && !col_names)) return ETLG_InvalidArgument;
   *out = nullptr;
-  if ((uint32_t)what != ETLG_DL_TUPLES && (uint32_t)what != ETLG_DL_PREDICATES) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_duckdb: what must be ETLG_DL_TUPLES or ETLG_DL_PREDICATES");
+  if ((uint32_t)what != ETLG_DL_TUPLES && (uint32_t)what != ETLG_DL_PREDICATES && (uint32_t)what != ETLG_DL_UPDATES) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_duckdb: what must be ETLG_DL_TUPLES, ETLG_DL_PREDICATES or ETLG_DL_UPDATES");
   if (slot < 0 || (size_t)slot >= c->slots.size()) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
   if (n_names != c->slots[(size_t)slot]->desc.n_cols) return lib_error(c, ETLG_InvalidArgument, "DuckLake row width mismatch: one column name per replicated column");
   NdKeys k;
@@ -591,7 +591,7 @@ int32_t etlg_batch_duckdb(etlg_ctx* c, etlg_batch* b, int32_t slot, int32_t what
 }
 
 // format 0: ClickHouse RowBinary (Insert / Update / Delete rows + the engine's CDC columns); 1: BigQuery protobuf; 2: Snowflake NDJSON;
-// 3: DuckLake SQL literals (dl_what: ETLG_DL_TUPLES / ETLG_DL_PREDICATES)
+// 3: DuckLake SQL literals (dl_what: ETLG_DL_TUPLES / ETLG_DL_PREDICATES / ETLG_DL_UPDATES)
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
                             uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd, uint32_t dl_what) {
   *out = nullptr;
@@ -604,6 +604,8 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   std::unique_ptr<etlg_rowbinary, void (*)(etlg_rowbinary*)> rb(new etlg_rowbinary, etlg_rowbinary_free);
   const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
   rb->v.on_device = on_dev ? 1u : 0u; rb->v.host_event = ~0ull;
+  const bool dl_upd = format == 3 && dl_what == ETLG_DL_UPDATES;   // partial Updates: two records per event and the col_ends array
+  rb->updates = dl_upd;
   std::vector<uint32_t> cols(2 * (size_t)nc);   // [nc, 2 nc): the key-layout words of the columns (RbJob.kcols)
   // A Delete that carries only the key: the reference expands it into a tombstone row (expand_key_row, clickhouse/core.rs:1437-1472)
   // when the replica identity is the primary key (or Full) — ensure_clickhouse_key_identity_is_primary_key, :1404-1427; identity
@@ -696,8 +698,9 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     q.row_full = sh.desc.row_bytes_full; q.row_key = sh.desc.row_bytes_key;
     q.blk = (uint32_t*)S; q.nblocks = nblk; q.row_event = (uint64_t*)A; q.row_base = (uint64_t*)(S + o_base);
     if (format == 3) {  // DuckLake: dl_selected (ducklake/core.rs:1824-1945, batches.rs:1128-1226)
-      q.dl = dl_what == ETLG_DL_TUPLES ? 1u : b->copy.active ? 3u : 2u;
+      q.dl = dl_upd ? 4u : dl_what == ETLG_DL_TUPLES ? 1u : b->copy.active ? 3u : 2u;
       q.dl_ident = sh.desc.n_ident != 0 ? 1u : 0u;
+      if (dl_upd) { q.n_cols = nc; q.fixed = bv.fixed; q.kcols = (const uint32_t*)(S + o_cols) + nc; }   // (the new row's cell states, the identity bits)
     }
     if (format == 1) {  // BigQuery: inserts, updates (one or two rows) and deletes (bigquery/core.rs:978-1036); the events the reference refuses stay with the host
       q.pb = 1; q.n_cols = nc; q.identity_pk = sh.identity_type == 1 ? 1u : 0u; q.pk_comparable = pk_comparable ? 1u : 0u;
@@ -724,7 +727,11 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     j.kcols = (const uint32_t*)(S + o_cols) + nc;
     j.nd_key_off = (const uint32_t*)(S + o_cols + (size_t)nc * 8); j.nd_keys = S + o_cols + (size_t)nc * 12 + 4;
     j.nd_zero_token = b->copy.active ? 1u : 0u;   // a table-copy batch (etlg_copy_decode): Insert rows under OffsetToken::zero (core.rs:683-699)
-    j.dl_what = dl_what == ETLG_DL_TUPLES ? 0u : b->copy.active ? 2u : 1u;   // (format 3; a copied row's predicate is over the primary key: delete_predicate_from_copy_row)
+    j.dl_what = dl_upd ? 3u : dl_what == ETLG_DL_TUPLES ? 0u : b->copy.active ? 2u : 1u;   // (format 3; a copied row's predicate is over the primary key: delete_predicate_from_copy_row)
+    if (dl_upd && n && nc) {  // col_ends: a block of its own, sized by the rows the select pass counted (not by 2 x events x columns)
+      HIPCHK(c, blk_take(c, (size_t)n * nc * 4 + 64, false, &rb->m.d_c, &rb->m.cap_c));
+      j.col_ends = (uint32_t*)rb->m.d_c;
+    }
   }
   int64_t total = 0;
   if (n) {
@@ -743,7 +750,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     if (code == 5) return set_error(c, ETLG_E_JSON, (int64_t)ev);   // a json cell that is not one JSON value: the decode error of codec/text.rs:126-134, as etlg_batch_columns reports it
     if (code == 3) {
       rb->v.status = ETLG_RB_NEEDS_HOST; rb->v.host_event = ev; rb->v.host_column = col;
-      blk_give(c, c->gen, rb->m.d_a, rb->m.cap_a, false); rb->m.d_a = nullptr;
+      blk_give(c, c->gen, rb->m.d_a, rb->m.cap_a, false); blk_give(c, c->gen, rb->m.d_c, rb->m.cap_c, false); rb->m.d_a = rb->m.d_c = nullptr;
       *out = rb.release();
       return ETLG_OK;
     }
@@ -782,13 +789,16 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   }
   const uint8_t* base_a = A; const uint8_t* base_b = (const uint8_t*)rb->m.d_b;
   if (!on_dev) {
-    HIPCHK(c, blk_take(c, o_len + al((size_t)total) + 64, true, (void**)&rb->m.h, &rb->m.cap_h));
+    const size_t ce_bytes = rb->m.d_c ? (size_t)n * nc * 4 : 0;
+    HIPCHK(c, blk_take(c, o_len + al((size_t)total) + ce_bytes + 64, true, (void**)&rb->m.h, &rb->m.cap_h));
     HIPCHK(c, hipMemcpyAsync(rb->m.h, A, o_off + (n + 1) * 8, hipMemcpyDeviceToHost, s));
     if (total) HIPCHK(c, hipMemcpyAsync(rb->m.h + o_len, rb->m.d_b, (size_t)total, hipMemcpyDeviceToHost, s));
     base_a = rb->m.h; base_b = rb->m.h + o_len;
-  }
+    if (ce_bytes) HIPCHK(c, hipMemcpyAsync(rb->m.h + o_len + al((size_t)total), rb->m.d_c, ce_bytes, hipMemcpyDeviceToHost, s));
+    if (ce_bytes) rb->col_ends = (const uint32_t*)(rb->m.h + o_len + al((size_t)total));
+  } else rb->col_ends = (const uint32_t*)rb->m.d_c;
   HIPCHK(c, hipStreamSynchronize(s));   // block S is freed on return
-  if (!on_dev) { blk_give(c, c->gen, rb->m.d_a, rb->m.cap_a, false); blk_give(c, c->gen, rb->m.d_b, rb->m.cap_b, false); rb->m.d_a = rb->m.d_b = nullptr; }
+  if (!on_dev) { blk_give(c, c->gen, rb->m.d_a, rb->m.cap_a, false); blk_give(c, c->gen, rb->m.d_b, rb->m.cap_b, false); blk_give(c, c->gen, rb->m.d_c, rb->m.cap_c, false); rb->m.d_a = rb->m.d_b = rb->m.d_c = nullptr; }
   rb->v.n_rows = n; rb->v.n_bytes = (uint64_t)total;
   rb->v.row_event = (const uint64_t*)base_a; rb->v.row_offsets = (const int64_t*)(base_a + o_off); rb->v.bytes = total ? base_b : nullptr;
   *out = rb.release();
@@ -798,6 +808,12 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
 int32_t etlg_rowbinary_view_get(const etlg_rowbinary* rb, etlg_rowbinary_view* out) {
   if (!rb || !out) return ETLG_InvalidArgument;
   *out = rb->v;
+  return ETLG_OK;
+}
+
+int32_t etlg_rowbinary_col_ends_get(const etlg_rowbinary* rb, const uint32_t** col_ends) {
+  if (!rb || !col_ends || !rb->updates) return ETLG_InvalidArgument;
+  *col_ends = rb->col_ends;
   return ETLG_OK;
 }
 

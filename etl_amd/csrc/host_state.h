@@ -511,5 +511,7 @@ struct etlg_columns {  // etlg_batch_columns, etlg_batch_iceberg
 struct etlg_rowbinary {
   etlg_rowbinary_view v{};
   HandoffBlocks m;
+  bool updates = false;               // built by etlg_batch_duckdb(ETLG_DL_UPDATES): `col_ends` is valid (etlg_rowbinary_col_ends_get)
+  const uint32_t* col_ends = nullptr; // [n_rows x n_cols]: block d_c (device) or behind the bytes in the pinned block (host); null without rows
 };
 

@@ -140,15 +140,18 @@ class Batch:
     def duckdb(self, slot, names, what=abi.DL_TUPLES, on_device=False):
         """DuckLake SQL literals of schema slot `slot`, encoded on the device (etlg_batch_duckdb): `what=abi.DL_TUPLES` one
         "(lit, lit, ...)" per row the sink upserts, `abi.DL_PREDICATES` one `"col" = lit AND ...` per row image it deletes / matches
-        by; no separator between records. `names` as for ndjson(). Raises EtlError for ETLG_E_JSON and bad arguments;
-        `RowBinary.status == abi.RB_NEEDS_HOST` when a cell has no device encoding."""
+        by, `abi.DL_UPDATES` two records per partial Update — its SET clause `"col" = lit, ...`, then its predicate — with
+        `RowBinary.col_ends()` cutting every record into its columns' pieces; no separator between records. `names` as for ndjson().
+        Raises EtlError for ETLG_E_JSON and bad arguments; `RowBinary.status == abi.RB_NEEDS_HOST` when a cell has no device encoding."""
         raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
         blob = b"".join(n + b"\0" for n in raw)
         out = C.c_void_p()
         rc = self.dec.L.etlg_batch_duckdb(self.dec.h, self.h, slot, what, blob, len(raw), abi.F_OUTPUT_ON_DEVICE if on_device else 0, C.byref(out))
         if rc != abi.OK or not out:
             raise self.dec.last_error()
-        return RowBinary(self.dec, out)
+        r = RowBinary(self.dec, out)
+        r.n_cols = len(raw)
+        return r
 
     def close(self):
         if self.h:
@@ -221,6 +224,7 @@ class RowBinary:
 
     def __init__(self, dec, handle):
         self.dec, self.h = dec, handle
+        self.n_cols = None      # the slot's width, of a Batch.duckdb() result (col_ends)
         self.view = abi.RowBinaryView()
         dec.L.etlg_rowbinary_view_get(handle, C.byref(self.view))
 
@@ -241,6 +245,18 @@ class RowBinary:
 
     def row_event(self):
         return self._np(self.view.row_event, self.n_rows * 8, np.uint64)
+
+    def col_ends_ptr(self):
+        """Address of the n_rows * n_cols u32 array of a Batch.duckdb(what=abi.DL_UPDATES) result (etlg_rowbinary_col_ends_get), on
+        the host or the device like the view's arrays. Raises EtlError (InvalidArgument) for any other object."""
+        p = C.c_void_p()
+        if self.dec.L.etlg_rowbinary_col_ends_get(self.h, C.byref(p)) != abi.OK:
+            raise EtlError(abi.InvalidArgument, abi.InvalidArgument, "etlg_rowbinary_col_ends_get: not an ETLG_DL_UPDATES result", None, -1)
+        return p.value or 0
+
+    def col_ends(self):
+        """[n_rows, n_cols] u32: bytes of record r written once column c is done (host-resident results)."""
+        return self._np(self.col_ends_ptr(), self.n_rows * self.n_cols * 4, np.uint32).reshape(self.n_rows, self.n_cols)
 
     def close(self):
         if self.h:

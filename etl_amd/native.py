@@ -21,7 +21,7 @@ EXPORTS = [
     "etlg_ctx_profile_read", "etlg_scan_boundaries", "etlg_copy_decode", "etlg_frame_tags",
     "etlg_table_forget", "etlg_table_cache_get", "etlg_host_alloc", "etlg_host_free", "etlg_control_stream", "etlg_shard_plan", "etlg_shard_replay",
     "etlg_batch_columns", "etlg_columns_view_get", "etlg_columns_free", "etlg_batch_iceberg", "etlg_columns_changelog_get",
-    "etlg_batch_rowbinary", "etlg_batch_protobuf", "etlg_batch_ndjson", "etlg_batch_duckdb", "etlg_rowbinary_view_get", "etlg_rowbinary_free", "etlg_batch_size_hints",
+    "etlg_batch_rowbinary", "etlg_batch_protobuf", "etlg_batch_ndjson", "etlg_batch_duckdb", "etlg_rowbinary_view_get", "etlg_rowbinary_col_ends_get", "etlg_rowbinary_free", "etlg_batch_size_hints",
     "etlg_batch_finish_cells",
 ]
 
@@ -104,6 +104,7 @@ def lib():
     L.etlg_batch_ndjson.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.etlg_batch_duckdb.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.etlg_rowbinary_view_get.argtypes = [C.c_void_p, C.c_void_p]
+    L.etlg_rowbinary_col_ends_get.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.etlg_rowbinary_free.argtypes = [C.c_void_p]
     L.etlg_rowbinary_free.restype = None
     L.etlg_batch_size_hints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]

@@ -873,7 +873,8 @@ int32_t etlg_batch_ndjson(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot,
  * call, with NO separator or terminator between them (row_offsets cut them):
  *   ETLG_DL_TUPLES      one "(lit, lit, ...)" per row the sink upserts (table_row_to_sql_literal_ref: hashed into the batch identity,
  *                       inserted as VALUES text): Insert -> the row; Update with a full new row -> the new row; a table-copy batch
- *                       (etlg_copy_decode) -> every row. A partial Update is counted in n_host_rows; Deletes give nothing.
+ *                       (etlg_copy_decode) -> every row. A partial Update is counted in n_host_rows; Deletes give nothing. (The partial
+ *                       Updates counted here are served by ETLG_DL_UPDATES.)
  *   ETLG_DL_PREDICATES  one `"col" = lit AND "col" IS NULL` per row image the sink deletes / matches by (delete_predicate_from_row,
  *                       batches.rs:1229-1316): Update / Delete -> from the old image (a full image: the cells at the identity columns'
  *                       positions; a key image: its cells), identity columns in slot order; an Update without an old image -> from the
@@ -881,7 +882,23 @@ int32_t etlg_batch_ndjson(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot,
  *                       image and a Delete without one are counted in n_host_rows; Inserts give nothing. A table-copy batch -> every
  *                       row, over the PRIMARY-KEY columns (etlg_col.primary_key). A NULL key cell is `"col" IS NULL`. A slot without
  *                       identity columns: every Update / Delete is counted in n_host_rows (the host raises "DuckLake delete requires a
- *                       replica identity"); a copy batch without primary-key columns gives empty records.
+ *                       replica identity"); a copy batch without primary-key columns gives empty records. (The partial Updates
+ *                       counted here are served by ETLG_DL_UPDATES.)
+ *   ETLG_DL_UPDATES     every PARTIAL Update (a new row with unchanged-TOAST columns no old image completes), which the sink applies as
+ *                       one `UPDATE ... SET <assignments> WHERE <predicate>` (ducklake/core.rs:1846-1913, batches.rs:1179-1190): TWO
+ *                       consecutive records with the same row_event.
+ *                       Record 2k, the SET clause: update_assignments_from_partial_row(...).join(", ") (batches.rs:1319-1399, 2125) —
+ *                       `"col" = lit` for every column whose cell is not MISSING, in slot order; a NULL cell is `"col" = NULL`; the
+ *                       literals are those of ETLG_DL_TUPLES.
+ *                       Record 2k+1, the predicate of the mutation's delete_row, as ETLG_DL_PREDICATES writes it: from the old image (a
+ *                       full image: the cells at the identity columns' positions; a key image: its cells); without an old image from
+ *                       the partial new row's cells at the identity columns (key_row_from_updated_partial_row, core.rs:846-).
+ *                       Counted in n_host_rows, without records (the host raises the reference's error at the first of them): a partial
+ *                       Update of a slot without identity columns ("DuckLake update requires a replica identity"), one without an old
+ *                       image whose identity column is MISSING ("DuckLake partial update is missing replica-identity columns") and one
+ *                       with no present cell at all ("DuckLake partial update row has no assignments"). Inserts, Deletes, Updates with
+ *                       a full new row and a table-copy batch give nothing and are NOT host rows for this `what`.
+ *                       etlg_rowbinary_col_ends_get gives where the columns' pieces of every record end.
  * col_names: as for etlg_batch_ndjson (n_names must be the slot's n_cols, ETLG_InvalidArgument otherwise; so is an unknown `what`).
  * Names are quoted like quote_double_identifier (ducklake/sql.rs:10-12): '"' doubled, nothing else changed.
  * Values: NULL; TRUE / FALSE; integers in decimal; float8 as Rust's f64 Display (shortest digits, positional, never an exponent: 1,
@@ -898,12 +915,22 @@ int32_t etlg_batch_ndjson(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot,
  * Errors: a json cell or element that is not one JSON value fails the call with ETLG_E_JSON at its event before anything else; the sink
  * has no encoding error on this path. A DEFERRED scalar, an array literal the walkers do not take apart and json beyond json_display's
  * limits give status ETLG_RB_NEEDS_HOST with the first such event and column in event order; for ETLG_DL_PREDICATES only the key
- * columns are looked at. Flags: ETLG_F_OUTPUT_ON_DEVICE. The result is an etlg_rowbinary (same view). */
+ * columns are looked at; for ETLG_DL_UPDATES the SET record looks at every present column and the predicate record at its key columns,
+ * and within an event the SET record's first such column is reported, else the predicate record's. Flags: ETLG_F_OUTPUT_ON_DEVICE. The result is an etlg_rowbinary (same view). */
 #define ETLG_DL_TUPLES 0u
 #define ETLG_DL_PREDICATES 1u
+#define ETLG_DL_UPDATES 3u
 int32_t etlg_batch_duckdb(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, int32_t what, const char* col_names, uint32_t n_names,
                           uint32_t flags, etlg_rowbinary** out);
 int32_t etlg_rowbinary_view_get(const etlg_rowbinary* rb, etlg_rowbinary_view* out);
+/* ETLG_DL_UPDATES only (any other object: ETLG_InvalidArgument): n_rows * n_cols u32 entries, on the host or the device like the
+ * other arrays of the view, freed with the object. col_ends[r * n_cols + c] is the number of bytes of record r written once column c
+ * is done; a column that contributes nothing (a MISSING cell, a column outside the key) repeats the previous value, or 0 in front.
+ * Piece c of a record is (col_ends[c - 1], col_ends[c]) without its leading separator (", " / " AND "): the host rebuilds
+ * Vec<String> assignments from the pieces and feeds hash_partial_table_row_ref (batches.rs:1562-1594) with (column index, literal),
+ * the literal being the piece minus len(quoted name) + 3. An object without records (n_rows == 0, also one that came back as
+ * ETLG_RB_NEEDS_HOST) gives ETLG_OK and a null pointer. */
+int32_t etlg_rowbinary_col_ends_get(const etlg_rowbinary* rb, const uint32_t** col_ends);
 void etlg_rowbinary_free(etlg_rowbinary* rb);
 
 /* --------------------------------------------------------------- size hints */

@@ -1,4 +1,5 @@
-"""etlg_batch_duckdb on HBM-resident 64 MiB batches (cfg2, cfg3, the type-matrix table), warm, both `what` values alternating with
+"""etlg_batch_duckdb on HBM-resident 64 MiB batches (cfg2, cfg3, the type-matrix table, and cfg3's table with every Update leaving
+one TEXT column unchanged: the workload of ETLG_DL_UPDATES), warm, the three `what` values alternating with
 etlg_batch_ndjson on the same batch in the same process (the yardstick: same kernels, similar bytes out): per call the median wall time
 (device output; the call synchronises its stream three times inside — row count, sizes, end — so wall time is what a caller sees) and
 the median time between two device events recorded on the CONTEXT'S stream around the call (the context is given a torch stream of
@@ -29,6 +30,7 @@ def one(name, prime, buf, offs, names, reps=20, warm=3):
     out = {"workload": name, "batch_bytes": int(len(buf))}
     calls = [("tuples", lambda: b.duckdb(0, names, what=abi.DL_TUPLES, on_device=True)),
              ("predicates", lambda: b.duckdb(0, names, what=abi.DL_PREDICATES, on_device=True)),
+             ("updates", lambda: b.duckdb(0, names, what=abi.DL_UPDATES, on_device=True)),
              ("ndjson", lambda: b.ndjson(0, names, on_device=True))]
     for fmt, call in list(calls):
         try:
@@ -62,16 +64,21 @@ def one(name, prime, buf, offs, names, reps=20, warm=3):
         o["out_GBps"] = round(o["bytes"] / (ms * 1e-3) / 1e9, 1)
         o["out_frac_of_hbm_peak"] = round(o["bytes"] / (ms * 1e-3) / HBM_PEAK, 4)
     if "ms_median" in out.get("ndjson", {}):
-        for fmt in ("tuples", "predicates"):
+        for fmt in ("tuples", "predicates", "updates"):
             if "ms_median" in out.get(fmt, {}):
                 out[fmt]["ratio_to_ndjson"] = round(out[fmt]["ms_median"] / out["ndjson"]["ms_median"], 2)
     b.close(); d.close()
     return out
 
 
+def cfg3_toast_updates():
+    """cfg3's table and mix, every Update without an old image and with 'u' on one TEXT column: partial Updates only."""
+    return synth.Workload([synth.table_mixed()], 0xE710003, rows_per_txn=500, mix=(60, 30, 10), upd_key=0, upd_toast=100, name="cfg3_toast_updates")
+
+
 def main():
     res = []
-    for mk in (synth.cfg2, synth.cfg3):
+    for mk in (synth.cfg2, synth.cfg3, cfg3_toast_updates):
         w = mk()
         buf, offs = w.fill(64 << 20)
         res.append(one(w.name if hasattr(w, "name") else mk.__name__, w.register, buf, offs, [c[0] for c in w.schema_cols(w.tables[0])]))
