@@ -10,7 +10,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libetl_gfx950.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["kernels.hip", "fused.hip", "cells.hip", "rows.hip", "plan.hip", "scan.hip", "copy.hip", "columns.hip", "host.cpp"]
+# in the order they are started: the sources that take longest to compile first (the row formats and the Arrow columns instantiate
+# json_display many times), so that a build takes about as long as its longest source
+SOURCES = ["rowformats.hip", "rowformats_dl.hip", "columns.hip", "kernels.hip", "finish.hip", "host.cpp", "cells.hip", "fused.hip", "rows.hip", "plan.hip", "scan.hip",
+           "copy.hip", "check.hip"]
 # per-source optimisation level: k_fused is measurably faster built for size (88 vs 93 us on cfg2, tools/variants.sh);
 # k_cells and the rest are not
 # (round 6: so is k_copy_cells — cells.hip at -Os 468 / 304 us against 482-486 / 313-317 on the two table-copy workloads, same box;
@@ -18,7 +21,7 @@ SOURCES = ["kernels.hip", "fused.hip", "cells.hip", "rows.hip", "plan.hip", "sca
 OPT = {"fused.hip": "-Os", "cells.hip": "-Os"}
 DEFS = {}   # no per-source feature flags: one code path per kernel
 # what every object depends on beside its own source (the shared headers); host.cpp also on its parts
-COMMON = ["../build.py", "dev_types.h", "codec.hip.h", "cellparse.hip.h", "check.hip.h", "lookback.hip.h", "utf8_swar.h", "float_fast.h", "float_slow.h", "pow5_table.h", "float_json.h", "ryu_table.h", "float_display.h", os.path.join("..", "..", "include", "etlg.h")]
+COMMON = ["../build.py", "dev_types.h", "codec.hip.h", "cellparse.hip.h", "handoff.hip.h", "rowformats.hip.h", "lookback.hip.h", "utf8_swar.h", "float_fast.h", "float_slow.h", "pow5_table.h", "float_json.h", "ryu_table.h", "float_display.h", os.path.join("..", "..", "include", "etlg.h")]
 EXTRA = {"fused.hip": ["fixed_tile.hip.h"], "host.cpp": ["host_state.h", "host_control.inc", "host_handoff.inc", "host_orchestrate.inc"]}
 DEPS = SOURCES + COMMON + [d for v in EXTRA.values() for d in v]   # (the library as a whole)
 
@@ -47,11 +50,11 @@ def build_native(force=False, verbose=False):
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
 
-    # the sources are independent translation units: compiled side by side, the longest (columns.hip: most of the build's time) first,
-    # so that the build takes as long as that one source instead of the sum of all
+    # the sources are independent translation units: compiled side by side in the order of SOURCES (longest first), so that the build
+    # takes as long as its longest source instead of the sum of all
     jobs = max(1, min(len(SOURCES), int(os.environ.get("MAX_JOBS", "0") or 0) or (os.cpu_count() or 1), 16))
     with ThreadPoolExecutor(jobs) as ex:
-        list(ex.map(compile_one, sorted(SOURCES, key=lambda s: s != "columns.hip")))
+        list(ex.map(compile_one, SOURCES))
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd))

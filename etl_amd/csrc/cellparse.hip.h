@@ -1,4 +1,4 @@
-// Cell-text grammars shared by the hand-off kernels (columns.hip) and the multi-pass decode (kernels.hip): is a json / jsonb text one
+// Cell-text grammars shared by the hand-off kernels (columns.hip, rowformats.hip, finish.hip) and the multi-pass decode (kernels.hip): is a json / jsonb text one
 // JSON value (json_valid), and the array-literal state machine of the reference with its element parsers (arr_strip_dims, arr_walk,
 // arr_spans). cell_text_error() joins them into the question ETLG_F_CHECK_CELLS asks of a DEFERRED cell: would the reference's
 // parse_cell_from_postgres_text have failed on this text, and with which code?

@@ -9,9 +9,8 @@
 //
 // No host stop: the event count is read from the result block on the device, the grid is sized from the frame count the host has (a
 // frame emits at most one event). Thread u takes (row image, column) u / n_events of event u % n_events, as the finish pass arranges
-// its cells (fin_thread_cell, columns.hip): the lanes of a wave hold ONE column of consecutive events — one class, one code path.
+// its cells (fin_thread_cell, finish.hip): the lanes of a wave hold ONE column of consecutive events — one class, one code path.
 // One ballot and at most one atomic per wave. Integer / byte work, no MFMA.
-#pragma once
 #include "cellparse.hip.h"
 
 namespace etlg {

@@ -217,7 +217,7 @@ struct PlanParams {
                                // (like the frames of a Begin's / Commit's length) and is priced as a key row when that is 'D'
 };
 
-// ---- columnar hand-off (columns.hip)
+// ---- columnar hand-off (columns.hip, rowformats.hip, finish.hip)
 struct ColSel {            // which events are rows of the hand-off
   const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_body;
   uint64_t n_events;
@@ -283,7 +283,7 @@ struct HintJob {           // Event::size_hint per event (k_size_hints)
   unsigned long long* out;
 };
 
-struct FinJob {            // the finish pass (k_fin_count / k_fin_fill, columns.hip)
+struct FinJob {            // the finish pass (k_fin_count / k_fin_fill, finish.hip)
   const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_body;
   uint8_t* fixed; uint8_t* heap;
   uint64_t n_events;

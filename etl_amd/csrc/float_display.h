@@ -1,4 +1,4 @@
-// float8 -> the text Rust's `f64` Display writes (`value.to_string()`), shared by the DuckLake literal kernels (columns.hip, dl_row)
+// float8 -> the text Rust's `f64` Display writes (`value.to_string()`), shared by the DuckLake literal kernels (rowformats.hip.h, dl_row)
 // and a host-side unit test (tests/test_float_display.py compiles this header with g++ and checks it against libstdc++'s
 // std::to_chars(..., std::chars_format::fixed) on tens of millions of bit patterns).
 //
@@ -9,7 +9,7 @@
 //   0 < kk < n      a '.' after the first kk digits            12.34
 //   kk <= 0         "0.", -kk zeros, the digits                0.1, 0.000...5 (5e-324: "0." + 323 zeros + "5", 326 bytes; 327 with a '-')
 // zero is "0", negative zero "-0", a leading '-' for negative values; never a trailing ".0". NaN / inf never get here (the DuckLake
-// sink writes CAST('NaN' AS DOUBLE) ... for them, columns.hip dl_float).
+// sink writes CAST('NaN' AS DOUBLE) ... for them, rowformats.hip.h dl_float).
 // A float4 is widened first (`f as f64`, exact), so 0.1f32 prints 0.10000000149011612: f32_widen_bits does that on the bits, so that
 // the result does not hang on the denormal mode the kernel was compiled with.
 #pragma once

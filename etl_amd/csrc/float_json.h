@@ -1,5 +1,5 @@
 // float4 / float8 -> the text serde_json writes for them (serialize_f32 / serialize_f64: ryu's `format32` / `format64`), shared by
-// the NDJSON row kernels (columns.hip, nd_row) and a host-side unit test (tests/test_float_json.py compiles this header with g++ and
+// the NDJSON row kernels (rowformats.hip.h, nd_row) and a host-side unit test (tests/test_float_json.py compiles this header with g++ and
 // checks it against libstdc++'s std::to_chars on tens of millions of bit patterns).
 //
 // ryu and serde_json are crates.io dependencies of the reference and are not vendored with it: what follows RESTATES their published

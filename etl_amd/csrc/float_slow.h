@@ -9,7 +9,7 @@
 // value — the same bits glibc strtod / strtof return, which is what the oracle compares against
 // (tests/native/float_slow_check.cpp: millions of hard cases through a host build of this header).
 //
-// Used only by the finish pass (columns.hip: k_fin_fill), one thread per cell: the digit buffer lives in the
+// Used only by the finish pass (finish.hip: k_fin_fill), one thread per cell: the digit buffer lives in the
 // thread's private memory, so no decode kernel pays for it.
 #pragma once
 #include <stdint.h>

@@ -1403,7 +1403,7 @@ void etlg_batch_free(etlg_batch* b) {
   delete b;
 }
 
-#include "host_handoff.inc"   // columnar hand-off: etlg_batch_columns / _rowbinary / _protobuf / _size_hints (columns.hip)
+#include "host_handoff.inc"   // columnar hand-off: etlg_batch_columns / _rowbinary / _protobuf / _size_hints (columns.hip, rowformats.hip, finish.hip)
 
 }  // extern "C"
 

@@ -1,7 +1,16 @@
-// Part of host.cpp (included there, one translation unit): the columnar hand-off calls over a decoded, device-resident batch (kernels: columns.hip).
+// Part of host.cpp (included there, one translation unit): the columnar hand-off calls over a decoded, device-resident batch (kernels: columns.hip, rowformats.hip, finish.hip).
 
 extern "C++" {
-// ---- columnar hand-off (columns.hip)
+// ---- columnar hand-off (columns.hip, rowformats.hip, finish.hip)
+// What every hand-off call does first: an ASYNC batch is synchronised — one that ended in a decode error gives the caller that error
+// (fail-fast, as the reference), not a hand-off of the prefix — and a batch that is not device-resident is refused. `refusal`: the
+// entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
+#define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
+static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal) {
+  if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }
+  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, refusal);
+  return ETLG_OK;
+}
 namespace {
 struct ColPlan { uint32_t kind, vbytes; bool var; uint32_t child = 0, child_bytes = 0, elem = 0, fmt = 0; };   // fmt: the kernels' internal kind of a formatted string column (columns.hip AK_*_STR)
 ColPlan list_plan(uint32_t elem) {  // array literals the device parses: element classes with a fixed-width value
@@ -52,11 +61,11 @@ ColPlan col_plan(uint32_t cls) {
 // updates, 2 full old rows of deletes); changelog: the Iceberg sink's rows — the refused events are counted in the selection's own
 // launches and read back with the row count, and the two CDC columns are written behind the data columns by one more launch
 // (etlg_k_col_cdc), so both calls stop for the device equally often.
+static bool slot_known(const etlg_ctx* c, int32_t slot) { return slot >= 0 && (size_t)slot < c->slots.size(); }
 static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t sel_kinds, uint32_t row_kinds, uint32_t flags, bool changelog, etlg_columns** out) {
   *out = nullptr;
-  if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }   // an ASYNC batch that ended in a decode error: the caller gets that error (fail-fast, as the reference), not a hand-off of the prefix
-  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, changelog ? "etlg_batch_iceberg needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)" : "etlg_batch_columns needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
-  if (slot < 0 || (size_t)slot >= c->slots.size() || !sel_kinds) return ETLG_InvalidArgument;
+  if (const int32_t rc = batch_ready(c, b, changelog ? "etlg_batch_iceberg" NEEDS_DEVICE : "etlg_batch_columns" NEEDS_DEVICE)) return rc;
+  if (!slot_known(c, slot) || !sel_kinds) return ETLG_InvalidArgument;
   const bool parse_arrays = (row_kinds & ETLG_ROWS_PARSE_ARRAYS) != 0;
   const bool format_json = (row_kinds & ETLG_ROWS_FORMAT_JSON) != 0;
   const SlotHost& sh = *c->slots[(size_t)slot];
@@ -364,8 +373,7 @@ int32_t etlg_columns_changelog_get(const etlg_columns* cs, etlg_changelog_info* 
 
 int32_t etlg_batch_size_hints(etlg_ctx* c, etlg_batch* b, const etlg_size_model* m, uint32_t flags, uint64_t* out) {
   if (!c || !b || !m || b->ctx != c) return ETLG_InvalidArgument;
-  if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }   // an ASYNC batch that ended in a decode error: the caller gets that error (fail-fast, as the reference), not a hand-off of the prefix
-  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, "etlg_batch_size_hints needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
+  if (const int32_t rc = batch_ready(c, b, "etlg_batch_size_hints" NEEDS_DEVICE)) return rc;
   const etlg_batch_view& bv = b->v;
   const uint64_t ne = bv.n_events;
   if (!ne) return ETLG_OK;
@@ -503,8 +511,7 @@ int32_t finish_cells(etlg_ctx* c, etlg_batch* b, uint32_t what, etlg_finish_stat
 
 int32_t etlg_batch_finish_cells(etlg_ctx* c, etlg_batch* b, uint32_t what, etlg_finish_stats* stats) {
   if (!c || !b || b->ctx != c) return ETLG_InvalidArgument;
-  if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }   // (an ASYNC batch that ended in a decode error: the caller gets that error)
-  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, "etlg_batch_finish_cells needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
+  if (const int32_t rc = batch_ready(c, b, "etlg_batch_finish_cells" NEEDS_DEVICE)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return finish_cells(c, b, what, stats);
 }
@@ -522,6 +529,20 @@ void etlg_columns_free(etlg_columns* cs) {
 }
 
 struct NdKeys { std::vector<uint32_t> off; std::string bytes; };   // format 2: the escaped `"name":` of every column, back to back
+// n NUL-separated names, each as '"' + its characters through esc(bytes, ch) + close; off: where every key begins, and the end
+static NdKeys quoted_names(const char* names, uint32_t n, const char* close, void (*esc)(std::string&, unsigned char)) {
+  NdKeys k;
+  const char* p = names;
+  for (uint32_t i = 0; i < n; i++) {
+    k.off.push_back((uint32_t)k.bytes.size());
+    k.bytes.push_back('"');
+    for (; *p; p++) esc(k.bytes, (unsigned char)*p);
+    p++;
+    k.bytes += close;
+  }
+  k.off.push_back((uint32_t)k.bytes.size());
+  return k;
+}
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
                             uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd = nullptr, uint32_t dl_what = 0u);
 
@@ -541,29 +562,19 @@ int32_t etlg_batch_protobuf(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t f
 int32_t etlg_batch_ndjson(etlg_ctx* c, etlg_batch* b, int32_t slot, const char* col_names, uint32_t n_names, uint32_t flags, etlg_rowbinary** out) {
   if (!c || !b || !out || b->ctx != c || (n_names && !col_names)) return ETLG_InvalidArgument;
   *out = nullptr;
-  if (slot < 0 || (size_t)slot >= c->slots.size()) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
   if (n_names != c->slots[(size_t)slot]->desc.n_cols) return lib_error(c, ETLG_InvalidArgument, "Snowflake row width mismatch: one column name per replicated column");
-  NdKeys k;
-  const char* p = col_names;
-  for (uint32_t i = 0; i < n_names; i++) {
-    k.off.push_back((uint32_t)k.bytes.size());
-    k.bytes.push_back('"');
-    for (; *p; p++) {
-      const unsigned char ch = (unsigned char)*p;
-      static const char hexd[] = "0123456789abcdef";
-      if (ch == '"' || ch == '\\') { k.bytes.push_back('\\'); k.bytes.push_back((char)ch); }
-      else if (ch == 8) k.bytes += "\\b";
-      else if (ch == 12) k.bytes += "\\f";
-      else if (ch == '\n') k.bytes += "\\n";
-      else if (ch == '\r') k.bytes += "\\r";
-      else if (ch == '\t') k.bytes += "\\t";
-      else if (ch < 0x20) { k.bytes += "\\u00"; k.bytes.push_back(hexd[ch >> 4]); k.bytes.push_back(hexd[ch & 15]); }
-      else k.bytes.push_back((char)ch);
-    }
-    p++;
-    k.bytes += "\":";
-  }
-  k.off.push_back((uint32_t)k.bytes.size());
+  const NdKeys k = quoted_names(col_names, n_names, "\":", [](std::string& o, unsigned char ch) {
+    static const char hexd[] = "0123456789abcdef";
+    if (ch == '"' || ch == '\\') { o.push_back('\\'); o.push_back((char)ch); }
+    else if (ch == 8) o += "\\b";
+    else if (ch == 12) o += "\\f";
+    else if (ch == '\n') o += "\\n";
+    else if (ch == '\r') o += "\\r";
+    else if (ch == '\t') o += "\\t";
+    else if (ch < 0x20) { o += "\\u00"; o.push_back(hexd[ch >> 4]); o.push_back(hexd[ch & 15]); }
+    else o.push_back((char)ch);
+  });
   return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, 2u, out, &k);
 }
 
@@ -575,18 +586,9 @@ int32_t etlg_batch_duckdb(etlg_ctx* c, etlg_batch* b, int32_t slot, int32_t what
   if (!c || !b || !out || b->ctx != c || (n_names && !col_names)) return ETLG_InvalidArgument;
   *out = nullptr;
   if ((uint32_t)what != ETLG_DL_TUPLES && (uint32_t)what != ETLG_DL_PREDICATES && (uint32_t)what != ETLG_DL_UPDATES) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_duckdb: what must be ETLG_DL_TUPLES, ETLG_DL_PREDICATES or ETLG_DL_UPDATES");
-  if (slot < 0 || (size_t)slot >= c->slots.size()) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
   if (n_names != c->slots[(size_t)slot]->desc.n_cols) return lib_error(c, ETLG_InvalidArgument, "DuckLake row width mismatch: one column name per replicated column");
-  NdKeys k;
-  const char* p = col_names;
-  for (uint32_t i = 0; i < n_names; i++) {
-    k.off.push_back((uint32_t)k.bytes.size());
-    k.bytes.push_back('"');
-    for (; *p; p++) { if (*p == '"') k.bytes.push_back('"'); k.bytes.push_back(*p); }
-    p++;
-    k.bytes.push_back('"');
-  }
-  k.off.push_back((uint32_t)k.bytes.size());
+  const NdKeys k = quoted_names(col_names, n_names, "\"", [](std::string& o, unsigned char ch) { if (ch == '"') o.push_back('"'); o.push_back((char)ch); });
   return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, 3u, out, &k, (uint32_t)what);
 }
 
@@ -595,9 +597,8 @@ int32_t etlg_batch_duckdb(etlg_ctx* c, etlg_batch* b, int32_t slot, int32_t what
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
                             uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd, uint32_t dl_what) {
   *out = nullptr;
-  if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }   // an ASYNC batch that ended in a decode error: the caller gets that error (fail-fast, as the reference), not a hand-off of the prefix
-  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, "etlg_batch_rowbinary needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
-  if (slot < 0 || (size_t)slot >= c->slots.size() || (engine != ETLG_CH_MERGE_TREE && engine != ETLG_CH_REPLACING_MERGE_TREE)) return ETLG_InvalidArgument;
+  if (const int32_t rc = batch_ready(c, b, "etlg_batch_rowbinary" NEEDS_DEVICE)) return rc;   // (the message names this entry point for all four formats)
+  if (!slot_known(c, slot) || (engine != ETLG_CH_MERGE_TREE && engine != ETLG_CH_REPLACING_MERGE_TREE)) return ETLG_InvalidArgument;
   const SlotHost& sh = *c->slots[(size_t)slot];
   const uint32_t nc = sh.desc.n_cols;
   if (format == 0 && n_flags != nc + 2) return lib_error(c, ETLG_ConversionError, "ClickHouse RowBinary row width mismatch");

@@ -97,7 +97,7 @@ constexpr int kCopyCells = 12;  // ... of the table-copy rows -> arena kernel (c
 constexpr int kPlanPre = 13;    // ... of the plan's sidecar pre-pass (plan.hip, k_plan_pre)
 constexpr int kRows = 14;       // ... of the row-synchronous kernel (rows.hip)
 constexpr int kWriteChk = 15;   // ... of k_write with ETLG_F_CHECK_CELLS (kernels.hip, k_write_chk)
-constexpr int kChkCells = 16;   // ... of the cell check behind a single-pass kernel (check.hip.h, k_chk_cells)
+constexpr int kChkCells = 16;   // ... of the cell check behind a single-pass kernel (check.hip, k_chk_cells)
 constexpr int kProfSlots = 17;
 
 namespace {

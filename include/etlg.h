@@ -911,7 +911,7 @@ int32_t etlg_batch_ndjson(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot,
  * quote_literal is pg_escape 0.1.1, RESTATED FROM THE CRATE'S DOCUMENTATION — its source is not vendored with the reference and the
  * reference's tests pin only the plain arm ('alice'): a ' is doubled; a text that holds a backslash has every backslash doubled and is
  * prefixed with a space and E (a\b -> " E'a\\b'" in C notation); otherwise plain '...'. The quote doubling and the backslash arm are
- * UNPINNED (one function on each side: dl_quote in columns.hip, quote_literal in tests/ducklake_literals.py).
+ * UNPINNED (one function on each side: dl_quote in rowformats.hip.h, quote_literal in tests/ducklake_literals.py).
  * Errors: a json cell or element that is not one JSON value fails the call with ETLG_E_JSON at its event before anything else; the sink
  * has no encoding error on this path. A DEFERRED scalar, an array literal the walkers do not take apart and json beyond json_display's
  * limits give status ETLG_RB_NEEDS_HOST with the first such event and column in event order; for ETLG_DL_PREDICATES only the key

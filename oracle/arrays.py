@@ -14,7 +14,7 @@ STRING_ARRAY_OIDS = {1009, 1015, 1014, 1002, 1003}      # text[] varchar[] bpcha
 NUMERIC_A, BYTEA_A, TIMETZ_A = 1231, 1001, 1270
 JSON_ARRAY_OIDS = {199, 3807}
 VAR_ARRAY_OIDS = STRING_ARRAY_OIDS | {NUMERIC_A, BYTEA_A, TIMETZ_A} | JSON_ARRAY_OIDS
-ELEM_MAX = 40                                           # kArrElemMax (columns.hip): a longer numeric / timetz element is handed back
+ELEM_MAX = 40                                           # kArrElemMax (cellparse.hip.h): a longer numeric / timetz element is handed back
 JSON_ELEM_MAX = 256                                     # kJsonElemMax: a longer json[] element is handed back
 E_JSON = 22                                             # etlg_err_code ETLG_E_JSON (checked against etl_amd.abi in tests/test_oracle_json_display.py)
 

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE — CPU restatement of what the reference's sinks write for a json / jsonb cell: serde_json's
 `from_str::<Value>` (crates/etl/src/postgres/codec/text.rs:126-134) followed by `Value::to_string()`
 (clickhouse/encoding.rs:73, bigquery/encoding.rs:173-176, iceberg/encoding.rs:356, ducklake/encoding.rs:173). For the parity tests of
-json_display (etl_amd/csrc/columns.hip). Never imported by the product path.
+json_display (etl_amd/csrc/handoff.hip.h). Never imported by the product path.
 
 serde_json 1.0.149 (Cargo.lock) is a crates.io dependency that is NOT under /root/reference; the reference builds it with the features
 `arbitrary_precision` + `std` and without `preserve_order` (crates/etl/Cargo.toml:36, crates/etl-destinations/Cargo.toml:121). Its

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — CPU restatement of the reference's BigQuery row encoder, for the parity test of etlg_batch_protobuf
-(etl_amd/csrc/columns.hip). Never imported by the product path.
+(etl_amd/csrc/rowformats.hip.h). Never imported by the product path.
 
 Follows crates/etl-destinations/src/bigquery/encoding.rs: cell_encode_prost :120-190 (which protobuf field type every Cell
 becomes), BigQueryTableRow::try_from :54-66 (tags = position + 1), and bigquery/core.rs:978-1036 + 1404-1754 (which rows an event

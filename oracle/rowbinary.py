@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — CPU restatement of the reference's ClickHouse RowBinary encoder, for the parity tests of
-etlg_batch_rowbinary (etl_amd/csrc/columns.hip). Never imported by the product path.
+etlg_batch_rowbinary (etl_amd/csrc/rowformats.hip.h). Never imported by the product path.
 
 Follows crates/etl-destinations/src/clickhouse/encoding.rs:
   cell_to_clickhouse_value :58-83   (which wire type every Cell becomes; Date range check :147-161; bytes_to_hex :176-185)

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — CPU restatement of the reference's size hints, for the parity test of etlg_batch_size_hints
-(etl_amd/csrc/columns.hip). Never imported by the product path.
+(etl_amd/csrc/finish.hip). Never imported by the product path.
 
 PARITY UNPINNED: the reference has no test that states a size hint as a number, and the hints are sums of Rust
 `size_of::<T>()` values that only a Rust build can supply — so this file restates the FORMULA (what is added for which

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — CPU restatement of the reference's DuckLake SQL literal grammar and of the rows etlg_batch_duckdb builds
-from it, for the parity tests of the device path (etl_amd/csrc/columns.hip, dl_row). Never imported by the product path.
+from it, for the parity tests of the device path (etl_amd/csrc/rowformats.hip.h, dl_row). Never imported by the product path.
 
 Follows crates/etl-destinations/src/ducklake/encoding.rs: table_row_to_sql_literal_ref :366-369 (`(` cells joined by `, ` `)`),
 cell_to_sql_literal :387-419, array_cell_to_sql_literal :470-585 (`[e, e, NULL]`), float_literal :588-612, encode_hex :615-617;
@@ -35,7 +35,7 @@ TUPLES, PREDICATES = 0, 1
 def quote_literal(b):
     """pg_escape 0.1.1 `quote_literal`, over bytes. UNPINNED beyond the plain arm — restated from the crate's documentation: a `'` is
     doubled; if the text holds a backslash, every backslash is doubled and the literal is prefixed with a space and `E`
-    (a\\b -> " E'a\\\\b'"); otherwise plain '...'. The device twin is dl_quote (columns.hip): a correction is one edit on each side."""
+    (a\\b -> " E'a\\\\b'"); otherwise plain '...'. The device twin is dl_quote (rowformats.hip.h): a correction is one edit on each side."""
     if isinstance(b, str):
         b = b.encode()
     b = bytes(b)

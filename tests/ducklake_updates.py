@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — CPU restatement of what the DuckLake sink makes of a partial Update, for the parity tests of
-etlg_batch_duckdb(ETLG_DL_UPDATES) (etl_amd/csrc/columns.hip, dl_selected / dl_row). Never imported by the product path.
+etlg_batch_duckdb(ETLG_DL_UPDATES) (etl_amd/csrc/columns.hip dl_selected, rowformats.hip.h dl_row). Never imported by the product path.
 
 Follows crates/etl-destinations/src/ducklake: core.rs:1846-1913 (the row choice: TableMutation::Update { delete_row, new_row: Partial },
 delete_row the old image, else the key row built from the partial row itself), core.rs:846-939 key_row_from_updated_partial_row,

@@ -10,11 +10,10 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "etl_amd", "csrc")
 OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libetlg_simt.so")
-KERNEL_SOURCES = ["kernels.hip", "fused.hip", "cells.hip", "rows.hip", "plan.hip", "scan.hip", "copy.hip", "columns.hip", "host.cpp"]
-DEPS = KERNEL_SOURCES + ["dev_types.h", "host_state.h", "host_control.inc", "host_handoff.inc", "host_orchestrate.inc", "codec.hip.h", "lookback.hip.h", "fixed_tile.hip.h", "utf8_swar.h", "float_fast.h", "pow5_table.h"]
 CXX = os.environ.get("CXX", "g++")
 sys.path.insert(0, ROOT)
-from etl_amd.build import DEFS as PRODUCT_DEFS  # noqa: E402
+from etl_amd.build import DEFS as PRODUCT_DEFS, DEPS as PRODUCT_DEPS, SOURCES as KERNEL_SOURCES  # noqa: E402  (one list of sources and headers: the product's)
+DEPS = [d for d in PRODUCT_DEPS if d != "../build.py"]
 FLAGS = ["-std=c++17", "-O1", "-g", "-fPIC", "-pthread", "-fno-strict-aliasing", "-Wno-unknown-pragmas", "-Wno-attributes",
          "-I", os.path.join(HERE, "include"), "-x", "c++"]
 

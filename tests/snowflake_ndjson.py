@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — CPU restatement of the reference's Snowflake row encoder, for the parity tests of etlg_batch_ndjson
-(etl_amd/csrc/columns.hip, nd_row). Never imported by the product path.
+(etl_amd/csrc/rowformats.hip.h, nd_row). Never imported by the product path.
 
 Follows crates/etl-destinations/src/snowflake/encoding.rs: serialize_row :57-72 (serde_json's compact map + '\\n'), RowSerializer
 :82-92 (the columns, then _cdc_operation / _cdc_sequence_number), CellSerializer :94-140 and ArrayCellSerializer :186-224 (what every

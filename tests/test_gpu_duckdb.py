@@ -1,4 +1,4 @@
-"""Device-side DuckLake SQL literals (etlg_batch_duckdb, etl_amd/csrc/columns.hip dl_row) byte for byte against tests/ducklake_literals.py
+"""Device-side DuckLake SQL literals (etlg_batch_duckdb, etl_amd/csrc/rowformats.hip.h dl_row) byte for byte against tests/ducklake_literals.py
 (restatement of crates/etl-destinations/src/ducklake/encoding.rs:366-612, batches.rs:1128-1316, 1477-1510 and core.rs:1824-1945), for
 both `what` values, host and device output: every scalar class and NULLs, quote_literal's arms in cells and quote_identifier in column
 names, Rust's float Display including the 300-byte texts, arrays of every element class as literals and typed, the update / delete

@@ -1,4 +1,4 @@
-"""Device-side DuckLake partial Updates (etlg_batch_duckdb with ETLG_DL_UPDATES, etl_amd/csrc/columns.hip dl_selected / dl_row) against
+"""Device-side DuckLake partial Updates (etlg_batch_duckdb with ETLG_DL_UPDATES, etl_amd/csrc/columns.hip dl_selected, rowformats.hip.h dl_row) against
 tests/ducklake_updates.py (restatement of ducklake/core.rs:846-939, 1846-1913 and batches.rs:1179-1190, 1229-1399): the bytes of both
 records of every partial Update, row_event, row_offsets, col_ends and n_host_rows, host and device output — under each identity shape,
 across the 256-event workgroups of the select kernels, for tables of 1 / 3 / 7 columns written with 1, 2 and 4 lanes per row and every

@@ -1,5 +1,5 @@
 """json / jsonb cells as the sinks write them — serde_json's `Value::to_string()` — built on the device (json_display,
-etl_amd/csrc/columns.hip) for all three hand-off formats, against oracle/json_display.py (pinned by tests/golden/json_display_kats.py to
+etl_amd/csrc/handoff.hip.h) for all three hand-off formats, against oracle/json_display.py (pinned by tests/golden/json_display_kats.py to
 the reference's own vectors): etlg_batch_columns with ETLG_ROWS_FORMAT_JSON (LargeUtf8), etlg_batch_rowbinary (String), etlg_batch_protobuf
 (string field behind validate_json_for_bigquery). Known answers, seeded random documents (repeated keys, escapes, every number shape,
 whitespace), the cells a lane leaves to the host, malformed cells, and the order of the reports."""

@@ -1,4 +1,4 @@
-"""Device-side Snowflake NDJSON rows (etlg_batch_ndjson, etl_amd/csrc/columns.hip nd_row) byte for byte against tests/snowflake_ndjson.py
+"""Device-side Snowflake NDJSON rows (etlg_batch_ndjson, etl_amd/csrc/rowformats.hip.h nd_row) byte for byte against tests/snowflake_ndjson.py
 (restatement of crates/etl-destinations/src/snowflake/encoding.rs:57-280 and core.rs:345-438, 572-608, 683-699): every scalar class and
 NULLs, serde_json's escapes in cells and column names, ryu's float layouts, the sink's encoding errors, arrays of every element class,
 the update / delete row choices under each replica identity, DEFERRED cells, table-copy batches, typed arrays, synthetic streams."""

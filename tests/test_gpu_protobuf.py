@@ -1,4 +1,4 @@
-"""Device-side BigQuery protobuf rows (etlg_batch_protobuf, etl_amd/csrc/columns.hip) byte for byte against oracle/protobuf.py
+"""Device-side BigQuery protobuf rows (etlg_batch_protobuf, etl_amd/csrc/rowformats.hip.h) byte for byte against oracle/protobuf.py
 (restatement of crates/etl-destinations/src/bigquery/encoding.rs:120-190 on the protobuf wire format): every class the device
 encodes incl. negative integers (10-byte varints), NULLs (absent fields), dates / times / timestamps as chrono strings, the
 trailing UPSERT / sequence-key fields; updates and deletes counted for the host; host-only classes reported."""

@@ -1,4 +1,4 @@
-"""Device-side ClickHouse RowBinary (etlg_batch_rowbinary, etl_amd/csrc/columns.hip) byte for byte against oracle/rowbinary.py
+"""Device-side ClickHouse RowBinary (etlg_batch_rowbinary, etl_amd/csrc/rowformats.hip.h) byte for byte against oracle/rowbinary.py
 (the restatement of crates/etl-destinations/src/clickhouse/encoding.rs + core.rs:96-114, pinned to the reference's own
 vectors by tests/test_oracle_rowbinary.py): every class the device encodes, both engines, nullable and non-nullable
 destinations, the reference's two ConversionErrors, and the rows / cells that stay with the host."""

@@ -1,4 +1,4 @@
-"""etlg_batch_size_hints (etl_amd/csrc/columns.hip) against oracle/size_hint.py, the restatement of Event::size_hint
+"""etlg_batch_size_hints (etl_amd/csrc/finish.hip) against oracle/size_hint.py, the restatement of Event::size_hint
 (crates/etl/src/event.rs:295-320) and estimate_table_row_allocated_bytes (crates/etl/src/data/table_row.rs:248-299):
 every event kind, full / key / partial rows, every cell class, and the events whose estimate the host must finish."""
 import os

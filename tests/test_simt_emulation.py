@@ -273,13 +273,13 @@ def test_scenarios_on_the_library_built_by_rocm_clang(emu_jobs):
 
 
 def test_columnar_hand_off(emu_jobs):
-    """etlg_batch_columns / etlg_batch_rowbinary (columns.hip): the Arrow-layout buffers built by the emulated kernels against
+    """etlg_batch_columns / etlg_batch_rowbinary (columns.hip, rowformats.hip): the Arrow-layout buffers built by the emulated kernels against
     the host hand-off of the oracle's arena, the RowBinary bytes against oracle/rowbinary.py."""
     _passed(emu_jobs, "hand_off")
 
 
 def test_finish_pass_typed_arrays_and_exact_floats(emu_jobs):
-    """etlg_batch_finish_cells / ETLG_F_FINISH_CELLS (columns.hip: k_fin_count / k_fin_fill, float_slow.h): the reference's array vectors
+    """etlg_batch_finish_cells / ETLG_F_FINISH_CELLS (finish.hip: k_fin_count / k_fin_fill, float_slow.h): the reference's array vectors
     through the emulated kernels, the type-matrix table, fuzzed literals in every image, the float matrix — tests/test_gpu_finish.py."""
     _passed(emu_jobs, "finish_pass")
 

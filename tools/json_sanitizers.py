@@ -1,4 +1,4 @@
-"""json_valid (etl_amd/csrc/cellparse.hip.h) / json_display (etl_amd/csrc/columns.hip) as plain host C++ under the sanitizers: the functions are cut out of the source,
+"""json_valid (etl_amd/csrc/cellparse.hip.h) / json_display (etl_amd/csrc/handoff.hip.h) as plain host C++ under the sanitizers: the functions are cut out of the source,
 compiled with g++ -fsanitize=address,undefined and with ROCm's clang++ -fsanitize=memory, and run over seeded random documents (the
 generator of tests/test_gpu_json_display.py) from heap blocks of the exact size — a read past a text's end, undefined behaviour or a
 read of an uninitialised value stops the run — with a byte-store writer; the output is compared with oracle/json_display.py.
@@ -48,11 +48,11 @@ int main(int argc, char** argv) {
 def main():
     ndocs = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-    # json_valid (and arr_hexv) live in cellparse.hip.h, shared with the multi-pass decode; json_display and its helpers in columns.hip
+    # json_valid (and arr_hexv) live in cellparse.hip.h, shared with the multi-pass decode; json_display and its helpers in handoff.hip.h
     shared = open(os.path.join(ROOT, "etl_amd", "csrc", "cellparse.hip.h")).read()
-    src = open(os.path.join(ROOT, "etl_amd", "csrc", "columns.hip")).read()
+    src = open(os.path.join(ROOT, "etl_amd", "csrc", "handoff.hip.h")).read()
     block = shared[shared.index("DEV int arr_hexv(uint32_t c)"):shared.index("// ---- array literals")] + \
-        src[src.index("// ---- serde_json 1.0.149 `Value::to_string()`"):src.index("DEV uint32_t numeric_str_len(const u8* ent);")]
+        src[src.index("// ---- serde_json 1.0.149 `Value::to_string()`"):src.index("// ---- Display strings of the classes every sink writes as text")]
     d = tempfile.mkdtemp(prefix="jsan")
     with open(os.path.join(d, "j.cpp"), "w") as f:
         f.write("#include <cstdint>\n#include <cstdio>\n#include <cstring>\n#include <cstdlib>\n#define DEV inline\ntypedef uint8_t u8;\n" + block + MAIN)
