@@ -109,6 +109,20 @@ struct FusedParams {
 };
 
 constexpr unsigned long long kNoErr = ~0ull;
+// DevResult.fused_fail bits, by name for the host (the kernels write the literals)
+constexpr uint32_t kFailLookback = 1u;     // a look-back spin gave up (never expected)
+constexpr uint32_t kFailPlanGaveUp = 2u;   // the fixed-width plan did not cover the batch (plan.hip)
+constexpr uint32_t kFailTooWide = 4u;      // a schema too wide for k_cells
+constexpr uint32_t kFailNotRun = 8u;       // the ASYNC predecessor of this batch failed: this one did not run
+constexpr uint32_t kFailRowsBack = 16u;    // k_rows handed the batch back (bits 8 and up: why; 1 = a tile beyond its LDS window, DevResult.dbg_t[11] holds what it needed)
+constexpr uint32_t kFailScanCount = 32u;   // decoded behind its boundary scan and the count read on the device was not usable (plan.hip)
+// DecParams.flags bits, likewise
+constexpr uint32_t kDecNoControl = 1u;     // bit 0: NO_CONTROL asserted
+constexpr uint32_t kDecCopyRows = 2u;      // bit 1: table-copy rows
+constexpr uint32_t kDecLateCarry = 16u;    // bit 4: `carry` belongs to a batch that may still be running on the other stream
+constexpr uint32_t kDecCtlPrePass = 32u;   // bit 5: the pre-pass of a pipelined control batch (the carried state comes from `carry`, kernels.hip)
+constexpr uint32_t kDecCheckCells = 64u;   // bit 6: ETLG_F_CHECK_CELLS
+constexpr uint32_t kDecAblations = 0xF00u; // bits 8-11: profiling ablations (ETLG_FUSED_DBG)
 constexpr int kBlock = 256;  // frames per workgroup (one lane per frame)
 
 // error stage ranks: for one frame the lowest rank wins, mirroring the order

@@ -29,11 +29,22 @@ void clear_error(etlg_ctx* c) { c->err = etlg_error{}; c->err.frame_index = -1; 
     hipError_t _e = (call);                                                      \
     if (_e != hipSuccess) return lib_error((ctx), ETLG_DeviceError, hipGetErrorString(_e)); \
   } while (0)
+#define RC(expr) do { const int32_t rc_ = (expr); if (rc_ != ETLG_OK) return rc_; } while (0)   // pass a non-OK code on
 
 #include "host_control.inc"   // control plane: schema slots, wire reader, JSON pull parser, Relation / DDL handlers, device slot table
 
 void side_release(etlg_batch* b) { if (b->side) { b->side->users--; b->side = nullptr; } }
 void side_use(etlg_batch* b, SideSet* ss) { if (b->side == ss) return; side_release(b); b->side = ss; ss->users++; }
+
+// etlg_ctx_profile: a pair of events around one launch on `s` (etlg_ctx_profile_read collects them)
+struct ProfScope {
+  etlg_ctx* c; hipStream_t s; ProfRec r;
+  ProfScope(etlg_ctx* c_, int which, hipStream_t s_) : c(c_), s(s_) {
+    r.which = which;
+    if (c->prof) { (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b); (void)hipEventRecord(r.a, s); }
+  }
+  ~ProfScope() { if (c->prof) { (void)hipEventRecord(r.b, s); c->prof_recs.push_back(r); } }
+};
 
 void launch_raw(etlg_ctx* c, int which, const DecParams& p) {
   if (which == kFused) etlg_k_launch_fused((int)c->fq.blk, &p, &c->fq, c->stream);
@@ -50,31 +61,30 @@ void launch_raw(etlg_ctx* c, int which, const DecParams& p) {
 // a json / jsonb / array column (the side inputs know: SideSet::chk_any). The event count is read on the device; p.nframes bounds it.
 void launch_chk_cells(etlg_ctx* c, const etlg_batch* b) {
   if (!b->check_cells || !b->side || !b->side->chk_any || !b->params.nframes) return;
-  ProfRec r; r.which = kChkCells;
-  if (c->prof) { (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b); (void)hipEventRecord(r.a, c->stream); }
+  ProfScope prof(c, kChkCells, c->stream);
   etlg_k_launch_chk_cells(&b->params, b->side->chk_maxc, b->params.nframes, c->stream);
-  if (c->prof) { (void)hipEventRecord(r.b, c->stream); c->prof_recs.push_back(r); }
 }
 
 void launch(etlg_ctx* c, int which, const DecParams& p) {
-  if (c->prof) {
-    ProfRec r; r.which = which;
-    (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b);
-    (void)hipEventRecord(r.a, c->stream);
-    launch_raw(c, which, p);
-    (void)hipEventRecord(r.b, c->stream);
-    c->prof_recs.push_back(r);
-  } else {
-    launch_raw(c, which, p);
-  }
+  ProfScope prof(c, which, c->stream);
+  launch_raw(c, which, p);
 }
 
 void launch_copy(etlg_ctx* c, const CopyJob& j, const DecParams& p) {
   if (!j.nrows) return;
-  ProfRec r; r.which = kCopy;
-  if (c->prof) { (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b); (void)hipEventRecord(r.a, c->stream); }
+  ProfScope prof(c, kCopy, c->stream);
   etlg_k_launch_copy(j.d_rows, j.d_row_offs, j.nrows, j.rows_len, j.ncols, j.rel_id, j.d_out, j.d_out_offs, j.lds, c->copy_lane_per_byte ? 1 : 0, &p, c->stream);
-  if (c->prof) { (void)hipEventRecord(r.b, c->stream); c->prof_recs.push_back(r); }
+}
+
+// The context's frame buffers, large enough for the batch's rows as Insert frames, under every name the batch holds for them.
+int32_t copy_point_at_frames(etlg_ctx* c, etlg_batch* b) {
+  CopyJob& j = b->copy;
+  HIPCHK(c, c->d_copy_out.ensure(j.syn_len + 64)); HIPCHK(c, c->d_copy_out_offs.ensure(((size_t)j.nrows + 1) * 4));
+  j.d_out = (uint8_t*)c->d_copy_out.p; j.d_out_offs = (uint32_t*)c->d_copy_out_offs.p;
+  DecParams& p = b->params;
+  p.in = j.d_out; p.offs = j.d_out_offs; p.in_len = j.syn_len;
+  b->d_in_ptr = j.d_out; b->dev_in = j.d_out; b->user_offs = j.d_out_offs;
+  return ETLG_OK;
 }
 
 // A table-copy batch whose first attempt was (or would have been) the rows -> arena kernel goes on as a batch of Insert frames:
@@ -84,13 +94,10 @@ int32_t copy_use_frames(etlg_ctx* c, etlg_batch* b) {
   // the frame buffers are the context's own: an ASYNC batch that needs them (k_cells cannot take its schema, or a kernel is forced) lets
   // everything enqueued before it finish — an earlier batch may still be reading them
   if (j.async) HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, c->d_copy_out.ensure(j.syn_len + 64)); HIPCHK(c, c->d_copy_out_offs.ensure(((size_t)j.nrows + 1) * 4));
-  j.d_out = (uint8_t*)c->d_copy_out.p; j.d_out_offs = (uint32_t*)c->d_copy_out_offs.p;
+  RC(copy_point_at_frames(c, b));
   j.direct = false;
-  DecParams& p = b->params;
-  p.in = j.d_out; p.offs = j.d_out_offs; p.in_len = j.syn_len;
-  b->len = (size_t)j.syn_len; b->d_in_ptr = j.d_out; b->dev_in = j.d_out; b->user_offs = j.d_out_offs;
-  launch_copy(c, j, p);
+  b->len = (size_t)j.syn_len;
+  launch_copy(c, j, b->params);
   return ETLG_OK;
 }
 
@@ -104,12 +111,7 @@ int32_t copy_repoint_frames(etlg_ctx* c, etlg_batch* b) {
   if (!j.active || j.direct) return ETLG_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
-  HIPCHK(c, c->d_copy_out.ensure(j.syn_len + 64)); HIPCHK(c, c->d_copy_out_offs.ensure(((size_t)j.nrows + 1) * 4));
-  j.d_out = (uint8_t*)c->d_copy_out.p; j.d_out_offs = (uint32_t*)c->d_copy_out_offs.p;
-  DecParams& p = b->params;
-  p.in = j.d_out; p.offs = j.d_out_offs; p.in_len = j.syn_len;
-  b->d_in_ptr = j.d_out; b->dev_in = j.d_out; b->user_offs = j.d_out_offs;
-  return ETLG_OK;
+  return copy_point_at_frames(c, b);
 }
 
 // The multi-pass pipeline (also the exact first-error path).
@@ -117,7 +119,7 @@ void launch_multipass(etlg_ctx* c, const DecParams& p, bool classify_done) {
   if (!classify_done) { if (p.nframes) launch(c, 0, p); launch(c, 1, p); }
   if (p.nframes) launch(c, 3, p);
   launch(c, 4, p);
-  if (p.nframes) launch(c, (p.flags & 64u) ? kWriteChk : 5, p);   // (flags bit 6: ETLG_F_CHECK_CELLS)
+  if (p.nframes) launch(c, (p.flags & kDecCheckCells) ? kWriteChk : 5, p);
   launch(c, 6, p);
   if (c->mp_tail) { (void)hipEventRecord(c->mp_tail, c->stream); c->mp_tail_set = true; }   // a pre-pass that runs ahead waits for it (shared scratch)
 }
@@ -144,16 +146,11 @@ void fill_view_common(etlg_batch* b) {
   b->v.slots = b->slot_descs.data();
 }
 
-// Reads the result block, resolves device vs host error, commits or rolls back
-// the control-plane state and (for host output) copies the arenas back.
 int32_t finish_batch(etlg_ctx* c, etlg_batch* b);
 extern "C" int32_t finish_cells(etlg_ctx* c, etlg_batch* b, uint32_t what, etlg_finish_stats* stats);   // (host_handoff.inc)
 int32_t drain_pending(etlg_ctx* c);
 int32_t download_batch(etlg_ctx* c, etlg_batch* b);
-struct BatchGuard {  // an etlg_decode that fails half way returns what the batch took from the context's pools
-  etlg_batch* b;
-  ~BatchGuard() { if (b) etlg_batch_free(b); }
-};
+struct BatchGuard { etlg_batch* b; ~BatchGuard() { if (b) etlg_batch_free(b); } };  // an etlg_decode that fails half way returns what the batch took from the context's pools
 int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec>& eps);
 int32_t setup_outputs(etlg_ctx* c, etlg_batch* b);
 int32_t setup_scratch(etlg_ctx* c, DecParams& p, int set = 0);
@@ -180,10 +177,104 @@ static inline void ht_mark(etlg_ctx* c, int i) {
   c->host_mark = t;
 }
 int32_t decode_tail(etlg_ctx* c, etlg_batch* b, size_t nframes, bool async, etlg_batch* prev);
-int32_t flush_deferred(etlg_ctx* c);
+int32_t flush_deferred(etlg_ctx* c);   // (an entry point that finds a deferred batch enqueues its decode first; a failure there belongs to THAT batch: `(void)`)
 void check_invariants(etlg_ctx* c, const char* where);
+struct StreamSwitch { etlg_ctx* c; hipStream_t saved; ~StreamSwitch() { c->stream = saved; } };   // work for another stream through the launchers: c->stream names it for a while
 struct InvariantScope { etlg_ctx* c; const char* where; ~InvariantScope() { if (c && c->debug_invariants) check_invariants(c, where); } };
 hipError_t sync_decode_streams(etlg_ctx* c);
+
+// ---- plumbing shared by the entry points and the orchestration
+
+int32_t take_event(etlg_ctx* c, hipEvent_t* out) {   // from the context's pool of untimed events (etlg_batch_free gives them back)
+  if (c->ev_pool.empty()) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_pool.push_back(e); }
+  *out = c->ev_pool.back(); c->ev_pool.pop_back();
+  return ETLG_OK;
+}
+int32_t take_result(etlg_ctx* c, DevResult** out) {   // a pinned result block, likewise
+  if (c->res_pool.empty()) { DevResult* r = nullptr; HIPCHK(c, hipHostMalloc((void**)&r, sizeof(DevResult), hipHostMallocDefault)); c->res_pool.push_back(r); }
+  *out = c->res_pool.back(); c->res_pool.pop_back();
+  return ETLG_OK;
+}
+int32_t ensure_stream2(etlg_ctx* c) {   // the second decode stream and the event behind its last kernel
+  if (c->stream2) return ETLG_OK;
+  HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+  HIPCHK(c, hipEventCreateWithFlags(&c->tail2, hipEventDisableTiming));
+  return ETLG_OK;
+}
+
+// Offsets are 32 bits wide and the kernels read up to `slack` bytes past the input; descriptors keep 30 bits for a frame number.
+int32_t batch_too_large(etlg_ctx* c, uint64_t len, uint64_t nframes, uint64_t slack = 16) {
+  if (len > 0xFFFFFFFFull - slack || nframes >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+  return ETLG_OK;
+}
+
+// Host input of a synchronous call: the bytes (and the sidecar, when the caller has one) go to the context's staging buffers on its stream.
+int32_t upload_input(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t* offs, size_t nframes) {
+  HIPCHK(c, c->d_in.ensure(len + 64));
+  if (offs) HIPCHK(c, c->d_offs.ensure((nframes + 1) * 4));
+  if (len) HIPCHK(c, hipMemcpyAsync(c->d_in.p, buf, len, hipMemcpyHostToDevice, c->stream));
+  if (offs) HIPCHK(c, hipMemcpyAsync(c->d_offs.p, offs, (nframes + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  return ETLG_OK;
+}
+
+// The synchronous calls that start from k_classify (etlg_frame_tags, etlg_shard_plan, etlg_control_stream), behind their own argument
+// checks: everything in flight finishes, host input is uploaded, `p` names the batch and the per-frame scratch, and the envelope + tag
+// of every frame is on its way (p.f_tag, on the context's stream).
+int32_t classify_begin(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t* offs, size_t nframes, uint32_t flags, DecParams& p) {
+  HIPCHK(c, hipSetDevice(c->device));
+  RC(drain_pending(c));
+  p = DecParams{};
+  p.in = buf; p.offs = offs;
+  if (!(flags & ETLG_F_INPUT_ON_DEVICE)) {
+    RC(upload_input(c, buf, len, offs, nframes));
+    p.in = (const uint8_t*)c->d_in.p; p.offs = (const uint32_t*)c->d_offs.p;
+  }
+  p.nframes = (uint32_t)nframes; p.nblocks = (p.nframes + kBlock - 1) / kBlock; p.in_len = len;
+  RC(setup_scratch(c, p));
+  launch(c, 0, p);
+  return ETLG_OK;
+}
+
+// Every ETLG_* environment variable of the host layer, read ONCE, when the context is created: name, field, default, parse rule — flag_on:
+// set by a value that starts with '1'; flag_off: cleared by one that starts with '0'; truth: an integer, non-zero = on; integer. (ETLG_ROWS_NW
+// belongs to the kernel launcher in rows.hip.)
+void read_knobs(etlg_ctx* c) {
+  auto flag_on = [](const char* name, bool& f) { const char* e = getenv(name); f = e && e[0] == '1'; };
+  auto flag_off = [](const char* name, bool& f) { const char* e = getenv(name); f = !(e && e[0] == '0'); };
+  auto truth = [](const char* name, bool& f, bool dflt) { const char* e = getenv(name); f = e ? atoi(e) != 0 : dflt; };
+  auto integer = [](const char* name, auto& f, long dflt) { const char* e = getenv(name); f = (std::remove_reference_t<decltype(f)>)(e ? atol(e) : dflt); };
+  int host_times = 0;
+  flag_on("ETLG_FORCE_MULTIPASS", c->force_multipass);            // tests exercise both paths
+  flag_on("ETLG_RING_H2D", c->ring_h2d);                          // measurement / bisect: the result ring re-initialised from the host template
+  flag_on("ETLG_COPY_KERNEL", c->copy_lane_per_byte);             // the lane-per-byte COPY splitter
+  flag_off("ETLG_COPY_DIRECT", c->copy_direct);                   // 0: table-copy rows always through the row -> frame rewrite
+  flag_off("ETLG_CTL_OVERLAP", c->ctl_overlap_mode);              // 0: batches on the control path stay on one decode stream
+  truth("ETLG_CHAIN_SPARE", c->chain_spare, true);                // 0: the batches behind a plan batch that was decoded again are always decoded again
+  truth("ETLG_PLAN_DELETES", c->plan_deletes, true);              // 0: a Delete gives the batch up to the generic kernels
+  truth("ETLG_SCAN_CHAIN", c->scan_chain_mode, true);             // 0: a batch without a sidecar always waits for its frame count on the host
+  truth("ETLG_CTL_HOLD", c->ctl_hold_mode, true);                 // 0: the held batch is flushed before the next pre-pass goes out
+  truth("ETLG_DEBUG_INVARIANTS", c->debug_invariants, false);     // check_invariants at every entry point
+  truth("ETLG_ROWS_TRACE", c->rows_trace, false);                 // k_rows' sizing and every second attempt on stderr
+  integer("ETLG_HOST_TIMES", host_times, 0);                      // 1: host microseconds per segment of the control path; 2: ... and outliers as they happen
+  integer("ETLG_CTRL_STAGE_CAP", c->ctrl_stage_cap_test, 0);      // tests: a staging buffer too small for the batch's control frames
+  integer("ETLG_RB_PARTS", c->rb_parts_test, 0);                  // tests: lanes per row in k_rb_rows (1-4) instead of the choice by row count
+  integer("ETLG_FUSED_DBG", c->fused_dbg, 0);                     // ablation bits, profiling only (results are wrong)
+  integer("ETLG_FUSED_KERNEL", c->fused_kernel, -1);              // 0 k_fused/256, 1 k_fused/64, 2 k_cells, 3 k_plan, 4 k_rows whenever eligible
+  integer("ETLG_ROWS", c->rows_mode, 1);                          // 0: never k_rows
+  integer("ETLG_ROWS_CF", c->rows_cf, 0);                         // k_rows' frames per tile
+  integer("ETLG_ROWS_LDS", c->rows_lds, -1);                      // k_rows' dynamic LDS bytes
+  integer("ETLG_ROWS_WIN_ROOM", c->rows_win_room, 64);            // head room of a resized k_rows window (a divisor)
+  integer("ETLG_LDS_MARGIN_PCT", c->lds_margin_pct, -1);          // k_fused / k_cells: margin of the staging window over the average tile
+  integer("ETLG_COPY_LDS", c->copy_lds, -1);                      // the COPY splitter's staging window
+  integer("ETLG_PLAN", c->plan_mode, 1);                          // 0: no fixed-width plan
+  integer("ETLG_PLAN_PRE", c->plan_pre, 1);                       // 0: k_plan runs its look-back itself; 1 / 2: tile prefixes from k_plan_pre
+  integer("ETLG_PLAN_MARGIN", c->plan_margin_pct, 4);             // k_plan's LDS window = 64 average frames + this margin
+  integer("ETLG_PLAN_DBG", c->plan_dbg, 0);                       // bit 0 = no LDS staging (tests of the in-place reader)
+  integer("ETLG_OVERLAP", c->overlap_mode, 1);                    // 0: one decode stream
+  integer("ETLG_CTL_ASYNC", c->ctl_async_mode, 1);                // 0: control batches are decoded synchronously
+  c->host_times = host_times == 1 || host_times == 2; c->host_times_slow = host_times == 2;
+  if (c->rows_win_room <= 0) c->rows_win_room = 64;
+}
 
 }  // namespace
 
@@ -224,6 +315,31 @@ static void handoff_release(HandoffBlocks& m) {
 struct ScratchBlk {  // a device block for the duration of one call
   etlg_ctx* c; void* p = nullptr; size_t cap = 0;
   ~ScratchBlk() { if (p) blk_give(c, c->gen, p, cap, false); }
+};
+
+// ASYNC with HOST input: the bytes and their offsets (frames or rows) are copied into ONE device block the batch owns, on a copy stream
+// of their own, beside the decode of the batch before it; `done` is recorded behind the two copies and whoever reads the block waits for
+// it on the device. The caller keeps the host buffers untouched until the batch is synced, as for every ASYNC batch (include/etlg.h).
+// Block and event go back to the pools when this goes out of scope, unless a batch has adopted them (etlg_batch_free returns them then).
+struct StagedInput {
+  etlg_ctx* c; void* blk = nullptr; size_t cap = 0, o_offs = 0; hipEvent_t done = nullptr;
+  explicit StagedInput(etlg_ctx* c_) : c(c_) {}
+  StagedInput(const StagedInput&) = delete;
+  ~StagedInput() { if (blk) blk_give(c, c->gen, blk, cap, false); if (done) c->ev_pool.push_back(done); }
+  int32_t upload(const uint8_t* buf, size_t len, const uint32_t* offs, size_t n) {
+    o_offs = (len + 16 + 255) & ~(size_t)255;   // the kernels' readers may touch up to 16 bytes past the input
+    HIPCHK(c, blk_take(c, o_offs + (n + 1) * 4 + 64, false, &blk, &cap));
+    if (!c->h2d_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
+    RC(take_event(c, &done));
+    if (len) HIPCHK(c, hipMemcpyAsync(blk, buf, len, hipMemcpyHostToDevice, c->h2d_stream));
+    HIPCHK(c, hipMemcpyAsync((uint8_t*)blk + o_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice, c->h2d_stream));
+    HIPCHK(c, hipEventRecord(done, c->h2d_stream));
+    c->staged_async++;
+    return ETLG_OK;
+  }
+  const uint8_t* bytes() const { return (const uint8_t*)blk; }
+  const uint32_t* offs() const { return (const uint32_t*)((const uint8_t*)blk + o_offs); }
+  void adopted_by(etlg_batch* b) { if (blk) { b->stage_blk = blk; b->stage_cap = cap; b->h2d_done = done; blk = nullptr; done = nullptr; } }
 };
 
 // A context spreads its work over up to seven HIP streams; ROCm multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware
@@ -269,41 +385,19 @@ int32_t etlg_ctx_create(int32_t hip_device, etlg_ctx** out) {
   if (e != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return fail("hipHostMalloc", e); }
   { DevResult init{}; init.first_err = kNoErr; *c->h_init = init; }
   e = hipHostMalloc((void**)&c->h_init_ring, sizeof(DevResult) * etlg_ctx::kResRing, hipHostMallocDefault);
-  if (e != hipSuccess) { snprintf(g_create_err, sizeof g_create_err, "hipHostMalloc: %s", hipGetErrorString(e)); delete c; return ETLG_DeviceError; }
+  if (e != hipSuccess) { delete c; return fail("hipHostMalloc", e); }
   for (uint32_t i = 0; i < etlg_ctx::kResRing; i++) c->h_init_ring[i] = *c->h_init;
   e = hipMalloc((void**)&c->d_init_ring, sizeof(DevResult) * etlg_ctx::kResRing);
   if (e == hipSuccess) e = hipMemcpy(c->d_init_ring, c->h_init_ring, sizeof(DevResult) * etlg_ctx::kResRing, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { snprintf(g_create_err, sizeof g_create_err, "hipMalloc: %s", hipGetErrorString(e)); delete c; return ETLG_DeviceError; }
+  if (e != hipSuccess) { delete c; return fail("hipMalloc", e); }
   // (a kernel whose static + dynamic LDS request exceeds a CU's 160 KB is refused here, not at its first launch)
   if (etlg_k_fused_set_lds() || etlg_k_cells_set_lds() || etlg_k_copy_set_lds() || etlg_k_rows_set_lds()) {
     snprintf(g_create_err, sizeof g_create_err, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) refused a kernel's LDS request");
     delete c; return ETLG_DeviceError;
   }
-  { const char* fm = getenv("ETLG_FORCE_MULTIPASS"); c->force_multipass = fm && fm[0] == '1'; }
-  { const char* e = getenv("ETLG_RING_H2D"); c->ring_h2d = e && e[0] == '1'; }
-  { const char* e = getenv("ETLG_COPY_KERNEL"); c->copy_lane_per_byte = e && e[0] == '1'; }
-  { const char* e = getenv("ETLG_COPY_DIRECT"); c->copy_direct = !(e && e[0] == '0'); }
-  { const char* ht = getenv("ETLG_HOST_TIMES"); c->host_times = ht && (ht[0] == '1' || ht[0] == '2'); c->host_times_slow = ht && ht[0] == '2'; }
-  { const char* sc = getenv("ETLG_CTRL_STAGE_CAP"); c->ctrl_stage_cap_test = sc ? (size_t)atol(sc) : 0; }
-  { const char* rp = getenv("ETLG_RB_PARTS"); c->rb_parts_test = rp ? (uint32_t)atoi(rp) : 0; }   // tests: lanes per row in k_rb_rows (1-4) instead of the choice by row count
-  { const char* fd = getenv("ETLG_FUSED_DBG"); c->fused_dbg = fd ? (uint32_t)atoi(fd) : 0; }
-  { const char* fk = getenv("ETLG_FUSED_KERNEL"); c->fused_kernel = fk ? atoi(fk) : -1; }
-  { const char* rm = getenv("ETLG_ROWS"); if (rm) c->rows_mode = atoi(rm); }
-  { const char* cr = getenv("ETLG_CHAIN_REISSUE"); if (cr) c->chain_reissue = atoi(cr) != 0; }
-  { const char* cs = getenv("ETLG_CHAIN_SPARE"); if (cs) c->chain_spare = atoi(cs) != 0; }
-  { const char* pd = getenv("ETLG_PLAN_DELETES"); if (pd) c->plan_deletes = atoi(pd) != 0; }
-  { const char* sc = getenv("ETLG_SCAN_CHAIN"); if (sc) c->scan_chain_mode = atoi(sc) != 0; }
-  { const char* di = getenv("ETLG_DEBUG_INVARIANTS"); if (di) c->debug_invariants = atoi(di) != 0; }
+  read_knobs(c);
   clear_error(c);
   (void)etlg_k_plan_set_lds();
-  if (const char* pm = getenv("ETLG_PLAN")) c->plan_mode = atoi(pm);
-  if (const char* pm = getenv("ETLG_PLAN_PRE")) c->plan_pre = atoi(pm);
-  if (const char* pm = getenv("ETLG_CTL_HOLD")) c->ctl_hold_mode = atoi(pm) != 0;
-  if (const char* pm = getenv("ETLG_PLAN_MARGIN")) c->plan_margin_pct = (uint32_t)atoi(pm);
-  if (const char* pm = getenv("ETLG_PLAN_DBG")) c->plan_dbg = (uint32_t)atoi(pm);
-  { const char* e = getenv("ETLG_CTL_OVERLAP"); c->ctl_overlap_mode = !(e && e[0] == '0'); }   // 0: batches on the control path stay on one decode stream
-  if (const char* pm = getenv("ETLG_OVERLAP")) c->overlap_mode = atoi(pm);
-  if (const char* pm = getenv("ETLG_CTL_ASYNC")) c->ctl_async_mode = atoi(pm);
   { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, hip_device) == hipSuccess && ncu > 0) c->n_cus = ncu; }
   { std::lock_guard<std::mutex> l(g_live_mu); c->gen = ++g_ctx_gen; g_live_ctx[c] = c->gen; }
   *out = c;
@@ -321,7 +415,8 @@ void etlg_ctx_destroy(etlg_ctx* c) {
     for (int i = 0; i < 8; i++) if (c->host_n[i]) fprintf(stderr, "etlg host times: %-26s %8.1f us x %llu\n", names[i], c->host_us[i] / (double)c->host_n[i], (unsigned long long)c->host_n[i]);
   }
   if (c->h_scan) { (void)hipHostFree(c->h_scan); c->h_scan = nullptr; }
-  for (DevBuf* b : {&c->d_copy_in, &c->d_copy_offs, &c->d_copy_out, &c->d_copy_out_offs, &c->d_scan, &c->d_in, &c->d_offs, &c->d_tag, &c->d_emit, &c->d_ffixed, &c->d_fheap, &c->d_blk32, &c->d_blk64, &c->d_ctrl, &c->d_ctrl_stage, &c->d_res, &c->d_desc, &c->d_colsel}) b->release();
+  for (DevBuf* b : {&c->d_copy_in, &c->d_copy_offs, &c->d_copy_out, &c->d_copy_out_offs, &c->d_scan, &c->d_in, &c->d_offs, &c->d_res, &c->d_desc, &c->d_colsel}) b->release();
+  for (CtlSet& cs : c->sets) cs.release();
   for (SideSet* ss : c->side_sets) { ss->dev.release(); if (ss->h) (void)hipHostFree(ss->h); if (ss->ready) (void)hipEventDestroy(ss->ready); delete ss; }
   for (OutSet* o : c->out_pool) { o->release(); delete o; }
   for (DevBuf* o : c->offs_pool) { o->release(); delete o; }
@@ -329,38 +424,32 @@ void etlg_ctx_destroy(etlg_ctx* c) {
   for (auto& b : c->blk_host) (void)hipHostFree(b.first);
   if (c->ctl_stream) (void)hipStreamDestroy(c->ctl_stream);
   if (c->mp_tail) (void)hipEventDestroy(c->mp_tail);
-  if (c->h_cnt_init) (void)hipHostFree(c->h_cnt_init);
-  if (c->h_hand) (void)hipHostFree(c->h_hand);
-  if (c->h_ctl_list) (void)hipHostFree(c->h_ctl_list);
-  if (c->h_ctl_stage) (void)hipHostFree(c->h_ctl_stage);
-  if (c->ctl_alt.h_ctl_list) (void)hipHostFree(c->ctl_alt.h_ctl_list);
-  if (c->ctl_alt.h_ctl_stage) (void)hipHostFree(c->ctl_alt.h_ctl_stage);
-  for (DevBuf* b : {&c->ctl_alt.d_tag, &c->ctl_alt.d_emit, &c->ctl_alt.d_ffixed, &c->ctl_alt.d_fheap, &c->ctl_alt.d_blk32, &c->ctl_alt.d_blk64, &c->ctl_alt.d_ctrl, &c->ctl_alt.d_ctrl_stage}) b->release();
+  for (void* h : {(void*)c->h_cnt_init, (void*)c->h_hand}) if (h) (void)hipHostFree(h);
   c->d_ctl_res.release();
-  if (c->scan_stream) (void)hipStreamDestroy(c->scan_stream);
-  if (c->h2d_stream) (void)hipStreamDestroy(c->h2d_stream);
-  if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
-  if (c->res_stream) (void)hipStreamDestroy(c->res_stream);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
+  for (hipStream_t st : {c->scan_stream, c->h2d_stream, c->d2h_stream, c->res_stream, c->stream2}) if (st) (void)hipStreamDestroy(st);
   c->d_pre.release();
-  if (c->tail2) (void)hipEventDestroy(c->tail2);
-  if (c->fence_ev) (void)hipEventDestroy(c->fence_ev);
+  for (hipEvent_t ev : {c->tail2, c->fence_ev}) if (ev) (void)hipEventDestroy(ev);
   for (auto& r : c->prof_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   for (auto& pr : c->harena_pool) (void)hipHostFree(pr.first);
-  if (c->h_init) (void)hipHostFree(c->h_init);
-  if (c->h_poison) (void)hipHostFree(c->h_poison);
-  if (c->h_init_ring) (void)hipHostFree(c->h_init_ring);
+  for (DevResult* h : {c->h_init, c->h_poison, c->h_init_ring}) if (h) (void)hipHostFree(h);
   if (c->d_init_ring) (void)hipFree(c->d_init_ring);
   for (DevResult* r : c->res_pool) (void)hipHostFree(r);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
-int32_t etlg_ctx_set_stream(etlg_ctx* c, void* s) {
-  if (!c) return ETLG_InvalidArgument;
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+// The calls that change what later batches decode against: the deferred batch goes out, the arguments are checked, then everything in
+// flight finishes (it was issued against the state before the call).
+static bool settle(etlg_ctx* c, bool args_ok = true) {
+  (void)flush_deferred(c);
+  if (!c || !args_ok) return false;
   (void)drain_pending(c);
+  return true;
+}
+
+int32_t etlg_ctx_set_stream(etlg_ctx* c, void* s) {
+  if (!settle(c)) return ETLG_InvalidArgument;
   (void)hipStreamSynchronize(c->stream);
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   if (s) { c->stream = (hipStream_t)s; c->own_stream = false; }
@@ -369,17 +458,13 @@ int32_t etlg_ctx_set_stream(etlg_ctx* c, void* s) {
 }
 
 int32_t etlg_ctx_set_worker(etlg_ctx* c, int32_t kind, uint32_t table_id, uint64_t bootstrap) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
-  if (!c) return ETLG_InvalidArgument;
-  (void)drain_pending(c);
+  if (!settle(c)) return ETLG_InvalidArgument;
   c->worker = kind; c->sync_table = table_id; c->bootstrap = bootstrap; c->side_valid = false; c->side_dirty = true;
   return ETLG_OK;
 }
 
 int32_t etlg_schema_put(etlg_ctx* c, uint32_t table_id, uint64_t snapshot, const char* nsp, const char* name, uint32_t ncols, const etlg_col* cols) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
-  if (!c || (ncols && !cols)) return ETLG_InvalidArgument;
-  (void)drain_pending(c);
+  if (!settle(c, !ncols || cols)) return ETLG_InvalidArgument;
   auto s = std::make_shared<StoredSchema>();
   s->table_id = table_id; s->snapshot = snapshot; s->nsp = nsp ? nsp : ""; s->name = name ? name : "";
   for (uint32_t i = 0; i < ncols; i++) {
@@ -393,18 +478,14 @@ int32_t etlg_schema_put(etlg_ctx* c, uint32_t table_id, uint64_t snapshot, const
 }
 
 int32_t etlg_table_state(etlg_ctx* c, uint32_t table_id, int32_t kind, uint64_t lsn) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
-  if (!c) return ETLG_InvalidArgument;
-  (void)drain_pending(c);
+  if (!settle(c)) return ETLG_InvalidArgument;
   if (kind == ETLG_TS_ABSENT) c->states.erase(table_id); else c->states[table_id] = TState{kind, lsn};
   c->side_dirty = true;
   return ETLG_OK;
 }
 
 int32_t etlg_table_ready(etlg_ctx* c, uint32_t table_id, uint64_t snapshot, const uint8_t* rmask, const uint8_t* imask, uint32_t n) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
-  if (!c || !rmask || !imask) return -ETLG_InvalidArgument;
-  (void)drain_pending(c);
+  if (!settle(c, rmask && imask)) return -ETLG_InvalidArgument;
   SchemaPtr sch = get_at_or_before(c->cs, table_id, snapshot);
   if (!sch || sch->cols.size() != n) return -ETLG_MissingTableSchema;
   std::vector<uint8_t> r(rmask, rmask + n), i(imask, imask + n);
@@ -415,9 +496,7 @@ int32_t etlg_table_ready(etlg_ctx* c, uint32_t table_id, uint64_t snapshot, cons
 }
 
 int32_t etlg_table_forget(etlg_ctx* c, uint32_t table_id) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
-  if (!c) return ETLG_InvalidArgument;
-  (void)drain_pending(c);
+  if (!settle(c)) return ETLG_InvalidArgument;
   c->cs.cache.erase(table_id);
   c->side_dirty = true;
   return ETLG_OK;
@@ -432,9 +511,7 @@ int32_t etlg_table_cache_get(const etlg_ctx* c, uint32_t table_id, int32_t* kind
 }
 
 int32_t etlg_ctx_reset_stream_state(etlg_ctx* c) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
-  if (!c) return ETLG_InvalidArgument;
-  (void)drain_pending(c);
+  if (!settle(c)) return ETLG_InvalidArgument;
   c->in_txn = false; c->final_lsn = 0; c->next_ord = 0;
   return ETLG_OK;
 }
@@ -450,23 +527,18 @@ int32_t etlg_ctx_slots(const etlg_ctx* c, uint32_t* n, const etlg_slot_desc** sl
   return ETLG_OK;
 }
 
-// debugging aid (not part of etlg.h): per-phase cycle sums of the last finished batch
-int32_t etlg_ctx_debug_times(etlg_ctx* c, unsigned long long* out12) {
-  if (!c || !out12) return ETLG_InvalidArgument;
-  for (int i = 0; i < 12; i++) out12[i] = c->last_dbg[i];
+// ---- debugging aids (not part of etlg.h): counters of the context, copied into the caller's words
+static int32_t debug_words(const etlg_ctx* c, unsigned long long* out, const unsigned long long* w, int n) {
+  if (!c || !out) return ETLG_InvalidArgument;
+  for (int i = 0; i < n; i++) out[i] = w[i];
   return ETLG_OK;
 }
-
-// debugging aid (not part of etlg.h): batches finished per path
-//   [0] k_fused  [1] k_cells  [2] multi-pass directly  [3] single-pass result discarded and redone by the multi-pass kernels
-int32_t etlg_ctx_debug_paths(etlg_ctx* c, unsigned long long* out4) {
-  if (!c || !out4) return ETLG_InvalidArgument;
-  for (int i = 0; i < 4; i++) out4[i] = c->path_n[i];
-  return ETLG_OK;
-}
-//   [4] k_plan  [5] plan result discarded and redone by the generic single-pass kernel  [6] batches that took the control path
-//   (a Relation / DDL frame, or a caller without ETLG_F_NO_CONTROL on the multi-pass path)  [7] ASYNC batches re-run because their predecessor failed
-// debugging aid (not part of etlg.h): ASYNC batches that were enqueued beside their predecessor on the second decode stream
+// per-phase cycle sums of the last finished batch
+int32_t etlg_ctx_debug_times(etlg_ctx* c, unsigned long long* out12) { return debug_words(c, out12, c ? c->last_dbg : nullptr, 12); }
+// batches finished per path (PathIdx, host_state.h): the first four, all eight
+int32_t etlg_ctx_debug_paths(etlg_ctx* c, unsigned long long* out4) { return debug_words(c, out4, c ? c->path_n : nullptr, 4); }
+int32_t etlg_ctx_debug_paths8(etlg_ctx* c, unsigned long long* out8) { return debug_words(c, out8, c ? c->path_n : nullptr, kPathCount); }
+// ASYNC batches that were enqueued beside their predecessor on the second decode stream
 unsigned long long etlg_ctx_debug_overlapped(etlg_ctx* c) { return c ? c->overlapped : 0; }
 unsigned long long etlg_ctx_debug_ctl_ahead(etlg_ctx* c) { return c ? c->ctl_ahead_n : 0; }
 unsigned long long etlg_ctx_debug_staged(etlg_ctx* c) { return c ? c->staged_async : 0; }   // ASYNC batches whose host input was staged on the copy stream
@@ -478,17 +550,11 @@ int32_t etlg_host_alloc(etlg_ctx* c, size_t bytes, void** out) {
   HIPCHK(c, hipHostMalloc(out, bytes, hipHostMallocDefault));
   return ETLG_OK;
 }
-void etlg_host_free(void* p) { if (p) (void)hipHostFree(p); }   // batches whose control pre-pass ran ahead of their decode
-// debugging aid (not part of etlg.h): [0] batches k_rows produced, [1] batches it handed back to k_cells / k_fused
-int32_t etlg_ctx_debug_rows(etlg_ctx* c, unsigned long long* out2) {   // (three words)
-  if (!c || !out2) return ETLG_InvalidArgument;
-  out2[0] = c->rows_n; out2[1] = c->rows_redone; out2[2] = c->rows_resized;
-  return ETLG_OK;
-}
-int32_t etlg_ctx_debug_paths8(etlg_ctx* c, unsigned long long* out8) {
-  if (!c || !out8) return ETLG_InvalidArgument;
-  for (int i = 0; i < 8; i++) out8[i] = c->path_n[i];
-  return ETLG_OK;
+void etlg_host_free(void* p) { if (p) (void)hipHostFree(p); }
+// debugging aid (not part of etlg.h), three words: [0] batches k_rows produced, [1] batches it handed back to k_cells / k_fused, [2] ... it took again with a larger window
+int32_t etlg_ctx_debug_rows(etlg_ctx* c, unsigned long long* out3) {
+  const unsigned long long w[3] = {c ? c->rows_n : 0, c ? c->rows_redone : 0, c ? c->rows_resized : 0};
+  return debug_words(c, out3, w, 3);
 }
 
 int32_t etlg_ctx_profile(etlg_ctx* c, int32_t enable) {
@@ -538,11 +604,9 @@ hipError_t scan_launch(etlg_ctx* c, ScanJob& j, bool sequential) {
   hipError_t e = j.offs->ensure((j.cap + 2) * 4); if (e != hipSuccess) return e;
   j.cur = j.res ? (uint8_t*)j.res : base;
   c->h_scan[0] = 0; c->h_scan[1] = 0;
-  ProfRec r; r.which = kBounds;
-  if (c->prof) { (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b); (void)hipEventRecord(r.a, s); }
+  ProfScope prof(c, kBounds, s);
   etlg_k_launch_bounds(j.d_in, len, (uint32_t*)j.offs->p, (uint32_t)std::min<size_t>(j.cap + 2, 0xFFFFFFFFu), base, j.res, (uint32_t*)(base + c->scan_half), c->h_scan,
                        sequential ? 1 : 0, s);
-  if (c->prof) { (void)hipEventRecord(r.b, s); c->prof_recs.push_back(r); }
   return hipSuccess;
 }
 
@@ -607,16 +671,15 @@ hipError_t device_scan(etlg_ctx* c, const uint8_t* d_in, size_t len, size_t* nfr
 
 int32_t etlg_scan_boundaries(etlg_ctx* c, const uint8_t* buf, size_t len, uint32_t flags, uint32_t* offsets_out, size_t cap,
                              size_t* nframes_out) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+  (void)flush_deferred(c);
   if (!c || !nframes_out || (!offsets_out && cap)) return ETLG_InvalidArgument;
   clear_error(c);
-  if (len > 0xFFFFFFFFull - 16) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+  RC(batch_too_large(c, len, 0));
   HIPCHK(c, hipSetDevice(c->device));
   const bool in_dev = flags & ETLG_F_INPUT_ON_DEVICE, out_dev = flags & ETLG_F_OUTPUT_ON_DEVICE;
   const uint8_t* d_in_ptr = buf;
   if (!in_dev) {
-    HIPCHK(c, c->d_in.ensure(len + 64));
-    if (len) HIPCHK(c, hipMemcpyAsync(c->d_in.p, buf, len, hipMemcpyHostToDevice, c->stream));
+    RC(upload_input(c, buf, len, nullptr, 0));
     d_in_ptr = (const uint8_t*)c->d_in.p;
   }
   size_t nf = 0;
@@ -630,26 +693,15 @@ int32_t etlg_scan_boundaries(etlg_ctx* c, const uint8_t* buf, size_t len, uint32
 
 int32_t etlg_frame_tags(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t* frame_offsets, size_t nframes, uint32_t flags,
                         uint8_t* tags_out) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+  (void)flush_deferred(c);
   if (!c || !frame_offsets || (!tags_out && nframes)) return ETLG_InvalidArgument;
   clear_error(c);
-  if (len > 0xFFFFFFFFull - 16 || nframes >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+  RC(batch_too_large(c, len, nframes));
   if (!nframes) return ETLG_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; }
-  const bool in_dev = flags & ETLG_F_INPUT_ON_DEVICE, out_dev = flags & ETLG_F_OUTPUT_ON_DEVICE;
+  const bool out_dev = flags & ETLG_F_OUTPUT_ON_DEVICE;
   hipStream_t s = c->stream;
-  DecParams p{};
-  p.in = buf; p.offs = frame_offsets;
-  if (!in_dev) {
-    HIPCHK(c, c->d_in.ensure(len + 64)); HIPCHK(c, c->d_offs.ensure((nframes + 1) * 4));
-    if (len) HIPCHK(c, hipMemcpyAsync(c->d_in.p, buf, len, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->d_offs.p, frame_offsets, (nframes + 1) * 4, hipMemcpyHostToDevice, s));
-    p.in = (const uint8_t*)c->d_in.p; p.offs = (const uint32_t*)c->d_offs.p;
-  }
-  p.nframes = (uint32_t)nframes; p.nblocks = (p.nframes + kBlock - 1) / kBlock; p.in_len = len;
-  { const int32_t rc = setup_scratch(c, p); if (rc != ETLG_OK) return rc; }
-  launch(c, 0, p);   // k_classify: envelope + tag of every frame
+  DecParams p;
+  RC(classify_begin(c, buf, len, frame_offsets, nframes, flags, p));   // k_classify: envelope + tag of every frame
   HIPCHK(c, hipMemcpyAsync(tags_out, p.f_tag, nframes, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return ETLG_OK;
@@ -657,29 +709,17 @@ int32_t etlg_frame_tags(etlg_ctx* c, const uint8_t* buf, size_t len, const uint3
 
 int32_t etlg_shard_plan(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t* frame_offsets, size_t nframes, uint32_t n_shards,
                         uint32_t flags, uint64_t* cuts_out) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+  (void)flush_deferred(c);
   if (!c || !frame_offsets || !cuts_out || !n_shards || n_shards > 4096) return ETLG_InvalidArgument;
   clear_error(c);
-  if (len > 0xFFFFFFFFull - 16 || nframes >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+  RC(batch_too_large(c, len, nframes));
   cuts_out[0] = 0;
   for (uint32_t k = 1; k <= n_shards; k++) cuts_out[k] = nframes;
   if (!nframes) { for (uint32_t k = 1; k < n_shards; k++) cuts_out[k] = 0; return ETLG_OK; }
   if (n_shards == 1) return ETLG_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; }
-  const bool in_dev = flags & ETLG_F_INPUT_ON_DEVICE;
   hipStream_t s = c->stream;
-  DecParams p{};
-  p.in = buf; p.offs = frame_offsets;
-  if (!in_dev) {
-    HIPCHK(c, c->d_in.ensure(len + 64)); HIPCHK(c, c->d_offs.ensure((nframes + 1) * 4));
-    if (len) HIPCHK(c, hipMemcpyAsync(c->d_in.p, buf, len, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->d_offs.p, frame_offsets, (nframes + 1) * 4, hipMemcpyHostToDevice, s));
-    p.in = (const uint8_t*)c->d_in.p; p.offs = (const uint32_t*)c->d_offs.p;
-  }
-  p.nframes = (uint32_t)nframes; p.nblocks = (p.nframes + kBlock - 1) / kBlock; p.in_len = len;
-  { const int32_t rc = setup_scratch(c, p); if (rc != ETLG_OK) return rc; }
-  launch(c, 0, p);   // k_classify: the tags stay on the device
+  DecParams p;
+  RC(classify_begin(c, buf, len, frame_offsets, nframes, flags, p));   // k_classify: the tags stay on the device
   HIPCHK(c, c->d_colsel.ensure((size_t)n_shards * 4 + 64));
   uint32_t* d_cuts = (uint32_t*)c->d_colsel.p;
   etlg_k_shard_cuts(p.f_tag, p.offs, p.nframes, n_shards, d_cuts, s);
@@ -707,28 +747,16 @@ int32_t etlg_shard_replay(etlg_ctx* c, const uint8_t* buf, size_t len, const uin
 int32_t etlg_control_stream(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t* frame_offsets, size_t nframes, uint32_t flags,
                             uint8_t* out_bytes, size_t out_cap, uint32_t* out_offsets, size_t out_offsets_cap,
                             size_t* n_bytes, size_t* n_frames, uint32_t* last_tag) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+  (void)flush_deferred(c);
   if (!c || !frame_offsets || !n_bytes || !n_frames) return ETLG_InvalidArgument;
   clear_error(c);
   *n_bytes = 0; *n_frames = 0;
   if (last_tag) *last_tag = 0;
-  if (len > 0xFFFFFFFFull - 16 || nframes >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+  RC(batch_too_large(c, len, nframes));
   if (!nframes) return ETLG_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; }
-  const bool in_dev = flags & ETLG_F_INPUT_ON_DEVICE;
   hipStream_t s = c->stream;
-  DecParams p{};
-  p.in = buf; p.offs = frame_offsets;
-  if (!in_dev) {
-    HIPCHK(c, c->d_in.ensure(len + 64)); HIPCHK(c, c->d_offs.ensure((nframes + 1) * 4));
-    if (len) HIPCHK(c, hipMemcpyAsync(c->d_in.p, buf, len, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->d_offs.p, frame_offsets, (nframes + 1) * 4, hipMemcpyHostToDevice, s));
-    p.in = (const uint8_t*)c->d_in.p; p.offs = (const uint32_t*)c->d_offs.p;
-  }
-  p.nframes = (uint32_t)nframes; p.nblocks = (p.nframes + kBlock - 1) / kBlock; p.in_len = len;
-  { const int32_t rc = setup_scratch(c, p); if (rc != ETLG_OK) return rc; }
-  launch(c, 0, p);   // k_classify: envelope + tag of every frame
+  DecParams p;
+  RC(classify_begin(c, buf, len, frame_offsets, nframes, flags, p));   // k_classify: envelope + tag of every frame
   constexpr uint32_t kCap = 1u << 16;   // control frames of one range the list holds
   // scratch: hdr (16 words) | list (kCap) | span (2 per frame) | keep frames (<= 3 per frame: the frame, its Begin, its Commit) |
   // lens (3 per frame) | out offsets (3 per frame + 1): 16 + 12 kCap + 1 words
@@ -785,29 +813,26 @@ int32_t etlg_control_stream(etlg_ctx* c, const uint8_t* buf, size_t len, const u
 
 // debugging aid (not part of etlg.h): [0] scans that needed a rerun with hints, [1] scans that fell back to the one-lane walk
 int32_t etlg_ctx_debug_scan(etlg_ctx* c, unsigned long long* out2) {
-  if (!c || !out2) return ETLG_InvalidArgument;
-  out2[0] = c->scan_reruns; out2[1] = c->scan_seq;
-  return ETLG_OK;
+  const unsigned long long w[2] = {c ? c->scan_reruns : 0, c ? c->scan_seq : 0};
+  return debug_words(c, out2, w, 2);
 }
 
 // debugging aid (not part of etlg.h): table-copy batches [0] produced by the rows -> arena kernel, [1] decoded through the row -> frame rewrite
-int32_t etlg_ctx_debug_copy(etlg_ctx* c, unsigned long long* out2) {
-  if (!c || !out2) return ETLG_InvalidArgument;
-  out2[0] = c->copy_n[0]; out2[1] = c->copy_n[1];
-  return ETLG_OK;
-}
+int32_t etlg_ctx_debug_copy(etlg_ctx* c, unsigned long long* out2) { return debug_words(c, out2, c ? c->copy_n : nullptr, 2); }
 
-// debugging aid (not part of etlg.h): [0] result blocks cleared again after a second attempt behind their lap's re-initialisation,
-// [1] chains finished early because their last batch was marked for a second attempt
-int32_t etlg_ctx_debug_ring(etlg_ctx* c, unsigned long long* out1) {
-  if (!c || !out1) return ETLG_InvalidArgument;
-  out1[0] = c->ring_recleared; out1[1] = c->chain_healed; out1[2] = c->chain_reissued; out1[3] = c->scan_chained_n; out1[4] = c->scan_chain_redone; out1[5] = c->chain_spared;   // (callers pass eight words)
-  return ETLG_OK;
+// debugging aid (not part of etlg.h), six words: [0] result blocks cleared again after a second attempt behind their lap's re-initialisation,
+// [1] chains finished early because their last batch was marked for a second attempt, [2] always 0 (it counted the batches of the re-issue
+// experiment, tools/experiments/r06_chain_reissue.diff), [3] batches whose decode was enqueued behind their boundary scan, [4] ... that were
+// decoded again with the count in hand, [5] second attempts of a plan batch whose successors stood
+int32_t etlg_ctx_debug_ring(etlg_ctx* c, unsigned long long* out6) {   // (callers pass eight words)
+  if (!c) return ETLG_InvalidArgument;
+  const unsigned long long w[6] = {c->ring_recleared, c->chain_healed, 0, c->scan_chained_n, c->scan_chain_redone, c->chain_spared};
+  return debug_words(c, out6, w, 6);
 }
 
 int32_t etlg_copy_decode(etlg_ctx* c, int32_t schema_slot, const uint8_t* buf, size_t len, const uint32_t* row_offsets, size_t nrows,
                          uint32_t flags, etlg_batch** out) {
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+  (void)flush_deferred(c);
   if (!c || !out || !row_offsets) return ETLG_InvalidArgument;
   *out = nullptr;
   clear_error(c);
@@ -816,7 +841,7 @@ int32_t etlg_copy_decode(etlg_ctx* c, int32_t schema_slot, const uint8_t* buf, s
   const uint32_t ncols = sh.desc.n_cols;
   const uint64_t per_row = etlg_k_copy_bytes_per_row(ncols);
   const uint64_t syn_len = (uint64_t)len + (uint64_t)nrows * per_row;
-  if (syn_len > 0xFFFFFFFFull - 64 || nrows >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+  RC(batch_too_large(c, syn_len, nrows, 64));
   HIPCHK(c, hipSetDevice(c->device));
   const bool in_dev = flags & ETLG_F_INPUT_ON_DEVICE;
   hipStream_t s = c->stream;
@@ -835,25 +860,16 @@ int32_t etlg_copy_decode(etlg_ctx* c, int32_t schema_slot, const uint8_t* buf, s
   // and the rows below must neither see that state nor be chained to it. (A synchronous call finishes everything, as before.)
   bool drain = !j.async;
   for (const etlg_batch* pb : c->pending) if (!pb->copy.active) drain = true;
-  if (drain) { const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; clear_error(c); }
-  // (a staging block / event `j` still holds when the call returns — an early return, or a decode that failed before there was a batch
-  // to adopt them — goes back to the pools)
-  struct StageGuard { etlg_ctx* c; CopyJob& j; ~StageGuard() { if (j.stage_blk) blk_give(c, c->gen, j.stage_blk, j.stage_cap, false); if (j.h2d_done) c->ev_pool.push_back(j.h2d_done); } } stage_guard{c, j};
+  if (drain) { RC(drain_pending(c)); clear_error(c); }
+  // (a staging block / event that no batch has adopted when the call returns — an early return, or a decode that failed before there was
+  // a batch — goes back to the pools)
+  StagedInput staged(c);
   if (in_dev) { j.d_rows = buf; j.d_row_offs = row_offsets; }
-  else if (j.async) {
-    // host rows: uploaded into a device block the batch owns, on the copy stream, beside the decode of the batch before it (the caller
-    // keeps buf / row_offsets untouched until the batch is synced, as for every ASYNC batch: include/etlg.h)
-    const size_t o_offs = (len + 16 + 255) & ~(size_t)255;
-    HIPCHK(c, blk_take(c, o_offs + (nrows + 1) * 4 + 64, false, &j.stage_blk, &j.stage_cap));
-    if (!c->h2d_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
-    if (c->ev_pool.empty()) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_pool.push_back(e); }
-    j.h2d_done = c->ev_pool.back(); c->ev_pool.pop_back();
-    if (len) HIPCHK(c, hipMemcpyAsync(j.stage_blk, buf, len, hipMemcpyHostToDevice, c->h2d_stream));
-    HIPCHK(c, hipMemcpyAsync((uint8_t*)j.stage_blk + o_offs, row_offsets, (nrows + 1) * 4, hipMemcpyHostToDevice, c->h2d_stream));
-    HIPCHK(c, hipEventRecord(j.h2d_done, c->h2d_stream));
-    HIPCHK(c, hipStreamWaitEvent(s, j.h2d_done, 0));
-    j.d_rows = (const uint8_t*)j.stage_blk; j.d_row_offs = (const uint32_t*)((const uint8_t*)j.stage_blk + o_offs);
-    c->staged_async++;
+  else if (j.async) {   // host rows: beside the decode of the batch before it
+    RC(staged.upload(buf, len, row_offsets, nrows));
+    HIPCHK(c, hipStreamWaitEvent(s, staged.done, 0));
+    j.d_rows = staged.bytes(); j.d_row_offs = staged.offs();
+    j.staged = &staged;
   } else {
     HIPCHK(c, c->d_copy_in.ensure(len + 64)); HIPCHK(c, c->d_copy_offs.ensure((nrows + 1) * 4));
     if (len) HIPCHK(c, hipMemcpyAsync(c->d_copy_in.p, buf, len, hipMemcpyHostToDevice, s));
@@ -867,7 +883,7 @@ int32_t etlg_copy_decode(etlg_ctx* c, int32_t schema_slot, const uint8_t* buf, s
   }
   const uint64_t avg = nrows ? (len + nrows - 1) / nrows : 0;
   j.lds = (uint32_t)std::min<uint64_t>(((256 * avg * 9 / 8 + 1024) + 255) & ~255ull, 150 * 1024);
-  { const char* e = getenv("ETLG_COPY_LDS"); if (e) j.lds = (uint32_t)atoi(e); }   // measurement knob: 0 = rows read in place (no staging window, more waves per CU)
+  if (c->copy_lds >= 0) j.lds = (uint32_t)c->copy_lds;   // ETLG_COPY_LDS, measurement knob: 0 = rows read in place (no staging window, more waves per CU)
   // the rows decode inside a virtual transaction of their own; the context's stream state is left alone (finish_batch keeps it
   // that way for a batch that is finished later)
   const bool sv_in = c->in_txn; const uint64_t sv_lsn = c->final_lsn, sv_ord = c->next_ord;
@@ -876,7 +892,6 @@ int32_t etlg_copy_decode(etlg_ctx* c, int32_t schema_slot, const uint8_t* buf, s
   const uint32_t dflags = (flags & (ETLG_F_OUTPUT_ON_DEVICE | ETLG_F_FINISH_CELLS | ETLG_F_CHECK_CELLS)) | ETLG_F_INPUT_ON_DEVICE | ETLG_F_NO_CONTROL | (j.async ? (uint32_t)ETLG_F_ASYNC : 0u);
   const int32_t rc = j.direct ? etlg_decode(c, j.d_rows, len, j.d_row_offs, nrows, dflags, out)
                               : etlg_decode(c, j.d_out, (size_t)syn_len, j.d_out_offs, nrows, dflags, out);
-  j.stage_blk = c->copy.stage_blk; j.h2d_done = c->copy.h2d_done;   // (nullptr once the batch has adopted them: etlg_decode)
   c->copy = CopyJob{};
   c->in_txn = sv_in; c->final_lsn = sv_lsn; c->next_ord = sv_ord;
   return rc;
@@ -888,7 +903,7 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
   SlowScope slow_scope_decode(c, "etlg_decode");
   *out = nullptr;
   clear_error(c);
-  if (len > 0xFFFFFFFFull - 16 || nframes >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+  RC(batch_too_large(c, len, nframes));
   HIPCHK(c, hipSetDevice(c->device));
   // (the batch a call left deferred — a boundary scan in flight, a control pre-pass running ahead — is flushed below, once this call
   // knows whether it is itself a batch of the pipelined control path: such a batch sends its own pre-pass out FIRST)
@@ -898,40 +913,28 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
   const bool scan = frame_offsets == nullptr;
   // ASYNC table-copy batches still in flight (etlg_copy_decode) finish before a WAL batch is taken: a chained batch would read the state
   // the last of them leaves — the end of a virtual transaction — as its carried transaction state
-  if (!c->copy.active) for (const etlg_batch* pb : c->pending) if (pb->copy.active) { const int32_t rc_ = flush_deferred(c); (void)rc_; const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; clear_error(c); break; }
+  if (!c->copy.active) for (const etlg_batch* pb : c->pending) if (pb->copy.active) { (void)flush_deferred(c); RC(drain_pending(c)); clear_error(c); break; }
   // Can this call turn out to be one that HOLDS the deferred batch (sends its own control pre-pass out first, see `hold` below)? If not,
   // the deferred batch is flushed right here, before this batch's upload is put in front of the decode streams: its control pass and
   // decode kernels must not queue behind the copy of the batch after it (the upload / decode overlap the staging exists for).
   const bool may_hold = (flags & ETLG_F_ASYNC) && out_dev && !no_ctrl && !scan && nframes && c->ctl_hold_mode && c->ctl_async_mode && c->last_had_ctrl &&
                         c->deferred && c->deferred->defer_ctl;
-  if (!may_hold) { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+  if (!may_hold) (void)flush_deferred(c);
   // ---- ASYNC with HOST input (the staging batcher of a Rust host, crates/etl-gfx950/src/batcher.rs: pinned buffers from
   //      etlg_host_alloc): the bytes and the sidecar are copied into a device block the batch owns, on a copy stream of their own,
   //      and from here on the batch IS a device-input batch — it joins the chain, and its upload runs beside the decode of the batch
   //      before it (double buffering: the caller fills its next buffer meanwhile). The caller keeps the host buffers untouched until
   //      the batch is synced, as for every ASYNC batch (include/etlg.h).
-  void* stage_blk = nullptr; size_t stage_cap = 0; hipEvent_t h2d_done = nullptr;
   // (in place before the first HIP call below: an early return gives the block and the event back)
-  struct StageGuard { etlg_ctx* c; void*& p; size_t& cap; hipEvent_t& ev; ~StageGuard() { if (p) blk_give(c, c->gen, p, cap, false); if (ev) c->ev_pool.push_back(ev); } } stage_guard{c, stage_blk, stage_cap, h2d_done};
+  StagedInput staged(c);
   if ((flags & ETLG_F_ASYNC) && out_dev && !in_dev && !scan && len && nframes && !c->copy.active && !c->force_multipass && len < (1ull << 31)) {
-    const size_t o_offs = (len + 16 + 255) & ~(size_t)255;   // the kernels' readers may touch up to 16 bytes past the input
-    HIPCHK(c, blk_take(c, o_offs + (nframes + 1) * 4 + 64, false, &stage_blk, &stage_cap));
-    if (!c->h2d_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
-    if (c->ev_pool.empty()) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_pool.push_back(e); }
-    h2d_done = c->ev_pool.back(); c->ev_pool.pop_back();
-    HIPCHK(c, hipMemcpyAsync(stage_blk, buf, len, hipMemcpyHostToDevice, c->h2d_stream));
-    HIPCHK(c, hipMemcpyAsync((uint8_t*)stage_blk + o_offs, frame_offsets, (nframes + 1) * 4, hipMemcpyHostToDevice, c->h2d_stream));
-    HIPCHK(c, hipEventRecord(h2d_done, c->h2d_stream));
-    if (!c->stream2) {   // the chain may put this batch on either decode stream: both exist before anything waits
-      HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-      HIPCHK(c, hipEventCreateWithFlags(&c->tail2, hipEventDisableTiming));
-    }
+    RC(staged.upload(buf, len, frame_offsets, nframes));
+    RC(ensure_stream2(c));   // the chain may put this batch on either decode stream: both exist before anything waits
     // (a call that may hold the deferred batch lets only the control stream wait now — its pre-pass reads the upload; the decode streams
     // get their wait once the held batch has been enqueued on them, below)
-    for (hipStream_t w : {may_hold ? (hipStream_t) nullptr : c->stream, may_hold ? (hipStream_t) nullptr : c->stream2, c->ctl_stream, c->scan_stream}) if (w) HIPCHK(c, hipStreamWaitEvent(w, h2d_done, 0));
-    buf = (const uint8_t*)stage_blk; frame_offsets = (const uint32_t*)((const uint8_t*)stage_blk + o_offs);
+    for (hipStream_t w : {may_hold ? (hipStream_t) nullptr : c->stream, may_hold ? (hipStream_t) nullptr : c->stream2, c->ctl_stream, c->scan_stream}) if (w) HIPCHK(c, hipStreamWaitEvent(w, staged.done, 0));
+    buf = staged.bytes(); frame_offsets = staged.offs();
     in_dev = true;
-    c->staged_async++;
   }
   // ASYNC batches are chained on the device (DecParams.carry) and may be decoded again when they are synced, so everything
   // they read must still be there then: device-resident input AND sidecar (the context's staging and scan buffers are shared
@@ -957,22 +960,21 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
   // them left on the device — nothing the host control plane of the held batch changes. Two pre-passes in flight: two sets of buffers.
   const bool hold = ctl_ahead && c->ctl_hold_mode && c->deferred && c->deferred->defer_ctl;
   if (!hold) {
-    const int32_t rc_ = flush_deferred(c); (void)rc_;
-    if (may_hold && h2d_done) for (hipStream_t w : {c->stream, c->stream2}) if (w) HIPCHK(c, hipStreamWaitEvent(w, h2d_done, 0));
+    (void)flush_deferred(c);
+    if (may_hold && staged.done) for (hipStream_t w : {c->stream, c->stream2}) if (w) HIPCHK(c, hipStreamWaitEvent(w, staged.done, 0));
   }
   hipStream_t s = c->stream;
-  if (!async) { const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; clear_error(c); }
+  if (!async) { RC(drain_pending(c)); clear_error(c); }
   // The result blocks live in a ring of kResRing: include/etlg.h asks for fewer than 32 batches in flight, and a caller that keeps more
   // (etlg_copy_decode(ASYNC) queues batches back to back too) must not get a block that a batch in flight — or one being decoded again —
   // still writes: the oldest batches are finished first. They stay the caller's: their sync returns what was found here.
-  while (c->pending.size() >= etlg_ctx::kResRing - 2) { const int32_t rc = finish_batch(c, c->pending.front()); (void)rc; }
+  while (c->pending.size() >= etlg_ctx::kResRing - 2) (void)finish_batch(c, c->pending.front());
 
   // ---- record boundaries: the caller's sidecar, or the device scan (scan.hip)
   const uint32_t* h_offs = frame_offsets;
   const uint8_t* d_in_ptr = buf;  // device address of the input
   if (!in_dev) {
-    HIPCHK(c, c->d_in.ensure(len + 64));
-    if (len) HIPCHK(c, hipMemcpyAsync(c->d_in.p, buf, len, hipMemcpyHostToDevice, s));
+    RC(upload_input(c, buf, len, nullptr, 0));
     d_in_ptr = (const uint8_t*)c->d_in.p;
   }
   auto* b = new etlg_batch();
@@ -981,14 +983,26 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
   b->user_no_ctrl = no_ctrl; b->out_dev = out_dev; b->in_dev = in_dev; b->scan = scan; b->len = len;
   b->finish_what = (flags & ETLG_F_FINISH_CELLS) ? (uint32_t)(ETLG_FINISH_ARRAYS | ETLG_FINISH_FLOATS) : 0u;
   b->check_cells = (flags & ETLG_F_CHECK_CELLS) != 0;
-  b->stage_blk = stage_blk; b->stage_cap = stage_cap; b->h2d_done = h2d_done;   // the batch owns them from here (etlg_batch_free)
-  stage_blk = nullptr; h2d_done = nullptr;
-  if (c->copy.active && c->copy.stage_blk) {   // an ASYNC table-copy batch whose rows were staged by etlg_copy_decode: likewise
-    b->stage_blk = c->copy.stage_blk; b->stage_cap = c->copy.stage_cap; b->h2d_done = c->copy.h2d_done;
-    c->copy.stage_blk = nullptr; c->copy.h2d_done = nullptr;
-  }
+  staged.adopted_by(b);   // the batch owns the block and the event from here (etlg_batch_free)
+  if (c->copy.active && c->copy.staged) { c->copy.staged->adopted_by(b); c->copy.staged = nullptr; }   // an ASYNC table-copy batch whose rows were staged by etlg_copy_decode: likewise
   b->host_in = in_dev ? nullptr : buf; b->host_offs = (in_dev || scan) ? nullptr : h_offs; b->dev_in = in_dev ? buf : nullptr;
   b->d_in_ptr = d_in_ptr; b->user_offs = frame_offsets;
+  // the decode goes out (decode_tail) and the batch is the caller's: pending at the end of the chain (ASYNC), or finished here
+  auto enqueue_and_hand_out = [&](size_t nf) -> int32_t {
+    RC(decode_tail(c, b, nf, async, (async && !c->pending.empty()) ? c->pending.back() : nullptr));
+    guard.b = nullptr;
+    *out = b;
+    if (!async) return finish_batch(c, b);
+    b->pending = true; b->v.on_device = 1; fill_view_common(b); c->pending.push_back(b);
+    return ETLG_OK;
+  };
+  auto hand_out_deferred = [&]() -> int32_t {   // ... or pending with its decode NOT enqueued: the next call on the context does that (flush_deferred)
+    b->deferred = true; b->pending = true; b->v.on_device = 1;
+    c->deferred = b; c->pending.push_back(b);
+    guard.b = nullptr;
+    *out = b;
+    return ETLG_OK;
+  };
   if (scan) {
     // Round 6: when the batch will be decoded by the fixed-width plan behind its sidecar pre-pass (the cfg2 shape) and the stream has
     // shown how many frames a batch of this size holds, the decode is enqueued AT ONCE behind the scan: the grids are sized by a bound,
@@ -1016,25 +1030,16 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
       HIPCHK(c, scan_begin(c, c->scan_job, d_in_ptr, len, b->scan_s, *b->scan_offs, b->d_scan_res));
       b->nf_est = nf_est;
       if (async) {
-        if (c->ev_pool.empty()) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_pool.push_back(e); }
-        hipEvent_t sev = c->ev_pool.back(); c->ev_pool.pop_back();
+        hipEvent_t sev = nullptr;
+        RC(take_event(c, &sev));
         HIPCHK(c, hipEventRecord(sev, c->scan_stream));
-        if (!c->stream2) {
-          HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-          HIPCHK(c, hipEventCreateWithFlags(&c->tail2, hipEventDisableTiming));
-        }
+        RC(ensure_stream2(c));
         for (hipStream_t w : {c->stream, c->stream2}) HIPCHK(c, hipStreamWaitEvent(w, sev, 0));
         c->ev_pool.push_back(sev);   // (recorded and waited for: the waits keep their own reference to this recording)
       }
       b->scan_chained = true;
       c->scan_chained_n++;
-      const int32_t rc = decode_tail(c, b, (size_t)bound, async, (async && !c->pending.empty()) ? c->pending.back() : nullptr);
-      if (rc != ETLG_OK) return rc;
-      guard.b = nullptr;
-      *out = b;
-      if (!async) return finish_batch(c, b);
-      b->pending = true; b->v.on_device = 1; fill_view_common(b); c->pending.push_back(b);
-      return ETLG_OK;
+      return enqueue_and_hand_out((size_t)bound);
     }
     if (async) {
       // The scan of THIS batch runs on its own stream while the previous batch is still being decoded on the context's, and
@@ -1042,14 +1047,10 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
       // the frame count and enqueues the decode. The input must be complete when the call is made (include/etlg.h).
       if (!c->scan_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->scan_stream, hipStreamNonBlocking));
       HIPCHK(c, scan_begin(c, c->scan_job, d_in_ptr, len, c->scan_stream, *b->scan_offs));
-      b->deferred = true; b->pending = true; b->v.on_device = 1;
-      c->deferred = b; c->pending.push_back(b);
-      guard.b = nullptr;
-      *out = b;
-      return ETLG_OK;
+      return hand_out_deferred();
     }
     HIPCHK(c, device_scan(c, d_in_ptr, len, &nframes, s, c->d_offs));
-    if (nframes >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+    RC(batch_too_large(c, 0, nframes));
   }
   if (ctl_ahead) {
     // the pre-pass goes out now, on the control stream; the host control plane and the decode follow when the next call comes in
@@ -1059,23 +1060,21 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
       HIPCHK(c, c->d_ctl_res.ensure(sizeof(DevResult) * etlg_ctx::kCtlRing));
       if (b->h2d_done) HIPCHK(c, hipStreamWaitEvent(c->ctl_stream, b->h2d_done, 0));
     }
-    b->nframes_in = nframes;
-    b->ctl_async = true;
-    DecParams& cp = b->ctl_params;
-    cp = DecParams{};
+    b->nframes_in = nframes; b->ctl_async = true;
+    DecParams& cp = b->ctl_params = DecParams{};
     cp.in = d_in_ptr; cp.offs = frame_offsets; cp.nframes = (uint32_t)nframes; cp.nblocks = ((uint32_t)nframes + kBlock - 1) / kBlock; cp.in_len = len;
     cp.worker_kind = (uint32_t)c->worker; cp.sync_table = c->sync_table; cp.copy_slot = -1; cp.host_err_frame = 0xFFFFFFFFu;
     cp.in_txn = c->in_txn; cp.final_lsn = c->final_lsn; cp.next_ord = c->next_ord;
-    cp.flags = 32u;
+    cp.flags = kDecCtlPrePass;
     etlg_batch* prev = c->pending.empty() ? nullptr : c->pending.back();
     if (prev && prev->pending) {
       if (prev->ctl_async && prev->ctl_params.res) cp.carry = prev->ctl_params.res;   // the pre-passes chain among themselves (control stream order)
       else if (prev->kdone) { HIPCHK(c, hipStreamWaitEvent(c->ctl_stream, prev->kdone, 0)); cp.carry = prev->d_res_blk; }   // an optimistic batch: its decode result
-      else { const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; cp.in_txn = c->in_txn; cp.final_lsn = c->final_lsn; cp.next_ord = c->next_ord; }
+      else { RC(drain_pending(c)); cp.in_txn = c->in_txn; cp.final_lsn = c->final_lsn; cp.next_ord = c->next_ord; }
     }
     b->ctl_set = (int)(c->ctl_seq & 1u);   // (the held batch's pre-pass wrote the other set)
     cp.res = (DevResult*)c->d_ctl_res.p + (c->ctl_seq++ % etlg_ctx::kCtlRing);
-    { const int32_t rc = ctl_begin(c, b, cp, c->ctl_stream, true); if (rc != ETLG_OK) { if (hold) { const int32_t rc_ = flush_deferred(c); (void)rc_; } return rc; } }
+    { const int32_t rc = ctl_begin(c, b, cp, c->ctl_stream, true); if (rc != ETLG_OK) { if (hold) (void)flush_deferred(c); return rc; } }
     if (hold) {   // now the held batch: its pre-pass result, its control plane, its decode
       const int32_t rc_ = flush_deferred(c);
       // (the held batch could not be enqueued: this batch's pre-pass was chained to a control result that will never be the state the
@@ -1083,27 +1082,17 @@ int32_t etlg_decode(etlg_ctx* c, const uint8_t* buf, size_t len, const uint32_t*
       if (rc_ != ETLG_OK) { b->force_rerun = true; b->ctl_started = false; }
       if (b->h2d_done) for (hipStream_t w : {c->stream, c->stream2}) if (w) HIPCHK(c, hipStreamWaitEvent(w, b->h2d_done, 0));
     }
-    b->deferred = true; b->defer_ctl = true; b->pending = true; b->v.on_device = 1;
-    c->deferred = b; c->pending.push_back(b);
+    b->defer_ctl = true;
     c->ctl_ahead_n++;
-    guard.b = nullptr;
-    *out = b;
-    return ETLG_OK;
+    return hand_out_deferred();
   }
   // A chain behind a batch that has to be decoded again does not heal by itself: every batch enqueued behind one that is marked for a
   // second attempt starts from that batch's unusable result, refuses to run, and is itself decoded again — synchronously — when it is
   // synced; with the caller keeping its window full that went on for the rest of the stream (one fixed-width batch with an UPDATE in it,
   // and every later batch was a poisoned first attempt plus a synchronous second one). The batches in flight are finished first, once;
   // this batch then starts a fresh chain from the host's exact state.
-  if (async && !c->pending.empty() && c->pending.back()->force_rerun) { const int32_t rc = drain_pending(c); if (rc != ETLG_OK) return rc; clear_error(c); c->chain_healed++; }
-  {
-    const int32_t rc = decode_tail(c, b, nframes, async, (async && !c->pending.empty()) ? c->pending.back() : nullptr);
-    if (rc != ETLG_OK) return rc;
-  }
-  guard.b = nullptr;
-  *out = b;
-  if (async) { b->pending = true; b->v.on_device = 1; fill_view_common(b); c->pending.push_back(b); return ETLG_OK; }
-  return finish_batch(c, b);
+  if (async && !c->pending.empty() && c->pending.back()->force_rerun) { RC(drain_pending(c)); clear_error(c); c->chain_healed++; }
+  return enqueue_and_hand_out(nframes);
 }
 
 }  // extern "C"
@@ -1125,8 +1114,7 @@ int32_t flush_deferred(etlg_ctx* c) {
   else {
     const hipError_t e = scan_collect(c, c->scan_job, &nframes);
     if (e != hipSuccess) rc = lib_error(c, ETLG_DeviceError, hipGetErrorString(e));
-    else if (nframes >= (1u << 30)) rc = lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
-    else { c->scan_last_nf = nframes; c->scan_last_len = b->len; }
+    else if ((rc = batch_too_large(c, 0, nframes)) == ETLG_OK) { c->scan_last_nf = nframes; c->scan_last_len = b->len; }
   }
   if (rc == ETLG_OK) {
     // A batch whose boundary scan was deferred joined the chain when the stream had shown no Relation / DDL frame. If it has by now (a
@@ -1158,6 +1146,81 @@ int32_t flush_deferred(etlg_ctx* c) {
   return ETLG_OK;
 }
 
+// ---- two streams. A batch whose first attempt is a single-pass kernel (k_plan, k_fused, k_cells) and whose predecessor in the
+//      chain is one too, and still in flight, is enqueued on the OTHER decode stream and told (flags bit 4) that the state it
+//      starts from arrives late: its kernel does not read the predecessor's result block at its start; the few tiles without a
+//      Begin before them in the batch poll for it (plan.hip plan_late_carry, lookback.hip.h txn_lookback). So the tail of batch k — its last waves, the write-back of its dirty lines, the dispatch of
+//      the next kernel — overlaps the staging and parsing of batch k+1: 63.9 -> 50.1 us per 64 MiB cfg2 batch measured with two
+//      independent chains (profiles/r03_plan_development.json). Ordering kept: k+1 starts after k-1 has completed (look-back
+//      buffers rotate with distance two; k's waves are all dispatched by then, so a tile of k+1 that polls cannot hold a slot k
+//      needs), side inputs unchanged (a change drains the chain), no lap boundary of the result ring.
+// Leaves the chosen stream in c->stream (decode_tail puts the context's back) and b->sidx; the plain single-pass case also sets up side inputs, outputs and b->plan_decided: the choice needs them.
+int32_t choose_decode_stream(etlg_ctx* c, etlg_batch* b, bool async, etlg_batch* prev) {
+  DecParams& p = b->params;
+  const hipStream_t first = c->stream;
+  const size_t len = b->len;
+  const bool no_ctrl = b->user_no_ctrl;
+  const uint32_t res_slot = c->res_seq % etlg_ctx::kResRing;
+  bool beside = false;
+  // (what both cases below ask for: a predecessor in flight on a single-pass kernel, a single-pass kernel for this batch, no lap boundary of the ring)
+  const bool may_go_beside = async && prev && prev->pending && prev->level <= 1 && prev->used_fused && !prev->force_rerun && c->overlap_mode && p.nframes &&
+                             !c->force_multipass && len < (1ull << 31) && c->res_seq != 0 && res_slot >= 2 && !b->copy.active && !c->prof_serial;
+  if (may_go_beside && (no_ctrl || !c->last_had_ctrl) && !b->ctl_async && c->side_valid && !c->side_dirty && !c->slots_dirty && c->last_epochs.empty()) {
+    p.flags |= kDecNoControl;
+    RC(build_side_inputs(c, b, std::vector<EpochRec>()));   // the unchanged-inputs path: no stream work
+    RC(setup_outputs(c, b));
+    b->plan_decided = plan_wanted(c, b) ? 1 : 0;
+    beside = true;   // (a look-back buffer that has to grow synchronises both streams: take_descriptors)
+  }
+  // Batches on the pipelined control path (their pre-pass ran ahead, ctl_async) alternate between the two decode streams as well
+  // (round 4): the decode kernel of batch k+1 — enqueued by standard_path, behind its own control pass, side-input set and
+  // outputs, all of which go to the stream chosen here — starts beside the tail of batch k's; it reads the carried transaction state
+  // late like every batch that runs beside its predecessor (flags bit 4). cfg5: the decode kernels were a single-stream chain.
+  else if (may_go_beside && prev->ctl_async && b->ctl_async && c->ctl_overlap_mode) beside = true;
+  if (beside) {
+    RC(ensure_stream2(c));
+    b->sidx = prev->sidx ^ 1;
+    c->stream = b->sidx ? c->stream2 : first;
+    // the batch before the predecessor must be complete; it is, when it ran on this stream — otherwise wait for its event
+    etlg_batch* pp = nullptr;
+    for (size_t i = 0; i + 1 < c->pending.size(); i++) if (c->pending[i + 1] == prev) pp = c->pending[i];
+    if (pp && pp->pending && pp->kdone && pp->sidx != b->sidx) HIPCHK(c, hipStreamWaitEvent(c->stream, pp->kdone, 0));
+    p.flags |= kDecLateCarry;
+    c->overlapped++;
+  } else {
+    b->sidx = 0;
+    if (c->tail2_set) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->tail2, 0)); c->tail2_set = false; }   // join: everything enqueued on stream2 so far
+  }
+  if (b->side && !(b->side->synced & (1u << b->sidx))) {   // the set was uploaded on the other decode stream: the first batch over here waits for it
+    HIPCHK(c, hipStreamWaitEvent(c->stream, b->side->ready, 0));
+    b->side->synced |= 1u << b->sidx;
+  }
+  return ETLG_OK;
+}
+
+// Result block: next slot of a ring that is re-initialised once per lap. Slot 31 is the carry source of the batch in
+// slot 0, so it is re-initialised one batch later than the others.
+int32_t take_ring_slot(etlg_ctx* c, etlg_batch* b, etlg_batch* prev) {
+  hipStream_t s = c->stream;
+  const uint32_t seq = c->res_seq++;
+  const uint32_t slot = seq % etlg_ctx::kResRing;
+  DevResult* ring = (DevResult*)c->d_res.p;
+  // the blocks about to be re-initialised belong to batches whose result copies travel on res_stream: with two decode streams a
+  // batch completes within microseconds of its predecessor, so "the copy of the batch before last is long done" no longer holds —
+  // wait (on the device) for the copy of the latest batch, which is behind all the others
+  { SlowScope sw1(c, "ring: wait event");
+  if ((slot == 0 || slot == 1) && prev && prev->pending && prev->done) HIPCHK(c, hipStreamWaitEvent(s, prev->done, 0)); }
+  { SlowScope sw2(c, "ring: init copy");
+  const void* init = c->ring_h2d ? (const void*)c->h_init_ring : (const void*)c->d_init_ring;
+  const hipMemcpyKind kind = c->ring_h2d ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  if (seq == 0) HIPCHK(c, hipMemcpyAsync(ring, init, sizeof(DevResult) * etlg_ctx::kResRing, kind, s));
+  else if (slot == 0) HIPCHK(c, hipMemcpyAsync(ring, init, sizeof(DevResult) * (etlg_ctx::kResRing - 1), kind, s));
+  else if (slot == 1) HIPCHK(c, hipMemcpyAsync(ring + (etlg_ctx::kResRing - 1), init, sizeof(DevResult), kind, s)); }
+  b->d_res_blk = ring + slot;
+  b->res_seq_no = seq;
+  return ETLG_OK;
+}
+
 // Everything of etlg_decode that needs the frame count: parameters, result block, side inputs, outputs, the first kernel.
 int32_t decode_tail(etlg_ctx* c, etlg_batch* b, size_t nframes, bool async, etlg_batch* prev) {
   SlowScope slow_scope_decode_tail(c, "decode_tail");
@@ -1165,26 +1228,24 @@ int32_t decode_tail(etlg_ctx* c, etlg_batch* b, size_t nframes, bool async, etlg
   b->plan_decided = -1;
   const bool scan = b->scan, in_dev = b->in_dev, no_ctrl = b->user_no_ctrl;
   const size_t len = b->len;
-  const uint8_t* d_in_ptr = b->d_in_ptr;
   const uint32_t* frame_offsets = b->user_offs;
-  const uint32_t* h_offs = b->user_offs;
   const uint32_t nf = (uint32_t)nframes;
   DecParams& p = b->params;
   p = DecParams{};
-  p.in = d_in_ptr;
+  p.in = b->d_in_ptr;
   if (scan) p.offs = (const uint32_t*)(b->scan_offs ? b->scan_offs->p : c->d_offs.p);
   else if (in_dev) p.offs = frame_offsets;
   else {
     HIPCHK(c, c->d_offs.ensure((nframes + 1) * 4));
-    HIPCHK(c, hipMemcpyAsync(c->d_offs.p, h_offs, (nframes + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->d_offs.p, frame_offsets, (nframes + 1) * 4, hipMemcpyHostToDevice, s));
     p.offs = (const uint32_t*)c->d_offs.p;
   }
   p.nframes = nf; p.nblocks = (nf + kBlock - 1) / kBlock; p.in_len = len;
   p.worker_kind = (uint32_t)c->worker; p.sync_table = c->sync_table;
-  p.flags = c->fused_dbg & 0xF00u;  // profiling ablations (results are wrong)
-  if (b->check_cells) p.flags |= 64u;   // ETLG_F_CHECK_CELLS: the multi-pass kernels validate json / array cells (k_write_chk)
+  p.flags = c->fused_dbg & kDecAblations;  // profiling ablations (results are wrong)
+  if (b->check_cells) p.flags |= kDecCheckCells;   // ETLG_F_CHECK_CELLS: the multi-pass kernels validate json / array cells (k_write_chk)
   p.copy_slot = -1;
-  if (c->copy.active) { p.flags |= 2u; p.copy_slot = c->copy.slot; b->copy = c->copy; }
+  if (c->copy.active) { p.flags |= kDecCopyRows; p.copy_slot = c->copy.slot; b->copy = c->copy; }
   p.host_err_frame = 0xFFFFFFFFu;
   // carried transaction state: the host's (every earlier batch is finished), or — behind pending ASYNC batches — whatever the
   // batch issued just before this one leaves in its result block
@@ -1193,81 +1254,16 @@ int32_t decode_tail(etlg_ctx* c, etlg_batch* b, size_t nframes, bool async, etlg
   p.nframes_dev = b->scan_chained ? b->d_scan_res : nullptr;
 
   HIPCHK(c, c->d_res.ensure(sizeof(DevResult) * etlg_ctx::kResRing));
-  const uint32_t res_slot = c->res_seq % etlg_ctx::kResRing;
-  // ---- two streams. A batch whose first attempt is a single-pass kernel (k_plan, k_fused, k_cells) and whose predecessor in the
-  //      chain is one too, and still in flight, is enqueued on the OTHER decode stream and told (flags bit 4) that the state it
-  //      starts from arrives late: its kernel does not read the predecessor's result block at its start; the few tiles without a
-  //      Begin before them in the batch poll for it (plan.hip plan_late_carry, lookback.hip.h txn_lookback). So the tail of batch k — its last waves, the write-back of its dirty lines, the dispatch of
-  //      the next kernel — overlaps the staging and parsing of batch k+1: 63.9 -> 50.1 us per 64 MiB cfg2 batch measured with two
-  //      independent chains (profiles/r03_plan_development.json). Ordering kept: k+1 starts after k-1 has completed (look-back
-  //      buffers rotate with distance two; k's waves are all dispatched by then, so a tile of k+1 that polls cannot hold a slot k
-  //      needs), side inputs unchanged (a change drains the chain), no lap boundary of the result ring. Decided before anything is
-  //      enqueued for the batch; everything below then runs on the chosen stream.
-  struct StreamSwitch { etlg_ctx* c; hipStream_t saved; ~StreamSwitch() { c->stream = saved; } } sw{c, c->stream};
+  // (decided before anything is enqueued for the batch; everything below then runs on the chosen stream)
+  StreamSwitch sw{c, c->stream};
   SlowScope slow_scope_pre(c, "decode_tail: whole after params");
-  bool beside = false;
-  const bool first_try_single = p.nframes && !c->force_multipass && len < (1ull << 31) && (no_ctrl || !c->last_had_ctrl) && !b->ctl_async;
-  if (async && prev && prev->pending && prev->level <= 1 && prev->used_fused && !prev->force_rerun && c->overlap_mode && first_try_single && c->res_seq != 0 && res_slot >= 2 &&
-      c->side_valid && !c->side_dirty && !c->slots_dirty && c->last_epochs.empty() && !b->copy.active && !c->prof_serial) {
-    p.flags |= 1u;
-    const std::vector<EpochRec> no_eps;
-    { const int32_t rc = build_side_inputs(c, b, no_eps); if (rc != ETLG_OK) return rc; }   // the unchanged-inputs path: no stream work
-    { const int32_t rc = setup_outputs(c, b); if (rc != ETLG_OK) return rc; }
-    b->plan_decided = plan_wanted(c, b) ? 1 : 0;
-    beside = true;   // (a look-back buffer that has to grow synchronises both streams: take_descriptors)
-  }
-  // Batches on the pipelined control path (their pre-pass ran ahead, ctl_async) alternate between the two decode streams as well
-  // (round 4): the decode kernel of batch k+1 — enqueued by standard_path below, behind its own control pass, side-input set and
-  // outputs, all of which go to the stream chosen here — starts beside the tail of batch k's; it reads the carried transaction state
-  // late like every batch that runs beside its predecessor (flags bit 4). cfg5: the decode kernels were a single-stream chain.
-  else if (async && prev && prev->pending && prev->ctl_async && b->ctl_async && prev->level <= 1 && prev->used_fused && !prev->force_rerun && c->overlap_mode &&
-           c->ctl_overlap_mode && p.nframes && !c->force_multipass && len < (1ull << 31) && c->res_seq != 0 && res_slot >= 2 && !b->copy.active && !c->prof_serial) {
-    beside = true;
-  }
-  if (beside) {
-    if (!c->stream2) {
-      HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-      HIPCHK(c, hipEventCreateWithFlags(&c->tail2, hipEventDisableTiming));
-    }
-    b->sidx = prev->sidx ^ 1;
-    c->stream = b->sidx ? c->stream2 : sw.saved;
-    // the batch before the predecessor must be complete; it is, when it ran on this stream — otherwise wait for its event
-    etlg_batch* pp = nullptr;
-    for (size_t i = 0; i + 1 < c->pending.size(); i++) if (c->pending[i + 1] == prev) pp = c->pending[i];
-    if (pp && pp->pending && pp->kdone && pp->sidx != b->sidx) HIPCHK(c, hipStreamWaitEvent(c->stream, pp->kdone, 0));
-    p.flags |= 16u;
-    c->overlapped++;
-  } else {
-    b->sidx = 0;
-    if (c->tail2_set) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->tail2, 0)); c->tail2_set = false; }   // join: everything enqueued on stream2 so far
-  }
+  RC(choose_decode_stream(c, b, async, prev));
   s = c->stream;
-  if (b->side && !(b->side->synced & (1u << b->sidx))) {   // the set was uploaded on the other decode stream: the first batch over here waits for it
-    HIPCHK(c, hipStreamWaitEvent(s, b->side->ready, 0));
-    b->side->synced |= 1u << b->sidx;
-  }
   SlowScope slow_scope_ring(c, "decode_tail: result ring and after");
-  {  // result block: next slot of a ring that is re-initialised once per lap. Slot 31 is the carry source of the batch in
-     // slot 0, so it is re-initialised one batch later than the others.
-    const uint32_t seq = c->res_seq++;
-    const uint32_t slot = seq % etlg_ctx::kResRing;
-    DevResult* ring = (DevResult*)c->d_res.p;
-    // the blocks about to be re-initialised belong to batches whose result copies travel on res_stream: with two decode streams a
-    // batch completes within microseconds of its predecessor, so "the copy of the batch before last is long done" no longer holds —
-    // wait (on the device) for the copy of the latest batch, which is behind all the others
-    { SlowScope sw1(c, "ring: wait event");
-    if ((slot == 0 || slot == 1) && prev && prev->pending && prev->done) HIPCHK(c, hipStreamWaitEvent(s, prev->done, 0)); }
-    { SlowScope sw2(c, "ring: init copy");
-    if (seq == 0) HIPCHK(c, hipMemcpyAsync(ring, c->ring_h2d ? (const void*)c->h_init_ring : (const void*)c->d_init_ring, sizeof(DevResult) * etlg_ctx::kResRing, c->ring_h2d ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    else if (slot == 0) HIPCHK(c, hipMemcpyAsync(ring, c->ring_h2d ? (const void*)c->h_init_ring : (const void*)c->d_init_ring, sizeof(DevResult) * (etlg_ctx::kResRing - 1), c->ring_h2d ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    else if (slot == 1) HIPCHK(c, hipMemcpyAsync(ring + (etlg_ctx::kResRing - 1), c->ring_h2d ? (const void*)c->h_init_ring : (const void*)c->d_init_ring, sizeof(DevResult), c->ring_h2d ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s)); }
-    b->d_res_blk = ring + slot;
-    b->res_seq_no = seq;
-  }
+  RC(take_ring_slot(c, b, prev));
   p.res = b->d_res_blk;
   { SlowScope slow_scope_pool(c, "decode_tail: pinned result block");
-  if (c->res_pool.empty()) { DevResult* r = nullptr; HIPCHK(c, hipHostMalloc((void**)&r, sizeof(DevResult), hipHostMallocDefault)); c->res_pool.push_back(r); }
-  b->h_res = c->res_pool.back(); c->res_pool.pop_back(); }
+  RC(take_result(c, &b->h_res)); }
   if (b->copy.active && !b->copy.direct) launch_copy(c, b->copy, p);  // rows -> Insert frames (writes p.in / p.offs), row-level errors
 
   // ---- first attempt. A single-pass kernel runs OPTIMISTICALLY as if the batch held no Relation / DDL frame (they are
@@ -1277,26 +1273,22 @@ int32_t decode_tail(etlg_ctx* c, etlg_batch* b, size_t nframes, bool async, etlg
   // ... unless the batch before this one held control frames and the caller asserts nothing: streams that change schemas often
   // (DDL messages every few hundred transactions) would pay for a wasted kernel on every batch
   if (b->plan_decided >= 0) {   // side inputs and outputs were set up for the stream decision above
-    { const int32_t rc = enqueue_single(c, b, b->plan_decided ? 0 : 1); if (rc != ETLG_OK) return rc; }
+    RC(enqueue_single(c, b, b->plan_decided ? 0 : 1));
   } else if (single_pass && (no_ctrl || !c->last_had_ctrl) && !b->ctl_async) {
-    p.flags |= 1u;
-    const std::vector<EpochRec> no_eps;
-    { const int32_t rc = build_side_inputs(c, b, no_eps); if (rc != ETLG_OK) return rc; }
-    { const int32_t rc = setup_outputs(c, b); if (rc != ETLG_OK) return rc; }
-    { const int32_t rc = enqueue_single(c, b, plan_wanted(c, b) ? 0 : 1); if (rc != ETLG_OK) return rc; }
+    p.flags |= kDecNoControl;
+    RC(build_side_inputs(c, b, std::vector<EpochRec>()));
+    RC(setup_outputs(c, b));
+    RC(enqueue_single(c, b, plan_wanted(c, b) ? 0 : 1));
   } else {
-    const int32_t rc = standard_path(c, b);
-    if (rc != ETLG_OK) return rc;
+    RC(standard_path(c, b));
   }
   if (b->n_slots_view == ~(size_t)0) b->n_slots_view = c->slots.size();
   SlowScope slow_scope_tail(c, "decode_tail: result copy");
   if (async) {
     // the result block is copied on a second stream: on the context's stream the next batch's kernel follows this one
     // directly (a 200-byte device-to-host copy is a 4 us blit kernel plus two dispatch gaps when it sits between them)
-    for (int k = 0; k < 2; k++) {
-      if (c->ev_pool.empty()) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_pool.push_back(e); }
-      (k ? b->done : b->kdone) = c->ev_pool.back(); c->ev_pool.pop_back();
-    }
+    RC(take_event(c, &b->kdone));
+    RC(take_event(c, &b->done));
     if (!c->res_stream) {   // highest priority: its small copies are blit kernels, and the decode streams keep every wave slot of the chip taken
       int lo = 0, hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -1323,7 +1315,7 @@ int32_t etlg_batch_sync(etlg_ctx* c, etlg_batch* b) {
   InvariantScope inv_scope{c, "etlg_batch_sync"};
   if (b->pending) {
     // batches finish in issue order: the carried transaction state of the context is the state after the LAST finished one
-    while (b->pending && !c->pending.empty()) { const int32_t rc = finish_batch(c, c->pending.front()); (void)rc; }
+    while (b->pending && !c->pending.empty()) (void)finish_batch(c, c->pending.front());
   }
   // the context's last error becomes this batch's (the reference returns the error of the call that hit it)
   c->err = b->err; c->err_detail = b->err_detail; c->err.detail = c->err_detail.empty() ? nullptr : c->err_detail.c_str();
@@ -1333,7 +1325,7 @@ int32_t etlg_batch_sync(etlg_ctx* c, etlg_batch* b) {
 int32_t etlg_batch_header_to_device(etlg_ctx* c, etlg_batch* b, void* dst) {
   if (!c || !b || !dst) return ETLG_InvalidArgument;
   static_assert(offsetof(DevResult, n_frames) == 56, "header layout");
-  if (b->deferred) { const int32_t rc = flush_deferred(c); if (rc != ETLG_OK) return rc; }
+  if (b->deferred) RC(flush_deferred(c));
   if (b->pending && b->kdone && c->res_stream) {   // in flight: behind its kernels on the stream its result block travels on (etlg_ctx_fence joins)
     HIPCHK(c, hipMemcpyAsync(dst, b->d_res_blk, 64, hipMemcpyDeviceToDevice, c->res_stream));
     c->hdr_in_flight = true;
@@ -1345,7 +1337,7 @@ int32_t etlg_batch_header_to_device(etlg_ctx* c, etlg_batch* b, void* dst) {
 
 int32_t etlg_ctx_fence(etlg_ctx* c) {
   if (!c) return ETLG_InvalidArgument;
-  { const int32_t rc_ = flush_deferred(c); (void)rc_; }
+  (void)flush_deferred(c);
   if (c->tail2_set) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->tail2, 0)); c->tail2_set = false; }
   if (c->hdr_in_flight && c->res_stream) {
     if (!c->fence_ev) HIPCHK(c, hipEventCreateWithFlags(&c->fence_ev, hipEventDisableTiming));
@@ -1358,7 +1350,7 @@ int32_t etlg_ctx_fence(etlg_ctx* c) {
 
 int32_t etlg_batch_download(etlg_ctx* c, etlg_batch* b) {
   if (!c || !b) return ETLG_InvalidArgument;
-  if (b->pending) { int32_t rc = etlg_batch_sync(c, b); (void)rc; }
+  if (b->pending) (void)etlg_batch_sync(c, b);
   return download_batch(c, b);
 }
 
@@ -1373,15 +1365,14 @@ void etlg_batch_free(etlg_batch* b) {
   if (b->ctx && ctx_alive(b->ctx, b->ctx_gen)) {
     etlg_ctx* c = b->ctx;
     if (b->pending) {  // freed without a sync: it still has to finish, in order, for the context's carried state to be right
-      while (b->pending && !c->pending.empty()) { const int32_t rc = finish_batch(c, c->pending.front()); (void)rc; }
+      while (b->pending && !c->pending.empty()) (void)finish_batch(c, c->pending.front());
       b->pending = false;
     }
     if (b->h_res) (void)hipStreamSynchronize(c->stream);
     side_release(b);
     if (b->ctl_ev) { if (b->ctl_started && c->ctl_stream) (void)hipStreamSynchronize(c->ctl_stream); c->ev_pool.push_back(b->ctl_ev); }
     if (b->h_ctl) c->res_pool.push_back(b->h_ctl);
-    if (b->done) c->ev_pool.push_back(b->done);
-    if (b->kdone) c->ev_pool.push_back(b->kdone);
+    for (hipEvent_t e : {b->done, b->kdone}) if (e) c->ev_pool.push_back(e);
     if (b->dev) c->out_pool.push_back(b->dev);
     if (b->scan_offs) c->offs_pool.push_back(b->scan_offs);
     if (b->h2d_done) c->ev_pool.push_back(b->h2d_done);
@@ -1392,13 +1383,8 @@ void etlg_batch_free(etlg_batch* b) {
     if (b->dev) { b->dev->release(); delete b->dev; }
     if (b->scan_offs) { b->scan_offs->release(); delete b->scan_offs; }
     if (b->stage_blk) (void)hipFree(b->stage_blk);
-    if (b->h2d_done) (void)hipEventDestroy(b->h2d_done);
-    if (b->done) (void)hipEventDestroy(b->done);
-    if (b->kdone) (void)hipEventDestroy(b->kdone);
-    if (b->ctl_ev) (void)hipEventDestroy(b->ctl_ev);
-    if (b->h_ctl) (void)hipHostFree(b->h_ctl);
-    if (b->h_res) (void)hipHostFree(b->h_res);
-    if (b->h_arena) (void)hipHostFree(b->h_arena);
+    for (hipEvent_t e : {b->h2d_done, b->done, b->kdone, b->ctl_ev}) if (e) (void)hipEventDestroy(e);
+    for (void* p : {(void*)b->h_ctl, (void*)b->h_res, (void*)b->h_arena}) if (p) (void)hipHostFree(p);
   }
   delete b;
 }

@@ -7,7 +7,7 @@ extern "C++" {
 // entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
 #define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
 static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal) {
-  if (b->pending) { const int32_t rc = etlg_batch_sync(c, b); if (rc != ETLG_OK) return rc; }
+  if (b->pending) RC(etlg_batch_sync(c, b));
   if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, refusal);
   return ETLG_OK;
 }
@@ -71,12 +71,11 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   const SlotHost& sh = *c->slots[(size_t)slot];
   hipStream_t s = c->stream;
   const etlg_batch_view& bv = b->v;
-  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
   std::unique_ptr<etlg_columns, void (*)(etlg_columns*)> cs(new etlg_columns, etlg_columns_free);
   const uint64_t ne = bv.n_events;
   const uint32_t nblk = (uint32_t)((ne + 255) / 256);
   // ---- 1. which events are rows (count -> scan -> scatter); row_event / row_base are sized for every event
-  const size_t o_ice = al((size_t)(nblk + 1) * 4);   // changelog: {refused events, -, -, min(event << 8 | reason)} behind the block counts
+  const size_t o_ice = al64((size_t)(nblk + 1) * 4);   // changelog: {refused events, -, -, min(event << 8 | reason)} behind the block counts
   HIPCHK(c, c->d_colsel.ensure(o_ice + 64));
   uint32_t* d_blk = (uint32_t*)c->d_colsel.p;
   cs->m.ctx = c; cs->m.ctx_gen = c->gen;
@@ -93,10 +92,10 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
     return ETLG_OK;
   };
   ScratchBlk rows_blk{c};
-  if (ne) HIPCHK(c, blk_take(c, al(ne * 8) * 2, false, &rows_blk.p, &rows_blk.cap));
+  if (ne) HIPCHK(c, blk_take(c, al64(ne * 8) * 2, false, &rows_blk.p, &rows_blk.cap));
   void* d_rows = rows_blk.p;
   uint64_t* d_row_event = (uint64_t*)d_rows;
-  uint64_t* d_row_base = (uint64_t*)((uint8_t*)d_rows + al(ne * 8));
+  uint64_t* d_row_base = (uint64_t*)((uint8_t*)d_rows + al64(ne * 8));
   uint32_t n_rows32 = 0;
   if (ne) {
     ColSel q{};
@@ -107,7 +106,7 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
     unsigned long long back[(64 + 32) / 8] = {0};   // the row count; changelog: ... up to the refusal words, which ride the same copy
     const size_t back_bytes = changelog ? o_ice + 32 - (size_t)nblk * 4 : 4;
     if (changelog) {
-      { const int32_t rc = cnt_init(1); if (rc != ETLG_OK) return rc; }
+      RC(cnt_init(1));
       q.ice = (unsigned long long*)((uint8_t*)d_blk + o_ice);
       HIPCHK(c, hipMemcpyAsync(q.ice, c->h_cnt_init, 32, hipMemcpyHostToDevice, s));
     }
@@ -125,10 +124,10 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   const uint64_t n = n_rows32;
   // ---- 2. block A: row_event | per column {validity, deferred, values or (lens, offsets)} | counters
   const uint32_t nc = sh.desc.n_cols;
-  const size_t bm = al(((size_t)n + 63) / 64 * 8);
+  const size_t bm = al64(((size_t)n + 63) / 64 * 8);
   struct Lay { ColPlan pl; size_t validity, deferred, values, lens, offsets; };
   std::vector<Lay> lay(nc);
-  size_t off = al(n * 8);
+  size_t off = al64(n * 8);
   for (uint32_t i = 0; i < nc; i++) {
     Lay& l = lay[i];
     l.pl = col_plan(sh.cols[i].type_class);
@@ -137,26 +136,26 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
     l.validity = l.deferred = l.values = l.lens = l.offsets = 0;
     if (l.pl.kind == ETLG_AK_NONE) continue;
     l.validity = off; off += bm; l.deferred = off; off += bm;
-    if (l.pl.var) { l.offsets = off; off += al((n + 1) * 8); l.lens = off; off += al(n * 4); }
-    else { l.values = off; off += l.pl.kind == ETLG_AK_BOOLEAN ? bm : al(n * l.pl.vbytes); }
+    if (l.pl.var) { l.offsets = off; off += al64((n + 1) * 8); l.lens = off; off += al64(n * 4); }
+    else { l.values = off; off += l.pl.kind == ETLG_AK_BOOLEAN ? bm : al64(n * l.pl.vbytes); }
   }
   // changelog: the two CDC columns — per column validity, deferred, offsets, values (fixed-width strings: sized here, in block A)
   const uint32_t cdc_w[2] = {6u, 33u};
   size_t cdc_validity[2] = {0, 0}, cdc_deferred[2] = {0, 0}, cdc_offsets[2] = {0, 0}, cdc_values[2] = {0, 0};
   if (changelog) for (int k = 0; k < 2; k++) {
     cdc_validity[k] = off; off += bm; cdc_deferred[k] = off; off += bm;
-    cdc_offsets[k] = off; off += al((n + 1) * 8); cdc_values[k] = off; off += al(n * cdc_w[k]);
+    cdc_offsets[k] = off; off += al64((n + 1) * 8); cdc_values[k] = off; off += al64(n * cdc_w[k]);
   }
-  const size_t o_cnt = off; off += al((size_t)nc * 32);   // per column: nulls, deferred, child nulls, first list error
-  const size_t o_tot = off; off += al((size_t)nc * 8);    // per var-len column: the bytes behind its offsets (one read-back for all)
+  const size_t o_cnt = off; off += al64((size_t)nc * 32);   // per column: nulls, deferred, child nulls, first list error
+  const size_t o_tot = off; off += al64((size_t)nc * 8);    // per var-len column: the bytes behind its offsets (one read-back for all)
   const uint32_t nrb = (uint32_t)((n + 255) / 256);
-  const size_t scan_one = al((size_t)(nrb + 1) * 8);
+  const size_t scan_one = al64((size_t)(nrb + 1) * 8);
   const size_t o_scan = off; off += scan_one * std::max<uint32_t>(nc, 1u);   // a scan scratch per column: the var-len columns' first passes run as ONE launch each (etlg_k_col_var_pack)
   const size_t a_bytes = off + 64;
   HIPCHK(c, blk_take(c, a_bytes, false, &cs->m.d_a, &cs->m.cap_a));
   uint8_t* A = (uint8_t*)cs->m.d_a;
   if (nc) {   // the counters' initial values
-    { const int32_t rc = cnt_init(nc); if (rc != ETLG_OK) return rc; }
+    RC(cnt_init(nc));
     HIPCHK(c, hipMemcpyAsync(A + o_cnt, c->h_cnt_init, (size_t)nc * 32, hipMemcpyHostToDevice, s));
   }
   if (n) HIPCHK(c, hipMemcpyAsync(A, d_row_event, n * 8, hipMemcpyDeviceToDevice, s));
@@ -255,13 +254,13 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
       const size_t bits = (tot + 63) / 64 * 8;
       if (var_child(lay[i].pl)) {   // child offsets first (i64), then lengths, scan scratch, validity
         any_text_list = true;
-        b_bytes += al((tot + 1) * 8); clen[i] = b_bytes; b_bytes += al(tot * 4); cscan[i] = b_bytes; b_bytes += al((tot / 256 + 2) * 8);
-        cvb[i] = b_bytes; b_bytes += al(bits);
+        b_bytes += al64((tot + 1) * 8); clen[i] = b_bytes; b_bytes += al64(tot * 4); cscan[i] = b_bytes; b_bytes += al64((tot / 256 + 2) * 8);
+        cvb[i] = b_bytes; b_bytes += al64(bits);
       } else {
         vbytes[i] = lay[i].pl.child == ETLG_AK_BOOLEAN ? bits : tot * lay[i].pl.child_bytes;
-        b_bytes += al(vbytes[i]); cvb[i] = b_bytes; b_bytes += al(bits);
+        b_bytes += al64(vbytes[i]); cvb[i] = b_bytes; b_bytes += al64(bits);
       }
-    } else { vbytes[i] = tot; b_bytes += al(tot); }
+    } else { vbytes[i] = tot; b_bytes += al64(tot); }
   }
   if (b_bytes) HIPCHK(c, blk_take(c, b_bytes + 64, false, &cs->m.d_b, &cs->m.cap_b));
   uint8_t* B = (uint8_t*)cs->m.d_b;
@@ -273,13 +272,13 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
       jobs[i].child_validity = (uint32_t*)(B + cvb[i]);
       if (var_child(lay[i].pl)) {   // pass A: byte length + validity of every element, then their offsets
         jobs[i].values = nullptr; jobs[i].child_lens = (uint32_t*)(B + clen[i]); jobs[i].child_offsets = (const int64_t*)(B + vb[i]);
-        HIPCHK(c, hipMemsetAsync(B + cvb[i], 0, al(((size_t)var_total[i] + 63) / 64 * 8), s));
+        HIPCHK(c, hipMemsetAsync(B + cvb[i], 0, al64(((size_t)var_total[i] + 63) / 64 * 8), s));
         etlg_k_col_list(&jobs[i], nullptr, nullptr, 1, s);
         etlg_k_scan_lens(jobs[i].child_lens, (uint64_t)var_total[i], (unsigned long long*)(B + cscan[i]), (int64_t*)(B + vb[i]), s);
         HIPCHK(c, hipMemcpyAsync(&text_total[i], B + vb[i] + (size_t)var_total[i] * 8, 8, hipMemcpyDeviceToHost, s));
       } else {
         jobs[i].values = B + vb[i];
-        HIPCHK(c, hipMemsetAsync(B + vb[i], 0, cvb[i] - vb[i] + al(((size_t)var_total[i] + 63) / 64 * 8), s));   // bitmaps are OR-ed into
+        HIPCHK(c, hipMemsetAsync(B + vb[i], 0, cvb[i] - vb[i] + al64(((size_t)var_total[i] + 63) / 64 * 8), s));   // bitmaps are OR-ed into
         etlg_k_col_list(&jobs[i], nullptr, nullptr, 1, s);
       }
     } else { jobs[i].values = B + vb[i]; var2_ids.push_back(i); }
@@ -298,7 +297,7 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   size_t c_bytes = 0;
   if (any_text_list) {
     HIPCHK(c, hipStreamSynchronize(s));
-    for (uint32_t i = 0; i < nc; i++) if (lay[i].pl.kind == ETLG_AK_LIST && var_child(lay[i].pl)) { vc[i] = c_bytes; vbytes[i] = (size_t)text_total[i]; c_bytes += al((size_t)text_total[i]) + 64; }
+    for (uint32_t i = 0; i < nc; i++) if (lay[i].pl.kind == ETLG_AK_LIST && var_child(lay[i].pl)) { vc[i] = c_bytes; vbytes[i] = (size_t)text_total[i]; c_bytes += al64((size_t)text_total[i]) + 64; }
     if (c_bytes) HIPCHK(c, blk_take(c, c_bytes + 64, false, &cs->m.d_c, &cs->m.cap_c));
     for (uint32_t i = 0; i < nc; i++)
       if (lay[i].pl.kind == ETLG_AK_LIST && var_child(lay[i].pl) && var_total[i] > 0) { jobs[i].values = (uint8_t*)cs->m.d_c + vc[i]; etlg_k_col_list(&jobs[i], nullptr, nullptr, 1, s); }
@@ -309,11 +308,11 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
   const uint8_t* base_a = A; const uint8_t* base_b = B; const uint8_t* base_c = Cb;
   if (!on_dev) {
-    HIPCHK(c, blk_take(c, al(o_cnt) + al(b_bytes) + c_bytes + 64, true, (void**)&cs->m.h, &cs->m.cap_h));
+    HIPCHK(c, blk_take(c, al64(o_cnt) + al64(b_bytes) + c_bytes + 64, true, (void**)&cs->m.h, &cs->m.cap_h));
     if (o_cnt) HIPCHK(c, hipMemcpyAsync(cs->m.h, A, o_cnt, hipMemcpyDeviceToHost, s));
-    if (b_bytes) HIPCHK(c, hipMemcpyAsync(cs->m.h + al(o_cnt), B, b_bytes, hipMemcpyDeviceToHost, s));
-    if (c_bytes) HIPCHK(c, hipMemcpyAsync(cs->m.h + al(o_cnt) + al(b_bytes), Cb, c_bytes, hipMemcpyDeviceToHost, s));
-    base_a = cs->m.h; base_b = cs->m.h + al(o_cnt); base_c = cs->m.h + al(o_cnt) + al(b_bytes);
+    if (b_bytes) HIPCHK(c, hipMemcpyAsync(cs->m.h + al64(o_cnt), B, b_bytes, hipMemcpyDeviceToHost, s));
+    if (c_bytes) HIPCHK(c, hipMemcpyAsync(cs->m.h + al64(o_cnt) + al64(b_bytes), Cb, c_bytes, hipMemcpyDeviceToHost, s));
+    base_a = cs->m.h; base_b = cs->m.h + al64(o_cnt); base_c = cs->m.h + al64(o_cnt) + al64(b_bytes);
   }
   HIPCHK(c, hipStreamSynchronize(s));   // row_base (freed on return) is read by the kernels above
   if (!on_dev) {
@@ -453,10 +452,9 @@ int32_t finish_cells(etlg_ctx* c, etlg_batch* b, uint32_t what, etlg_finish_stat
   if (!maxfin) return ETLG_OK;
   const uint64_t n = ne * 2ull * maxfin;
   const uint32_t nb = (uint32_t)((n + 255) / 256);
-  auto up = [](size_t x) { return (x + 63) & ~(size_t)63; };
-  const size_t o_cols = up(tab.size() * 4), o_fin = o_cols + up(cols.size() * 4), o_stats = o_fin + up(fin.size() * 4 + 4), o_lens = o_stats + 64;
-  const size_t o_cnts = o_lens + (any_arrays ? up(n * 4) : 0);
-  const size_t o_offs = o_cnts + (any_arrays ? up(n * 4) : 0), o_blk = o_offs + (any_arrays ? up((n + 1) * 8) : 0), total = o_blk + (any_arrays ? up(((size_t)nb + 2) * 8) : 0) + 64;
+  const size_t o_cols = al64(tab.size() * 4), o_fin = o_cols + al64(cols.size() * 4), o_stats = o_fin + al64(fin.size() * 4 + 4), o_lens = o_stats + 64;
+  const size_t o_cnts = o_lens + (any_arrays ? al64(n * 4) : 0);
+  const size_t o_offs = o_cnts + (any_arrays ? al64(n * 4) : 0), o_blk = o_offs + (any_arrays ? al64((n + 1) * 8) : 0), total = o_blk + (any_arrays ? al64(((size_t)nb + 2) * 8) : 0) + 64;
   ScratchBlk dblk{c};
   HIPCHK(c, blk_take(c, total, false, &dblk.p, &dblk.cap));
   uint8_t* d = (uint8_t*)dblk.p;
@@ -646,13 +644,12 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   }
   hipStream_t s = c->stream;
   const etlg_batch_view& bv = b->v;
-  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
   const uint64_t ne = bv.n_events;
   const uint64_t nr_cap = format ? 2 * ne : ne;   // BigQuery: an update that changes the primary key is two rows
   const uint32_t nblk = (uint32_t)((ne + 255) / 256);
   // block S (freed on return): block counts | host-row counter | error word | column words | row_base
   const size_t nd_bytes = nd ? (size_t)(nc + 1) * 4 + nd->bytes.size() : 0;   // (format 2: the keys' offsets and bytes behind the column words)
-  const size_t o_cnt = al((size_t)(nblk + 1) * 4), o_cols = o_cnt + 64, o_base = o_cols + al((size_t)nc * 8 + 8 + nd_bytes), s_bytes = o_base + al(nr_cap * 8) + 64;
+  const size_t o_cnt = al64((size_t)(nblk + 1) * 4), o_cols = o_cnt + 64, o_base = o_cols + al64((size_t)nc * 8 + 8 + nd_bytes), s_bytes = o_base + al64(nr_cap * 8) + 64;
   rb->m.ctx = c; rb->m.ctx_gen = c->gen;
   ScratchBlk sblk{c};
   HIPCHK(c, blk_take(c, s_bytes, false, &sblk.p, &sblk.cap));
@@ -661,7 +658,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   // pinned staging: [host rows = 0 | error word = ~0 | total | pad to 64 | column words] goes up in one copy (S + o_cnt .. lies the same
   // way); [row count] and [host rows | error word | total] come back in one copy each. (From / to pageable memory every one of these
   // small copies was a stop of its own.)
-  const size_t up_bytes = 64 + (size_t)nc * 8 + nd_bytes, hand_bytes = al(up_bytes) + 64;
+  const size_t up_bytes = 64 + (size_t)nc * 8 + nd_bytes, hand_bytes = al64(up_bytes) + 64;
   if (c->h_hand_cap < hand_bytes) {
     if (c->h_hand) { HIPCHK(c, hipStreamSynchronize(s)); (void)hipHostFree(c->h_hand); c->h_hand = nullptr; c->h_hand_cap = 0; }
     HIPCHK(c, hipHostMalloc((void**)&c->h_hand, hand_bytes + 4096, hipHostMallocDefault));
@@ -677,10 +674,10 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     }
     HIPCHK(c, hipMemcpyAsync(S + o_cnt, c->h_hand, up_bytes, hipMemcpyHostToDevice, s));
   }
-  volatile unsigned long long* down = (volatile unsigned long long*)(c->h_hand + al(up_bytes));   // [0] row count, [1..3] host rows, error word, total
+  volatile unsigned long long* down = (volatile unsigned long long*)(c->h_hand + al64(up_bytes));   // [0] row count, [1..3] host rows, error word, total
   // block A: row_event | row_offsets | lens | scan scratch (sized for every event being a row)
   const uint32_t nblk_r = (uint32_t)((nr_cap + 255) / 256);
-  const size_t o_off = al(nr_cap * 8), o_len = o_off + al((nr_cap + 1) * 8), o_scan = o_len + al(nr_cap * 4), o_part = o_scan + al((size_t)(nblk_r + 1) * 8), a_bytes = o_part + 3 * al(nr_cap * 4) + 64;   // (o_part: where the parts of a row begin, k_rb_rows)
+  const size_t o_off = al64(nr_cap * 8), o_len = o_off + al64((nr_cap + 1) * 8), o_scan = o_len + al64(nr_cap * 4), o_part = o_scan + al64((size_t)(nblk_r + 1) * 8), a_bytes = o_part + 3 * al64(nr_cap * 4) + 64;   // (o_part: where the parts of a row begin, k_rb_rows)
   HIPCHK(c, blk_take(c, a_bytes, false, &rb->m.d_a, &rb->m.cap_a));
   uint8_t* A = (uint8_t*)rb->m.d_a;
   uint32_t n32 = 0;
@@ -791,12 +788,12 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   const uint8_t* base_a = A; const uint8_t* base_b = (const uint8_t*)rb->m.d_b;
   if (!on_dev) {
     const size_t ce_bytes = rb->m.d_c ? (size_t)n * nc * 4 : 0;
-    HIPCHK(c, blk_take(c, o_len + al((size_t)total) + ce_bytes + 64, true, (void**)&rb->m.h, &rb->m.cap_h));
+    HIPCHK(c, blk_take(c, o_len + al64((size_t)total) + ce_bytes + 64, true, (void**)&rb->m.h, &rb->m.cap_h));
     HIPCHK(c, hipMemcpyAsync(rb->m.h, A, o_off + (n + 1) * 8, hipMemcpyDeviceToHost, s));
     if (total) HIPCHK(c, hipMemcpyAsync(rb->m.h + o_len, rb->m.d_b, (size_t)total, hipMemcpyDeviceToHost, s));
     base_a = rb->m.h; base_b = rb->m.h + o_len;
-    if (ce_bytes) HIPCHK(c, hipMemcpyAsync(rb->m.h + o_len + al((size_t)total), rb->m.d_c, ce_bytes, hipMemcpyDeviceToHost, s));
-    if (ce_bytes) rb->col_ends = (const uint32_t*)(rb->m.h + o_len + al((size_t)total));
+    if (ce_bytes) HIPCHK(c, hipMemcpyAsync(rb->m.h + o_len + al64((size_t)total), rb->m.d_c, ce_bytes, hipMemcpyDeviceToHost, s));
+    if (ce_bytes) rb->col_ends = (const uint32_t*)(rb->m.h + o_len + al64((size_t)total));
   } else rb->col_ends = (const uint32_t*)rb->m.d_c;
   HIPCHK(c, hipStreamSynchronize(s));   // block S is freed on return
   if (!on_dev) { blk_give(c, c->gen, rb->m.d_a, rb->m.cap_a, false); blk_give(c, c->gen, rb->m.d_b, rb->m.cap_b, false); blk_give(c, c->gen, rb->m.d_c, rb->m.cap_c, false); rb->m.d_a = rb->m.d_b = rb->m.d_c = nullptr; }

@@ -14,10 +14,9 @@ int32_t download_batch(etlg_ctx* c, etlg_batch* b) {
   etlg_batch_view& v = b->v;
   const size_t n = (size_t)v.n_events;
   // layout of the pinned block: 8-byte arrays first, then 4-byte, then bytes (every part 64-byte aligned)
-  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-  const size_t o_start = 0, o_commit = o_start + al(n * 8), o_ord = o_commit + al(n * 8), o_body = o_ord + al(n * 8);
-  const size_t o_table = o_body + al(n * 8), o_slot = o_table + al(n * 4), o_kind = o_slot + al(n * 4), o_flags = o_kind + al(n);
-  const size_t o_fixed = o_flags + al(n), o_heap = o_fixed + al((size_t)v.fixed_bytes), total = o_heap + al((size_t)v.heap_bytes) + 64;
+  const size_t o_start = 0, o_commit = o_start + al64(n * 8), o_ord = o_commit + al64(n * 8), o_body = o_ord + al64(n * 8);
+  const size_t o_table = o_body + al64(n * 8), o_slot = o_table + al64(n * 4), o_kind = o_slot + al64(n * 4), o_flags = o_kind + al64(n);
+  const size_t o_fixed = o_flags + al64(n), o_heap = o_fixed + al64((size_t)v.fixed_bytes), total = o_heap + al64((size_t)v.heap_bytes) + 64;
   if (b->h_arena_cap < total) {
     if (b->h_arena) { c->harena_pool.emplace_back(b->h_arena, b->h_arena_cap); b->h_arena = nullptr; b->h_arena_cap = 0; }
     // smallest pooled block that fits, else a new one (rounded up so that similar batches can share it)
@@ -34,16 +33,9 @@ int32_t download_batch(etlg_ctx* c, etlg_batch* b) {
     }
   }
   uint8_t* h = b->h_arena;
-  if (n) {
-    HIPCHK(c, hipMemcpyAsync(h + o_kind, os->kind.p, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h + o_flags, os->flags.p, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h + o_table, os->table.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h + o_slot, os->slot.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h + o_start, os->start.p, n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h + o_commit, os->commit.p, n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h + o_ord, os->ord.p, n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(h + o_body, os->body.p, n * 8, hipMemcpyDeviceToHost, s));
-  }
+  const struct { size_t off; const DevBuf& d; size_t width; } arrays[] = {{o_kind, os->kind, 1}, {o_flags, os->flags, 1}, {o_table, os->table, 4}, {o_slot, os->slot, 4},
+                                                                          {o_start, os->start, 8}, {o_commit, os->commit, 8}, {o_ord, os->ord, 8}, {o_body, os->body, 8}};
+  if (n) for (const auto& a : arrays) HIPCHK(c, hipMemcpyAsync(h + a.off, a.d.p, n * a.width, hipMemcpyDeviceToHost, s));
   if (v.fixed_bytes) HIPCHK(c, hipMemcpyAsync(h + o_fixed, os->fixed.p, (size_t)v.fixed_bytes, hipMemcpyDeviceToHost, s));
   if (v.heap_bytes) HIPCHK(c, hipMemcpyAsync(h + o_heap, os->heap.p, (size_t)v.heap_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
@@ -61,17 +53,15 @@ int32_t download_batch(etlg_ctx* c, etlg_batch* b) {
 // Per-frame scratch of the multi-pass kernels (context-shared, grow-only): (re)binds the pointers of `p`.
 int32_t setup_scratch(etlg_ctx* c, DecParams& p, int set) {
   const uint32_t nf = p.nframes, nblocks = p.nblocks;
-  DevBuf& d_tag = set ? c->ctl_alt.d_tag : c->d_tag; DevBuf& d_emit = set ? c->ctl_alt.d_emit : c->d_emit;
-  DevBuf& d_ffixed = set ? c->ctl_alt.d_ffixed : c->d_ffixed; DevBuf& d_fheap = set ? c->ctl_alt.d_fheap : c->d_fheap;
-  DevBuf& d_blk32 = set ? c->ctl_alt.d_blk32 : c->d_blk32; DevBuf& d_blk64 = set ? c->ctl_alt.d_blk64 : c->d_blk64;
-  HIPCHK(c, d_tag.ensure(nf + 16)); HIPCHK(c, d_emit.ensure(nf + 16));
-  HIPCHK(c, d_ffixed.ensure((size_t)nf * 4 + 16)); HIPCHK(c, d_fheap.ensure((size_t)nf * 4 + 16));
-  HIPCHK(c, d_blk32.ensure((size_t)(nblocks + 1) * 4 * 3 + 64));
-  HIPCHK(c, d_blk64.ensure((size_t)(nblocks + 1) * 8 * 5 + 64));
-  p.f_tag = (uint8_t*)d_tag.p; p.f_emit = (uint8_t*)d_emit.p;
-  p.f_fixed = (uint32_t*)d_ffixed.p; p.f_heap = (uint32_t*)d_fheap.p;
-  p.blk_cnt = (uint32_t*)d_blk32.p; p.blk_last = p.blk_cnt + (nblocks + 1); p.blk_ev = p.blk_last + (nblocks + 1);
-  p.blk_fixed = (uint64_t*)d_blk64.p; p.blk_heap = p.blk_fixed + (nblocks + 1); p.blk_payload = p.blk_heap + (nblocks + 1);
+  CtlSet& cs = c->sets[set];
+  HIPCHK(c, cs.d_tag.ensure(nf + 16)); HIPCHK(c, cs.d_emit.ensure(nf + 16));
+  HIPCHK(c, cs.d_ffixed.ensure((size_t)nf * 4 + 16)); HIPCHK(c, cs.d_fheap.ensure((size_t)nf * 4 + 16));
+  HIPCHK(c, cs.d_blk32.ensure((size_t)(nblocks + 1) * 4 * 3 + 64));
+  HIPCHK(c, cs.d_blk64.ensure((size_t)(nblocks + 1) * 8 * 5 + 64));
+  p.f_tag = (uint8_t*)cs.d_tag.p; p.f_emit = (uint8_t*)cs.d_emit.p;
+  p.f_fixed = (uint32_t*)cs.d_ffixed.p; p.f_heap = (uint32_t*)cs.d_fheap.p;
+  p.blk_cnt = (uint32_t*)cs.d_blk32.p; p.blk_last = p.blk_cnt + (nblocks + 1); p.blk_ev = p.blk_last + (nblocks + 1);
+  p.blk_fixed = (uint64_t*)cs.d_blk64.p; p.blk_heap = p.blk_fixed + (nblocks + 1); p.blk_payload = p.blk_heap + (nblocks + 1);
   return ETLG_OK;
 }
 
@@ -87,7 +77,7 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
     p.tables = (const DevTable*)(d + ss->o_tables); p.epochs = (const DevEpoch*)(d + ss->o_epochs); p.n_tables = n_tables; p.n_epochs = n_epochs;
     p.slots = (const DevSlot*)(d + ss->o_slots); p.cols = (const DevCol*)(d + ss->o_cols);
     p.n_slots = ss->n_slots; p.n_cols = ss->n_cols;
-    if (p.flags & 2u) p.copy_slot = (int32_t)(std::lower_bound(c->last_live.begin(), c->last_live.end(), b->copy.slot) - c->last_live.begin());   // device index of the caller's slot
+    if (p.flags & kDecCopyRows) p.copy_slot = (int32_t)(std::lower_bound(c->last_live.begin(), c->last_live.end(), b->copy.slot) - c->last_live.begin());   // device index of the caller's slot
     side_use(b, ss);
   };
   if (eps.empty() && c->side_valid && !c->side_dirty && !c->slots_dirty && c->last_epochs.empty() && !b->have_snapshot && !b->copy.active) {
@@ -145,10 +135,7 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
         if (host_slot < 0 || (size_t)host_slot >= c->slots.size()) continue;
         const SlotHost& sh = *c->slots[(size_t)host_slot];
         bool ok = sh.desc.n_cols > 0;
-        for (auto& sc : sh.cols) {
-          const int32_t k = sc.type_class;
-          if (!(k == ETLG_TC_BOOL || k == ETLG_TC_I16 || k == ETLG_TC_I32 || k == ETLG_TC_I64 || k == ETLG_TC_U32)) ok = false;
-        }
+        for (auto& sc : sh.cols) if (!int_class(sc.type_class)) ok = false;
         if (!ok) continue;
         PlanTab e{};
         e.rel_id = t.table_id; e.slot = (uint32_t)host_slot; e.n_cols = sh.desc.n_cols; e.row_dwords = sh.desc.row_bytes_full / 4;   // (the plan writes the arena's id, it does not index the slot table)
@@ -167,13 +154,12 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
     side_release(b);   // (a batch that is decoded again lets go of the set its first attempt read)
     for (SideSet* x : c->side_sets) if (x->users == 0) { ss = x; break; }
     if (!ss) { ss = new SideSet(); c->side_sets.push_back(ss); HIPCHK(c, hipEventCreateWithFlags(&ss->ready, hipEventDisableTiming)); }
-    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
     ss->o_tables = 0;
-    ss->o_epochs = al(tv.size() * sizeof(DevTable) + 16);
-    ss->o_slots = ss->o_epochs + al(ev.size() * sizeof(DevEpoch) + 16);
-    ss->o_cols = ss->o_slots + al(ds.size() * sizeof(DevSlot) + 16);
-    ss->o_ptabs = ss->o_cols + al(dc.size() * (sizeof(DevCol) + 1) + 16);   // (the records, then one element-class byte per record)
-    ss->o_pcols = ss->o_ptabs + al(pt.size() * sizeof(PlanTab) + 16);
+    ss->o_epochs = al64(tv.size() * sizeof(DevTable) + 16);
+    ss->o_slots = ss->o_epochs + al64(ev.size() * sizeof(DevEpoch) + 16);
+    ss->o_cols = ss->o_slots + al64(ds.size() * sizeof(DevSlot) + 16);
+    ss->o_ptabs = ss->o_cols + al64(dc.size() * (sizeof(DevCol) + 1) + 16);   // (the records, then one element-class byte per record)
+    ss->o_pcols = ss->o_ptabs + al64(pt.size() * sizeof(PlanTab) + 16);
     // ETLG_F_CHECK_CELLS: the element class of every array column, in DevCol order (build_slots pushes no column for a dead slot),
     // stored directly behind the DevCol records (chk_elem_table, codec.hip.h)
     std::vector<uint8_t> ce;
@@ -189,7 +175,7 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
       if (any) { ss->chk_any = true; ss->chk_maxc = std::max<uint32_t>(ss->chk_maxc, sh.desc.n_cols); }
     }
     if (ce.size() != dc.size()) return lib_error(c, ETLG_InvalidState, "side inputs: element classes and columns differ in number");
-    const size_t total = ss->o_pcols + al(pc.size() * 4 + 16);
+    const size_t total = ss->o_pcols + al64(pc.size() * 4 + 16);
     if (total > ss->h_cap) {
       if (ss->h) (void)hipHostFree(ss->h);
       ss->h = nullptr; ss->h_cap = 0;
@@ -291,7 +277,7 @@ int32_t setup_outputs(etlg_ctx* c, etlg_batch* b) {
 bool plan_wanted(etlg_ctx* c, const etlg_batch* b) {
   const DecParams& p = b->params;
   if (c->plan_mode == 0 || (c->fused_kernel >= 0 && c->fused_kernel != 3)) return false;  // ETLG_PLAN=0 / a forced generic kernel
-  if (!c->n_plan_tabs || !c->plan_covers_all || p.n_epochs || (p.flags & 2u) || c->worker != ETLG_WORKER_APPLY) return false;
+  if (!c->n_plan_tabs || !c->plan_covers_all || p.n_epochs || (p.flags & kDecCopyRows) || c->worker != ETLG_WORKER_APPLY) return false;
   if (p.nframes >= (1u << 29) || p.fixed_cap >= (1ull << 34) || c->fused_dbg) return false;   // descriptor: mark 30 bits, fixed dwords 32 bits
   if (c->plan_max_row > 512) return false;   // 64 rows of the widest table sit in LDS beside the staging window
   if (c->fused_kernel == 3) return true;
@@ -304,9 +290,8 @@ bool plan_wanted(etlg_ctx* c, const etlg_batch* b) {
 // Distance two, not one: batch k+1 may run BESIDE batch k on the second stream (it uses a buffer batch k-1 cleared, which
 // completed before k+1 started), and the buffer k clears was last used by batch k-2, which completed before k started.
 hipError_t sync_decode_streams(etlg_ctx* c) {
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess && c->stream2) e = hipStreamSynchronize(c->stream2);
-  return e;
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  return (e == hipSuccess && c->stream2) ? hipStreamSynchronize(c->stream2) : e;
 }
 int32_t take_descriptors(etlg_ctx* c, size_t dbytes, uint8_t** cur_out, uint8_t** oth_out) {
   SlowScope slow_scope_take_descriptors(c, "take_descriptors");
@@ -330,6 +315,19 @@ int32_t take_descriptors(etlg_ctx* c, size_t dbytes, uint8_t** cur_out, uint8_t*
   return ETLG_OK;
 }
 
+// ... for the q.ntiles tiles of a generic single-pass launch (k_fused, k_cells, k_rows): three words per tile and per group of 64, a ticket
+int32_t take_tile_descriptors(etlg_ctx* c, FusedParams& q) {
+  const size_t ngroups = (q.ntiles + 63) / 64;
+  const size_t per = (size_t)q.ntiles + ngroups;  // tile descriptors followed by group descriptors
+  const size_t dbytes = per * 8 * 3 + 64;
+  uint8_t *dcur, *doth;
+  RC(take_descriptors(c, dbytes, &dcur, &doth));
+  q.d_txn = (unsigned long long*)dcur; q.d_outa = q.d_txn + per; q.d_outb = q.d_outa + per;
+  q.ticket = (uint32_t*)(q.d_outb + per);
+  q.d_clear = (unsigned long long*)doth; q.clear_words = (uint32_t)(dbytes / 8);
+  return ETLG_OK;
+}
+
 // A batch whose decode was enqueued behind its boundary scan (DecParams.nframes_dev) and that now needs its frame count on the host — a
 // kernel that does not read the count from the device, or a second attempt: the scan is waited for; when it did not hold (or the batch
 // outgrew the bound its grids were sized by) the boundaries are scanned again, synchronously, with the hints / one-lane fallback of
@@ -344,7 +342,7 @@ int32_t resolve_scan_count(etlg_ctx* c, etlg_batch* b) {
   if (res[1] != 0 || res[2] != 0 || nframes == 0) {   // (a count beyond the bound with no flag raised: the offsets are complete — the buffer holds len / 24 + 1024 of them — only the grids were too small)
     HIPCHK(c, sync_decode_streams(c));   // (nothing may still be reading the offsets this scan rewrites)
     HIPCHK(c, device_scan(c, b->d_in_ptr, b->len, &nframes, c->stream, *b->scan_offs));
-    if (nframes >= (1u << 30)) return lib_error(c, ETLG_InvalidArgument, "batch too large (max 4 GiB, 2^30 frames)");
+    RC(batch_too_large(c, 0, nframes));
     p.offs = (const uint32_t*)b->scan_offs->p;
     b->user_offs = p.offs;
     if (res[2] != 0) {
@@ -359,7 +357,7 @@ int32_t resolve_scan_count(etlg_ctx* c, etlg_batch* b) {
   p.nframes = (uint32_t)nframes; p.nblocks = ((uint32_t)nframes + kBlock - 1) / kBlock;
   p.nframes_dev = nullptr;
   b->scan_chained = false;
-  if (outgrown) { const int32_t rc = setup_outputs(c, b); if (rc != ETLG_OK) return rc; }   // (the event arrays and the arena were sized by the bound)
+  if (outgrown) RC(setup_outputs(c, b));   // (the event arrays and the arena were sized by the bound)
   c->scan_last_nf = nframes; c->scan_last_len = b->len;
   return ETLG_OK;
 }
@@ -368,7 +366,7 @@ int32_t resolve_scan_count(etlg_ctx* c, etlg_batch* b) {
 // kernel (fused.hip) or, for wide frames, the column-parallel one (cells.hip).
 int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
   SlowScope slow_scope_enqueue_single(c, "enqueue_single");
-  if (b->scan_chained && level != 0) { const int32_t rc = resolve_scan_count(c, b); if (rc != ETLG_OK) return rc; }   // (only the plan kernels read the count on the device)
+  if (b->scan_chained && level != 0) RC(resolve_scan_count(c, b));   // (only the plan kernels read the count on the device)
   const DecParams& p = b->params;
   const uint32_t nf = p.nframes;
   b->level = level;
@@ -384,7 +382,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
     cells_ok = widest <= etlg_k_cells_maxc() && q.side_bytes != 0;  // k_cells keeps the side tables in LDS
     // table-copy rows: the rows -> arena kernel is k_cells with another first phase; where k_cells cannot run (or another kernel is
     // forced) the rows are rewritten as Insert frames first
-    if (b->copy.active && b->copy.direct && (!cells_ok || c->fused_kernel >= 0)) { const int32_t rc = copy_use_frames(c, b); if (rc != ETLG_OK) return rc; }
+    if (b->copy.active && b->copy.direct && (!cells_ok || c->fused_kernel >= 0)) RC(copy_use_frames(c, b));
   }
   const bool direct = b->copy.active && b->copy.direct;
   const uint64_t nf_avg = b->scan_chained && b->nf_est ? b->nf_est : nf;   // (decoded behind its scan: nf is a bound)
@@ -409,7 +407,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
     q.desc = nullptr; q.d_clear = nullptr; q.clear_words = 0;
     if (!pre) {   // (behind the pre-pass no kernel reads or writes a look-back word: no buffer is taken, none is cleared)
       uint8_t *dcur, *doth;
-      { const int32_t rc = take_descriptors(c, dbytes, &dcur, &doth); if (rc != ETLG_OK) return rc; }
+      RC(take_descriptors(c, dbytes, &dcur, &doth));
       q.desc = (unsigned long long*)dcur;
       q.d_clear = (unsigned long long*)doth; q.clear_words = (uint32_t)(dbytes / 8);
     }
@@ -448,10 +446,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
   // kernel choice: narrow frames -> one lane per frame, 256 frames per tile (k_fused); wide frames ->
   // 64 frames per tile with the waves spread over the columns (k_cells, schemas up to 32 columns: a second instantiation beyond 16)
   bool any_var = false;   // a table the batch may carry has TEXT / NUMERIC / ... columns: one lane per frame crawls on those
-  for (int32_t li : c->last_live) for (auto& sc : c->slots[(size_t)li]->cols) {
-    const int32_t k = sc.type_class;
-    if (!(k == ETLG_TC_BOOL || k == ETLG_TC_I16 || k == ETLG_TC_I32 || k == ETLG_TC_I64 || k == ETLG_TC_U32 || k == ETLG_TC_UUID)) any_var = true;
-  }
+  for (int32_t li : c->last_live) for (auto& sc : c->slots[(size_t)li]->cols) if (!fixed_class(sc.type_class)) any_var = true;
   int kernel = (avg <= 192 && !(any_var && cells_ok && avg > 96)) ? 0 : (cells_ok ? 2 : 1);  // 0 fused/256, 1 fused/64, 2 cells
   if (c->fused_kernel >= 0 && c->fused_kernel <= 2) kernel = c->fused_kernel == 2 && !cells_ok ? 1 : c->fused_kernel;
   if (direct) kernel = 2;
@@ -460,16 +455,12 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
   b->used_rows = false;
   if (kernel != 0 || c->fused_kernel == 4) {
     uint32_t maxh = 1, maxh_old = 0, maxrow = 16;
-    bool ok = !b->copy.active && !(p.flags & 2u) && !b->any_sync_done && !(c->fused_dbg & ~(8u | 32u)) && q.side_bytes != 0 && ((uintptr_t)p.in & 15) == 0 &&
+    bool ok = !b->copy.active && !(p.flags & kDecCopyRows) && !b->any_sync_done && !(c->fused_dbg & ~(8u | 32u)) && q.side_bytes != 0 && ((uintptr_t)p.in & 15) == 0 &&
               widest <= etlg_k_rows_max_cols() && !b->no_rows && c->rows_mode != 0 && (c->fused_kernel < 0 || c->fused_kernel == 4);
     for (int32_t li : c->last_live) {
       const SlotHost& sh = *c->slots[(size_t)li];
       uint32_t nh = 0, nhi = 0;
-      for (auto& sc : sh.cols) {
-        const int32_t k = sc.type_class;
-        if (!(k == ETLG_TC_BOOL || k == ETLG_TC_I16 || k == ETLG_TC_I32 || k == ETLG_TC_I64 || k == ETLG_TC_U32 || k == ETLG_TC_UUID ||
-              k == ETLG_TC_DATE || k == ETLG_TC_TIME || k == ETLG_TC_TIMESTAMP || k == ETLG_TC_TIMETZ || k == ETLG_TC_TIMESTAMPTZ)) { nh++; if (sc.identity) nhi++; }
-      }
+      for (auto& sc : sh.cols) if (!heapless_class(sc.type_class)) { nh++; if (sc.identity) nhi++; }
       maxh = std::max(maxh, nh); maxh_old = std::max(maxh_old, nhi);
       maxrow = std::max<uint32_t>(maxrow, sh.desc.row_bytes_full + std::max<uint32_t>(sh.desc.row_bytes_key, sh.desc.n_ident == sh.desc.n_cols ? sh.desc.row_bytes_full : 0u));
     }
@@ -486,7 +477,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
       uint32_t cf = 64;
       uint64_t need = 0, tabb = 0;
       const uint64_t max_wgs = 4ull * (uint64_t)etlg_k_rows_waves_per_simd() / (uint64_t)etlg_k_rows_waves();   // (the register file: ETLG_ROWS_MINBLOCKS waves per SIMD)
-      static const uint32_t cf_forced = [] { const char* e = getenv("ETLG_ROWS_CF"); return e ? (uint32_t)atoi(e) : 0u; }();   // (experiments / tests: 8 .. 64, a multiple of 8)
+      const uint32_t cf_forced = c->rows_cf;   // (ETLG_ROWS_CF, experiments / tests: 8 .. 64, a multiple of 8)
       auto need_of = [&](uint32_t f, uint64_t& tb) {
         tb = etlg_k_rows_table_bytes(maxh_old, maxh, widest, f);
         return stat + q.side_bytes + tb + std::max<uint64_t>((uint64_t)f * avg * 9 / 8 + 1024, c->rows_win_min * f / 64 + 64);
@@ -506,7 +497,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
         if (cf_forced >= 8 && cf_forced < 16 && !(cf_forced & 7u)) cf = cf_forced;
         need = need_of(cf, tabb);
       }
-      if (getenv("ETLG_ROWS_TRACE") && (need > 150 * 1024 || (uint64_t)cf * maxrow > 0x3FFFFull)) fprintf(stderr, "[rows] not taken: cf %u need %llu maxrow %u widest %u avg %llu\n", cf, (unsigned long long)need, maxrow, widest, (unsigned long long)avg);
+      if (c->rows_trace && (need > 150 * 1024 || (uint64_t)cf * maxrow > 0x3FFFFull)) fprintf(stderr, "[rows] not taken: cf %u need %llu maxrow %u widest %u avg %llu\n", cf, (unsigned long long)need, maxrow, widest, (unsigned long long)avg);
       if (need > 150 * 1024 || (uint64_t)cf * maxrow > 0x3FFFFull) ok = false;   // (a tile's piece of the fixed arena is addressed by 16-bit dword offsets)
       else {
         const uint64_t wgs = std::max<uint64_t>(1, wgs_of(need));
@@ -515,16 +506,9 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
         q.lds_bytes = (uint32_t)std::min<uint64_t>(tot, 150 * 1024);
         q.seq_lookback = 0; q.in_aligned = 1; q.dbg = c->fused_dbg; q.copy_rel = 0;
         q.ntiles = (nf + cf - 1) / cf;
-        const size_t ngroups = (q.ntiles + 63) / 64;
-        const size_t per = (size_t)q.ntiles + ngroups;
-        const size_t dbytes = per * 8 * 3 + 64;
-        uint8_t *dcur, *doth;
-        { const int32_t rc = take_descriptors(c, dbytes, &dcur, &doth); if (rc != ETLG_OK) return rc; }
-        q.d_txn = (unsigned long long*)dcur; q.d_outa = q.d_txn + per; q.d_outb = q.d_outa + per;
-        q.ticket = (uint32_t*)(q.d_outb + per);
-        q.d_clear = (unsigned long long*)doth; q.clear_words = (uint32_t)(dbytes / 8);
-        if (const char* ov = getenv("ETLG_ROWS_LDS")) q.lds_bytes = (uint32_t)atoi(ov);   // (experiments)
-        if (getenv("ETLG_ROWS_TRACE")) fprintf(stderr, "[rows] cf %u maxc %u maxh %u lds %u (static %llu) side %u tables %llu need %llu (window min %llu, avg frame %llu) -> %d workgroups per CU by the runtime's count, %llu planned\n", cf, widest, maxh, q.lds_bytes, (unsigned long long)stat, q.side_bytes, (unsigned long long)tabb, (unsigned long long)need, (unsigned long long)c->rows_win_min, (unsigned long long)avg, etlg_k_rows_occupancy(q.lds_bytes), (unsigned long long)wgs);
+        RC(take_tile_descriptors(c, q));
+        if (c->rows_lds >= 0) q.lds_bytes = (uint32_t)c->rows_lds;   // (ETLG_ROWS_LDS, experiments)
+        if (c->rows_trace) fprintf(stderr, "[rows] cf %u maxc %u maxh %u lds %u (static %llu) side %u tables %llu need %llu (window min %llu, avg frame %llu) -> %d workgroups per CU by the runtime's count, %llu planned\n", cf, widest, maxh, q.lds_bytes, (unsigned long long)stat, q.side_bytes, (unsigned long long)tabb, (unsigned long long)need, (unsigned long long)c->rows_win_min, (unsigned long long)avg, etlg_k_rows_occupancy(q.lds_bytes), (unsigned long long)wgs);
         launch(c, kRows, p);
         launch_chk_cells(c, b);
         b->used_fused = true; b->used_cells = false; b->used_rows = true;
@@ -537,7 +521,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
   q.maxc = widest;
   // LDS window per tile: the average tile plus a margin; a tile that does not fit reads the input in place
   uint64_t cap = kernel == 1 ? (uint64_t)q.blk * avg * 5 / 4 + 2048 : (uint64_t)q.blk * avg * 9 / 8 + 1024;
-  if (const char* lm = getenv("ETLG_LDS_MARGIN_PCT")) cap = (uint64_t)q.blk * avg * (100 + (uint64_t)atoi(lm)) / 100 + 1024;
+  if (c->lds_margin_pct >= 0) cap = (uint64_t)q.blk * avg * (100 + (uint64_t)c->lds_margin_pct) / 100 + 1024;   // (ETLG_LDS_MARGIN_PCT)
   cap = (cap + 255) & ~255ull;
   if (use_cells) {
     cap = direct ? etlg_k_copy_cells_lds(widest, (uint32_t)cap) : std::max<uint64_t>(cap + etlg_k_cells_table_bytes(widest), etlg_k_cells_lds_floor(widest));
@@ -553,14 +537,7 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
   q.ntiles = (nf + q.blk - 1) / q.blk;
   q.in_aligned = ((uintptr_t)p.in & 15) == 0;
   q.dbg = c->fused_dbg;
-  const size_t ngroups = (q.ntiles + 63) / 64;
-  const size_t per = (size_t)q.ntiles + ngroups;  // tile descriptors followed by group descriptors
-  const size_t dbytes = per * 8 * 3 + 64;
-  uint8_t *dcur, *doth;
-  { const int32_t rc = take_descriptors(c, dbytes, &dcur, &doth); if (rc != ETLG_OK) return rc; }
-  q.d_txn = (unsigned long long*)dcur; q.d_outa = q.d_txn + per; q.d_outb = q.d_outa + per;
-  q.ticket = (uint32_t*)(q.d_outb + per);
-  q.d_clear = (unsigned long long*)doth; q.clear_words = (uint32_t)(dbytes / 8);
+  RC(take_tile_descriptors(c, q));
   q.copy_rel = direct ? b->copy.rel_id : 0u;
   launch(c, direct ? kCopyCells : use_cells ? kCells : kFused, p);
   launch_chk_cells(c, b);
@@ -575,46 +552,49 @@ int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
 // decode of the batch before (etlg_decode); otherwise on the context's stream, collected at once (run_control_pass).
 int32_t ctl_begin(etlg_ctx* c, etlg_batch* b, DecParams& p, hipStream_t s, bool ahead) {
   SlowScope slow_scope_ctl_begin(c, "ctl_begin");
-  struct StreamSwitch { etlg_ctx* c; hipStream_t saved; ~StreamSwitch() { c->stream = saved; } } sw{c, c->stream};
+  StreamSwitch sw{c, c->stream};
   c->stream = s;
   const uint32_t nf = p.nframes;
   // which set of buffers this pre-pass writes: a pre-pass that runs ahead takes them in turn (two may be in flight, etlg_decode); one
   // that is collected at once takes set 0 — behind whatever is still running on the control stream
   const int set = ahead ? b->ctl_set : 0;
   if (!ahead) { b->ctl_set = 0; if (c->ctl_stream) HIPCHK(c, hipStreamSynchronize(c->ctl_stream)); }
-  CtrlFrame*& h_list = set ? c->ctl_alt.h_ctl_list : c->h_ctl_list;
-  uint8_t*& h_stage = set ? c->ctl_alt.h_ctl_stage : c->h_ctl_stage;
-  DevBuf& d_ctrl = set ? c->ctl_alt.d_ctrl : c->d_ctrl;
-  DevBuf& d_ctrl_stage = set ? c->ctl_alt.d_ctrl_stage : c->d_ctrl_stage;
-  if (!h_list) {
-    HIPCHK(c, hipHostMalloc((void**)&h_list, sizeof(CtrlFrame) * etlg_ctx::kCtlListCap, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&h_stage, etlg_ctx::kCtlStageCap, hipHostMallocDefault));
+  CtlSet& cs = c->sets[set];
+  if (!cs.h_ctl_list) {
+    HIPCHK(c, hipHostMalloc((void**)&cs.h_ctl_list, sizeof(CtrlFrame) * etlg_ctx::kCtlListCap, hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc((void**)&cs.h_ctl_stage, etlg_ctx::kCtlStageCap, hipHostMallocDefault));
   }
   if (ahead) {
     if (c->mp_tail_set) { HIPCHK(c, hipStreamWaitEvent(s, c->mp_tail, 0)); c->mp_tail_set = false; }   // the multi-pass kernels share the per-frame scratch
-    if (c->res_pool.empty()) { DevResult* r = nullptr; HIPCHK(c, hipHostMalloc((void**)&r, sizeof(DevResult), hipHostMallocDefault)); c->res_pool.push_back(r); }
-    b->h_ctl = c->res_pool.back(); c->res_pool.pop_back();
-    if (c->ev_pool.empty()) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_pool.push_back(e); }
-    b->ctl_ev = c->ev_pool.back(); c->ev_pool.pop_back();
+    RC(take_result(c, &b->h_ctl));
+    RC(take_event(c, &b->ctl_ev));
     HIPCHK(c, hipMemcpyAsync(p.res, c->d_init_ring, sizeof(DevResult), hipMemcpyDeviceToDevice, s));
   }
-  { const int32_t rc = setup_scratch(c, p, set); if (rc != ETLG_OK) return rc; }
+  RC(setup_scratch(c, p, set));
   launch(c, 0, p);
   launch(c, 1, p);
-  HIPCHK(c, d_ctrl.ensure((size_t)nf * sizeof(CtrlFrame) + 64));
-  p.ctrl = (CtrlFrame*)d_ctrl.p; p.ctrl_cap = nf;
+  HIPCHK(c, cs.d_ctrl.ensure((size_t)nf * sizeof(CtrlFrame) + 64));
+  p.ctrl = (CtrlFrame*)cs.d_ctrl.p; p.ctrl_cap = nf;
   {  // room for the control frames' bytes: a batch rarely carries more than a few hundred KB of them
     size_t want = std::min<size_t>(std::max<size_t>(b->len / 16, 64 << 10), 8 << 20);
     if (c->ctrl_stage_cap_test) want = c->ctrl_stage_cap_test;   // ETLG_CTRL_STAGE_CAP (tests): a staging buffer too small for the batch's control frames
-    HIPCHK(c, d_ctrl_stage.ensure(want));
-    p.ctrl_stage = (uint8_t*)d_ctrl_stage.p; p.ctrl_stage_cap = (uint32_t)want;
+    HIPCHK(c, cs.d_ctrl_stage.ensure(want));
+    p.ctrl_stage = (uint8_t*)cs.d_ctrl_stage.p; p.ctrl_stage_cap = (uint32_t)want;
   }
   launch(c, 2, p);
   HIPCHK(c, hipMemcpyAsync(ahead ? b->h_ctl : b->h_res, p.res, sizeof(DevResult), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(h_list, d_ctrl.p, (size_t)std::min<uint32_t>(nf, etlg_ctx::kCtlListCap) * sizeof(CtrlFrame), hipMemcpyDeviceToHost, s));
-  if (b->in_dev) HIPCHK(c, hipMemcpyAsync(h_stage, d_ctrl_stage.p, std::min<size_t>(p.ctrl_stage_cap, etlg_ctx::kCtlStageCap), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(cs.h_ctl_list, cs.d_ctrl.p, (size_t)std::min<uint32_t>(nf, etlg_ctx::kCtlListCap) * sizeof(CtrlFrame), hipMemcpyDeviceToHost, s));
+  if (b->in_dev) HIPCHK(c, hipMemcpyAsync(cs.h_ctl_stage, cs.d_ctrl_stage.p, std::min<size_t>(p.ctrl_stage_cap, etlg_ctx::kCtlStageCap), hipMemcpyDeviceToHost, s));
   if (ahead) { HIPCHK(c, hipEventRecord(b->ctl_ev, s)); b->ctl_started = true; }
   return ETLG_OK;
+}
+
+// One Relation / DDL frame through the host control plane (handle_relation / handle_ddl): the frame's bytes from its CopyData envelope on.
+HostErr apply_ctrl_frame(etlg_ctx* c, const CtrlFrame& cf, const uint8_t* fr, size_t flen, std::vector<EpochRec>& eps) {
+  // classify guaranteed 'd' len 'w' hdr tag: body starts at +31
+  uint64_t wal_start = 0;
+  for (int k = 0; k < 8; k++) wal_start = wal_start << 8 | fr[6 + k];
+  return cf.tag == 'R' ? handle_relation(c, cf, fr + 31, flen - 31, eps) : handle_ddl(c, cf, wal_start, fr + 31, flen - 31, eps);
 }
 
 // The control pre-pass of one batch (device half above, unless it ran ahead), then the host control plane (handle_relation /
@@ -635,22 +615,19 @@ int32_t run_control_pass(etlg_ctx* c, etlg_batch* b, std::vector<EpochRec>& eps)
     HIPCHK(c, hipEventSynchronize(b->ctl_ev));
     s = c->ctl_stream;   // what did not fit the pinned heads is fetched on the stream the pre-pass ran on
   } else {
-    { const int32_t rc = ctl_begin(c, b, p, s, false); if (rc != ETLG_OK) return rc; }
+    RC(ctl_begin(c, b, p, s, false));
     HIPCHK(c, hipStreamSynchronize(s));
   }
   ht_mark(c, 0);
   const DevResult& cr = ahead ? *b->h_ctl : *b->h_res;
-  const CtrlFrame* h_list = b->ctl_set ? c->ctl_alt.h_ctl_list : c->h_ctl_list;   // (the set this batch's pre-pass wrote)
-  const uint8_t* h_stage = b->ctl_set ? c->ctl_alt.h_ctl_stage : c->h_ctl_stage;
-  DevBuf& d_ctrl = b->ctl_set ? c->ctl_alt.d_ctrl : c->d_ctrl;
-  DevBuf& d_ctrl_stage = b->ctl_set ? c->ctl_alt.d_ctrl_stage : c->d_ctrl_stage;
+  const CtlSet& cs = c->sets[b->ctl_set];   // (the set this batch's pre-pass wrote)
   const uint32_t nctrl = std::min<uint32_t>(cr.n_ctrl, p.ctrl_cap);
   if (!nctrl) return ETLG_OK;
   std::vector<CtrlFrame>& ctrl = b->ctrl;
   ctrl.resize(nctrl);
   const uint32_t nhead = std::min<uint32_t>(nctrl, etlg_ctx::kCtlListCap);
-  memcpy(ctrl.data(), h_list, (size_t)nhead * sizeof(CtrlFrame));
-  if (nctrl > nhead) HIPCHK(c, hipMemcpy(ctrl.data() + nhead, (const CtrlFrame*)d_ctrl.p + nhead, (size_t)(nctrl - nhead) * sizeof(CtrlFrame), hipMemcpyDeviceToHost));
+  memcpy(ctrl.data(), cs.h_ctl_list, (size_t)nhead * sizeof(CtrlFrame));
+  if (nctrl > nhead) HIPCHK(c, hipMemcpy(ctrl.data() + nhead, (const CtrlFrame*)cs.d_ctrl.p + nhead, (size_t)(nctrl - nhead) * sizeof(CtrlFrame), hipMemcpyDeviceToHost));
   std::sort(ctrl.begin(), ctrl.end(), [](const CtrlFrame& a, const CtrlFrame& b2) { return a.frame < b2.frame; });
   ht_mark(c, 1);
   // the frames' bytes: already on the host, or the gathered copy k_ctrl_list left in the staging buffer (its head is in pinned
@@ -658,13 +635,13 @@ int32_t run_control_pass(etlg_ctx* c, etlg_batch* b, std::vector<EpochRec>& eps)
   std::vector<uint8_t> stage, extra;
   std::vector<size_t> at(nctrl + 1, 0);
   for (uint32_t i = 0; i < nctrl; i++) at[i + 1] = at[i] + (ctrl[i].stage_off == 0xFFFFFFFFu ? ctrl[i].o1 - ctrl[i].o0 : 0u);
-  const uint8_t* staged_bytes = h_stage;
+  const uint8_t* staged_bytes = cs.h_ctl_stage;
   if (b->in_dev) {
     const uint32_t staged = std::min<uint32_t>(cr.ctrl_bytes, p.ctrl_stage_cap);
     bool wait = false;
     if (staged > etlg_ctx::kCtlStageCap) {   // more gathered bytes than the pinned head holds: one copy of everything
       stage.resize((size_t)staged + 16);
-      HIPCHK(c, hipMemcpyAsync(stage.data(), d_ctrl_stage.p, staged, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipMemcpyAsync(stage.data(), cs.d_ctrl_stage.p, staged, hipMemcpyDeviceToHost, s));
       staged_bytes = stage.data(); wait = true;
     }
     extra.resize(at[nctrl] + 16);
@@ -681,10 +658,7 @@ int32_t run_control_pass(etlg_ctx* c, etlg_batch* b, std::vector<EpochRec>& eps)
     const uint8_t* fr = !b->in_dev ? b->host_in + cf.o0 : cf.stage_off != 0xFFFFFFFFu ? staged_bytes + cf.stage_off : extra.data() + at[i];
     const size_t flen = cf.o1 - cf.o0;
     b->ctrl_raw.emplace_back(fr, fr + flen);
-    // classify guaranteed 'd' len 'w' hdr tag: body starts at +31
-    uint64_t wal_start = 0;
-    for (int k = 0; k < 8; k++) wal_start = wal_start << 8 | fr[6 + k];
-    HostErr he = cf.tag == 'R' ? handle_relation(c, cf, fr + 31, flen - 31, eps) : handle_ddl(c, cf, wal_start, fr + 31, flen - 31, eps);
+    const HostErr he = apply_ctrl_frame(c, cf, fr, flen, eps);
     if (he.code) { b->host_err_code = he.code; b->host_err_frame = cf.frame; b->host_err_rank = he.rank; b->params.host_err_frame = cf.frame; break; }
   }
   ht_mark(c, 3);
@@ -699,25 +673,23 @@ int32_t standard_path(etlg_ctx* c, etlg_batch* b) {
   DecParams& p = b->params;
   const uint32_t nf = p.nframes;
   std::vector<EpochRec> eps;
-  p.flags &= ~1u;
-  if (b->user_no_ctrl) p.flags |= 1u;
-  else { const int32_t rc = run_control_pass(c, b, eps); if (rc != ETLG_OK) return rc; c->path_n[6]++; b->n_slots_view = c->slots.size(); }
+  p.flags &= ~kDecNoControl;
+  if (b->user_no_ctrl) p.flags |= kDecNoControl;
+  else { RC(run_control_pass(c, b, eps)); c->path_n[kPathControl]++; b->n_slots_view = c->slots.size(); }
   b->eps_saved = eps;
   ht_start(c);
-  { const int32_t rc = build_side_inputs(c, b, eps); if (rc != ETLG_OK) return rc; }
+  RC(build_side_inputs(c, b, eps));
   ht_mark(c, 4);
-  { const int32_t rc = setup_outputs(c, b); if (rc != ETLG_OK) return rc; }
+  RC(setup_outputs(c, b));
   ht_mark(c, 5);
-  // (Round 6, measured and dropped: letting a batch whose control pass found no Relation / DDL frame take the fixed-width plan here. With
-  // it tools/async_long_fuzz.py ddl_fixed found 317 wrong batches in 16 958 on the MI355X (none on the emulator), none with the generic
-  // kernel here — the likely cause: on a chain whose control passes run ahead, a plan that gives the batch up is decoded again against
-  // the side inputs of NOW, the schemas of batches BEHIND it. The gain was one batch per stream. profiles/r06zw_plan_behind_control_dropped.txt)
+  // (always the generic kernel: the fixed-width plan behind a control pass gave wrong ddl_fixed batches on the MI355X and gained one batch
+  // per stream — measured and dropped in round 6, profiles/r06zw_plan_behind_control_dropped.txt)
   if (nf && !b->host_err_code && !c->force_multipass && b->len < (1ull << 31)) { const int32_t rc = enqueue_single(c, b, 1); ht_mark(c, 6); return rc; }
   if (p.carry) {
     // chained to a batch in flight and in need of the multi-pass kernels (the host control plane failed on one of its frames): they
     // take the carried state from the host. The batch is marked "did not run" — the batches behind it stop at that — and is decoded
     // when it is synced, from the exact state (finish_batch, the forced re-run).
-    DevResult poison = *c->h_init; poison.fused_fail = 8u;
+    DevResult poison = *c->h_init; poison.fused_fail = kFailNotRun;
     if (!c->h_poison) { HIPCHK(c, hipHostMalloc((void**)&c->h_poison, sizeof(DevResult), hipHostMallocDefault)); *c->h_poison = poison; }
     HIPCHK(c, hipMemcpyAsync(b->d_res_blk, c->h_poison, sizeof(DevResult), hipMemcpyHostToDevice, c->stream));
     b->level = 1; b->used_fused = true; b->used_cells = false;
@@ -728,7 +700,7 @@ int32_t standard_path(etlg_ctx* c, etlg_batch* b) {
   // pre-pass, not per batch that reaches this line): it finishes first. Rare path — a host control-plane error, or a forced /
   // oversized batch — so the wait costs nothing that matters.
   if (c->ctl_stream) HIPCHK(c, hipStreamSynchronize(c->ctl_stream));
-  { const int32_t rc = setup_scratch(c, p); if (rc != ETLG_OK) return rc; }
+  RC(setup_scratch(c, p));
   launch_multipass(c, p, b->ctrl_done && nf != 0 && !b->ctl_started);
   b->level = 2; b->used_fused = false; b->used_cells = false;
   return ETLG_OK;
@@ -770,6 +742,7 @@ void check_invariants(etlg_ctx* c, const char* where) {
   for (size_t i = 0; i < c->pending.size(); i++) {
     const etlg_batch* b = c->pending[i];
     if (b->ctx != c || !b->pending || b->finished) fail("a batch in the pending list is not pending", i);
+    if (b->copy.staged) fail("a batch names the staged input of an etlg_copy_decode call that has returned", i);
     const BatchState st = batch_state(b);
     if (seen_deferred) fail("a batch was queued behind one whose decode is not enqueued yet", i);
     switch (st) {
@@ -803,267 +776,243 @@ void check_invariants(etlg_ctx* c, const char* where) {
 
 int32_t drain_pending(etlg_ctx* c) {
   SlowScope slow_scope_drain_pending(c, "drain_pending");
-  while (!c->pending.empty()) { const int32_t rc = finish_batch(c, c->pending.front()); (void)rc; }
+  while (!c->pending.empty()) (void)finish_batch(c, c->pending.front());
   return ETLG_OK;
 }
 
-// The batches queued behind one that has just been decoded again started from a result that was not final (they saw its poison mark and
-// did nothing). Rather than decoding each of them again, synchronously, at its own sync — a chain that restarts with a bubble per batch —
-// they are ENQUEUED again here, in order, chained to the new result block of the batch in front (VERDICT r5 #3, DESIGN §8 item 10 of
-// round 5). Only the plain case: device-side chain, first attempt a single-pass kernel, no control pre-pass, no boundary scan in flight,
-// no table-copy batch; the first batch that is anything else keeps the old treatment, and so does everything behind it.
-void reissue_successors(etlg_ctx* c, etlg_batch* b) {
-  hipStream_t s = c->stream;
-  DevResult* prev_blk = b->d_res_blk;
-  size_t i = 0;
-  for (; i < c->pending.size(); i++) {
-    etlg_batch* pb = c->pending[i];
-    const bool plain = !pb->copy.active && !pb->deferred && !pb->ctl_async && !pb->ctl_started && !pb->ctrl_done && pb->level <= 1 && pb->used_fused &&
-                       pb->params.nframes && pb->h_res && pb->kdone && pb->done && (pb->user_no_ctrl || !c->last_had_ctrl) && c->res_stream;
-    if (!plain) break;
-    {  // a block the ring's re-initialisation for the NEXT lap has already passed over must not be written again here: its next user would
-       // meet what this run leaves (finish_batch clears such a block again after a second attempt; these batches go that way)
-      const uint32_t ring_n = etlg_ctx::kResRing;
-      const uint32_t sl = (uint32_t)(pb->d_res_blk - (DevResult*)c->d_res.p);
-      const uint32_t next_lap = (pb->res_seq_no / ring_n + 1) * ring_n;
-      if (c->res_seq > (sl == ring_n - 1 ? next_lap + 1 : next_lap)) break;
-    }
-    DecParams& pp = pb->params;
-    pp.carry = prev_blk;
-    pp.flags &= ~16u;
-    pp.flags |= 1u;
-    if (hipMemcpyAsync(pb->d_res_blk, c->d_init_ring, sizeof(DevResult), hipMemcpyDeviceToDevice, s) != hipSuccess) break;
-    if (build_side_inputs(c, pb, std::vector<EpochRec>()) != ETLG_OK) break;
-    if (enqueue_single(c, pb, 1) != ETLG_OK) break;   // the generic kernel: a batch that is being enqueued for the second time does not try the plan again (whatever made its
-                                                     // predecessor fall off it tends to come in runs, and a second give-up would re-issue everything behind it once more)
-    pb->sidx = 0;
-    pb->force_rerun = false;
-    pb->n_slots_view = c->slots.size();   // (decoded against the side inputs of NOW: its view lists the schema slots of now — see the second-attempt path of finish_batch)
-    (void)hipEventRecord(pb->kdone, s);
-    (void)hipStreamWaitEvent(c->res_stream, pb->kdone, 0);
-    (void)hipMemcpyAsync(pb->h_res, pb->d_res_blk, sizeof(DevResult), hipMemcpyDeviceToHost, c->res_stream);
-    (void)hipEventRecord(pb->done, c->res_stream);
-    prev_blk = pb->d_res_blk;
-    c->chain_reissued++;
-  }
-  c->tail2_set = false;   // (both decode streams were idle when this began, and everything above went to the first)
+// ---- finish_batch, step by step. What the steps hand to each other:
+struct FinishState {
+  bool forced = false;           // a batch before this one in the chain was decoded again: this one started from a state that was not final
+  bool decoded_again = false, redone_mp = false;   // a second attempt wrote the batch's result block at finish time; ... and it was the multi-pass kernels
+  bool plan_gave_up = false; uint32_t plan_streak_before = 0;
+  bool spare = false; uint32_t spare_in_txn = 0; uint64_t spare_lsn = 0, spare_ord = 0;   // the batches behind this one stand if the second attempt leaves the carried state the first one published (these words)
+};
+
+// A step that fails finishes the batch with that error: the code and the context's error record, without the detail string
+// (flush_deferred stores both for a batch that was never enqueued).
+int32_t finished_with(etlg_ctx* c, etlg_batch* b, int32_t rc) {
+  b->pending = false; b->finished = true; b->rc = rc; b->err = c->err;
+  if (!c->err.detail) b->err_detail.clear();   // (a library / HIP error has none)
+  return rc;
+}
+#define FB(step) do { const int32_t rc_ = (step); if (rc_ != ETLG_OK) return finished_with(c, b, rc_); } while (0)
+
+int32_t wait_for_result(etlg_ctx* c, etlg_batch* b) {   // (by its own event: batches queued behind this one keep running)
+  HIPCHK(c, b->done ? hipEventSynchronize(b->done) : hipStreamSynchronize(c->stream));
+  return ETLG_OK;
+}
+int32_t fetch_result(etlg_ctx* c, etlg_batch* b) {   // behind a second attempt: its result block, waited for
+  HIPCHK(c, hipMemcpyAsync(b->h_res, b->d_res_blk, sizeof(DevResult), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ETLG_OK;
 }
 
-// Finishes one batch: waits for its result block; when the optimistic attempt did not hold, decodes the batch again on
-// the next path (plan -> generic single pass -> control path / multi-pass exact error cut); resolves device vs host
-// error, commits or rolls back the control-plane state, updates the carried transaction state of the context and (for
-// host output) copies the arenas back. Batches finish in issue order.
-int32_t finish_batch(etlg_ctx* c, etlg_batch* b) {
-  SlowScope slow_scope_finish_batch(c, "finish_batch");
+// k_rows handed the batch back. A tile beyond its LDS window: the kernel reported what it would have needed, the next attempt
+// (and the batches behind it) size the tile by that; anything else, or a second failure: not that kernel for this batch
+void note_rows_hand_back(etlg_ctx* c, etlg_batch* b, uint32_t ff, const DevResult& r0) {
+  const uint32_t why = ff >> 8;
+  const uint64_t win = r0.dbg_t[11];
+  if (why == 0x1u && b->rows_tries++ < 2 && win <= 100 * 1024) {
+    // (the head room decides how many tiles share a CU, not how large the window is — the window takes whatever its share of the LDS
+    // leaves: with win / 8 cfg5's tiles missed the four-per-CU budget by a few hundred bytes and ran three per CU)
+    c->rows_win_min = std::max<uint64_t>(c->rows_win_min, win + win / (uint64_t)c->rows_win_room);   // (ETLG_ROWS_WIN_ROOM)
+    c->rows_resized++;
+  } else b->no_rows = true;
+}
+
+// Batches behind this one may be running beside it (second stream), chained to a result that is being replaced: both decode streams drain, and the successors are marked for a second attempt of their own — or, for now, spared:
+// Round 6: what a batch takes from its predecessor is three words — in_txn, final_lsn, next_ord (DevResult.out_*; the generic kernels
+// also refuse to start behind a failed block and mark themselves, load_carry). A fixed-width plan that GAVE THE BATCH UP over a shape
+// it does not cover (a Delete, an Update with a key image: fused_fail == 2, no error) has still published those words from the
+// Begin / Commit frames it did read, and the plan batches behind it ran from them. When the second attempt ends without an error
+// and leaves the SAME three words, every batch behind this one started from the final state: none of them is decoded again
+// (they used to be, all of them: a cfg2 stream with a Delete in every 10th batch ran 46 batches twice in 240). Decided in settle_spare,
+// once the second attempt's result is in; only chains of plain sidecar batches (no scan in flight, no control pass running ahead).
+int32_t mark_or_spare_successors(etlg_ctx* c, etlg_batch* b, bool first_attempt, uint32_t ff, const DevResult& r0, FinishState& st) {
+  if (c->pending.empty()) return ETLG_OK;
+  HIPCHK(c, sync_decode_streams(c));
+  bool plain = c->chain_spare && first_attempt && b->level == 0 && ff == kFailPlanGaveUp && r0.first_err == kNoErr && !b->copy.active && !b->ctl_async && !b->scan_chained;
+  for (const etlg_batch* pb : c->pending) if (pb->copy.active || pb->deferred || pb->ctl_async || pb->scan_chained || pb->force_rerun) plain = false;
+  st.spare = plain;
+  if (st.spare) { st.spare_in_txn = r0.out_in_txn; st.spare_lsn = r0.out_final_lsn; st.spare_ord = r0.out_next_ord; }
+  // (table-copy batches are not chained to anything: the ones behind this one stand)
+  else for (etlg_batch* pb : c->pending) if (!pb->copy.active) { pb->force_rerun = true; if (pb->deferred) pb->ctl_started = false; }   // (a pre-pass that ran ahead started from a state that was not final)
+  return ETLG_OK;
+}
+
+// The rungs of the second-attempt ladder, and which one a batch takes — from what its last attempt left (`ff`: its fused_fail bits,
+// kFailNotRun for a batch marked by a predecessor's second attempt) and from how it was decoded. Nothing is enqueued here.
+enum class Rung {
+  COPY_FRAMES,         // the rows -> arena kernel met something it leaves to the other path: the rows become Insert frames, decoded as a batch of those (and, should that fail as well, once more by the multi-pass kernels)
+  SAME_WITH_COUNT,     // decoded behind its boundary scan and the count read on the device was not usable: the same path again, with the count
+  SAME_AGAIN,          // the batch before this one failed, so this one never ran: the same path again, now from the right state
+  CONTROL_AGAIN,       // ... and it took the control path: its control pass ran against a history that has changed
+  EMPTY_AGAIN,         // ... and it is EMPTY: no single-pass kernel to enqueue again (round 6: this divided by its zero frames)
+  GENERIC_AFTER_ROWS,  // k_rows handed the batch back (a tile beyond its window / image): k_cells / k_fused, and back off
+  GENERIC_AFTER_PLAN,  // the fixed-width plan did not cover the batch: generic kernel, and back off
+  CONTROL_PATH,        // a Relation / DDL frame: the control path
+  MULTI_PASS,          // an error (or a look-back give-up): the multi-pass kernels know the exact cut at the failing frame
+};
+Rung choose_second_attempt(const etlg_batch* b, uint32_t ff, const DevResult& r0, bool ctrl_hint) {
+  if (b->copy.active && b->copy.direct) return Rung::COPY_FRAMES;
+  if ((ff & kFailScanCount) && r0.first_err == kNoErr && !(ff & ~kFailScanCount)) return Rung::SAME_WITH_COUNT;
+  if (ff & kFailNotRun) return b->ctl_async ? Rung::CONTROL_AGAIN : !b->params.nframes ? Rung::EMPTY_AGAIN : Rung::SAME_AGAIN;
+  if (b->used_rows && (ff & kFailRowsBack) && !ctrl_hint) return Rung::GENERIC_AFTER_ROWS;   // (errors recorded beside a tile that gave up mean nothing: its frames were left out of the transaction scan)
+  if (b->level == 0) return Rung::GENERIC_AFTER_PLAN;
+  if (ctrl_hint && !(ff & kFailLookback)) return Rung::CONTROL_PATH;
+  return Rung::MULTI_PASS;
+}
+
+int32_t single_again(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec>& eps, int level) {   // side inputs, then ONE single-pass kernel
+  RC(build_side_inputs(c, b, eps));
+  return enqueue_single(c, b, level);
+}
+int32_t enqueue_second_attempt(etlg_ctx* c, etlg_batch* b, Rung rung, FinishState& st) {
+  const std::vector<EpochRec> no_eps;
+  if (rung == Rung::SAME_WITH_COUNT) c->scan_chain_redone++;
+  if (rung == Rung::SAME_AGAIN || rung == Rung::CONTROL_AGAIN || rung == Rung::EMPTY_AGAIN) c->path_n[kPathChainRerun]++;
+  switch (rung) {
+    case Rung::COPY_FRAMES:
+      RC(copy_use_frames(c, b));
+      RC(setup_outputs(c, b));
+      return enqueue_single(c, b, 1);
+    case Rung::SAME_WITH_COUNT: case Rung::SAME_AGAIN:
+      return single_again(c, b, no_eps, b->level);
+    case Rung::CONTROL_AGAIN:
+      // Back to the state before the batch — its own snapshot, unless a rollback since then has already discarded everything behind the failed batch — and again.
+      if (b->have_snapshot && b->snap_gen == c->cs_gen) { c->cs = b->snapshot; c->slots.resize(b->snapshot.n_slots); c->slots_dirty = true; c->side_dirty = true; }
+      b->ctrl_done = false; b->ctl_started = false; b->have_snapshot = false;
+      return standard_path(c, b);
+    case Rung::EMPTY_AGAIN: case Rung::CONTROL_PATH:
+      return standard_path(c, b);
+    case Rung::GENERIC_AFTER_ROWS:
+      if (b->no_rows) { c->rows_redone++; c->rows_skip = c->rows_penalty; c->rows_penalty = std::min<uint32_t>(c->rows_penalty * 2, 1024); c->rows_streak = 0; }
+      return single_again(c, b, b->eps_saved, 1);
+    case Rung::GENERIC_AFTER_PLAN:
+      c->path_n[kPathPlanRedone]++;
+      // (the back-off: the batches behind a give-up skip the plan for a while, twice as long after every give-up that follows closely. A
+      // give-up whose successors stand — `spare`, decided after this attempt — costs one wasted kernel and one generic decode, less than
+      // four batches on the generic kernel do: when at least four plan batches finished since the last one, there is no back-off for it)
+      st.plan_gave_up = true; st.plan_streak_before = c->plan_streak;
+      c->plan_skip = c->plan_penalty; c->plan_penalty = std::min<uint32_t>(c->plan_penalty * 2, 4096); c->plan_streak = 0;
+      return single_again(c, b, no_eps, 1);
+    case Rung::MULTI_PASS:
+      RC(build_side_inputs(c, b, b->eps_saved)); RC(setup_scratch(c, b->params));
+      launch_multipass(c, b->params, false);
+      b->level = 2; b->used_fused = false;
+      c->path_n[kPathRedoneMulti]++; st.redone_mp = true;
+  }
+  return ETLG_OK;
+}
+
+// When the optimistic attempt did not hold, the batch is decoded again on the next path (plan -> generic single pass -> control path /
+// multi-pass exact error cut), synchronously, until an attempt holds or the multi-pass kernels have had it.
+int32_t second_attempts(etlg_ctx* c, etlg_batch* b, FinishState& st) {
   hipStream_t s = c->stream;
-  // A table-copy batch decodes inside a virtual transaction of its own (etlg_copy_decode): whatever finishing it does to the carried
-  // transaction state of the context — the state a second attempt starts from, the state the batch leaves — is undone on the way out.
-  // (For a synchronous call this runs inside etlg_copy_decode's own save / restore and changes nothing.)
-  struct TxnKeep { etlg_ctx* c; bool on, in_txn; uint64_t lsn, ord; ~TxnKeep() { if (on) { c->in_txn = in_txn; c->final_lsn = lsn; c->next_ord = ord; } } } txn_keep{c, b->copy.active, c->in_txn, c->final_lsn, c->next_ord};
-  if (b->copy.active) { c->in_txn = true; c->final_lsn = 0; c->next_ord = 0; }
-  if (b->deferred) {  // its boundary scan is still in flight: collect it and enqueue the decode first
-    const int32_t rc = flush_deferred(c);
-    if (rc != ETLG_OK) return rc;   // the batch is finished, with that error
-  }
-  if (b->pending) {  // must be the oldest pending batch
-    if (c->pending.empty() || c->pending.front() != b) return lib_error(c, ETLG_InvalidArgument, "ASYNC batches must be synced in issue order");
-    c->pending.erase(c->pending.begin());
-  }
-  auto fail_hip = [&](hipError_t e) {
-    b->pending = false; b->finished = true;
-    b->rc = lib_error(c, ETLG_DeviceError, hipGetErrorString(e));
-    b->err = c->err; b->err_detail.clear();
-    return b->rc;
-  };
-#define FB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail_hip(e_); } while (0)
-#define FB_RC(call) do { const int32_t rc_ = (call); if (rc_ != ETLG_OK) { b->pending = false; b->finished = true; b->rc = rc_; b->err = c->err; return rc_; } } while (0)
-  ht_start(c);
-  if (b->done) FB_HIP(hipEventSynchronize(b->done));   // batches queued behind this one keep running
-  else FB_HIP(hipStreamSynchronize(s));
-  ht_mark(c, 7);
-  bool redone_mp = false;
-  bool decoded_again = false;   // a second attempt wrote the batch's result block at finish time
-  bool forced = b->force_rerun;   // a batch before this one in the chain was decoded again: this one started from a state that was not final
-  b->force_rerun = false;
-  bool plan_gave_up = false; uint32_t plan_streak_before = 0;
-  bool spare = false;             // the batches behind this one stand if the second attempt leaves the carried state the first one published
-  uint32_t spare_in_txn = 0; uint64_t spare_lsn = 0, spare_ord = 0;
   for (int guard = 0; guard < 8; guard++) {
     const DevResult& r0 = *b->h_res;
-    const bool failed = forced || r0.first_err != kNoErr || r0.fused_fail;
+    const bool failed = st.forced || r0.first_err != kNoErr || r0.fused_fail;
     const bool ctrl_hint = r0.first_err != kNoErr && (uint32_t)(r0.first_err & 0xFF) == ETLG_E_CTRL_HINT && !b->user_no_ctrl && !b->ctrl_done;
     if (!failed || (b->level == 2 && !ctrl_hint)) break;
     // ---- decode again. Every earlier batch is finished, so the host's carried state is exact: no device chaining.
-    decoded_again = true;
+    st.decoded_again = true;
     DecParams& p = b->params;
-    p.carry = nullptr;
-    p.flags &= ~16u;
+    p.carry = nullptr; p.flags &= ~kDecLateCarry;
     p.in_txn = c->in_txn; p.final_lsn = c->final_lsn; p.next_ord = c->next_ord;
     // the batch is decoded against the side inputs of NOW: its view lists the schema slots of now (an optimistic ASYNC batch queued
     // behind one that carried the stream's first Relation frames was enqueued when there were none: its events named slots its view
     // did not list — found by tools/async_fuzz.py). A control pass below (standard_path) sets the count again behind its own frames.
     if (!b->ctl_async && !b->ctrl_done) b->n_slots_view = c->slots.size();   // (a batch whose control pass has run keeps what that pass counted)
-    const uint32_t ff = forced ? 8u : r0.fused_fail;
-    forced = false;
-    if (getenv("ETLG_ROWS_TRACE")) fprintf(stderr, "[%s] batch redone: first_err frame %llu rank %u code %u, fused_fail %u (len %zu, frames %u, level %d, scan %d chained %d deferred %d)\n", b->used_rows ? "rows" : b->used_cells ? "cells" : b->level == 0 ? "plan" : "fused", (unsigned long long)(r0.first_err >> 16), (unsigned)((r0.first_err >> 8) & 0xFF), (unsigned)(r0.first_err & 0xFF), r0.fused_fail, b->len, b->params.nframes, b->level, (int)b->scan, (int)b->scan_chained, (int)b->deferred);
-    if (b->used_rows && (ff & 16u)) {
-      // k_rows handed the batch back. A tile beyond its LDS window: the kernel reported what it would have needed, the next attempt
-      // (and the batches behind it) size the tile by that; anything else, or a second failure: not that kernel for this batch
-      const uint32_t why = ff >> 8;
-      const uint64_t win = r0.dbg_t[11];
-      if (why == 0x1u && b->rows_tries++ < 2 && win <= 100 * 1024) {
-        // (the head room decides how many tiles share a CU, not how large the window is — the window takes whatever its share of the LDS
-        // leaves: with win / 8 cfg5's tiles missed the four-per-CU budget by a few hundred bytes and ran three per CU)
-        static const uint64_t room_div = [] { const char* e = getenv("ETLG_ROWS_WIN_ROOM"); const int v = e ? atoi(e) : 64; return (uint64_t)(v > 0 ? v : 64); }();
-        c->rows_win_min = std::max<uint64_t>(c->rows_win_min, win + win / room_div);
-        c->rows_resized++;
-      } else b->no_rows = true;
-    }
-    if (c->ctl_stream) FB_HIP(hipStreamSynchronize(c->ctl_stream));   // (a pre-pass running ahead shares the scratch and the pinned heads with what follows)
-    if (!c->pending.empty()) {   // batches behind this one may be running beside it (second stream) and chained to a result that is being replaced
-      FB_HIP(sync_decode_streams(c));
-      // Round 6: what a batch takes from its predecessor is three words — in_txn, final_lsn, next_ord (DevResult.out_*; the generic kernels
-      // also refuse to start behind a failed block and mark themselves, load_carry). A fixed-width plan that GAVE THE BATCH UP over a shape
-      // it does not cover (a Delete, an Update with a key image: fused_fail == 2, no error) has still published those words from the
-      // Begin / Commit frames it did read, and the plan batches behind it ran from them. When the second attempt ends without an error
-      // and leaves the SAME three words, every batch behind this one started from the final state: none of them is decoded again
-      // (they used to be, all of them: a cfg2 stream with a Delete in every 10th batch ran 46 batches twice in 240). Decided below, once
-      // the second attempt's result is in; only chains of plain sidecar batches (no scan in flight, no control pass running ahead).
-      bool plain = c->chain_spare && guard == 0 && b->level == 0 && ff == 2u && r0.first_err == kNoErr && !b->copy.active && !b->ctl_async && !b->scan_chained;
-      for (const etlg_batch* pb : c->pending) if (pb->copy.active || pb->deferred || pb->ctl_async || pb->scan_chained || pb->force_rerun) plain = false;
-      spare = plain;
-      if (spare) { spare_in_txn = r0.out_in_txn; spare_lsn = r0.out_final_lsn; spare_ord = r0.out_next_ord; }
-      // (table-copy batches are not chained to anything: the ones behind this one stand)
-      else for (etlg_batch* pb : c->pending) if (!pb->copy.active) { pb->force_rerun = true; if (pb->deferred) pb->ctl_started = false; }   // (a pre-pass that ran ahead started from a state that was not final)
-    }
-    FB_HIP(hipMemcpyAsync(b->d_res_blk, c->d_init_ring, sizeof(DevResult), hipMemcpyDeviceToDevice, s));
-    if (b->copy.active && b->copy.direct) {
-      // the rows -> arena kernel met something it leaves to the other path: the rows become Insert frames, which are decoded as a batch
-      // of those (and, should that fail as well, once more by the multi-pass kernels, which know the exact cut)
-      FB_RC(copy_use_frames(c, b));
-      FB_RC(setup_outputs(c, b));
-      FB_RC(enqueue_single(c, b, 1));
-      FB_HIP(hipMemcpyAsync(b->h_res, b->d_res_blk, sizeof(DevResult), hipMemcpyDeviceToHost, s));
-      FB_HIP(hipStreamSynchronize(s));
-      continue;
-    }
-    if (b->copy.active) { FB_RC(copy_repoint_frames(c, b)); launch_copy(c, b->copy, p); }
-    if (b->scan_chained) FB_RC(resolve_scan_count(c, b));   // (a second attempt has its frame count in hand)
-    if ((ff & 32u) && r0.first_err == kNoErr && !(ff & ~32u)) {   // the count read on the device was not usable: the same path again, with the count
-      c->scan_chain_redone++;
-      FB_RC(build_side_inputs(c, b, std::vector<EpochRec>()));
-      FB_RC(enqueue_single(c, b, b->level));
-    } else if (ff & 8u) {  // the batch before this one failed, so this one never ran: same path again, now from the right state
-      c->path_n[7]++;
-      if (b->ctl_async) {
-        // it took the control path: its control pass ran against a history that has changed. Back to the state before the batch —
-        // its own snapshot, unless a rollback since then has already discarded everything behind the failed batch — and again.
-        if (b->have_snapshot && b->snap_gen == c->cs_gen) { c->cs = b->snapshot; c->slots.resize(b->snapshot.n_slots); c->slots_dirty = true; c->side_dirty = true; }
-        b->ctrl_done = false; b->ctl_started = false; b->have_snapshot = false;
-        FB_RC(standard_path(c, b));
-      } else if (!p.nframes) {
-        FB_RC(standard_path(c, b));   // (an EMPTY batch queued behind a pending one: no single-pass kernel to enqueue again — round 6: this divided by its zero frames)
-      } else {
-        FB_RC(build_side_inputs(c, b, std::vector<EpochRec>()));
-        FB_RC(enqueue_single(c, b, b->level));
-      }
-    } else if (b->used_rows && (ff & 16u) && !ctrl_hint) {   // (errors recorded beside a tile that gave up mean nothing: its frames were left out of the transaction scan)  // k_rows handed the batch back (a tile beyond its window / image): k_cells / k_fused, and back off
-      if (b->no_rows) { c->rows_redone++; c->rows_skip = c->rows_penalty; c->rows_penalty = std::min<uint32_t>(c->rows_penalty * 2, 1024); c->rows_streak = 0; }
-      FB_RC(build_side_inputs(c, b, b->eps_saved));
-      FB_RC(enqueue_single(c, b, 1));
-    } else if (b->level == 0) {  // the fixed-width plan did not cover the batch: generic kernel, and back off
-      c->path_n[5]++;
-      // (the back-off: the batches behind a give-up skip the plan for a while, twice as long after every give-up that follows closely. A
-      // give-up whose successors stand — `spare`, decided after this attempt — costs one wasted kernel and one generic decode, less than
-      // four batches on the generic kernel do: when at least four plan batches finished since the last one, there is no back-off for it)
-      plan_gave_up = true; plan_streak_before = c->plan_streak;
-      c->plan_skip = c->plan_penalty; c->plan_penalty = std::min<uint32_t>(c->plan_penalty * 2, 4096); c->plan_streak = 0;
-      FB_RC(build_side_inputs(c, b, std::vector<EpochRec>()));
-      FB_RC(enqueue_single(c, b, 1));
-    } else if (ctrl_hint && !(ff & 1u)) {
-      FB_RC(standard_path(c, b));  // a Relation / DDL frame: the control path
-    } else {  // an error (or a look-back give-up): the multi-pass kernels know the exact cut at the failing frame
-      FB_RC(build_side_inputs(c, b, b->eps_saved));
-      FB_RC(setup_scratch(c, p));
-      launch_multipass(c, p, false);
-      b->level = 2; b->used_fused = false;
-      c->path_n[3]++; redone_mp = true;
-    }
-    FB_HIP(hipMemcpyAsync(b->h_res, b->d_res_blk, sizeof(DevResult), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    const uint32_t ff = st.forced ? kFailNotRun : r0.fused_fail;
+    st.forced = false;
+    if (c->rows_trace) fprintf(stderr, "[%s] batch redone: first_err frame %llu rank %u code %u, fused_fail %u (len %zu, frames %u, level %d, scan %d chained %d deferred %d)\n", b->used_rows ? "rows" : b->used_cells ? "cells" : b->level == 0 ? "plan" : "fused", (unsigned long long)(r0.first_err >> 16), (unsigned)((r0.first_err >> 8) & 0xFF), (unsigned)(r0.first_err & 0xFF), r0.fused_fail, b->len, b->params.nframes, b->level, (int)b->scan, (int)b->scan_chained, (int)b->deferred);
+    if (b->used_rows && (ff & kFailRowsBack)) note_rows_hand_back(c, b, ff, r0);
+    if (c->ctl_stream) HIPCHK(c, hipStreamSynchronize(c->ctl_stream));   // (a pre-pass running ahead shares the scratch and the pinned heads with what follows)
+    RC(mark_or_spare_successors(c, b, guard == 0, ff, r0, st));
+    HIPCHK(c, hipMemcpyAsync(b->d_res_blk, c->d_init_ring, sizeof(DevResult), hipMemcpyDeviceToDevice, s));
+    if (b->copy.active && !b->copy.direct) { RC(copy_repoint_frames(c, b)); launch_copy(c, b->copy, p); }
+    if (b->scan_chained) RC(resolve_scan_count(c, b));   // (a second attempt has its frame count in hand)
+    const Rung rung = choose_second_attempt(b, ff, r0, ctrl_hint);   // (behind the count: an empty batch takes a rung of its own)
+    RC(enqueue_second_attempt(c, b, rung, st));
+    RC(fetch_result(c, b));
   }
-  if (spare) {
-    const DevResult& r1 = *b->h_res;
-    if (getenv("ETLG_ROWS_TRACE")) fprintf(stderr, "[spare] first attempt left in_txn %u lsn %llx ord %llu, second err %d ff %u host_err %d in_txn %u lsn %llx ord %llu\n", spare_in_txn, (unsigned long long)spare_lsn, (unsigned long long)spare_ord, r1.first_err != kNoErr, r1.fused_fail, (int)b->host_err_code, r1.out_in_txn, (unsigned long long)r1.out_final_lsn, (unsigned long long)r1.out_next_ord);
-    if (r1.first_err == kNoErr && !r1.fused_fail && !b->host_err_code && (r1.out_in_txn != 0) == (spare_in_txn != 0) &&
-        (!r1.out_in_txn || (r1.out_final_lsn == spare_lsn && r1.out_next_ord == spare_ord))) {   // (outside a transaction the other two words are dead: a Begin sets both before anything reads them — apply.rs:2279-2296 — and every other frame that would is an "Invalid transaction state"; the kernels leave different leftovers there)
-      c->chain_spared++;
-      if (plan_gave_up && plan_streak_before >= 4) { c->plan_skip = 0; c->plan_penalty = 4; }
-    }
-    else { spare = false; for (etlg_batch* pb : c->pending) if (!pb->copy.active) pb->force_rerun = true; }
+  return ETLG_OK;
+}
+
+// The spare decision (mark_or_spare_successors), with the second attempt's result in: the successors stand, or are marked after all.
+void settle_spare(etlg_ctx* c, etlg_batch* b, FinishState& st) {
+  const DevResult& r1 = *b->h_res;
+  if (c->rows_trace) fprintf(stderr, "[spare] first attempt left in_txn %u lsn %llx ord %llu, second err %d ff %u host_err %d in_txn %u lsn %llx ord %llu\n", st.spare_in_txn, (unsigned long long)st.spare_lsn, (unsigned long long)st.spare_ord, r1.first_err != kNoErr, r1.fused_fail, (int)b->host_err_code, r1.out_in_txn, (unsigned long long)r1.out_final_lsn, (unsigned long long)r1.out_next_ord);
+  if (r1.first_err == kNoErr && !r1.fused_fail && !b->host_err_code && (r1.out_in_txn != 0) == (st.spare_in_txn != 0) &&
+      (!r1.out_in_txn || (r1.out_final_lsn == st.spare_lsn && r1.out_next_ord == st.spare_ord))) {   // (outside a transaction the other two words are dead: a Begin sets both before anything reads them — apply.rs:2279-2296 — and every other frame that would is an "Invalid transaction state"; the kernels leave different leftovers there)
+    c->chain_spared++;
+    if (st.plan_gave_up && st.plan_streak_before >= 4) { c->plan_skip = 0; c->plan_penalty = 4; }
   }
-  if (decoded_again) {
-    // The result ring is re-initialised once per lap, when the batch that takes slot 0 (slot 1 for the last block) is ISSUED. With
-    // batches in flight across that point, a batch of the old lap that is decoded again HERE writes its block after the new lap's
-    // re-initialisation has gone out: what the second attempt leaves behind — payload shards that are added to, first_err / fused_fail
-    // that are min-ed / or-ed into, carry_ready — would meet the slot's next user 32 batches later (found by tools/copy_async_fuzz.py:
-    // a transaction's payload_bytes 489 instead of 71 behind a table-copy batch that had been redone through the frame rewrite). The
-    // block is cleared again in that case; the decode streams are idle here (the second attempt was waited for), and nothing else may
-    // start before the clear is done (the slot's next user may run on the other decode stream).
-    const uint32_t ring_n = etlg_ctx::kResRing;
-    const uint32_t sl = (uint32_t)(b->d_res_blk - (DevResult*)c->d_res.p);
-    const uint32_t next_lap = (b->res_seq_no / ring_n + 1) * ring_n;
-    const uint32_t cleaner = sl == ring_n - 1 ? next_lap + 1 : next_lap;   // the batch whose issue re-initialises this slot for the next lap
-    if (c->res_seq > cleaner) {
-      FB_HIP(hipMemcpyAsync(b->d_res_blk, c->d_init_ring, sizeof(DevResult), hipMemcpyDeviceToDevice, s));
-      FB_HIP(sync_decode_streams(c));
-      c->ring_recleared++;
-    } else if (!c->pending.empty() && c->pending.front()->force_rerun && b->h_res->first_err == kNoErr && b->h_res->fused_fail == 0 && !b->host_err_code && c->chain_reissue) {
-      reissue_successors(c, b);   // (the block stays as it is: it is the state the batch behind this one starts from)
-    }
-  }
+  else { st.spare = false; for (etlg_batch* pb : c->pending) if (!pb->copy.active) pb->force_rerun = true; }
+}
+
+// The result ring is re-initialised once per lap, when the batch that takes slot 0 (slot 1 for the last block) is ISSUED. With
+// batches in flight across that point, a batch of the old lap that is decoded again at finish time writes its block after the new lap's
+// re-initialisation has gone out: what the second attempt leaves behind — payload shards that are added to, first_err / fused_fail
+// that are min-ed / or-ed into, carry_ready — would meet the slot's next user 32 batches later (found by tools/copy_async_fuzz.py:
+// a transaction's payload_bytes 489 instead of 71 behind a table-copy batch that had been redone through the frame rewrite). The
+// block is cleared again in that case; the decode streams are idle here (the second attempt was waited for), and nothing else may
+// start before the clear is done (the slot's next user may run on the other decode stream).
+int32_t reclear_lapped_block(etlg_ctx* c, etlg_batch* b) {
+  const uint32_t ring_n = etlg_ctx::kResRing;
+  const uint32_t sl = (uint32_t)(b->d_res_blk - (DevResult*)c->d_res.p);
+  const uint32_t next_lap = (b->res_seq_no / ring_n + 1) * ring_n;
+  const uint32_t cleaner = sl == ring_n - 1 ? next_lap + 1 : next_lap;   // the batch whose issue re-initialises this slot for the next lap
+  if (c->res_seq <= cleaner) return ETLG_OK;
+  HIPCHK(c, hipMemcpyAsync(b->d_res_blk, c->d_init_ring, sizeof(DevResult), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, sync_decode_streams(c));
+  c->ring_recleared++;
+  return ETLG_OK;
+}
+
+void count_path(etlg_ctx* c, const etlg_batch* b, const FinishState& st) {
   if (b->copy.active) c->copy_n[b->copy.direct ? 0 : 1]++;
-  if (b->level == 0) { c->path_n[4]++; if (++c->plan_streak >= 16) c->plan_penalty = 4; }
+  if (b->level == 0) { c->path_n[kPathPlan]++; if (++c->plan_streak >= 16) c->plan_penalty = 4; }
   else if (b->used_fused && b->used_rows) { c->rows_n++; if (++c->rows_streak >= 16) c->rows_penalty = 4; }
-  else if (b->used_fused) c->path_n[b->used_cells ? 1 : 0]++;
-  else if (!redone_mp) c->path_n[2]++;
-  DevResult r = *b->h_res;
-  if (b->used_fused) for (int k = 0; k < 3; k++) { r.payload[k] = 0; for (int sh = 0; sh < 32; sh++) r.payload[k] += r.pay_shard[sh][k]; }
-  for (int i = 0; i < 12; i++) c->last_dbg[i] = r.dbg_t[i];
-  c->res_pool.push_back(b->h_res);
-  b->h_res = nullptr;
-  // ---- first error: device (frame, rank) vs host control plane (frame, rank)
+  else if (b->used_fused) c->path_n[b->used_cells ? kPathCells : kPathFused]++;
+  else if (!st.redone_mp) c->path_n[kPathMulti]++;
+}
+
+// First error: device (frame, rank) vs host control plane (frame, rank). Returns the code (0: none) and the failing frame.
+int32_t first_error(const etlg_batch* b, const DevResult& r, int64_t* frame_out) {
   int32_t code = 0; int64_t frame = -1; uint32_t rank = 0xFF;
   if (r.first_err != kNoErr) { frame = (int64_t)(r.first_err >> 16); rank = (uint32_t)((r.first_err >> 8) & 0xFF); code = (int32_t)(r.first_err & 0xFF); }
   if (b->host_err_code) {
     const int64_t hf = b->host_err_frame;
     if (frame < 0 || hf < frame || (hf == frame && b->host_err_rank < rank)) { frame = hf; rank = b->host_err_rank; code = b->host_err_code; }
   }
-  // ---- control-plane state: keep only effects of frames before the failing one
-  if (code && b->have_snapshot) {
-    bool later = false;
-    for (auto& cf : b->ctrl) if ((int64_t)cf.frame >= frame) later = true;
-    if (later || b->host_err_code) {
-      // roll back, then replay the prefix (rare path; errors end the stream anyway)
-      c->cs = b->snapshot;
-      c->cs_gen++;
-      c->slots.resize(b->snapshot.n_slots);
-      c->slots_dirty = true; c->side_dirty = true;
-      // Effects of the control frames before `frame` are re-applied from the copies of their bytes kept
-      // by the first pass (the input itself may be device-resident, or have come without a sidecar).
-      std::vector<EpochRec> eps;
-      for (size_t i = 0; i < b->ctrl.size() && i < b->ctrl_raw.size(); i++) {
-        const CtrlFrame& cf = b->ctrl[i];
-        if ((int64_t)cf.frame >= frame) break;
-        const uint8_t* fr = b->ctrl_raw[i].data();
-        const size_t flen = b->ctrl_raw[i].size();
-        uint64_t wal_start = 0;
-        for (int k = 0; k < 8; k++) wal_start = wal_start << 8 | fr[6 + k];
-        if (cf.tag == 'R') (void)handle_relation(c, cf, fr + 31, flen - 31, eps); else (void)handle_ddl(c, cf, wal_start, fr + 31, flen - 31, eps);
-      }
-      b->n_slots_view = c->slots.size();
-    }
+  *frame_out = frame;
+  return code;
+}
+
+// Control-plane state of a batch that failed at `frame`: keep only effects of frames before the failing one.
+void rollback_control_state(etlg_ctx* c, etlg_batch* b, int64_t frame) {
+  bool later = false;
+  for (auto& cf : b->ctrl) if ((int64_t)cf.frame >= frame) later = true;
+  if (!later && !b->host_err_code) return;
+  // roll back, then replay the prefix (rare path; errors end the stream anyway)
+  c->cs = b->snapshot;
+  c->cs_gen++;
+  c->slots.resize(b->snapshot.n_slots);
+  c->slots_dirty = true; c->side_dirty = true;
+  // Effects of the control frames before `frame` are re-applied from the copies of their bytes kept
+  // by the first pass (the input itself may be device-resident, or have come without a sidecar).
+  std::vector<EpochRec> eps;
+  for (size_t i = 0; i < b->ctrl.size() && i < b->ctrl_raw.size(); i++) {
+    const CtrlFrame& cf = b->ctrl[i];
+    if ((int64_t)cf.frame >= frame) break;
+    (void)apply_ctrl_frame(c, cf, b->ctrl_raw[i].data(), b->ctrl_raw[i].size(), eps);
   }
+  b->n_slots_view = c->slots.size();
+}
+
+// What the batch leaves in the context (stream state, "the stream carries control frames") and the view of its arrays.
+void carry_state_and_view(etlg_ctx* c, etlg_batch* b, const DevResult& r, int32_t code, int64_t frame) {
   if (!b->user_no_ctrl) c->last_had_ctrl = b->ctrl_done && !b->ctrl.empty();
   b->have_snapshot = false;
   b->snapshot = ControlState{};
@@ -1082,30 +1031,67 @@ int32_t finish_batch(etlg_ctx* c, etlg_batch* b) {
   v.ev_kind = (const uint8_t*)os->kind.p; v.ev_flags = (const uint8_t*)os->flags.p; v.ev_table_id = (const uint32_t*)os->table.p; v.ev_schema_slot = (const uint32_t*)os->slot.p;
   v.ev_start_lsn = (const uint64_t*)os->start.p; v.ev_commit_lsn = (const uint64_t*)os->commit.p; v.ev_tx_ordinal = (const uint64_t*)os->ord.p; v.ev_body_off = (const uint64_t*)os->body.p;
   v.fixed = (const uint8_t*)os->fixed.p; v.heap = (const uint8_t*)os->heap.p;
+}
+
+// TableCopyPayloadMetadata: the bytes of the rows that were decoded
+void copy_payload_bytes(etlg_batch* b) {
+  const CopyJob& j = b->copy;
+  const uint64_t done = b->v.n_frames;
+  uint32_t o[2] = {0, 0};
+  if (b->rc == ETLG_OK && j.direct && done == j.nrows && b->used_cells && b->copy_span) { o[1] = b->copy_span; }   // the rows -> arena kernel measured them (no device round trips here)
+  else {
+    (void)hipMemcpy(&o[0], j.d_row_offs, 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&o[1], j.d_row_offs + done, 4, hipMemcpyDeviceToHost);
+  }
+  b->v.payload_bytes[0] = o[1] - o[0]; b->v.payload_bytes[1] = 0; b->v.payload_bytes[2] = 0;
+}
+
+// Finishes one batch: waits for its result block; when the optimistic attempt did not hold, decodes the batch again on
+// the next path (second_attempts); resolves device vs host error, commits or rolls back the control-plane state, updates
+// the carried transaction state of the context and (for host output) copies the arenas back. Batches finish in issue order.
+int32_t finish_batch(etlg_ctx* c, etlg_batch* b) {
+  SlowScope slow_scope_finish_batch(c, "finish_batch");
+  // A table-copy batch decodes inside a virtual transaction of its own (etlg_copy_decode): whatever finishing it does to the carried
+  // transaction state of the context — the state a second attempt starts from, the state the batch leaves — is undone on the way out.
+  // (For a synchronous call this runs inside etlg_copy_decode's own save / restore and changes nothing.)
+  struct TxnKeep { etlg_ctx* c; bool on, in_txn; uint64_t lsn, ord; ~TxnKeep() { if (on) { c->in_txn = in_txn; c->final_lsn = lsn; c->next_ord = ord; } } } txn_keep{c, b->copy.active, c->in_txn, c->final_lsn, c->next_ord};
+  if (b->copy.active) { c->in_txn = true; c->final_lsn = 0; c->next_ord = 0; }
+  if (b->deferred) RC(flush_deferred(c));   // its boundary scan is still in flight: collect it and enqueue the decode first (a failure: the batch is finished, with that error)
+  if (b->pending) {  // must be the oldest pending batch
+    if (c->pending.empty() || c->pending.front() != b) return lib_error(c, ETLG_InvalidArgument, "ASYNC batches must be synced in issue order");
+    c->pending.erase(c->pending.begin());
+  }
+  FinishState st;
+  ht_start(c);
+  FB(wait_for_result(c, b));
+  ht_mark(c, 7);
+  st.forced = b->force_rerun;
+  b->force_rerun = false;
+  FB(second_attempts(c, b, st));
+  if (st.spare) settle_spare(c, b, st);
+  if (st.decoded_again) FB(reclear_lapped_block(c, b));
+  count_path(c, b, st);
+  DevResult r = *b->h_res;
+  if (b->used_fused) for (int k = 0; k < 3; k++) { r.payload[k] = 0; for (int sh = 0; sh < 32; sh++) r.payload[k] += r.pay_shard[sh][k]; }
+  for (int i = 0; i < 12; i++) c->last_dbg[i] = r.dbg_t[i];
+  c->res_pool.push_back(b->h_res);
+  b->h_res = nullptr;
+  int64_t frame = -1;
+  const int32_t code = first_error(b, r, &frame);
+  if (code && b->have_snapshot) rollback_control_state(c, b, frame);
+  carry_state_and_view(c, b, r, code, frame);
   b->pending = false; b->finished = true;
   side_release(b);   // its kernels are done: the set may take the next change of the side inputs
-  if (b->finish_what && v.n_events) FB_RC(finish_cells(c, b, b->finish_what, nullptr));   // ETLG_F_FINISH_CELLS: typed arrays, exact floats (host_handoff.inc)
-  if (!b->out_dev) FB_RC(download_batch(c, b));
+  if (b->finish_what && b->v.n_events) FB(finish_cells(c, b, b->finish_what, nullptr));   // ETLG_F_FINISH_CELLS: typed arrays, exact floats (host_handoff.inc)
+  if (!b->out_dev) FB(download_batch(c, b));
   fill_view_common(b);
   clear_error(c);
   b->rc = code ? set_error(c, code, frame) : (int32_t)ETLG_OK;
   b->err = c->err; b->err_detail = c->err_detail;
-  if (b->copy.active) {
-    // TableCopyPayloadMetadata: the bytes of the rows that were decoded
-    const CopyJob& j = b->copy;
-    const uint64_t done = b->v.n_frames;
-    uint32_t o[2] = {0, 0};
-    if (b->rc == ETLG_OK && j.direct && done == j.nrows && b->used_cells && b->copy_span) { o[1] = b->copy_span; }   // the rows -> arena kernel measured them (no device round trips here)
-    else {
-      (void)hipMemcpy(&o[0], j.d_row_offs, 4, hipMemcpyDeviceToHost);
-      (void)hipMemcpy(&o[1], j.d_row_offs + done, 4, hipMemcpyDeviceToHost);
-    }
-    b->v.payload_bytes[0] = o[1] - o[0]; b->v.payload_bytes[1] = 0; b->v.payload_bytes[2] = 0;
-  }
+  if (b->copy.active) copy_payload_bytes(b);
   return b->rc;
-#undef FB_HIP
-#undef FB_RC
 }
+#undef FB
 
 }  // namespace
 

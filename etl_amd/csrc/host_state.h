@@ -22,11 +22,11 @@
 #include <chrono>
 #include <map>
 #include <mutex>
-#include <set>
 #include <memory>
 #include <set>
 #include <string>
 #include <string_view>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -99,6 +99,8 @@ constexpr int kRows = 14;       // ... of the row-synchronous kernel (rows.hip)
 constexpr int kWriteChk = 15;   // ... of k_write with ETLG_F_CHECK_CELLS (kernels.hip, k_write_chk)
 constexpr int kChkCells = 16;   // ... of the cell check behind a single-pass kernel (check.hip, k_chk_cells)
 constexpr int kProfSlots = 17;
+
+struct StagedInput;   // (host.cpp)
 
 namespace {
 
@@ -187,6 +189,12 @@ int32_t type_class(uint32_t oid) {
   return ETLG_TC_STRING;
 }
 
+// value classes by what a cell needs: the integers (all the fixed-width plan takes); ... and uuid (one lane per frame does not crawl on them);
+// ... and the temporal classes (everything that stays out of the heap)
+bool int_class(int32_t k) { return k == ETLG_TC_BOOL || k == ETLG_TC_I16 || k == ETLG_TC_I32 || k == ETLG_TC_I64 || k == ETLG_TC_U32; }
+bool fixed_class(int32_t k) { return int_class(k) || k == ETLG_TC_UUID; }
+bool heapless_class(int32_t k) { return fixed_class(k) || k == ETLG_TC_DATE || k == ETLG_TC_TIME || k == ETLG_TC_TIMESTAMP || k == ETLG_TC_TIMETZ || k == ETLG_TC_TIMESTAMPTZ; }
+
 uint32_t slot_bytes(int32_t cls) {
   switch (cls) {
     case ETLG_TC_BOOL: case ETLG_TC_I16: case ETLG_TC_I32: case ETLG_TC_U32: return 4;
@@ -217,6 +225,8 @@ struct ControlState {  // everything a failed batch must be able to roll back
   size_t n_slots = 0;
 };
 
+inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }   // the parts of a shared block start at multiples of 64 bytes
+
 struct DevBuf {
   void* p = nullptr; size_t cap = 0;
   hipError_t ensure(size_t n) {
@@ -240,6 +250,28 @@ struct OutSet {  // device output arrays of one batch
 struct ProfRec { int which; hipEvent_t a, b; };
 struct ScanJob { const uint8_t* d_in = nullptr; size_t len = 0; hipStream_t s = nullptr; DevBuf* offs = nullptr; size_t cap = 0; uint8_t* cur = nullptr; uint32_t* res = nullptr; };
 struct HostErr { int32_t code = 0; uint32_t rank = 0; };
+
+// Everything one control pre-pass writes: the per-frame scratch of the multi-pass kernels, the control list, the gathered bytes of the
+// Relation / DDL frames (k_ctrl_list gathers them) and the pinned heads of both. The context holds two (etlg_ctx::sets).
+struct CtlSet {
+  DevBuf d_tag, d_emit, d_ffixed, d_fheap, d_blk32, d_blk64, d_ctrl, d_ctrl_stage;
+  CtrlFrame* h_ctl_list = nullptr;    // pinned: the first kCtlListCap entries of the control list ...
+  uint8_t* h_ctl_stage = nullptr;     // ... and the first kCtlStageCap gathered bytes, copied behind the pre-pass without asking for their sizes
+  void release() {   // (etlg_ctx_destroy)
+    for (DevBuf* b : {&d_tag, &d_emit, &d_ffixed, &d_fheap, &d_blk32, &d_blk64, &d_ctrl, &d_ctrl_stage}) b->release();
+    for (void* h : {(void*)h_ctl_list, (void*)h_ctl_stage}) if (h) (void)hipHostFree(h);
+  }
+};
+
+// etlg_ctx::path_n: batches finished per path (etlg_ctx_debug_paths / _paths8)
+enum PathIdx {
+  kPathFused = 0, kPathCells = 1, kPathMulti = 2,   // produced by k_fused / by k_cells / by the multi-pass kernels directly
+  kPathRedoneMulti = 3,                             // a single-pass result discarded and redone by the multi-pass kernels
+  kPathPlan = 4, kPathPlanRedone = 5,               // produced by k_plan / a plan result discarded and redone by the generic single-pass kernel
+  kPathControl = 6,      // batches that took the control path (a Relation / DDL frame, or a caller without ETLG_F_NO_CONTROL on the multi-pass path)
+  kPathChainRerun = 7,   // ASYNC batches re-run because their predecessor failed
+  kPathCount = 8
+};
 struct EpochRec { uint32_t table_id; DevEpoch ep; };
 
 // A table-copy batch in flight (etlg_copy_decode): the rows that k_copy_frames turns into Insert frames.
@@ -254,8 +286,10 @@ struct CopyJob {
   uint64_t syn_len = 0;     // bytes of the Insert frames the rows rewrite to (sizes d_out and the arenas)
   bool async = false;       // etlg_copy_decode with ETLG_F_ASYNC: enqueued only, finished by etlg_batch_sync (rows -> arena kernel only)
   // ASYNC with host input: the rows and their offsets were uploaded into a device block of the batch's own, on the copy stream; the
-  // batch adopts both in etlg_decode (whatever is still set afterwards is given back by etlg_copy_decode)
-  void* stage_blk = nullptr; size_t stage_cap = 0; hipEvent_t h2d_done = nullptr;
+  // batch adopts both in etlg_decode (what it does not adopt goes back to the pools when etlg_copy_decode returns). The pointer names an
+  // object on etlg_copy_decode's stack: it is set in etlg_ctx::copy only, for the length of that call, and etlg_decode clears it when the
+  // batch adopts the block — BEFORE decode_tail copies the job into etlg_batch::copy, which therefore never holds it (check_invariants)
+  StagedInput* staged = nullptr;
 };
 
 // One uploaded copy of the side inputs (table states + cache timeline, schema slots + columns, the fixed-width plan's tables):
@@ -315,10 +349,6 @@ struct etlg_ctx {
   uint64_t scan_last_nf = 0, scan_last_len = 0;   // frames and bytes of the last batch whose boundaries were scanned on the device: the next one's grids are sized by its bytes per frame (+ 25 %)
   bool scan_chain_mode = true;   // ETLG_SCAN_CHAIN=0: a batch without a sidecar always waits for its frame count on the host before its decode is enqueued (round 5)
   uint64_t scan_chained_n = 0, scan_chain_redone = 0;
-  uint64_t chain_reissued = 0;   // ASYNC batches enqueued again behind a batch that was decoded again (finish_batch, reissue_successors)
-  bool chain_reissue = false;    // ETLG_CHAIN_REISSUE=1: the successors of a batch that was decoded again are enqueued again, chained to its new result
-                                 // (reissue_successors). Built and measured in round 6 — it LOST on the delete-in-every-10th-batch leg (548 against 905 GB/s:
-                                 // every give-up re-runs the whole window on one stream) — so the default stays each successor decoded again at its own sync
   bool chain_spare = true;       // ETLG_CHAIN_SPARE=0: the batches behind a plan batch that was decoded again are always decoded again (the rule before round 6's last session)
   uint64_t chain_spared = 0;     // second attempts of a plan batch that left the carried state its first attempt had published: the batches behind it stood (finish_batch)
   uint64_t chain_healed = 0;     // ASYNC chains finished early because their last batch was marked for a second attempt (etlg_decode)
@@ -333,17 +363,15 @@ struct etlg_ctx {
   uint32_t* h_scan = nullptr;  // pinned: its 4-word result
   size_t scan_half = 0, scan_tiles_cap = 0;  // scan scratch: bytes in front of the hints, tiles it is laid out for
   unsigned long long scan_reruns = 0, scan_seq = 0;  // debugging aid: batches that needed hints / the one-lane walk
-  DevBuf d_ctrl_stage;   // bytes of a batch's Relation / DDL frames (k_ctrl_list gathers them)
   // ETLG_HOST_TIMES=1: wall-clock microseconds the host spends between marks of the control path, printed when the context goes
   bool host_times = false, host_times_slow = false; double host_us[12] = {0}; uint64_t host_n[12] = {0};
   size_t ctrl_stage_cap_test = 0;
   std::chrono::steady_clock::time_point host_mark;
-  DevBuf d_in, d_offs, d_tag, d_emit, d_ffixed, d_fheap, d_blk32, d_blk64, d_ctrl, d_res, d_desc;
+  DevBuf d_in, d_offs, d_res, d_desc;
   std::vector<SideSet*> side_sets;   // every set ever built (a handful)
   SideSet* side_cur = nullptr;       // the latest upload: what last_tables / last_epochs / last_live describe
   FusedParams fq{};
   PlanParams pq{};
-  uint32_t n_dev_slots = 0, n_dev_cols = 0;
   // the fixed-width plan (plan.hip): eligible tables of the current side inputs, and the back-off after a batch that did not conform
   uint32_t n_plan_tabs = 0, plan_max_row = 16;
   bool plan_covers_all = false;
@@ -375,13 +403,10 @@ struct etlg_ctx {
   DevBuf d_ctl_res;                   // ring of kCtlRing pre-pass result blocks (the pre-passes chain their transaction state through them)
   static constexpr uint32_t kCtlRing = 4, kCtlListCap = 4096, kCtlStageCap = 512u << 10;
   uint32_t ctl_seq = 0;
-  // A second set of everything a control pre-pass writes (per-frame scratch, the control list, the gathered bytes and their pinned
-  // heads): the pre-pass of batch k + 1 goes out BEFORE the host control plane of batch k has read batch k's (etlg_decode), so two
-  // are in flight and take turns (etlg_batch::ctl_set).
-  struct CtlAlt { DevBuf d_tag, d_emit, d_ffixed, d_fheap, d_blk32, d_blk64, d_ctrl, d_ctrl_stage; CtrlFrame* h_ctl_list = nullptr; uint8_t* h_ctl_stage = nullptr; } ctl_alt;
+  // Two sets of everything a control pre-pass writes (CtlSet): the pre-pass of batch k + 1 goes out BEFORE the host control plane of batch
+  // k has read batch k's (etlg_decode), so two are in flight and take turns (etlg_batch::ctl_set). Everything else takes set 0.
+  CtlSet sets[2];
   bool ctl_hold_mode = true;          // ETLG_CTL_HOLD=0: the held batch is flushed before the next pre-pass goes out (round 3's order)
-  CtrlFrame* h_ctl_list = nullptr;    // pinned: the first kCtlListCap entries of the control list ...
-  uint8_t* h_ctl_stage = nullptr;     // ... and the first kCtlStageCap gathered bytes, copied behind the pre-pass without asking for their sizes
   hipEvent_t mp_tail = nullptr; bool mp_tail_set = false;   // behind the last multi-pass launch (it shares the per-frame scratch with the pre-pass)
   int ctl_async_mode = 1;             // ETLG_CTL_ASYNC=0: control batches are decoded synchronously, as in round 2
   uint64_t cs_gen = 0;                // bumped by every rollback of the control state
@@ -409,8 +434,11 @@ struct etlg_ctx {
   std::vector<DevEpoch> last_epochs;
   bool side_valid = false;
   bool force_multipass = false;  // ETLG_FORCE_MULTIPASS=1 (tests exercise both paths)
+  // measurement / experiment knobs of the kernel ladder, ETLG_ROWS_TRACE / _ROWS_CF / _ROWS_WIN_ROOM / _ROWS_LDS / _LDS_MARGIN_PCT / _COPY_LDS
+  // (read_knobs in host.cpp says what each does; -1: not set)
+  bool rows_trace = false; uint32_t rows_cf = 0; int rows_win_room = 64, rows_lds = -1, lds_margin_pct = -1, copy_lds = -1;
   unsigned long long last_dbg[12] = {0};
-  unsigned long long path_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long path_n[kPathCount] = {0};   // (PathIdx)
   unsigned long long copy_n[2] = {0, 0};   // table-copy batches produced by k_copy_cells / decoded through the row -> frame rewrite
   bool copy_direct = true;                 // ETLG_COPY_DIRECT=0: always the row -> frame rewrite
   int fused_kernel = -1;         // ETLG_FUSED_KERNEL: 0 k_fused/256, 1 k_fused/64, 2 k_cells, 3 k_plan whenever eligible, 4 k_rows whenever eligible (default: plan, else by frame size)
@@ -457,7 +485,7 @@ struct etlg_batch {
   uint64_t nf_est = 0;              // ... the frame count the stream has shown (params.nframes is the bound the grids are sized by; LDS windows are sized by this)
   int plan_decided = -1;      // decode_tail: -1 not decided yet, 0 / 1 = the first attempt is the generic kernel / the fixed-width plan
   int sidx = 0;               // decode stream the batch's first attempt was enqueued on (0: etlg_ctx::stream, 1: stream2)
-  int ctl_set = 0;            // which set of control pre-pass buffers its pre-pass wrote (etlg_ctx::ctl_alt is set 1)
+  int ctl_set = 0;            // which set of control pre-pass buffers its pre-pass wrote (etlg_ctx::sets)
   bool force_rerun = false;   // a batch of the chain before this one had to be decoded again: whatever this one produced started from the wrong state
   hipEvent_t kdone = nullptr; // ASYNC: recorded behind the batch's kernels on its decode stream (the result copy waits for it)
   hipEvent_t done = nullptr;  // recorded behind the copy of the result block: syncing a batch waits for IT, not for the whole stream

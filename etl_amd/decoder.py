@@ -477,7 +477,8 @@ class Decoder:
         return int(out[3]), int(out[4])
 
     def debug_chain_reissued(self):
-        """ASYNC batches enqueued again — chained to the new result — behind a batch that was decoded again (debugging aid)."""
+        """Always 0: it counted the ASYNC batches of the re-issue experiment (tools/experiments/r06_chain_reissue.diff), which left the tree;
+        the word of etlg_ctx_debug_ring stays so that callers keep their layout (debugging aid)."""
         out = (C.c_ulonglong * 8)()
         self.L.etlg_ctx_debug_ring(self.h, out)
         return int(out[2])
