@@ -140,6 +140,46 @@ impl GpuDecoder {
     }
 }
 
+/// DuckLake's Arrow copy staging of a table-copy batch (`etlg_batch_ducklake_copy`): what `prepare_copy_rows` builds with
+/// `copy_rows_to_arrow_record_batch` (crates/etl-destinations/src/ducklake/encoding.rs:32-49, :303-340), as column buffers in host
+/// memory. `view.cols[i].offsets` of an `ETLG_AK_UTF8` / `ETLG_AK_BINARY` column points at `n_rows + 1` i32 entries.
+pub struct DuckLakeCopyColumns {
+    cols: *mut etlg_columns,
+    pub view: etlg_columns_view,
+    /// `ETLG_DLC_OK`, or why nothing was built: `ETLG_DLC_NOT_ARROW` (the sink takes `prepare_rows`) / `ETLG_DLC_OFFSETS_OVERFLOW`
+    /// (split the batch), with the column it was decided by.
+    pub info: etlg_ducklake_copy_info,
+}
+
+impl Drop for DuckLakeCopyColumns {
+    fn drop(&mut self) {
+        if !self.cols.is_null() {
+            unsafe { etlg_columns_free(self.cols) };
+            self.cols = std::ptr::null_mut();
+        }
+    }
+}
+
+impl GpuDecoder {
+    /// The call after `copy_decode_async`, while the batch is still on the device: the sink's Arrow payload for a table whose columns
+    /// `arrow_column_kinds` accepts (the call waits for the batch itself). The caller must not ask for a table with an array column
+    /// outside the value codec's table (`is_array_type`, crates/etl-postgres/src/type_utils.rs:14-18): only it can tell those.
+    pub fn copy_ducklake_arrow(&mut self, schema_slot: u32, f: &CopyInFlight) -> EtlResult<DuckLakeCopyColumns> {
+        let mut cols = std::ptr::null_mut();
+        let rc = unsafe { etlg_batch_ducklake_copy(self.ctx, f.batch, schema_slot as i32, 0, &mut cols) };
+        if rc != ETLG_OK || cols.is_null() {
+            return Err(self.last_error());
+        }
+        let mut view = std::mem::MaybeUninit::<etlg_columns_view>::uninit();
+        let mut info = std::mem::MaybeUninit::<etlg_ducklake_copy_info>::uninit();
+        unsafe {
+            etlg_columns_view_get(cols, view.as_mut_ptr());
+            etlg_columns_ducklake_get(cols, info.as_mut_ptr());
+            Ok(DuckLakeCopyColumns { cols, view: view.assume_init(), info: info.assume_init() })
+        }
+    }
+}
+
 /// A table-copy batch in flight. Dropping it without `copy_finish` frees the batch FIRST (the library waits for its kernels and its
 /// upload: `etlg_batch_free` finishes a pending batch) and only then the pinned staging — the order `InFlight` keeps for WAL batches
 /// (lib.rs; both exercised by tests/native/shim_twin.cpp).

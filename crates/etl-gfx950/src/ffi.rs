@@ -255,6 +255,13 @@ pub struct etlg_changelog_info {
 }
 
 #[repr(C)]
+pub struct etlg_ducklake_copy_info {
+    pub status: u32,
+    pub column: u32,
+    pub _pad: [u32; 2],
+}
+
+#[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
     pub arrays_typed: u64,
@@ -280,6 +287,13 @@ pub const ETLG_ROWS_FORMAT_JSON: u32 = 8;
 pub const ETLG_ICE_PARTIAL_UPDATE: u32 = 1;
 pub const ETLG_ICE_KEY_ONLY_DELETE: u32 = 2;
 pub const ETLG_ICE_DELETE_WITHOUT_OLD_ROW: u32 = 3;
+pub const ETLG_DLC_OK: u32 = 0;
+pub const ETLG_DLC_NOT_ARROW: u32 = 1;
+pub const ETLG_DLC_OFFSETS_OVERFLOW: u32 = 2;
+pub const ETLG_AK_INT16: u32 = 14;
+pub const ETLG_AK_UINT64: u32 = 15;
+pub const ETLG_AK_UTF8: u32 = 16;
+pub const ETLG_AK_BINARY: u32 = 17;
 pub const ETLG_CH_MERGE_TREE: i32 = 0;
 pub const ETLG_CH_REPLACING_MERGE_TREE: i32 = 1;
 pub const ETLG_RB_OK: u32 = 0;
@@ -407,6 +421,8 @@ extern "C" {
     pub fn etlg_columns_free(cols: *mut etlg_columns);
     pub fn etlg_batch_iceberg(ctx: *mut etlg_ctx, batch: *mut etlg_batch, schema_slot: i32, opts: u32, flags: u32, out: *mut *mut etlg_columns) -> i32;
     pub fn etlg_columns_changelog_get(cols: *const etlg_columns, out: *mut etlg_changelog_info) -> i32;
+    pub fn etlg_batch_ducklake_copy(ctx: *mut etlg_ctx, batch: *mut etlg_batch, schema_slot: i32, flags: u32, out: *mut *mut etlg_columns) -> i32;
+    pub fn etlg_columns_ducklake_get(cols: *const etlg_columns, out: *mut etlg_ducklake_copy_info) -> i32;
     pub fn etlg_batch_rowbinary(
         ctx: *mut etlg_ctx,
         batch: *mut etlg_batch,

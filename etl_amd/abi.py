@@ -118,6 +118,10 @@ class ChangelogInfo(C.Structure):   # etlg_changelog_info
     _fields_ = [("n_host_rows", C.c_uint64), ("host_event", C.c_uint64), ("host_reason", C.c_uint32), ("n_data_cols", C.c_uint32)]
 
 
+class DuckLakeCopyInfo(C.Structure):   # etlg_ducklake_copy_info
+    _fields_ = [("status", C.c_uint32), ("column", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
 class RowBinaryView(C.Structure):   # etlg_rowbinary_view
     _fields_ = [("n_rows", C.c_uint64), ("n_bytes", C.c_uint64), ("n_host_rows", C.c_uint64), ("status", C.c_uint32),
                 ("on_device", C.c_uint32), ("host_event", C.c_uint64), ("host_column", C.c_uint32), ("_pad", C.c_uint32),
@@ -139,7 +143,9 @@ RB_OK, RB_NEEDS_HOST = 0, 3
 DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)
+AK_INT16, AK_UINT64, AK_UTF8, AK_BINARY = 14, 15, 16, 17   # etlg_batch_ducklake_copy only; UTF8 / BINARY: int32 offsets
 AK_NONE = 255
+DLC_OK, DLC_NOT_ARROW, DLC_OFFSETS_OVERFLOW = 0, 1, 2   # etlg_ducklake_copy_info.status
 ROWS_INSERT, ROWS_UPDATE, ROWS_PARSE_ARRAYS, ROWS_FORMAT_JSON = 1, 2, 4, 8
 ICE_PARTIAL_UPDATE, ICE_KEY_ONLY_DELETE, ICE_DELETE_WITHOUT_OLD_ROW = 1, 2, 3
 NO_EVENT = (1 << 64) - 1   # etlg_changelog_info.host_event: no refused event

@@ -254,9 +254,13 @@ __global__ __launch_bounds__(256) void k_col_cdc(CdcJob j) {
 }
 
 enum : uint32_t { AK_BOOL = 0, AK_I32 = 1, AK_I64 = 2, AK_F32 = 3, AK_F64 = 4, AK_DATE32 = 5, AK_TIME64 = 6, AK_TS = 7, AK_TSTZ = 8, AK_FIXED16 = 9,
-                  AK_UTF8 = 10, AK_BINARY = 11, AK_TEXT_FORM = 12, AK_NUMERIC_STR = 14, AK_TIMETZ_STR = 15, AK_JSON_STR = 16, AK_NONE = 255 };   // 14 / 15 / 16: internal (host.cpp ColPlan.fmt), LargeUtf8 to the caller
+                  AK_UTF8 = 10, AK_BINARY = 11, AK_TEXT_FORM = 12, AK_I16 = 14 /* ETLG_AK_INT16 (etlg_batch_ducklake_copy) */,
+                  AK_NUMERIC_STR = kAkNumericStr, AK_TIMETZ_STR = kAkTimetzStr, AK_JSON_STR = kAkJsonStr, AK_NONE = 255 };   // 64 / 65 / 66: internal (dev_types.h kAkNumericStr ..; ColPlan.fmt), never the caller's: a string column to it
 
 // One thread per row: state, value, validity / deferred words through wave ballots.
+// (DLC: etlg_batch_ducklake_copy's launch, which alone has the 2-byte arm — an instantiation of its own, so that the kernels behind
+// etlg_batch_columns / etlg_batch_iceberg compile from the text they had)
+template <bool DLC = false>
 DEV void col_fixed_body(const ColJob& j, uint32_t bx) {
   const uint64_t r = (uint64_t)bx * 256 + threadIdx.x;
   const bool live = r < j.n_rows;
@@ -278,6 +282,9 @@ DEV void col_fixed_body(const ColJob& j, uint32_t bx) {
   }
   if (!live) return;
   uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+  if constexpr (DLC) {   // Int16 (ducklake/encoding.rs:236-257): the low half of the 4-byte slot (nothing behind it is read); a null slot holds 0
+    if (j.kind == AK_I16) { ((uint16_t*)j.values)[r] = valid ? (uint16_t)ld32a(slot) : (uint16_t)0; return; }
+  }
   if (valid) { w0 = ld32a(slot); if (j.kind != AK_I32 && j.kind != AK_F32 && j.kind != AK_DATE32) w1 = ld32a(slot + 4); }
   switch (j.kind) {
     case AK_I32: case AK_F32: ((uint32_t*)j.values)[r] = w0; break;
@@ -309,6 +316,7 @@ __global__ __launch_bounds__(256) void k_col_fixed(ColJob j) { col_fixed_body(j,
 constexpr int kPack = 20;
 struct ColPack { ColJob j[kPack]; unsigned long long* blk[kPack]; int64_t* offs[kPack]; unsigned long long* tot[kPack]; };   // tot: where the column's byte total goes (one read-back for all)
 __global__ __launch_bounds__(256) void k_col_fixed_pack(ColPack p) { col_fixed_body(p.j[blockIdx.y], blockIdx.x); }
+__global__ __launch_bounds__(256) void k_col_fixed_pack_dlc(ColPack p) { col_fixed_body<true>(p.j[blockIdx.y], blockIdx.x); }
 
 
 // var-len columns, pass 1: validity / deferred words + the byte length of every row's entry
@@ -391,24 +399,29 @@ __global__ __launch_bounds__(256) void k_col_len_scan_pack(ColPack p, uint32_t n
   __shared__ uint64_t lds[4];
   col_len_scan_body(p.blk[blockIdx.x], n, lds);
 }
-DEV void col_offsets_body(const uint32_t* lens, uint64_t n, const unsigned long long* blk, int64_t* offsets, uint32_t bx, uint64_t* lds, unsigned long long* tot = nullptr) {
+// (O: int64_t, or int32_t for the Utf8 / Binary columns of etlg_batch_ducklake_copy — the host refuses a column whose total passes
+// 2^31 - 1 before anyone reads its offsets, so the narrowing is exact wherever it is looked at)
+template <class O = int64_t>
+DEV void col_offsets_body(const uint32_t* lens, uint64_t n, const unsigned long long* blk, O* offsets, uint32_t bx, uint64_t* lds, unsigned long long* tot = nullptr) {
   const uint64_t i = (uint64_t)bx * 256 + threadIdx.x;
   const uint64_t ex = block_scan_excl64(i < n ? lens[i] : 0u, lds, nullptr);
-  if (i < n) offsets[i] = (int64_t)(blk[bx] + ex);
-  if (i == n - 1) { offsets[n] = (int64_t)(blk[bx] + ex + lens[i]); if (tot) *tot = blk[bx] + ex + lens[i]; }
+  if (i < n) offsets[i] = (O)(blk[bx] + ex);
+  if (i == n - 1) { offsets[n] = (O)(blk[bx] + ex + lens[i]); if (tot) *tot = blk[bx] + ex + lens[i]; }
 }
 __global__ __launch_bounds__(256) void k_col_offsets(const uint32_t* lens, uint64_t n, const unsigned long long* blk, int64_t* offsets, unsigned long long* tot = nullptr) {
   __shared__ uint64_t lds[4];
   col_offsets_body(lens, n, blk, offsets, blockIdx.x, lds, tot);
 }
+template <class O>
 __global__ __launch_bounds__(256) void k_col_offsets_pack(ColPack p) {
   __shared__ uint64_t lds[4];
   const ColJob& j = p.j[blockIdx.y];
-  col_offsets_body(j.lens, j.n_rows, p.blk[blockIdx.y], p.offs[blockIdx.y], blockIdx.x, lds, p.tot[blockIdx.y]);
+  col_offsets_body(j.lens, j.n_rows, p.blk[blockIdx.y], (O*)p.offs[blockIdx.y], blockIdx.x, lds, p.tot[blockIdx.y]);
 }
 
 // var-len columns, pass 2: one wave per 64 rows; the wave moves one row at a time, 4 bytes per lane per step where both ends
 // allow it (heap entries start 4-byte aligned; the destination is wherever the previous row ended)
+template <class O = int64_t>
 DEV void col_copy_body(const ColJob& j, uint32_t bx) {
   // A wave takes 64 consecutive rows (their bytes are consecutive in `values`): eight lanes per row, eight rows at a time, eight bytes
   // per lane and step. (One row at a time with a byte per lane was a load and a store instruction per row of up to 64 bytes: 44 us per
@@ -418,7 +431,7 @@ DEV void col_copy_body(const ColJob& j, uint32_t bx) {
   if (r0 >= j.n_rows) return;
   const uint64_t r = r0 + lane;
   uint32_t len = 0, src = 0; int64_t dst = 0;
-  if (r < j.n_rows) { len = j.lens[r]; dst = j.offsets[r]; if (len) src = ld32a(j.fixed + j.row_base[r] + j.off_full); }
+  if (r < j.n_rows) { len = j.lens[r]; dst = ((const O*)j.offsets)[r]; if (len) src = ld32a(j.fixed + j.row_base[r] + j.off_full); }
   const uint32_t sub = lane & 7u, grp = lane >> 3;
   for (uint32_t it = 0; it < 8; it++) {
     const int k = (int)(it * 8u + grp);
@@ -436,7 +449,7 @@ DEV void col_copy_body(const ColJob& j, uint32_t bx) {
 __global__ __launch_bounds__(256) void k_col_copy(ColJob j) { col_copy_body(j, blockIdx.x); }
 
 // formatted string columns (numeric, timetz), pass 2: one thread per row writes its Display string at its offset
-template <bool JS>
+template <bool JS, class O = int64_t>
 DEV void col_fmt_body(const ColJob& j, uint32_t bx) {
   const uint64_t r = (uint64_t)bx * 256 + threadIdx.x;
   if (r >= j.n_rows || !j.lens[r]) return;
@@ -445,7 +458,7 @@ DEV void col_fmt_body(const ColJob& j, uint32_t bx) {
   // writer did worse than that: its instantiation faulted on the MI355X — a store address with its low or high half replaced — while
   // the same function under a bounds-checked byte writer, under RbWrite in k_rb_rows and on the emulator was right
   // (profiles/r05x_json_arrow_fault.txt; not pursued further).
-  RbWrite w(j.values + j.offsets[r]);
+  RbWrite w(j.values + ((const O*)j.offsets)[r]);
   if (j.kind == AK_NUMERIC_STR) numeric_str(w, j.heap + ld32a(slot));
   else if (j.kind == AK_TIMETZ_STR) timetz_str(w, slot);
   else if (JS) {   // json: the Display string, or (the rows pass 1 marked DEFERRED) the source text as it is
@@ -458,10 +471,10 @@ DEV void col_fmt_body(const ColJob& j, uint32_t bx) {
 template <bool JS>
 __global__ __launch_bounds__(256) void k_col_fmt(ColJob j) { col_fmt_body<JS>(j, blockIdx.x); }
 // pass 2 of several var-len columns in one launch: a column is copied or formatted by what it is (uniform per blockIdx.y)
-template <bool JS>
+template <bool JS, class O = int64_t>
 __global__ __launch_bounds__(256) void k_col_var2_pack(ColPack p) {
   const ColJob& j = p.j[blockIdx.y];
-  if (j.kind == AK_NUMERIC_STR || j.kind == AK_TIMETZ_STR || j.kind == AK_JSON_STR) col_fmt_body<JS>(j, blockIdx.x); else col_copy_body(j, blockIdx.x);
+  if (j.kind == AK_NUMERIC_STR || j.kind == AK_TIMETZ_STR || j.kind == AK_JSON_STR) col_fmt_body<JS, O>(j, blockIdx.x); else col_copy_body<O>(j, blockIdx.x);
 }
 
 
@@ -645,7 +658,8 @@ void etlg_k_col_fixed_pack(const void* jobs, uint32_t n, hipStream_t st) {
   const ColJob* j = (const ColJob*)jobs;
   if (!n || !j[0].n_rows) return;
   ColPack p; fill_pack(p, j, n, nullptr, nullptr);
-  hipLaunchKernelGGL(k_col_fixed_pack, dim3((uint32_t)((j[0].n_rows + 255) / 256), n), dim3(256), 0, st, p);
+  const dim3 grid((uint32_t)((j[0].n_rows + 255) / 256), n);
+  if (j[0].off32) hipLaunchKernelGGL(k_col_fixed_pack_dlc, grid, dim3(256), 0, st, p); else hipLaunchKernelGGL(k_col_fixed_pack, grid, dim3(256), 0, st, p);
 }
 void etlg_k_col_var_pack(const void* jobs, uint32_t n, unsigned long long* const* blk, int64_t* const* offs, unsigned long long* const* tot, int step, hipStream_t st) {
   const ColJob* j = (const ColJob*)jobs;
@@ -654,10 +668,13 @@ void etlg_k_col_var_pack(const void* jobs, uint32_t n, unsigned long long* const
   ColPack p; fill_pack(p, j, n, blk, offs, tot);
   bool js = false;
   for (uint32_t i = 0; i < n; i++) js |= j[i].kind == AK_JSON_STR;
+  const bool o32 = j[0].off32 != 0;   // (one hand-off, one offset width: etlg_batch_ducklake_copy, whose tables have no json column)
   if (step == 0) {
     if (js) hipLaunchKernelGGL(k_col_lens_pack<true>, dim3(nb, n), dim3(256), 0, st, p); else hipLaunchKernelGGL(k_col_lens_pack<false>, dim3(nb, n), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_col_len_scan_pack, dim3(n), dim3(256), 0, st, p, nb);
-    hipLaunchKernelGGL(k_col_offsets_pack, dim3(nb, n), dim3(256), 0, st, p);
+    if (o32) hipLaunchKernelGGL(k_col_offsets_pack<int32_t>, dim3(nb, n), dim3(256), 0, st, p); else hipLaunchKernelGGL(k_col_offsets_pack<int64_t>, dim3(nb, n), dim3(256), 0, st, p);
+  } else if (o32) {
+    hipLaunchKernelGGL((k_col_var2_pack<false, int32_t>), dim3(nb, n), dim3(256), 0, st, p);
   } else {
     if (js) hipLaunchKernelGGL(k_col_var2_pack<true>, dim3(nb, n), dim3(256), 0, st, p); else hipLaunchKernelGGL(k_col_var2_pack<false>, dim3(nb, n), dim3(256), 0, st, p);
   }

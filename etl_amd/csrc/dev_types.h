@@ -262,6 +262,8 @@ struct ColSel {            // which events are rows of the hand-off
 };
 constexpr unsigned long long kPbDelete = 1ull << 63, kPbKey = 1ull << 62, kPbSecond = 1ull << 61, kPbBase = (1ull << 61) - 1;
 
+// the kernels' private column kinds, behind the public ETLG_AK_* numbers (include/etlg.h): formatted string columns (columns.hip AK_*_STR)
+constexpr uint32_t kAkNumericStr = 64, kAkTimetzStr = 65, kAkJsonStr = 66;
 struct ColJob {
   const uint8_t* fixed; const uint8_t* heap; const uint64_t* row_base;
   uint64_t n_rows;
@@ -270,7 +272,8 @@ struct ColJob {
   unsigned long long* null_count; unsigned long long* deferred_count;
   uint32_t* lens; const int64_t* offsets;   // var-len
   // list columns (array literals parsed on the device): element class, child validity words, child null counter, first error
-  uint32_t elem_cls, _pad;
+  uint32_t elem_cls;
+  uint32_t off32;            // a job of etlg_batch_ducklake_copy: a var-len column's `offsets` is int32 entries (Utf8 / Binary), not int64, and the fixed-width launch has the Int16 arm
   uint32_t* child_validity; unsigned long long* child_nulls; unsigned long long* err;
   uint32_t* child_lens; const int64_t* child_offsets;   // lists of strings: byte length / start of every element
 };
@@ -330,10 +333,14 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   // whether the batch is a table copy (every row's sequence number is the zero token)
   const uint8_t* nd_keys; const uint32_t* nd_key_off;
   uint32_t nd_zero_token;
+  // formats 0 / 1 on a table-copy batch (etlg_copy_decode): the tail of a copied row, not of a CDC row — RowBinary: the CDC columns of
+  // (Insert, commit_lsn 0, tx_ordinal 0) (clickhouse/core.rs:739-773); protobuf: _CHANGE_TYPE alone, no _CHANGE_SEQUENCE_NUMBER field
+  // (bigquery/core.rs:602-649). Uniform over the launch: the counting pass and the byte pass read the same word
+  uint32_t copy_tail;
   // format 3 (DuckLake, dl_row): nd_keys are the quoted identifiers; 0 tuples, 1 predicates over the identity columns, 2 predicates
   // over the primary-key columns (a table-copy batch), 3 partial Updates: a row whose base carries kPbSecond is a predicate over the
   // identity columns, any other row the SET clause `"c" = lit, ...` of the cells that are not MISSING
-  uint32_t dl_what;
+  uint32_t dl_what, _pad;
   // col_ends (dl_what 3, else null): [n_rows x n_cols] bytes of a record written once a column is done, from the counting pass
   uint32_t* col_ends;
 };

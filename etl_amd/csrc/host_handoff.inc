@@ -49,9 +49,25 @@ ColPlan col_plan(uint32_t cls) {
     case ETLG_TC_STRING: return {ETLG_AK_LARGE_UTF8, 0, true};
     case ETLG_TC_BYTEA: return {ETLG_AK_LARGE_BINARY, 0, true};
     // Display strings in every sink (cell_to_string, iceberg/encoding.rs:349-352; n.to_string() / t.to_string()): formatted on the device
-    case ETLG_TC_NUMERIC: return {ETLG_AK_LARGE_UTF8, 0, true, 0, 0, 0, 14u};
-    case ETLG_TC_TIMETZ: return {ETLG_AK_LARGE_UTF8, 0, true, 0, 0, 0, 15u};
+    case ETLG_TC_NUMERIC: return {ETLG_AK_LARGE_UTF8, 0, true, 0, 0, 0, etlg::kAkNumericStr};
+    case ETLG_TC_TIMETZ: return {ETLG_AK_LARGE_UTF8, 0, true, 0, 0, 0, etlg::kAkTimetzStr};
     default: return {ETLG_AK_TEXT_FORM, 0, true};
+  }
+}
+// DuckLake's Arrow copy staging: arrow_column_kind (ducklake/encoding.rs:236-257) by type class — Int16 for int2, UInt64 for oid, Utf8 /
+// Binary (32-bit offsets) for text / bytea, Utf8 of the Display string for numeric / timetz (push_cell :170-171); the rest as
+// etlg_batch_columns has it. `fmt`: the kernels' kind where the public one is not theirs. ETLG_AK_NONE: arrow_column_kinds gives None
+// for the table (uuid, json, arrays).
+ColPlan dlc_plan(uint32_t cls) {
+  switch (cls) {
+    case ETLG_TC_I16: return {ETLG_AK_INT16, 2, false};
+    case ETLG_TC_U32: return {ETLG_AK_UINT64, 8, false, 0, 0, 0, ETLG_AK_INT64};   // (the widening of cell_to_i64: k_col_fixed's I64 arm by class)
+    case ETLG_TC_STRING: return {ETLG_AK_UTF8, 0, true, 0, 0, 0, ETLG_AK_LARGE_UTF8};
+    case ETLG_TC_BYTEA: return {ETLG_AK_BINARY, 0, true, 0, 0, 0, ETLG_AK_LARGE_BINARY};
+    case ETLG_TC_NUMERIC: return {ETLG_AK_UTF8, 0, true, 0, 0, 0, etlg::kAkNumericStr};
+    case ETLG_TC_TIMETZ: return {ETLG_AK_UTF8, 0, true, 0, 0, 0, etlg::kAkTimetzStr};
+    case ETLG_TC_UUID: case ETLG_TC_JSON: case ETLG_TC_ARRAY: return {ETLG_AK_NONE, 0, false};
+    default: { const ColPlan p = col_plan(cls); return p.kind == ETLG_AK_TEXT_FORM ? ColPlan{ETLG_AK_NONE, 0, false} : p; }
   }
 }
 }  // namespace
@@ -62,10 +78,15 @@ ColPlan col_plan(uint32_t cls) {
 // launches and read back with the row count, and the two CDC columns are written behind the data columns by one more launch
 // (etlg_k_col_cdc), so both calls stop for the device equally often.
 static bool slot_known(const etlg_ctx* c, int32_t slot) { return slot >= 0 && (size_t)slot < c->slots.size(); }
-static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t sel_kinds, uint32_t row_kinds, uint32_t flags, bool changelog, etlg_columns** out) {
+// dlc: etlg_batch_ducklake_copy — a table-copy batch's rows under dlc_plan's kinds, Utf8 / Binary with int32 offsets; the same launches
+// and the same stops as etlg_batch_columns(INSERT) on the slot.
+enum class ColCaller { Columns, Iceberg, DuckLakeCopy };   // which entry point build_columns serves
+static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t sel_kinds, uint32_t row_kinds, uint32_t flags, ColCaller who, etlg_columns** out) {
   *out = nullptr;
-  if (const int32_t rc = batch_ready(c, b, changelog ? "etlg_batch_iceberg" NEEDS_DEVICE : "etlg_batch_columns" NEEDS_DEVICE)) return rc;
+  const bool changelog = who == ColCaller::Iceberg, dlc = who == ColCaller::DuckLakeCopy;
+  if (const int32_t rc = batch_ready(c, b, dlc ? "etlg_batch_ducklake_copy" NEEDS_DEVICE : changelog ? "etlg_batch_iceberg" NEEDS_DEVICE : "etlg_batch_columns" NEEDS_DEVICE)) return rc;
   if (!slot_known(c, slot) || !sel_kinds) return ETLG_InvalidArgument;
+  if (dlc && !b->copy.active) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_ducklake_copy takes a table-copy batch (etlg_copy_decode): the sink stages copy rows only as Arrow");
   const bool parse_arrays = (row_kinds & ETLG_ROWS_PARSE_ARRAYS) != 0;
   const bool format_json = (row_kinds & ETLG_ROWS_FORMAT_JSON) != 0;
   const SlotHost& sh = *c->slots[(size_t)slot];
@@ -80,6 +101,15 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   uint32_t* d_blk = (uint32_t*)c->d_colsel.p;
   cs->m.ctx = c; cs->m.ctx_gen = c->gen;
   cs->changelog = changelog; cs->ci.host_event = ~0ull; cs->ci.n_data_cols = sh.desc.n_cols;
+  cs->ducklake = dlc;
+  // nothing is built and nothing handed over: the view has no rows and no columns, `di` says why and for which column
+  auto dlc_refuse = [&](uint32_t status, uint32_t column) -> int32_t {
+    cs->di.status = status; cs->di.column = column;
+    cs->v.on_device = (flags & ETLG_F_OUTPUT_ON_DEVICE) ? 1u : 0u;
+    *out = cs.release();
+    return ETLG_OK;
+  };
+  if (dlc) for (uint32_t i = 0; i < sh.desc.n_cols; i++) if (dlc_plan(sh.cols[i].type_class).kind == ETLG_AK_NONE) return dlc_refuse(ETLG_DLC_NOT_ARROW, i);
   // pinned {0, 0, 0, ~0} records: the initial values of the columns' counters (and of the changelog's refusal words) go up as an
   // asynchronous copy (a pageable source made it a synchronisation)
   auto cnt_init = [&](size_t want) -> int32_t {
@@ -130,13 +160,13 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   size_t off = al64(n * 8);
   for (uint32_t i = 0; i < nc; i++) {
     Lay& l = lay[i];
-    l.pl = col_plan(sh.cols[i].type_class);
+    l.pl = dlc ? dlc_plan(sh.cols[i].type_class) : col_plan(sh.cols[i].type_class);
     if (parse_arrays && sh.cols[i].type_class == ETLG_TC_ARRAY) l.pl = list_plan((uint32_t)etlg_array_elem_class(sh.cols[i].type_oid));
-    if (format_json && sh.cols[i].type_class == ETLG_TC_JSON) l.pl = {ETLG_AK_LARGE_UTF8, 0, true, 0, 0, 0, 16u};   // `j.to_string()` written on the device (AK_JSON_STR)
+    if (format_json && sh.cols[i].type_class == ETLG_TC_JSON) l.pl = {ETLG_AK_LARGE_UTF8, 0, true, 0, 0, 0, etlg::kAkJsonStr};   // `j.to_string()` written on the device (AK_JSON_STR)
     l.validity = l.deferred = l.values = l.lens = l.offsets = 0;
     if (l.pl.kind == ETLG_AK_NONE) continue;
     l.validity = off; off += bm; l.deferred = off; off += bm;
-    if (l.pl.var) { l.offsets = off; off += al64((n + 1) * 8); l.lens = off; off += al64(n * 4); }
+    if (l.pl.var) { l.offsets = off; off += al64((n + 1) * (dlc ? 4 : 8)); l.lens = off; off += al64(n * 4); }
     else { l.values = off; off += l.pl.kind == ETLG_AK_BOOLEAN ? bm : al64(n * l.pl.vbytes); }
   }
   // changelog: the two CDC columns — per column validity, deferred, offsets, values (fixed-width strings: sized here, in block A)
@@ -185,7 +215,7 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
     j.col_index = i; j.off_full = sh.cols[i].off_full; j.cls = sh.cols[i].type_class; j.kind = l.pl.fmt ? l.pl.fmt : l.pl.kind;
     j.validity = (unsigned long long*)(A + l.validity); j.deferred = (unsigned long long*)(A + l.deferred);
     j.null_count = (unsigned long long*)(A + o_cnt + (size_t)i * 32); j.deferred_count = j.null_count + 1;
-    j.child_nulls = j.null_count + 2; j.err = j.null_count + 3; j.elem_cls = l.pl.elem;
+    j.child_nulls = j.null_count + 2; j.err = j.null_count + 3; j.elem_cls = l.pl.elem; j.off32 = dlc ? 1u : 0u;
     if (l.pl.var) {
       j.lens = (uint32_t*)(A + l.lens); j.offsets = (const int64_t*)(A + l.offsets);
       if (n) {
@@ -238,6 +268,13 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
       uint64_t ev = 0;
       HIPCHK(c, hipMemcpy(&ev, d_row_event + (first >> 8), 8, hipMemcpyDeviceToHost));
       return set_error(c, (int32_t)(first & 0xFF), (int64_t)ev);
+    }
+  }
+  if (dlc) {   // arrow-rs panics when a StringArray's / BinaryArray's bytes pass i32::MAX: the totals came back with the counters
+    const uint64_t cap = c->dlc_offset_cap_test ? c->dlc_offset_cap_test : 0x7FFFFFFFull;
+    for (uint32_t i : var_ids) if ((uint64_t)var_total[i] > cap) {
+      blk_give(c, c->gen, cs->m.d_a, cs->m.cap_a, false); cs->m.d_a = nullptr;
+      return dlc_refuse(ETLG_DLC_OFFSETS_OVERFLOW, i);
     }
   }
   // ---- 3. block B: the bytes of the var-len columns; list columns: child values (or, for lists of strings, child offsets +
@@ -354,14 +391,27 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
 
 int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t row_kinds, uint32_t flags, etlg_columns** out) {
   if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
-  return build_columns(c, b, slot, row_kinds & 3u, row_kinds, flags, false, out);
+  return build_columns(c, b, slot, row_kinds & 3u, row_kinds, flags, ColCaller::Columns, out);
 }
 
 int32_t etlg_batch_iceberg(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t opts, uint32_t flags, etlg_columns** out) {
   if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
   *out = nullptr;
   if (opts & ~(ETLG_ROWS_PARSE_ARRAYS | ETLG_ROWS_FORMAT_JSON)) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_iceberg: opts takes ETLG_ROWS_PARSE_ARRAYS | ETLG_ROWS_FORMAT_JSON only (the row kinds are fixed)");
-  return build_columns(c, b, slot, 7u, opts, flags, true, out);
+  return build_columns(c, b, slot, 7u, opts, flags, ColCaller::Iceberg, out);
+}
+
+// DuckLake's copy payload for a table arrow_column_kinds accepts (prepare_copy_rows -> copy_rows_to_arrow_record_batch,
+// ducklake/encoding.rs:32-49, :303-340): build_columns' third caller, with a kind table of its own.
+int32_t etlg_batch_ducklake_copy(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t flags, etlg_columns** out) {
+  if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
+  return build_columns(c, b, slot, 1u, 1u, flags, ColCaller::DuckLakeCopy, out);
+}
+
+int32_t etlg_columns_ducklake_get(const etlg_columns* cs, etlg_ducklake_copy_info* out) {
+  if (!cs || !out || !cs->ducklake) return ETLG_InvalidArgument;
+  *out = cs->di;
+  return ETLG_OK;
 }
 
 int32_t etlg_columns_changelog_get(const etlg_columns* cs, etlg_changelog_info* out) {
@@ -716,6 +766,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   j.n_rows = n; j.n_cols = nc; j.engine = (uint32_t)engine;
   j.cdc_nullable = nullable_flags ? (nullable_flags[nc] ? 1u : 0u) | (nullable_flags[nc + 1] ? 2u : 0u) : 0u;
   j.format = format;
+  j.copy_tail = (format <= 1 && b->copy.active) ? 1u : 0u;   // a table-copy batch: write_table_rows' rows (clickhouse/core.rs:739-773, bigquery/core.rs:602-649)
   j.cols = (const uint32_t*)(S + o_cols); j.kcols = (key_ok || format) ? (const uint32_t*)(S + o_cols) + nc : nullptr; j.ev_flags = bv.ev_flags; j.lens = (uint32_t*)(A + o_len); j.offsets = (const int64_t*)(A + o_off);
   j.err = (unsigned long long*)(S + o_cnt) + 1;
   for (uint32_t i = 0; i < nc; i++) if (sh.cols[i].type_class == ETLG_TC_JSON || (sh.cols[i].type_class == ETLG_TC_ARRAY && (uint32_t)etlg_array_elem_class(sh.cols[i].type_oid) == ETLG_TC_JSON)) j.has_json = 1;

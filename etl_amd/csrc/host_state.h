@@ -425,6 +425,7 @@ struct etlg_ctx {
   std::vector<std::pair<void*, size_t>> blk_dev, blk_host;  // hand-off calls (columns / RowBinary / size hints): pooled device and pinned blocks
   DevBuf d_colsel;                   // etlg_batch_columns: block counts of the row selection
   uint32_t rb_parts_test = 0;        // ETLG_RB_PARTS (tests)
+  uint64_t dlc_offset_cap_test = 0;  // ETLG_DLC_OFFSET_CAP (tests): the bytes a Utf8 / Binary column of etlg_batch_ducklake_copy may hold, instead of 2^31 - 1
   uint8_t* h_hand = nullptr; size_t h_hand_cap = 0;   // pinned: the row formats' small uploads (initial counters + column words, one copy) and read-backs (row count; totals + counters, one copy each)
   unsigned long long* h_cnt_init = nullptr; size_t h_cnt_init_cols = 0;   // pinned {0, 0, 0, ~0} per column: the hand-off's counters start from it (an asynchronous copy; the content never changes)
   std::vector<etlg_batch*> pending;  // ASYNC batches not finished yet, in issue order
@@ -528,12 +529,14 @@ struct HandoffBlocks {  // two device blocks (+ one pinned block when downloaded
   void* d_a = nullptr; void* d_b = nullptr; void* d_c = nullptr; uint8_t* h = nullptr;
   size_t cap_a = 0, cap_b = 0, cap_c = 0, cap_h = 0;
 };
-struct etlg_columns {  // etlg_batch_columns, etlg_batch_iceberg
+struct etlg_columns {  // etlg_batch_columns, etlg_batch_iceberg, etlg_batch_ducklake_copy
   etlg_columns_view v{};
   std::vector<etlg_column> cols;
   HandoffBlocks m;
   bool changelog = false;          // built by etlg_batch_iceberg: `ci` is valid (etlg_columns_changelog_get)
   etlg_changelog_info ci{};
+  bool ducklake = false;           // built by etlg_batch_ducklake_copy: `di` is valid (etlg_columns_ducklake_get)
+  etlg_ducklake_copy_info di{};
 };
 
 struct etlg_rowbinary {

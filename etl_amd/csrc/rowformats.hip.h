@@ -207,7 +207,9 @@ DEV uint32_t rb_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
   // trailing CDC columns (core.rs:96-114); never NULL, a Nullable() destination column still takes its marker byte
   const uint64_t ev = j.row_event[r];
   const uint32_t kind = j.ev_kind[ev];
-  const uint64_t lsn = j.ev_commit[ev], ord = j.ev_ord[ev];
+  // (a table-copy batch: append_cdc_columns(Insert, PgLsn 0, tx_ordinal 0), clickhouse/core.rs:739-773 — the virtual transaction's
+  // events are Inserts already; its ordinals count up)
+  const uint64_t lsn = j.copy_tail ? 0ull : j.ev_commit[ev], ord = j.copy_tail ? 0ull : j.ev_ord[ev];
   if (j.cdc_nullable & 1u) s.put(0);
   if (j.engine == 0) {
     s.put(6);
@@ -398,6 +400,7 @@ DEV uint32_t pb_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
   const uint64_t ev = j.row_event[r];
   pb_key(s, j.n_cols + 1, 2); s.varint64(6);
   { const char* op = del ? "DELETE" : "UPSERT"; for (int k = 0; k < 6; k++) s.put((u8)op[k]); }
+  if (j.copy_tail) return 0;   // a copied row has no _CHANGE_SEQUENCE_NUMBER field (write_table_rows, bigquery/core.rs:602-649)
   pb_key(s, j.n_cols + 2, 2); s.varint64(50);
   pb_hex16(s, j.ev_commit[ev]); s.put('/'); pb_hex16(s, j.ev_ord[ev]); s.put('/'); pb_hex16(s, (rbase & kPbSecond) ? 1 : 0);   // bigquery_sequence_key (:1405-1407)
   return 0;

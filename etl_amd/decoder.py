@@ -89,6 +89,22 @@ class Batch:
         assert rc == abi.OK, rc
         return cols
 
+    def ducklake_copy(self, slot, on_device=False):
+        """DuckLake's Arrow copy staging of schema slot `slot` of a table-copy batch (etlg_batch_ducklake_copy): every row, as the
+        column buffers of the RecordBatch the sink appends — Int16 for int2, UInt64 for oid, Utf8 / Binary with int32 offsets. Returns a
+        `Columns` whose `.ducklake` (abi.DuckLakeCopyInfo) says whether anything was built: status abi.DLC_NOT_ARROW (a uuid, json or
+        array column: the sink takes its row path) and abi.DLC_OFFSETS_OVERFLOW (a column's bytes pass 2^31 - 1) name the column and
+        come without rows. Raises EtlError (InvalidArgument) for a batch that is not a table copy."""
+        out = C.c_void_p()
+        rc = self.dec.L.etlg_batch_ducklake_copy(self.dec.h, self.h, slot, abi.F_OUTPUT_ON_DEVICE if on_device else 0, C.byref(out))
+        if rc != abi.OK or not out:
+            raise self.dec.last_error()
+        cols = Columns(self.dec, out)
+        cols.ducklake = abi.DuckLakeCopyInfo()
+        rc = self.dec.L.etlg_columns_ducklake_get(out, C.byref(cols.ducklake))
+        assert rc == abi.OK, rc
+        return cols
+
     def finish_cells(self, what=abi.FINISH_ARRAYS | abi.FINISH_FLOATS):
         """Typed arrays / exact floats in the arena, on the device (etlg_batch_finish_cells). Returns abi.FinishStats."""
         st = abi.FinishStats()
@@ -171,6 +187,7 @@ class Columns:
     def __init__(self, dec, handle):
         self.dec, self.h = dec, handle
         self.changelog = None   # abi.ChangelogInfo of a Batch.iceberg() result
+        self.ducklake = None    # abi.DuckLakeCopyInfo of a Batch.ducklake_copy() result
         self.view = abi.ColumnsView()
         dec.L.etlg_columns_view_get(handle, C.byref(self.view))
 
@@ -188,12 +205,14 @@ class Columns:
         return np.frombuffer((C.c_uint8 * nbytes).from_address(ptr), dtype=dtype)
 
     def host_arrays(self, i):
-        """(validity bits u8[], deferred bits u8[], values u8[], offsets i64[] | None) of column i (views into the block)."""
+        """(validity bits u8[], deferred bits u8[], values u8[], offsets i64[] | None) of column i (views into the block); the offsets
+        of an abi.AK_UTF8 / AK_BINARY column are i32[]."""
         k, n = self.view.cols[i], self.n_rows
         if k.arrow_kind == abi.AK_NONE:
             return None
         bm = (n + 63) // 64 * 8
-        offs = self._np(k.offsets, (n + 1) * 8, np.int64) if k.offsets else None
+        o32 = k.arrow_kind in (abi.AK_UTF8, abi.AK_BINARY)
+        offs = self._np(k.offsets, (n + 1) * (4 if o32 else 8), np.int32 if o32 else np.int64) if k.offsets else None
         return self._np(k.validity, bm, np.uint8), self._np(k.deferred, bm, np.uint8), self._np(k.values, int(k.values_bytes), np.uint8), offs
 
     def child_validity(self, i):

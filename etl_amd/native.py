@@ -20,7 +20,7 @@ EXPORTS = [
     "etlg_batch_view_get", "etlg_batch_sync", "etlg_batch_download", "etlg_batch_header_to_device", "etlg_ctx_fence", "etlg_batch_free", "etlg_ctx_slots", "etlg_ctx_profile",
     "etlg_ctx_profile_read", "etlg_scan_boundaries", "etlg_copy_decode", "etlg_frame_tags",
     "etlg_table_forget", "etlg_table_cache_get", "etlg_host_alloc", "etlg_host_free", "etlg_control_stream", "etlg_shard_plan", "etlg_shard_replay",
-    "etlg_batch_columns", "etlg_columns_view_get", "etlg_columns_free", "etlg_batch_iceberg", "etlg_columns_changelog_get",
+    "etlg_batch_columns", "etlg_columns_view_get", "etlg_columns_free", "etlg_batch_iceberg", "etlg_columns_changelog_get", "etlg_batch_ducklake_copy", "etlg_columns_ducklake_get",
     "etlg_batch_rowbinary", "etlg_batch_protobuf", "etlg_batch_ndjson", "etlg_batch_duckdb", "etlg_rowbinary_view_get", "etlg_rowbinary_col_ends_get", "etlg_rowbinary_free", "etlg_batch_size_hints",
     "etlg_batch_finish_cells",
 ]
@@ -96,6 +96,8 @@ def lib():
     L.etlg_batch_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.etlg_batch_iceberg.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.etlg_columns_changelog_get.argtypes = [C.c_void_p, C.POINTER(abi.ChangelogInfo)]
+    L.etlg_batch_ducklake_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.etlg_columns_ducklake_get.argtypes = [C.c_void_p, C.POINTER(abi.DuckLakeCopyInfo)]
     L.etlg_columns_view_get.argtypes = [C.c_void_p, C.c_void_p]
     L.etlg_columns_free.argtypes = [C.c_void_p]
     L.etlg_columns_free.restype = None

@@ -670,6 +670,11 @@ typedef enum etlg_arrow_kind {
                              * json[] / jsonb[] (round 6): LargeUtf8 child of `j.to_string()` per element (ArrayCell::Json,
                              * iceberg/encoding.rs:577-585); an element of more than 256 bytes or beyond the json writer's limits
                              * (depth 16, 64 members) hands its row back (`deferred`), one that is not JSON is ETLG_E_JSON */
+  /* etlg_batch_ducklake_copy only (arrow_column_kind, crates/etl-destinations/src/ducklake/encoding.rs:236-257) */
+  ETLG_AK_INT16 = 14,       /* int2: 2-byte values */
+  ETLG_AK_UINT64 = 15,      /* oid, widened */
+  ETLG_AK_UTF8 = 16,        /* text and the Display strings of numeric / timetz: i32 offsets + bytes */
+  ETLG_AK_BINARY = 17,      /* bytea: i32 offsets + bytes */
   ETLG_AK_NONE = 255        /* not handed off - no buffers (no class maps to it today) */
 } etlg_arrow_kind;
 
@@ -684,7 +689,8 @@ typedef struct etlg_column {
   const uint8_t* deferred;  /* same shape: cells the kernels handed back ETLG_CELL_DEFERRED. In a fixed-width
                              * column they are null in `validity`; in a TEXT_FORM column their entry is the source text */
   const uint8_t* values;
-  const int64_t* offsets;   /* var-len kinds: n_rows + 1 entries, else NULL */
+  const int64_t* offsets;   /* var-len kinds: n_rows + 1 entries, else NULL. ETLG_AK_UTF8 / ETLG_AK_BINARY: the pointer is to n_rows + 1
+                             * INT32 entries (Arrow's Utf8 / Binary) — read it as const int32_t* */
   uint64_t values_bytes;    /* bytes behind `values` */
   /* ETLG_AK_LIST only */
   uint32_t child_kind;      /* the element column's etlg_arrow_kind (BOOLEAN, INT32, INT64, FLOAT32/64, DATE32, TIME64_US, TIMESTAMP_US[_UTC], FIXED16,
@@ -770,6 +776,39 @@ int32_t etlg_batch_iceberg(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot
 /* ETLG_InvalidArgument for an object that etlg_batch_columns built. */
 int32_t etlg_columns_changelog_get(const etlg_columns* cols, etlg_changelog_info* out);
 
+/* DuckLake's Arrow copy staging for ONE schema slot of a TABLE-COPY batch (etlg_copy_decode): the column buffers of the RecordBatch
+ * prepare_copy_rows appends through the DuckDB appender (crates/etl-destinations/src/ducklake/encoding.rs:32-49,
+ * copy_rows_to_arrow_record_batch :303-340) — every row of the batch, in order. Column kinds by type class (arrow_column_kind :236-257):
+ *   BOOL BOOLEAN | I16 INT16 | I32 INT32 | I64 INT64 | U32 UINT64 | F32 / F64 FLOAT32 / FLOAT64 | DATE DATE32 | TIME TIME64_US |
+ *   TIMESTAMP TIMESTAMP_US | TIMESTAMPTZ TIMESTAMP_US_UTC | BYTEA BINARY | STRING, NUMERIC, TIMETZ UTF8 (numeric / timetz: their
+ *   Display strings, push_cell :170-171, as in etlg_batch_columns).
+ * Null slots hold zero values (arrow's From<Vec<Option<T>>>), a null var-len entry is empty; validity, null_count and `nullable` (the
+ * column's, for the Field) as in etlg_batch_columns. A DEFERRED cell (a float text the fast rule does not settle) is null, set in
+ * `deferred` and counted in deferred_count, as there: a caller that wants none decodes with ETLG_F_FINISH_CELLS.
+ * A slot with a UUID, JSON or ARRAY class column has no Arrow form (arrow_column_kinds returns None; the sink takes prepare_rows, which
+ * ETLG_DL_TUPLES and the host cover): the call gives ETLG_OK and builds nothing — n_rows = 0, n_cols = 0, status ETLG_DLC_NOT_ARROW,
+ * `column` = the first such column. Array types outside the value codec's table decode as ETLG_TC_STRING and cannot be told here: only
+ * the caller has is_array_type, and it MUST NOT ask for the Arrow form of such a table.
+ * 32-bit offsets: arrow-rs panics when a StringArray's / BinaryArray's bytes pass i32::MAX. A var-len column whose bytes exceed
+ * 2^31 - 1 gives ETLG_OK, no buffers (n_rows = 0, n_cols = 0), status ETLG_DLC_OFFSETS_OVERFLOW and the first such column; the caller
+ * splits the batch. (Tests lower the cap with the environment variable ETLG_DLC_OFFSET_CAP=<bytes>, read when the context is created.)
+ * No conversion error exists on this path: date_days_since_epoch cannot fail (chrono's dates span about +-96 million days, which fits
+ * i32) and time_micros_since_midnight cannot fail, so no error path is built for them.
+ * A batch that is not a table-copy batch is ETLG_InvalidArgument (the reference uses this form for copy rows only). Batch
+ * requirements and ETLG_F_OUTPUT_ON_DEVICE as for etlg_batch_columns; the call synchronises with the device exactly as often as
+ * etlg_batch_columns does for the same slot. The result is read with etlg_columns_view_get and freed with etlg_columns_free. */
+#define ETLG_DLC_OK 0u
+#define ETLG_DLC_NOT_ARROW 1u
+#define ETLG_DLC_OFFSETS_OVERFLOW 2u
+typedef struct etlg_ducklake_copy_info {
+  uint32_t status;  /* ETLG_DLC_* */
+  uint32_t column;  /* NOT_ARROW / OFFSETS_OVERFLOW: the first column that has no Arrow form / whose bytes pass the cap; else 0 */
+  uint32_t _pad[2];
+} etlg_ducklake_copy_info;
+int32_t etlg_batch_ducklake_copy(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, uint32_t flags, etlg_columns** out);
+/* ETLG_InvalidArgument for any other object (etlg_batch_columns, etlg_batch_iceberg). */
+int32_t etlg_columns_ducklake_get(const etlg_columns* cols, etlg_ducklake_copy_info* out);
+
 /* ClickHouse RowBinary rows for ONE schema slot of a decoded batch, encoded on the device: what
  * cell_to_clickhouse_value + encode_to_row_binary (crates/etl-destinations/src/clickhouse/encoding.rs:58-83,
  * :188-283) and append_cdc_columns (clickhouse/core.rs:96-114) produce for the rows core.rs:1078-1127 collects:
@@ -816,7 +855,11 @@ typedef struct etlg_rowbinary etlg_rowbinary;
  * columns (nullable_flags_from_clickhouse_columns, clickhouse/core.rs:162-209); n_flags must be n_cols + 2
  * ("ClickHouse RowBinary row width mismatch", encoding.rs:263-274, otherwise). A NULL in a non-nullable column and a
  * date outside 1900-01-01..=2299-12-31 fail the call with ETLG_ConversionError like the reference (etlg_last_error:
- * the description, frame_index = the event index). Same batch requirements as etlg_batch_columns. */
+ * the description, frame_index = the event index). Same batch requirements as etlg_batch_columns.
+ * A table-copy batch (etlg_copy_decode): every row of the slot is kept, in row order, its data columns encoded as an Insert event's
+ * under the same nullable_flags rules and errors, and the CDC tail is that of append_cdc_columns(Insert, PgLsn 0, tx_ordinal 0, engine)
+ * (write_table_rows_inner, clickhouse/core.rs:739-773): MergeTree String("INSERT") + UInt64 0, ReplacingMergeTree UInt128 0 + UInt8 0.
+ * n_host_rows is 0. */
 int32_t etlg_batch_rowbinary(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const uint8_t* nullable_flags,
                              uint32_t n_flags, int32_t engine, uint32_t flags, etlg_rowbinary** out);
 /* BigQuery Storage Write rows for ONE schema slot: the protobuf bytes of the BigQueryTableRows the sink builds for the slot's events
@@ -843,7 +886,10 @@ int32_t etlg_batch_rowbinary(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_sl
  * detail), a numeric element of more than 38 decimal places / a json element's integer outside u64 / i64 with
  * ETLG_UnsupportedValueInDestination (validate_elements, validation.rs:143-188). A literal the device cannot take apart (see
  * etlg_batch_rowbinary), DEFERRED cells and json cells beyond json_display's limits return ETLG_RB_NEEDS_HOST.
- * The result is an etlg_rowbinary (same view; n_rows can exceed the number of events). */
+ * The result is an etlg_rowbinary (same view; n_rows can exceed the number of events).
+ * A table-copy batch (etlg_copy_decode): one row per source row (row_event[i] = i), the cells under tags 1..n, then _CHANGE_TYPE =
+ * "UPSERT" under tag n + 1 and NOTHING under n + 2 — write_table_rows appends only the change type (bigquery/core.rs:602-649; compare
+ * bigquery_upsert_row :1410-1418, which pushes both). The validation rules are unchanged. */
 int32_t etlg_batch_protobuf(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, uint32_t flags, etlg_rowbinary** out);
 /* Snowflake Snowpipe Streaming rows for ONE schema slot: the NDJSON line serialize_row writes for every row the sink builds
  * (crates/etl-destinations/src/snowflake/encoding.rs:57-72; core.rs:345-438), in event order, at most one row per event, each line
