@@ -178,6 +178,57 @@ impl GpuDecoder {
             Ok(DuckLakeCopyColumns { cols, view: view.assume_init(), info: info.assume_init() })
         }
     }
+
+    /// The fingerprints of the copy batch's atomic batches (`build_copy_batch_identity`,
+    /// crates/etl-destinations/src/ducklake/batches.rs:1449-1464), hashed on the device while the batch is still there
+    /// (`etlg_ducklake_fingerprints` over the `ETLG_DL_PREDICATES` / `ETLG_DL_TUPLES` records, which stay in device memory): one per
+    /// range of rows, from the range's seed — the `BatchIdHasher` state after `"copy"` and `table_name.id()`, which the caller hashes
+    /// itself, as it formats the id (`build_batch_identity`, batches.rs:1536-1553). `col_names`: the slot's replicated column names,
+    /// each NUL-terminated, back to back. `info.status == ETLG_RB_NEEDS_HOST` (a record object handed back by the device, or a row without a
+    /// record): no fingerprint was written, the host hashes the batch from `info.host_event` on.
+    pub fn copy_ducklake_fingerprints(&mut self, schema_slot: u32, f: &CopyInFlight, col_names: &[u8], n_names: u32, ranges: &[etlg_dl_range]) -> EtlResult<(Vec<u64>, etlg_dl_fp_info)> {
+        let names = col_names.as_ptr() as *const std::os::raw::c_char;
+        let mut recs = [std::ptr::null_mut::<etlg_rowbinary>(); 2];
+        for (k, what) in [ETLG_DL_TUPLES, ETLG_DL_PREDICATES].into_iter().enumerate() {
+            let rc = unsafe { etlg_batch_duckdb(self.ctx, f.batch, schema_slot as i32, what, names, n_names, ETLG_F_OUTPUT_ON_DEVICE, &mut recs[k]) };
+            if rc != ETLG_OK || recs[k].is_null() {
+                let e = self.last_error();
+                unsafe { etlg_rowbinary_free(recs[0]) };
+                return Err(e);
+            }
+        }
+        let mut out = vec![0u64; ranges.len()];
+        let mut info = etlg_dl_fp_info { status: ETLG_RB_OK, _pad: 0, host_event: u64::MAX };
+        // a record object the device handed back (a DEFERRED cell ...): nothing to hash — the same answer as for a missing record
+        for r in recs {
+            let mut v = std::mem::MaybeUninit::<etlg_rowbinary_view>::uninit();
+            let v = unsafe {
+                etlg_rowbinary_view_get(r, v.as_mut_ptr());
+                v.assume_init()
+            };
+            if v.status == ETLG_RB_NEEDS_HOST {
+                info.status = ETLG_RB_NEEDS_HOST;
+                info.host_event = info.host_event.min(v.host_event);
+            }
+        }
+        if info.status == ETLG_RB_NEEDS_HOST {
+            unsafe {
+                etlg_rowbinary_free(recs[0]);
+                etlg_rowbinary_free(recs[1]);
+            }
+            return Ok((out, info));
+        }
+        let rc = unsafe {
+            etlg_ducklake_fingerprints(self.ctx, f.batch, schema_slot as i32, recs[0], recs[1], std::ptr::null(), names, n_names, ranges.as_ptr(),
+                                       ranges.len() as u32, out.as_mut_ptr(), &mut info)
+        };
+        let status = if rc == ETLG_OK { Ok(()) } else { Err(self.last_error()) };
+        unsafe {
+            etlg_rowbinary_free(recs[0]);
+            etlg_rowbinary_free(recs[1]);
+        }
+        status.map(|_| (out, info))
+    }
 }
 
 /// A table-copy batch in flight. Dropping it without `copy_finish` frees the batch FIRST (the library waits for its kernels and its

@@ -262,6 +262,20 @@ pub struct etlg_ducklake_copy_info {
 }
 
 #[repr(C)]
+pub struct etlg_dl_range {
+    pub first_event: u64,
+    pub end_event: u64,
+    pub seed: u64,
+}
+
+#[repr(C)]
+pub struct etlg_dl_fp_info {
+    pub status: u32,
+    pub _pad: u32,
+    pub host_event: u64,
+}
+
+#[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
     pub arrays_typed: u64,
@@ -456,6 +470,20 @@ extern "C" {
     pub fn etlg_rowbinary_view_get(rb: *const etlg_rowbinary, out: *mut etlg_rowbinary_view) -> i32;
     pub fn etlg_rowbinary_col_ends_get(rb: *const etlg_rowbinary, col_ends: *mut *const u32) -> i32;
     pub fn etlg_rowbinary_free(rb: *mut etlg_rowbinary);
+    pub fn etlg_ducklake_fingerprints(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        schema_slot: i32,
+        tuples: *const etlg_rowbinary,
+        predicates: *const etlg_rowbinary,
+        updates: *const etlg_rowbinary,
+        col_names: *const c_char,
+        n_names: u32,
+        ranges: *const etlg_dl_range,
+        n_ranges: u32,
+        out: *mut u64,
+        info: *mut etlg_dl_fp_info,
+    ) -> i32;
     pub fn etlg_batch_size_hints(ctx: *mut etlg_ctx, batch: *mut etlg_batch, model: *const etlg_size_model, flags: u32, out: *mut u64) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;
     pub fn etlg_ctx_slots(ctx: *const etlg_ctx, n_slots: *mut u32, slots: *mut *const etlg_slot_desc) -> i32;

@@ -128,6 +128,14 @@ class RowBinaryView(C.Structure):   # etlg_rowbinary_view
                 ("bytes", C.c_void_p), ("row_offsets", C.c_void_p), ("row_event", C.c_void_p)]
 
 
+class DlRange(C.Structure):   # etlg_dl_range
+    _fields_ = [("first_event", C.c_uint64), ("end_event", C.c_uint64), ("seed", C.c_uint64)]
+
+
+class DlFpInfo(C.Structure):   # etlg_dl_fp_info
+    _fields_ = [("status", C.c_uint32), ("_pad", C.c_uint32), ("host_event", C.c_uint64)]
+
+
 class SizeModel(C.Structure):   # etlg_size_model
     _fields_ = [(n, C.c_uint32) for n in ("begin_event", "commit_event", "insert_event", "update_event", "delete_event", "truncate_event",
                                           "relation_event", "replicated_table_schema", "table_row", "cell")] + [("_reserved", C.c_uint32 * 2)]

@@ -13,7 +13,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # in the order they are started: the sources that take longest to compile first (the row formats and the Arrow columns instantiate
 # json_display many times), so that a build takes about as long as its longest source
 SOURCES = ["rowformats.hip", "rowformats_dl.hip", "columns.hip", "kernels.hip", "finish.hip", "host.cpp", "cells.hip", "fused.hip", "rows.hip", "plan.hip", "scan.hip",
-           "copy.hip", "check.hip"]
+           "copy.hip", "check.hip", "fingerprint.hip"]
 # per-source optimisation level: k_fused is measurably faster built for size (88 vs 93 us on cfg2, tools/variants.sh);
 # k_cells and the rest are not
 # (round 6: so is k_copy_cells — cells.hip at -Os 468 / 304 us against 482-486 / 313-317 on the two table-copy workloads, same box;

@@ -345,5 +345,28 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   uint32_t* col_ends;
 };
 
+struct FpRecs {            // the device-resident arrays of one etlg_batch_duckdb result
+  const uint64_t* row_event; const int64_t* row_offsets; const uint8_t* bytes; uint64_t n_rows;
+};
+struct FpJob {             // DuckLake batch identities (fingerprint.hip)
+  const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_start; const uint64_t* ev_commit;
+  uint64_t n_events;
+  uint32_t slot, copy;             // copy: a table-copy batch (`P FF T FF` per row, no LSNs)
+  uint32_t n_cols, n_ranges;
+  FpRecs t, p, u;                  // ETLG_DL_TUPLES / _PREDICATES / _UPDATES (u.n_rows == 0 when the caller has none)
+  const uint32_t* u_ends;          // col_ends of the updates [u.n_rows x n_cols]
+  const uint32_t* name_len;        // per column: len(quoted name) + 3, what a SET piece holds in front of its literal
+  const uint64_t* ranges;          // n_ranges x {first_event, end_event, seed}
+  uint32_t* plan;                  // per event: what it hashes (FP_*) and its records' indexes {tag, t, p, u}
+  uint32_t* lens; const int64_t* offs;   // per event: bytes of its stream; their exclusive scan (n_events + 1)
+  uint8_t* stream;                 // the byte stream of every slot event of the batch, back to back
+  uint64_t* bounds;                // n_ranges x {begin, end} in stream bytes
+  uint8_t* perm;                   // per piece: the low-byte permutation (256 bytes)
+  uint8_t* lin;                    // per piece: the low byte it is entered with
+  uint64_t* maps;                  // per piece: {P^n, C}
+  unsigned long long* result;      // [0] the first event inside a range that lacks a record (~0 none), [1 + i] fingerprint of range i
+  uint32_t n_chunks;               // an upper bound of the stream's chunks (the launches' grids)
+};
+
 
 }  // namespace etlg

@@ -655,6 +655,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   rb->v.on_device = on_dev ? 1u : 0u; rb->v.host_event = ~0ull;
   const bool dl_upd = format == 3 && dl_what == ETLG_DL_UPDATES;   // partial Updates: two records per event and the col_ends array
   rb->updates = dl_upd;
+  if (format == 3) { rb->dl_batch = b; rb->dl_serial = b->serial; rb->dl_slot = slot; rb->dl_what = dl_what; }
   std::vector<uint32_t> cols(2 * (size_t)nc);   // [nc, 2 nc): the key-layout words of the columns (RbJob.kcols)
   // A Delete that carries only the key: the reference expands it into a tombstone row (expand_key_row, clickhouse/core.rs:1437-1472)
   // when the replica identity is the primary key (or Full) — ensure_clickhouse_key_identity_is_primary_key, :1404-1427; identity
@@ -851,6 +852,68 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   rb->v.n_rows = n; rb->v.n_bytes = (uint64_t)total;
   rb->v.row_event = (const uint64_t*)base_a; rb->v.row_offsets = (const int64_t*)(base_a + o_off); rb->v.bytes = total ? base_b : nullptr;
   *out = rb.release();
+  return ETLG_OK;
+}
+
+// DuckLake batch identities (fingerprint.hip): the three record objects of one batch and slot stay where they are, in HBM; what goes up is
+// the ranges and the quoted names' lengths, what comes back the fingerprints and the first event that lacks a record — one stop, at the end.
+int32_t etlg_ducklake_fingerprints(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_rowbinary* tuples, const etlg_rowbinary* predicates,
+                                   const etlg_rowbinary* updates, const char* col_names, uint32_t n_names, const etlg_dl_range* ranges,
+                                   uint32_t n_ranges, uint64_t* out, etlg_dl_fp_info* info) {
+  if (!c || !b || b->ctx != c || !tuples || !predicates || !info || (n_names && !col_names) || (n_ranges && (!ranges || !out))) return ETLG_InvalidArgument;
+  info->status = ETLG_RB_OK; info->_pad = 0; info->host_event = ~0ull;
+  if (const int32_t rc = batch_ready(c, b, "etlg_ducklake_fingerprints" NEEDS_DEVICE)) return rc;
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  const uint32_t nc = c->slots[(size_t)slot]->desc.n_cols;
+  if (n_names != nc) return lib_error(c, ETLG_InvalidArgument, "DuckLake row width mismatch: one column name per replicated column");
+  auto mine = [&](const etlg_rowbinary* r, uint32_t what) { return r->dl_batch == b && r->dl_serial == b->serial && r->dl_slot == slot && r->dl_what == what && r->v.on_device && r->v.status == ETLG_RB_OK; };
+  if (!mine(tuples, ETLG_DL_TUPLES) || !mine(predicates, ETLG_DL_PREDICATES) || (updates && !mine(updates, ETLG_DL_UPDATES)))
+    return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_fingerprints takes the ETLG_DL_TUPLES, ETLG_DL_PREDICATES and ETLG_DL_UPDATES objects etlg_batch_duckdb built for this batch and slot, on the device (ETLG_F_OUTPUT_ON_DEVICE) and with status ETLG_RB_OK");
+  const etlg_batch_view& bv = b->v;
+  const uint64_t ne = bv.n_events;
+  for (uint32_t i = 0; i < n_ranges; i++)
+    if (ranges[i].first_event > ranges[i].end_event || ranges[i].end_event > ne || (i && ranges[i].first_event < ranges[i - 1].end_event))
+      return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_fingerprints: the ranges must be [first, end) within the batch's events, ascending and disjoint");
+  if (!n_ranges) return ETLG_OK;
+  if (!ne) { for (uint32_t i = 0; i < n_ranges; i++) out[i] = ranges[i].seed; return ETLG_OK; }
+  std::vector<uint64_t> up(3 * (size_t)n_ranges);
+  for (uint32_t i = 0; i < n_ranges; i++) { up[3 * (size_t)i] = ranges[i].first_event; up[3 * (size_t)i + 1] = ranges[i].end_event; up[3 * (size_t)i + 2] = ranges[i].seed; }
+  std::vector<uint32_t> name_len(nc);   // quote_double_identifier's length + " = "
+  { const char* p = col_names; for (uint32_t i = 0; i < nc; i++) { uint32_t n = 2 + 3; for (; *p; p++) n += *p == '"' ? 2u : 1u; p++; name_len[i] = n; } }
+  const etlg_rowbinary_view& tv = tuples->v; const etlg_rowbinary_view& pv = predicates->v;
+  const uint64_t u_rows = updates ? updates->v.n_rows : 0, u_bytes = updates ? updates->v.n_bytes : 0;
+  // an upper bound of the stream: every record's bytes once, and per event the LSNs, the tag and two 0xFF (a partial Update: the column
+  // count and per column its index and 0xFF as well)
+  const uint64_t n_max = tv.n_bytes + pv.n_bytes + u_bytes + ne * 26 + (u_rows / 2) * (8 + 9 * (uint64_t)nc);
+  const uint64_t chunk = etlg_k_fp_chunk_bytes(), n_chunks = n_max / chunk + 1, n_pieces = n_chunks + n_ranges;
+  if (n_chunks > 0x7FFFFFFFull) return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_fingerprints: the batch's records are beyond what one call hashes");
+  const size_t o_names = al64(up.size() * 8), o_plan = o_names + al64((size_t)nc * 4 + 4), o_lens = o_plan + al64(ne * 16), o_offs = o_lens + al64(ne * 4),
+               o_blk = o_offs + al64((ne + 1) * 8), o_bounds = o_blk + al64((ne / 256 + 2) * 8), o_result = o_bounds + al64((size_t)n_ranges * 16),
+               o_lin = o_result + al64(((size_t)n_ranges + 1) * 8), o_maps = o_lin + al64(n_pieces), o_perm = o_maps + al64(n_pieces * 16),
+               o_stream = o_perm + al64(n_pieces * 256), total = o_stream + al64(n_max) + 64;
+  hipStream_t s = c->stream;
+  ScratchBlk dblk{c};
+  HIPCHK(c, blk_take(c, total, false, &dblk.p, &dblk.cap));
+  uint8_t* d = (uint8_t*)dblk.p;
+  HIPCHK(c, hipMemcpyAsync(d, up.data(), up.size() * 8, hipMemcpyHostToDevice, s));
+  if (nc) HIPCHK(c, hipMemcpyAsync(d + o_names, name_len.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(d + o_result, 0xFF, 8, s));
+  FpJob j{};
+  j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot; j.ev_start = bv.ev_start_lsn; j.ev_commit = bv.ev_commit_lsn;
+  j.n_events = ne; j.slot = (uint32_t)slot; j.copy = b->copy.active ? 1u : 0u; j.n_cols = nc; j.n_ranges = n_ranges;
+  j.t = FpRecs{tv.row_event, tv.row_offsets, tv.bytes, tv.n_rows};
+  j.p = FpRecs{pv.row_event, pv.row_offsets, pv.bytes, pv.n_rows};
+  if (updates) { j.u = FpRecs{updates->v.row_event, updates->v.row_offsets, updates->v.bytes, u_rows}; j.u_ends = updates->col_ends; }
+  j.name_len = (const uint32_t*)(d + o_names); j.ranges = (const uint64_t*)d;
+  j.plan = (uint32_t*)(d + o_plan); j.lens = (uint32_t*)(d + o_lens); j.offs = (const int64_t*)(d + o_offs); j.stream = d + o_stream;
+  j.bounds = (uint64_t*)(d + o_bounds); j.perm = d + o_perm; j.lin = d + o_lin; j.maps = (uint64_t*)(d + o_maps);
+  j.result = (unsigned long long*)(d + o_result); j.n_chunks = (uint32_t)n_chunks;
+  etlg_k_fingerprints(&j, (unsigned long long*)(d + o_blk), s);
+  std::vector<uint64_t> back((size_t)n_ranges + 1);
+  HIPCHK(c, hipMemcpyAsync(back.data(), d + o_result, back.size() * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop; the scratch block is freed on return
+  if (back[0] != ~0ull) { info->status = ETLG_RB_NEEDS_HOST; info->host_event = back[0]; return ETLG_OK; }
+  memcpy(out, back.data() + 1, (size_t)n_ranges * 8);
   return ETLG_OK;
 }
 

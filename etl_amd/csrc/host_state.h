@@ -27,6 +27,7 @@
 #include <string>
 #include <string_view>
 #include <type_traits>
+#include <atomic>
 #include <unordered_map>
 #include <vector>
 
@@ -87,6 +88,8 @@ extern "C" uint32_t etlg_k_cells_lds_floor(uint32_t maxc);
 extern "C" uint32_t etlg_k_cells_static_lds(uint32_t maxc);
 extern "C" uint32_t etlg_k_copy_cells_static_lds(uint32_t maxc);
 extern "C" void etlg_k_launch_chk_cells(const DecParams* p, uint32_t maxc, uint32_t ev_bound, hipStream_t s);
+extern "C" void etlg_k_fingerprints(const void* job, unsigned long long* blk, hipStream_t s);
+extern "C" uint32_t etlg_k_fp_chunk_bytes(void);
 
 constexpr int kFused = 7;  // profiling slot of the fused kernel
 constexpr int kCells = 8;  // ... of the column-parallel kernel (cells.hip)
@@ -459,8 +462,13 @@ struct etlg_ctx {
   uint64_t prof_n[kProfSlots] = {0};
 };
 
+// every batch of the process gets a number of its own: an object built from a batch (etlg_batch_duckdb) names the batch by address AND
+// by this number, so that a batch allocated later at a freed batch's address is not taken for it
+inline uint64_t next_batch_serial() { static std::atomic<uint64_t> n{0}; return ++n; }
+
 struct etlg_batch {
   etlg_ctx* ctx = nullptr;
+  uint64_t serial = next_batch_serial();
   etlg_batch_view v{};
   OutSet* dev = nullptr;  // owned device arrays (OUTPUT_ON_DEVICE) — returned to the pool on free
   // host copy of the arena (etlg_batch_download / host-output decode): one pinned block from the context's pool
@@ -544,5 +552,7 @@ struct etlg_rowbinary {
   HandoffBlocks m;
   bool updates = false;               // built by etlg_batch_duckdb(ETLG_DL_UPDATES): `col_ends` is valid (etlg_rowbinary_col_ends_get)
   const uint32_t* col_ends = nullptr; // [n_rows x n_cols]: block d_c (device) or behind the bytes in the pinned block (host); null without rows
+  // built by etlg_batch_duckdb: of which batch, slot and `what` (etlg_ducklake_fingerprints takes the three objects of ONE batch and slot)
+  const etlg_batch* dl_batch = nullptr; uint64_t dl_serial = 0; int32_t dl_slot = -1; uint32_t dl_what = ~0u;
 };
 

@@ -169,6 +169,25 @@ class Batch:
         r.n_cols = len(raw)
         return r
 
+    def ducklake_fingerprints(self, slot, names, ranges, tuples, predicates, updates=None):
+        """DuckLake batch identities of schema slot `slot`, hashed on the device (etlg_ducklake_fingerprints): for every
+        (first_event, end_event, seed) of `ranges` — ascending, disjoint — the FNV-1a-64 state after `seed` has absorbed the byte stream
+        of the slot's Insert / Update / Delete events in [first_event, end_event). `tuples` / `predicates` / `updates` (or None): the
+        device-resident results of duckdb(slot, names, what=abi.DL_TUPLES / DL_PREDICATES / DL_UPDATES, on_device=True) on this batch.
+        Returns (np.uint64[len(ranges)], abi.DlFpInfo); with info.status == abi.RB_NEEDS_HOST the array holds nothing."""
+        raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        blob = b"".join(n + b"\0" for n in raw)
+        rs = (abi.DlRange * max(1, len(ranges)))()
+        for i, (first, end, seed) in enumerate(ranges):
+            rs[i].first_event, rs[i].end_event, rs[i].seed = int(first), int(end), int(seed)
+        out = np.zeros(len(ranges), dtype=np.uint64)
+        info = abi.DlFpInfo()
+        rc = self.dec.L.etlg_ducklake_fingerprints(self.dec.h, self.h, slot, tuples.h, predicates.h, updates.h if updates is not None else None, blob, len(raw),
+                                                   C.addressof(rs), len(ranges), out.ctypes.data, C.byref(info))
+        if rc != abi.OK:
+            raise self.dec.last_error()
+        return out, info
+
     def close(self):
         if self.h:
             self.dec.L.etlg_batch_free(self.h)

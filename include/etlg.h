@@ -979,6 +979,56 @@ int32_t etlg_rowbinary_view_get(const etlg_rowbinary* rb, etlg_rowbinary_view* o
 int32_t etlg_rowbinary_col_ends_get(const etlg_rowbinary* rb, const uint32_t** col_ends);
 void etlg_rowbinary_free(etlg_rowbinary* rb);
 
+/* DuckLake batch identities for ONE schema slot, hashed on the device: the fingerprint of the `batch_id` every atomic batch of the sink
+ * gets (build_mutation_batch_identity, crates/etl-destinations/src/ducklake/batches.rs:1402-1446; build_copy_batch_identity :1449-1464).
+ * The fingerprint is BatchIdHasher (:260-289), FNV-1a-64: h = (h ^ byte) * 0x100000001b3 from 0xcbf29ce484222325, byte by byte over
+ * every literal of every row of the batch — the texts etlg_batch_duckdb wrote. `tuples`, `predicates` and `updates` (may be NULL) are the
+ * objects etlg_batch_duckdb returned for THIS batch and slot with ETLG_DL_TUPLES, ETLG_DL_PREDICATES and ETLG_DL_UPDATES, built with
+ * ETLG_F_OUTPUT_ON_DEVICE and of status ETLG_RB_OK: their bytes are hashed where they lie, nothing is encoded again or downloaded.
+ * out[i] (HOST, n_ranges entries) is the hasher's state after ranges[i].seed has absorbed the byte stream of the slot's Insert / Update /
+ * Delete events with index in [first_event, end_event), in event order; events of other slots and of every other kind are skipped, an
+ * empty range gives its seed. The host keeps what is cheap and serial: cutting the batch into atomic batches
+ * (prepare_mutation_table_batches), the seed — the state after "mutation" or "copy" and table_name.id(), both hashed as strings — and the
+ * format! of the id (build_batch_identity :1536-1553).
+ * The byte stream restates Rust's Hash impls as the reference drives them through Hasher::write: a str / String is its bytes followed by
+ * one 0xFF, a u64 / usize 8 little-endian bytes. Per event of a WAL batch: le64(start_lsn) le64(commit_lsn), then, with T the event's
+ * ETLG_DL_TUPLES record and P its ETLG_DL_PREDICATES record:
+ *   Insert                                                    "insert" FF T FF
+ *   Delete                                                    "delete" FF P FF
+ *   full Update with an old image (ETLG_OLD_FULL / _KEY)      "update" FF P FF T FF
+ *   full Update without one (TableMutation::Replace)          "replace" FF P FF T FF
+ *   partial Update (records 2k, 2k + 1 of `updates`)          "update" FF R(2k+1) FF le64(n_cols), then for every column c that is not
+ *                                                             MISSING, in slot order: le64(c) lit_c FF — lit_c cut out of record 2k by
+ *                                                             col_ends, minus the quoted name and " = " (hash_partial_table_row_ref,
+ *                                                             :1562-1594; etlg_rowbinary_col_ends_get)
+ * Per row of a table-copy batch: P FF T FF, P over the primary-key columns, no LSNs (:1458-1461).
+ * col_names / n_names as for etlg_batch_duckdb (the quoted names' lengths cut the SET pieces).
+ * A slot event inside a range that has no record where the table needs one — the events the reference refuses, which the three calls
+ * count in n_host_rows, and a partial Update when `updates` is NULL — gives ETLG_OK with info->status ETLG_RB_NEEDS_HOST, host_event =
+ * the first such event, and no fingerprint is written. ETLG_InvalidArgument: an object of another batch, slot or `what`, one on the
+ * host or of status ETLG_RB_NEEDS_HOST; n_names other than the slot's column count; ranges that are not ascending and disjoint.
+ * (An object names its batch by address and by a number every batch of the process gets once: an object that outlived its batch is
+ * refused too, also when a later batch lies at the freed one's address.)
+ * Batch requirements as for etlg_batch_columns. The call stops for the device once, at its end.
+ * THE STREAM IS UNPINNED. The reference's tests (batches.rs:3290-3396) assert only that ids are equal or differ; no fingerprint is
+ * written down anywhere as a number. Pinned are FNV-1a itself (the standard vectors "" cbf29ce484222325, "a" af63dc4c8601ec8c, "foobar"
+ * 85944171f73967e8) and the records' bytes (the DuckLake tests). The interleaving above is restated in one function on each side —
+ * fp_walk in etl_amd/csrc/fingerprint.hip, event_stream in tests/ducklake_identity.py — and a deployment that switches between
+ * host-computed and device-computed ids across a restart depends on that restatement. */
+typedef struct etlg_dl_range {
+  uint64_t first_event; /* [first_event, end_event) in the batch's event order */
+  uint64_t end_event;
+  uint64_t seed;        /* the hasher's state the range starts from */
+} etlg_dl_range;
+typedef struct etlg_dl_fp_info {
+  uint32_t status;      /* ETLG_RB_OK | ETLG_RB_NEEDS_HOST */
+  uint32_t _pad;
+  uint64_t host_event;  /* NEEDS_HOST: the first slot event inside a range that lacks a record; else ~0 */
+} etlg_dl_fp_info;
+int32_t etlg_ducklake_fingerprints(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const etlg_rowbinary* tuples,
+                                   const etlg_rowbinary* predicates, const etlg_rowbinary* updates, const char* col_names, uint32_t n_names,
+                                   const etlg_dl_range* ranges, uint32_t n_ranges, uint64_t* out, etlg_dl_fp_info* info);
+
 /* --------------------------------------------------------------- size hints */
 
 /* Event::size_hint (crates/etl/src/event.rs:295-320) for every event of a batch, computed on the device from the
