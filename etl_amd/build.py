@@ -2,6 +2,7 @@
 + C ABI, cross-compiled for gfx950 with hipcc — works without a GPU) and
 libetlg_synth.so (synthetic WAL generator, plain g++)."""
 import os
+import re
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
@@ -20,10 +21,25 @@ SOURCES = ["rowformats.hip", "rowformats_dl.hip", "columns.hip", "kernels.hip", 
 # -O2, -fno-unroll-loops and the scheduler strategies move nothing on rows.hip / plan.hip: profiles/r06zv_compile_flag_sweep.txt)
 OPT = {"fused.hip": "-Os", "cells.hip": "-Os"}
 DEFS = {}   # no per-source feature flags: one code path per kernel
-# what every object depends on beside its own source (the shared headers); host.cpp also on its parts
-COMMON = ["../build.py", "dev_types.h", "codec.hip.h", "cellparse.hip.h", "handoff.hip.h", "rowformats.hip.h", "lookback.hip.h", "utf8_swar.h", "float_fast.h", "float_slow.h", "pow5_table.h", "float_json.h", "ryu_table.h", "float_display.h", os.path.join("..", "..", "include", "etlg.h")]
-EXTRA = {"fused.hip": ["fixed_tile.hip.h"], "host.cpp": ["host_state.h", "host_control.inc", "host_handoff.inc", "host_orchestrate.inc"]}
-DEPS = SOURCES + COMMON + [d for v in EXTRA.values() for d in v]   # (the library as a whole)
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
+
+
+def headers_of(src):
+    """The project headers a source includes, directly or through other headers (its .inc parts too): the #include "..." lines followed
+    from the file that names them, as paths relative to csrc. No compiler runs; an include inside an #if counts whether it is taken or not."""
+    seen, todo = [], [src]
+    while todo:
+        cur = todo.pop()
+        for inc in _INCLUDE.findall(open(os.path.join(CSRC, cur)).read()):
+            rel = os.path.normpath(os.path.join(os.path.dirname(cur), inc))
+            if rel not in seen and rel != src:
+                seen.append(rel)
+                todo.append(rel)
+    return sorted(seen)
+
+
+# the library as a whole: every source and the union of their headers
+DEPS = SOURCES + sorted({h for s in SOURCES for h in headers_of(s)}) + ["../build.py"]
 
 
 def _stale(target, deps):
@@ -41,7 +57,8 @@ def build_native(force=False, verbose=False):
 
     def compile_one(src):
         obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
-        if force or _stale(obj, [os.path.join(CSRC, d) for d in [src] + COMMON + EXTRA.get(src, [])]):
+        # an object is stale against its own source, the headers that source includes, and this file
+        if force or _stale(obj, [os.path.join(CSRC, d) for d in [src] + headers_of(src) + ["../build.py"]]):
             cmd = [HIPCC, "--offload-arch=gfx950", OPT.get(src, "-O3"), "-std=c++17", "-fPIC", "-Wall",
                    "-Wno-unused-function"] + DEFS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
             if src.endswith(".cpp"):

@@ -3,7 +3,7 @@
 // arr_spans). cell_text_error() joins them into the question ETLG_F_CHECK_CELLS asks of a DEFERRED cell: would the reference's
 // parse_cell_from_postgres_text have failed on this text, and with which code?
 #pragma once
-#include "codec.hip.h"
+#include "values.hip.h"
 #include "float_slow.h"
 
 namespace etlg {

@@ -27,14 +27,17 @@
 // Table-copy rows (etlg_copy_decode) run through the same tile: k_cells<.., COPYK> stages 64 COPY text
 // rows instead of 64 frames and cells_tile<.., 2, ..> replaces P1's tuple walk by the COPY field splitter
 // (window bitmaps -> row walk in registers -> the fields with backslashes finished by all waves).
-#define ETLG_FLOAT_CALL static __device__ __attribute__((noinline))
-#define ETLG_DBG_WORD dbg_u   // cells_tile / k_cells keep the debug word in a scalar register of its own
-#define ETLG_TSTAMP_WHO (wave == 0 && lane == 0)   // phase clocks are taken by the tile's spine wave (its role rotates, see cells_tile)
 #include <type_traits>
 #include "lookback.hip.h"
 #include "utf8_swar.h"
 
+// cells_tile / k_cells keep the debug word in a scalar register of its own; phase clocks are taken by the tile's spine wave (its role
+// rotates, see cells_tile)
+#define TSTAMP(k) ETLG_PHASE_STAMP(k, dbg_u, wave == 0 && lane == 0)
+
 namespace etlg {
+
+constexpr uint32_t kCellsCodec = CODEC_FLOAT_CALL;   // the codec variant of this kernel (values.hip.h): floats parsed out of line
 
 constexpr int CF = 64;         // frames per tile
 // Replicated columns per slot: two instantiations. NARROW: <= 16 columns — one 32-bit state word per row image, 16 + 16-bit column
@@ -620,10 +623,10 @@ DEV void cells_tile(const DecParams& p, const DecParams& pg, const FusedParams& 
           const uint32_t u = __builtin_amdgcn_readfirstlane(cls);
           if (cls == u) {
             if (FC != 0 && (u == ETLG_TC_F32 || u == ETLG_TC_F64)) {  // parsed once: P3 takes the value from the cache
-              const int r = parse_float_fast(d, len, u == ETLG_TC_F32, fbits, use_lds);
+              const int r = parse_float_fast_call(d, len, u == ETLG_TC_F32, fbits, use_lds);
               h = r == 1 ? pad4(len) : 0u;
               fok = r == 0;
-            } else h = cell_heap_bytes(u, d, len, use_lds);
+            } else h = cell_heap_bytes<kCellsCodec>(u, d, len, use_lds);
             done = true;
           }
         }
@@ -675,7 +678,7 @@ DEV void cells_tile(const DecParams& p, const DecParams& pg, const FusedParams& 
         }
       } else {
         RowMsg dummy{};
-        size_frame(p, v, tx, wire_ok, dummy, emit, fixed, heap, pay, row_slot, seq_lb != 0);
+        size_frame<kCellsCodec>(p, v, tx, wire_ok, dummy, emit, fixed, heap, pay, row_slot, seq_lb != 0);
       }
     }
     {  // exclusive prefix of the cells' heap bytes in tuple order (old image, then new image): all
@@ -854,7 +857,7 @@ DEV void cells_tile(const DecParams& p, const DecParams& pg, const FusedParams& 
       bool done = false;
       while (!done) {  // waterfall over the distinct classes of this wave's cells
         const uint32_t u = __builtin_amdgcn_readfirstlane(cls);
-        if (cls == u) { err = decode_text_cell<false>(u, base + pos, len, slotp, pg.heap, hcur, st, use_lds); done = true; }
+        if (cls == u) { err = decode_text_cell<false, kCellsCodec>(u, base + pos, len, slotp, pg.heap, hcur, st, use_lds); done = true; }
       }
     } else if (act && kind == CT_N) {
       if (!col.nullable && !(pg.flags & 2u)) err = ETLG_E_REQUIRED_NULL; else slot_zero(slotp, cls);
@@ -928,7 +931,7 @@ DEV void cells_tile(const DecParams& p, const DecParams& pg, const FusedParams& 
     pg.ev_body[ev_idx] = fx_off;
   } else {
     RowMsg dummy{};
-    write_frame(p, v, tx, dummy, -1, ev_idx, fx_off, hp_off, nullptr, use_lds);
+    write_frame<false, kCellsCodec>(p, v, tx, dummy, -1, ev_idx, fx_off, hp_off, nullptr, use_lds);
   }
   TSTAMP(8);
 }
@@ -962,10 +965,7 @@ __global__ __launch_bounds__(NW * 64, ETLG_CELLS_MINBLOCKS) void k_cells(DecPara
   __shared__ uint8_t vinv[COPYK ? 64 : 1];
   __shared__ uint32_t cxm[COPYK ? CF : 1];
   const uint32_t tid = threadIdx.x;
-  if (q.clear_words) {  // descriptors are double buffered: this launch clears the buffer the next batch will use
-    const uint32_t per = (q.clear_words + gridDim.x - 1) / gridDim.x;
-    for (uint32_t i = tid; i < per; i += NW * 64) { const uint32_t w = blockIdx.x * per + i; if (w < q.clear_words) q.d_clear[w] = 0; }
-  }
+  clear_next_descriptors<NW * 64>(q.d_clear, q.clear_words, tid);
   if (!(pg.flags & 16u) && !load_carry(pg)) return;  // ASYNC chain: the state the batch before this one left (flags bit 4: read late, by the tiles that need it — txn_lookback)
   if constexpr (COPYK) { if (blockIdx.x == 0 && tid == 0) pg.res->copy_span = pg.offs[pg.nframes] - pg.offs[0]; }
   DecParams p = pg;

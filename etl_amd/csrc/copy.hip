@@ -23,7 +23,7 @@
 // becomes an all-NULL tuple); "not properly terminated" / more / fewer columns come after the
 // errors of the cells that were completed before them (rank COPY_SHAPE > DECODE; missing cells
 // are padded with NULLs so that the completed ones still decode and report theirs).
-#include "codec.hip.h"
+#include "frames.hip.h"
 
 namespace etlg {
 

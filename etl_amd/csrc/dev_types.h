@@ -154,7 +154,7 @@ struct DecParams {
   const DevEpoch* epochs;
   const DevSlot* slots;
   const DevCol* cols;   // ETLG_F_CHECK_CELLS: the n_cols records are followed by n_cols bytes, the element class of every array column
-                        // (etlg_array_elem_class; 0 otherwise) — chk_elem_table(), codec.hip.h. The structure itself did not grow: the
+                        // (etlg_array_elem_class; 0 otherwise) — chk_elem_table(), values.hip.h. The structure itself did not grow: the
                         // argument blocks of the single-pass kernels are laid out as before
   // per-frame scratch
   uint8_t* f_tag;

@@ -20,7 +20,9 @@
 //   k_fp_fold    (D) per range: the pieces' maps folded in order from the seed
 // Piece (chunk c, range i) has id c + i: along the stream a next piece has a larger chunk or a larger range, so ids are unique, and the
 // pieces of one range are consecutive.
-#include "codec.hip.h"
+#include "../../include/etlg.h"
+#include "dev_types.h"
+#include "device.hip.h"
 
 extern "C" void etlg_k_scan_lens(const uint32_t* lens, uint64_t n, unsigned long long* blk, int64_t* offsets, hipStream_t st);   // columns.hip
 

@@ -1,4 +1,4 @@
-// float4 / float8 text -> IEEE bits: the exact fast path shared by the kernels (codec.hip.h) and a
+// float4 / float8 text -> IEEE bits: the exact fast path shared by the kernels (values.hip.h) and a
 // host-side unit test (tests/test_float_fast.py compiles this header with g++ and checks it against
 // strtod / strtof on millions of texts).
 #pragma once

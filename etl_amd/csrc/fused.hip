@@ -33,6 +33,8 @@
 #endif
 #include "fixed_tile.hip.h"  // fixed-width plan: schema-constant sizing for tiles of Begin / Commit / fixed-width Insert frames
 
+#define TSTAMP(k) ETLG_PHASE_STAMP(k, q.dbg, threadIdx.x == 0)
+
 namespace etlg {
 
 // Everything after staging; `base` points at byte `win0` of the input (LDS or global).
@@ -165,10 +167,7 @@ __global__ __launch_bounds__(BLK, ETLG_MINWAVES) void k_fused(DecParams pg, Fuse
   __shared__ uint32_t s32[16];
   __shared__ uint64_t s64[8];
   const uint32_t tid = threadIdx.x;
-  if (q.clear_words) {  // descriptors are double buffered: this launch clears the buffer the next batch will use
-    const uint32_t per = (q.clear_words + gridDim.x - 1) / gridDim.x;
-    for (uint32_t i = tid; i < per; i += BLK) { const uint32_t w = blockIdx.x * per + i; if (w < q.clear_words) q.d_clear[w] = 0; }
-  }
+  clear_next_descriptors<BLK>(q.d_clear, q.clear_words, tid);
   if (!(pg.flags & 16u) && !load_carry(pg)) return;  // ASYNC chain: the state the batch before this one left (flags bit 4: read late, by the tiles that need it — txn_lookback)
   DecParams p = pg;  // side-table pointers of `p` are redirected to the LDS copy below
   if ((q.dbg & 8) && tid == 0) s64[7] = clock64();

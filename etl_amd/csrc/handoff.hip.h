@@ -2,7 +2,6 @@
 // Display of a json cell (json_display), the Display strings of numeric / time / timetz, and the byte sinks the row formats and the
 // formatted Arrow columns write through. Only DEV functions, templates, structs and constants: no kernel, no extern "C".
 #pragma once
-#include "codec.hip.h"
 #include "cellparse.hip.h"   // json_valid, arr_walk, arr_spans: shared with the multi-pass decode (kernels.hip)
 #include <type_traits>
 

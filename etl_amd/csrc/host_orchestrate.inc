@@ -161,7 +161,7 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
     ss->o_ptabs = ss->o_cols + al64(dc.size() * (sizeof(DevCol) + 1) + 16);   // (the records, then one element-class byte per record)
     ss->o_pcols = ss->o_ptabs + al64(pt.size() * sizeof(PlanTab) + 16);
     // ETLG_F_CHECK_CELLS: the element class of every array column, in DevCol order (build_slots pushes no column for a dead slot),
-    // stored directly behind the DevCol records (chk_elem_table, codec.hip.h)
+    // stored directly behind the DevCol records (chk_elem_table, values.hip.h)
     std::vector<uint8_t> ce;
     ss->chk_any = false; ss->chk_maxc = 0;
     for (int32_t li : live) {

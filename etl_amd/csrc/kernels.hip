@@ -22,7 +22,7 @@
 //
 // Integer / byte work only: no MFMA. All inter-workgroup data flows through
 // kernel boundaries (no in-kernel hand-offs), so there are no spin waits.
-#include "codec.hip.h"
+#include "frames.hip.h"
 #include "cellparse.hip.h"   // ETLG_F_CHECK_CELLS: k_write_chk validates json / array cells where it defers them
 
 namespace etlg {
@@ -226,7 +226,7 @@ DEV void write_body(const DecParams& p) {
   write_frame<CHECK>(p, v, tx, m, -1, ev_idx, fx_off, hp_off);
 }
 __global__ __launch_bounds__(kBlock) void k_write(DecParams p) { write_body<false>(p); }
-// ETLG_F_CHECK_CELLS: the same pass with the json / array cells validated where they are deferred (write_row<true>, codec.hip.h), so
+// ETLG_F_CHECK_CELLS: the same pass with the json / array cells validated where they are deferred (write_row<true>, frames.hip.h), so
 // that a cell the reference rejects ends the batch at its frame, in the reference's order (old image before new image, column order)
 __global__ __launch_bounds__(kBlock) void k_write_chk(DecParams p) { write_body<true>(p); }
 

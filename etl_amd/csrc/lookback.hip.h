@@ -1,6 +1,8 @@
-// Two-level decoupled look-back shared by the single-pass kernels (fused.hip, cells.hip).
+// Two-level decoupled look-back shared by the single-pass kernels (fused.hip, cells.hip, rows.hip, plan.hip, scan.hip), with the
+// pieces of a single-pass kernel's head and tail that go with it: the descriptor clear, the transaction look-back, the side-table
+// copy, the sampled phase clocks. Restates no reference section of its own (the transaction state it carries is A1/A2, frames.hip.h).
 #pragma once
-#include "codec.hip.h"
+#include "frames.hip.h"
 
 namespace etlg {
 
@@ -48,19 +50,9 @@ struct OpAdd {
 DEV void lookback_publish(unsigned long long* desc, uint32_t tile, uint64_t agg) {
   if ((threadIdx.x & 63) == 0) __hip_atomic_store(&desc[tile], ST_AGG | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// The first words a resolve looks at, requested ahead of time (a wave that resolves two tiles back to back asks for both tiles'
-// words before it waits for the first: their round trips overlap). A word that has not been published yet is simply polled again.
+// The first words a resolve looks at, where a caller requested them ahead of time (lane l: desc[g * 64 + l] for l < j, and
+// gdesc[g - 64 + l]). A word that has not been published yet is simply polled again.
 struct LookbackPre { unsigned long long w0 = 0, w1 = 0; bool valid = false; };
-DEV LookbackPre lookback_prefetch(unsigned long long* desc, unsigned long long* gdesc, uint32_t tile) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t g = tile >> 6, j = tile & 63;
-  LookbackPre r;
-  r.valid = true;
-  if ((uint32_t)lane < j) r.w0 = __hip_atomic_load(&desc[(g << 6) + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int64_t idx = (int64_t)g - 1 - 63 + lane;
-  if (idx >= 0) r.w1 = __hip_atomic_load(&gdesc[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return r;
-}
 template <class Op>
 DEV uint64_t lookback_resolve(unsigned long long* desc, unsigned long long* gdesc, uint32_t tile, uint64_t agg, uint64_t carry, uint32_t* fail,
                               const LookbackPre& pre = LookbackPre());
@@ -100,7 +92,7 @@ DEV uint64_t lookback_resolve(unsigned long long* desc, unsigned long long* gdes
   }
   // ordered fold, lower lane = older: inclusive scan then take lane j-1
   uint64_t v0 = (uint32_t)lane < j ? (uint64_t)(w0 & ~ST_MASK) : Op::id();
-  // DPP ladder (see wave_scan_incl in codec.hip.h) on the two halves of the 64-bit payload; Op::id() == 0
+  // DPP ladder (see wave_scan_incl in device.hip.h) on the two halves of the 64-bit payload; Op::id() == 0
 #define ETLG_LB_DPP(ctrl, rmask) { \
     const uint32_t lo_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v0, ctrl, rmask, 0xF, false); \
     const uint32_t hi_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v0 >> 32), ctrl, rmask, 0xF, false); \
@@ -150,14 +142,22 @@ DEV uint64_t lookback_resolve(unsigned long long* desc, unsigned long long* gdes
   return Op::f(acc, local);
 }
 
-// phase clocks are sampled (1 tile in 16): thousands of same-address atomics would distort what they measure
-#ifndef ETLG_DBG_WORD
-#define ETLG_DBG_WORD q.dbg
-#endif
-#ifndef ETLG_TSTAMP_WHO
-#define ETLG_TSTAMP_WHO (threadIdx.x == 0)
-#endif
-#define TSTAMP(k) do { if ((ETLG_DBG_WORD & 8) && ETLG_TSTAMP_WHO && (blockIdx.x & 15) == 3) { const unsigned long long _t = clock64(); atomicAdd(&p.res->dbg_t[k], _t - s64[7]); s64[7] = _t; } } while (0)
+// Phase clock k of a single-pass kernel (debug word `dbg`, bit 3): the cycles since the last stamp, kept in s64[7], added to dbg_t[k] by
+// the one lane `who` names. Sampled (1 tile in 16): thousands of same-address atomics would distort what they measure. The debug word
+// and the predicate are arguments; each kernel source wraps this in a short TSTAMP(k) with its own. Expands in the kernel's scope (`p`,
+// `s64`) and stays a macro: as a DEV function, with the predicate a bool or a lambda, k_fused came out ~1 KB shorter, and the kernels are
+// to stay what they were.
+#define ETLG_PHASE_STAMP(k, dbg, who) do { if (((dbg) & 8) && (who) && (blockIdx.x & 15) == 3) { const unsigned long long _t = clock64(); atomicAdd(&p.res->dbg_t[k], _t - s64[7]); s64[7] = _t; } } while (0)
+
+// The look-back descriptors are double buffered: every launch of a single-pass kernel clears the buffer the next batch will use,
+// each workgroup its share. NT = threads per workgroup.
+template <int NT>
+DEV void clear_next_descriptors(unsigned long long* d_clear, uint32_t clear_words, uint32_t tid) {
+  if (clear_words) {
+    const uint32_t per = (clear_words + gridDim.x - 1) / gridDim.x;
+    for (uint32_t i = tid; i < per; i += NT) { const uint32_t w = blockIdx.x * per + i; if (w < clear_words) d_clear[w] = 0; }
+  }
+}
 
 DEV uint32_t seg_pack30(uint32_t seg) { return ((seg >> 31) << 29) | (seg & 0x1FFFFFFFu); }
 DEV uint32_t seg_unpack30(uint32_t s30) { return ((s30 >> 29) << 31) | (s30 & 0x1FFFFFFFu); }

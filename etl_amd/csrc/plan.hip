@@ -31,6 +31,10 @@
 // INT2/INT4/INT8/OID/BOOL (codec/text.rs:35-51,135-138, codec/bool.rs:11-19), payload accounting (codec/event.rs:261-297).
 #include "lookback.hip.h"
 
+#ifndef ETLG_PLAN_MINWAVES
+#define ETLG_PLAN_MINWAVES 5   // k_plan: waves per SIMD the register allocator leaves room for (96 VGPRs; the ~8 KB LDS window per wave allows ~5)
+#endif
+
 namespace etlg {
 
 // ---- aligned readers: `off` is a byte offset into the tile's window
@@ -58,7 +62,7 @@ template <class M> DEV uint64_t rd64(const M& m, uint32_t off) {
 }
 DEV uint64_t bswap64(uint64_t v) { return __builtin_bswap64(v); }
 
-// Four ASCII digits, most significant in byte 0 (codec.hip.h digits4 without the flag plumbing): value, and a
+// Four ASCII digits, most significant in byte 0 (values.hip.h digits4 without the flag plumbing): value, and a
 // non-zero `bad` accumulator when a byte is not a digit.
 DEV uint32_t dig4(uint32_t w, uint32_t& bad) {
   const uint32_t t = w - 0x30303030u;
@@ -487,7 +491,7 @@ DEV void plan_local(const DecParams& p, const PlanParams& q, const M& m, u8* row
   // (storing the header columns that do not depend on the look-back here, early, was tried: the descriptor loads of the finish
   // phase then queue behind those stores — memory operations of a wave return in order — and the kernel got 4 us slower)
   L.tbl = isB ? b_xid : (isI || isD) ? rel : 0u; L.slot_id = (isI || isD) ? slot_id : 0u; L.pm = pm; L.x_fx = x_fx; L.fixed_dw = fixed_dw; L.vbytes = vbytes; L.bad = bad;
-  if (isD) c_flags = ETLG_OLD_KEY;   // the event's flags column: which old row a Delete carries (write_frame, codec.hip.h)
+  if (isD) c_flags = ETLG_OLD_KEY;   // the event's flags column: which old row a Delete carries (write_frame, frames.hip.h)
   L.tagf = tag | (c_flags << 8) | (((isI || isD) ? 1u : 0u) << 16) | ((isB ? 1u : 0u) << 17) | ((isC ? 1u : 0u) << 18) | ((live ? 1u : 0u) << 19);
   L.wal_start = wal_start; L.b_lsn = b_lsn; L.rimg = rimg;
   if (keep) {
@@ -728,10 +732,7 @@ DEV void plan_kernel(DecParams& p, const PlanParams& q_in, u8* smem) {
   unsigned long long tprev = (q.dbg & 32u) ? clock64() : 0ull;
   const uint32_t tile = blockIdx.x;   // (the timeline's slot)
   WSTAMP(0);
-  if (q.clear_words) {  // descriptors are double buffered: this launch clears the buffer the next batch will use
-    const uint32_t per = (q.clear_words + gridDim.x - 1) / gridDim.x;
-    for (uint32_t i = lane; i < per; i += 64) { const uint32_t w = blockIdx.x * per + i; if (w < q.clear_words) q.d_clear[w] = 0; }
-  }
+  clear_next_descriptors<64>(q.d_clear, q.clear_words, lane);
   // ASYNC chain: the state the batch before this one left on the device — read now (that batch has finished: same stream), or, for
   // a batch the host put on the second stream, by the few tiles that need it, when they need it (plan_late_carry)
   if (!(p.flags & 16u) && !load_carry(p)) return;

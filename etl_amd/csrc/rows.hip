@@ -27,14 +27,15 @@
 // frame with more than 32 KiB of heap entries or longer than 64 KiB, more than 16 groups in one tile. Errors are recorded
 // at their frame like everywhere else and send the batch to the multi-pass kernels for the exact cut (the code recorded
 // here only has to be SOME error of that frame).
-#define ETLG_FLOAT_CALL static __device__ __attribute__((noinline))
-#define ETLG_DBG_WORD dbg_u
-#define ETLG_TSTAMP_WHO (spine && lane == 0)
-#define ETLG_TEMPORAL_SWAR 1   // timestamps / whole-hour offsets decided from registers (codec.hip.h)
 #include "lookback.hip.h"
 #include "utf8_swar.h"
 
+#define TSTAMP(k) ETLG_PHASE_STAMP(k, dbg_u, spine && lane == 0)
+
 namespace etlg {
+
+// the codec variant of this kernel (values.hip.h): timestamps / whole-hour offsets decided from registers, floats parsed out of line
+constexpr uint32_t kRowsCodec = CODEC_TEMPORAL_SWAR | CODEC_FLOAT_CALL;
 
 constexpr int RNW = 4;          // waves per tile
 constexpr uint32_t kRowsGaveUp = 16u;
@@ -68,10 +69,7 @@ __global__ __launch_bounds__(NW * 64, ETLG_ROWS_MINBLOCKS) void k_rows(DecParams
   __shared__ uint32_t s32[16];
   __shared__ uint64_t s64[12];
   const uint32_t tid = threadIdx.x, lane = tid & 63;
-  if (q.clear_words) {  // descriptors are double buffered: this launch clears the buffer the next batch will use
-    const uint32_t per = (q.clear_words + gridDim.x - 1) / gridDim.x;
-    for (uint32_t i = tid; i < per; i += NW * 64) { const uint32_t w = blockIdx.x * per + i; if (w < q.clear_words) q.d_clear[w] = 0; }
-  }
+  clear_next_descriptors<NW * 64>(q.d_clear, q.clear_words, tid);
   if (!(pg.flags & 16u) && !load_carry(pg)) return;  // ASYNC chain: the state the batch before this one left (flags bit 4: read late, by the tiles that need it)
   DecParams p = pg;
   uint32_t dbg_u, cf, maxc;
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(NW * 64, ETLG_ROWS_MINBLOCKS) void k_rows(DecParams
     } else if (live && !isrow) {
       RowMsg dummy{};
       int rs = -1;
-      size_frame(p, v, tx, wire_ok, dummy, emit, fixed, heap, pay, rs, false, true);   // (records the wire error of a malformed frame)
+      size_frame<kRowsCodec>(p, v, tx, wire_ok, dummy, emit, fixed, heap, pay, rs, false, true);   // (records the wire error of a malformed frame)
     }
     const uint32_t ifx = wave_scan_add(fixed >> 2);
     tot_f = wave_last(ifx);
@@ -394,7 +392,7 @@ __global__ __launch_bounds__(NW * 64, ETLG_ROWS_MINBLOCKS) void k_rows(DecParams
             nbytes = len >= 2 ? (len - 2) >> 1 : 0u; kind = HK_BYTEA;
           } else if (cls == ETLG_TC_F32 || cls == ETLG_TC_F64) {
             uint64_t bits = 0;
-            const int r = parse_float_fast(d, len, cls == ETLG_TC_F32, bits, true);
+            const int r = parse_float_fast_call(d, len, cls == ETLG_TC_F32, bits, true);
             if (r == 2) bad = 1;
             if (r == 0) { st64(slotp, bits); kind = HK_NONE; nbytes = 0; }
             else st = ETLG_CELL_DEFERRED;
@@ -414,7 +412,7 @@ __global__ __launch_bounds__(NW * 64, ETLG_ROWS_MINBLOCKS) void k_rows(DecParams
         } else {
           uint32_t tmp[4] = {0, 0, 0, 0};
           uint32_t hdummy = 0;
-          const uint32_t err = decode_text_cell<false>(cls, d, len, tmp, nullptr, hdummy, st, true);
+          const uint32_t err = decode_text_cell<false, kRowsCodec>(cls, d, len, tmp, nullptr, hdummy, st, true);
           if (err) bad = 1;
           else {
             const uint32_t nw = slot_bytes(cls) >> 2;
@@ -622,7 +620,7 @@ __global__ __launch_bounds__(NW * 64, ETLG_ROWS_MINBLOCKS) void k_rows(DecParams
       } else {
         // Truncate / Relation events (rare): the generic writer
         RowMsg dummy{};
-        write_frame(p, v, tx, dummy, -1, ev_idx, fx_off, 0, nullptr, true);
+        write_frame<false, kRowsCodec>(p, v, tx, dummy, -1, ev_idx, fx_off, 0, nullptr, true);
       }
     }
     ETLG_WAVE_PRIO(0);
@@ -664,7 +662,7 @@ __global__ __launch_bounds__(NW * 64, ETLG_ROWS_MINBLOCKS) void k_rows(DecParams
           slotp[0] = dst;
           if (kind != HK_COPY) {
             uint32_t tmp[4] = {0, 0, 0, 0}, st = 0, hcur = dst;
-            const uint32_t err = decode_text_cell<false>(kind == HK_NUMERIC ? (uint32_t)ETLG_TC_NUMERIC : (uint32_t)ETLG_TC_BYTEA, base + pos, len, tmp, pg.heap, hcur, st, true);
+            const uint32_t err = decode_text_cell<false, kRowsCodec>(kind == HK_NUMERIC ? (uint32_t)ETLG_TC_NUMERIC : (uint32_t)ETLG_TC_BYTEA, base + pos, len, tmp, pg.heap, hcur, st, true);
             if (err) record_error(pg, f0 + lane, RK_DECODE, err);
             else slotp[1] = tmp[1];
           }

@@ -1,440 +1,19 @@
-// Device-side codec shared by the multi-pass kernels (kernels.hip) and the fused
-// single-pass kernel (fused.hip): byte readers, workgroup scans, pgoutput message
-// walkers, the text value codecs and the row writers. Everything is
-// __forceinline__ and pointer based: called with a pointer derived from LDS the
-// loads become ds_read, with a pointer into the input buffer global_load.
+// Text value codecs: one Postgres text cell -> its arena slot words / heap entry. UTF-8, integers, numeric, the temporal
+// parsers with the chrono fall-back, uuid / hex, floats; what a cell costs on the heap (cell_heap_bytes), the slot layout rule
+// (slot_bytes), decode_text_cell, and the 2-bit cell states of a row. Shared by the decode kernels (through frames.hip.h) and by the
+// hand-off kernels (through cellparse.hip.h), which never see a frame. All pointer based, see device.hip.h.
 //
 // Reference sections restated here (paths relative to the supabase/etl checkout):
-//   wire grammar (A0)          postgres-replication 0.6.7 / PostgreSQL protocol docs
-//   payload accounting (A3)    crates/etl/src/postgres/codec/event.rs:261-297
-//   tuple -> row (A4/A5)       crates/etl/src/postgres/codec/event.rs:554-587, 938-983
+//   tuple cell -> value (A5)   crates/etl/src/postgres/codec/event.rs:938-983 (str::from_utf8 at :976)
 //   value codecs (A6-A10)      crates/etl/src/postgres/codec/{text.rs:32-153,bool.rs:11-19,hex.rs:11-52,time.rs:75-161},
 //                              crates/etl-postgres/src/{numeric.rs:108-458,time.rs:121-207}
-//   update/delete (A11/A12)    crates/etl/src/postgres/codec/event.rs:437-527, 605-923
-//   ownership / cache (A2/A14) crates/etl/src/replication/apply.rs:2836-2867, 3514-3519, 3705-3734
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/etlg.h"
 #include "dev_types.h"
+#include "device.hip.h"
 #include "float_fast.h"
 
 namespace etlg {
-
-typedef uint8_t u8;
-
-#define DEV __device__ __forceinline__
-// The declarations the SIMT test emulator (tests/simt/simt.h) has to substitute: reconvergence markers, out-of-line device
-// functions defined in this header, and the dynamic LDS window of a kernel.
-#ifndef DEV_NOINLINE
-#define DEV_NOINLINE __device__ __attribute__((noinline))
-#endif
-#ifndef ETLG_SCALAR_COPY   // a wave-uniform value in a scalar register of its own (not a member of a spilled register tuple)
-#define ETLG_SCALAR_COPY(dst, src) asm volatile("s_mov_b32 %0, %1" : "=s"(dst) : "s"(src))
-#endif
-#ifndef ETLG_WAVE_PRIO   // s_setprio: the issue arbiter of a SIMD prefers the wave with the higher value (0..3)
-#define ETLG_WAVE_PRIO(n) __builtin_amdgcn_s_setprio(n)
-#endif
-#ifndef ETLG_WAVE_JOIN   // reconvergence point of a divergent region with wave collectives inside: nothing on the GPU
-#define ETLG_WAVE_JOIN() ((void)0)
-#endif
-#ifndef ETLG_CONST_AS      // constant address space (scalar loads of wave-uniform descriptors); the emulator has one address space
-#define ETLG_CONST_AS __attribute__((address_space(4)))
-#endif
-#ifndef ETLG_DYNAMIC_LDS
-#define ETLG_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) u8 name[]
-#endif
-// LDS-DMA (plan.hip): every lane moves 16 bytes from its own global address to (wave-uniform LDS base) + 16 * lane; the data
-// never passes through VGPRs. The wave waits for its pieces with ETLG_VMEM_WAIT before it reads the window.
-#ifndef ETLG_GLDS16
-#define ETLG_GLDS16(g, l) __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(g), (void __attribute__((address_space(3)))*)(l), 16, 0, 0)
-#define ETLG_VMEM_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-// One aligned ds_read_b32. Volatile keeps the compiler from fusing neighbouring dwords into a ds_read_b64 / b128 with 4-byte
-// alignment, which the LDS serves at the misaligned rate (tools/ubench/lds_align.hip: 3.3x the cycles of an aligned read).
-#define ETLG_LDS_AS __attribute__((address_space(3)))
-#define ETLG_LDS_LD32(p) (*(volatile const ETLG_LDS_AS uint32_t*)(p))
-#endif
-// A pair of look-back words (plan.hip): ONE 16-byte load / store that bypasses the non-coherent caches (volatile: sc0 sc1), tracked by
-// the compiler's own s_waitcnt bookkeeping (an inline-asm load would not be). Each 8-byte half validates itself (status bits),
-// so nothing depends on the 16 bytes arriving as one.
-#ifndef ETLG_LD_PAIR
-typedef unsigned int etlg_v4u __attribute__((ext_vector_type(4)));
-#define ETLG_LD_PAIR(ptr, a, l) do { const etlg_v4u t_ = *(const volatile __attribute__((address_space(1))) etlg_v4u*)(ptr); \
-    (a) = ((unsigned long long)t_.y << 32) | t_.x; (l) = ((unsigned long long)t_.w << 32) | t_.z; } while (0)
-#define ETLG_ST_PAIR(ptr, a, l) do { etlg_v4u t_; t_.x = (unsigned int)(a); t_.y = (unsigned int)((unsigned long long)(a) >> 32); t_.z = (unsigned int)(l); \
-    t_.w = (unsigned int)((unsigned long long)(l) >> 32); *(volatile __attribute__((address_space(1))) etlg_v4u*)(ptr) = t_; } while (0)
-#endif
-#ifndef ETLG_PLAN_MINWAVES
-#define ETLG_PLAN_MINWAVES 5   // k_plan: waves per SIMD the register allocator leaves room for (96 VGPRs; the ~8 KB LDS window per wave allows ~5)
-#endif
-#define DEV_DECODE DEV
-
-// ------------------------------------------------------------- staging (k_fused, k_cells)
-// Eight independent 16-byte loads per lane in flight before the first LDS store: one HBM round trip for a
-// 113-byte-per-lane tile.
-template <int NT>
-DEV void stage_chunks(const uint8_t* in, uint8_t* stage, uint32_t a0, uint32_t full_end, uint32_t tid) {
-  constexpr int W = 8;
-  for (uint32_t c = a0 + 16 * tid; c < full_end; c += 16 * NT * W) {
-    uint4 v[W];
-#pragma unroll
-    for (int k = 0; k < W; k++) {
-      const uint32_t ck = c + 16 * NT * k;
-      v[k] = make_uint4(0, 0, 0, 0);
-      if (ck < full_end) v[k] = *(const uint4*)(in + ck);
-    }
-#pragma unroll
-    for (int k = 0; k < W; k++) {
-      const uint32_t ck = c + 16 * NT * k;
-      if (ck < full_end) *(uint4*)(stage + (ck - a0)) = v[k];
-    }
-  }
-}
-
-// ------------------------------------------------------------- byte helpers
-DEV uint32_t ld_be32(const u8* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return __builtin_bswap32(v); }
-DEV uint64_t ld_be64(const u8* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return __builtin_bswap64(v); }
-DEV uint32_t ld_be16(const u8* p) { return ((uint32_t)p[0] << 8) | p[1]; }
-DEV uint32_t pad4(uint32_t n) { return (n + 3u) & ~3u; }
-
-// Unaligned 4 / 8 byte loads built from ALIGNED dword loads + v_alignbyte. LDS serves a misaligned
-// ds_read_b32 / b64 lane by lane (measured: ~1k cycles per wave-wide access with random alignment),
-// while aligned dword reads run at full rate. These read up to the end of the last dword touched,
-// i.e. at most 3 (ldu32) / 3 (ldu64) bytes beyond the value plus the alignment slack below it.
-DEV uint32_t ldu32(const u8* p) {
-  const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
-  const uint32_t* q = (const uint32_t*)(p - sh);
-  return __builtin_amdgcn_alignbyte(q[1], q[0], sh);
-}
-DEV uint64_t ldu64(const u8* p) {
-  const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
-  const uint32_t* q = (const uint32_t*)(p - sh);
-  const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
-  return __builtin_amdgcn_alignbyte(w1, w0, sh) | ((uint64_t)__builtin_amdgcn_alignbyte(w2, w1, sh) << 32);
-}
-DEV bool is_digit(uint32_t c) { return c - '0' < 10u; }
-DEV uint32_t lower(uint32_t c) { return (c - 'A' < 26u) ? c + 32 : c; }
-
-DEV void st64(uint32_t* w, uint64_t v) { w[0] = (uint32_t)v; w[1] = (uint32_t)(v >> 32); }
-
-// Sequential byte reader. With `over` (the caller guarantees 7 readable bytes past any index it
-// asks for: LDS-staged tiles keep 16 bytes of slack) it fetches 8 bytes per load, i.e. one memory
-// round trip per 8 characters instead of one per character; without it every access is a byte load.
-struct ByteWin {
-  const u8* s; bool over;
-  uint32_t base = 0x80000000u; uint64_t w = 0;
-  DEV uint32_t at(uint32_t i) {  // ascending access
-    if (!over) return s[i];
-    uint32_t d = i - base;
-    if (d >= 8u) { base = i; __builtin_memcpy(&w, s + i, 8); d = 0; }
-    return (uint32_t)(w >> (8 * d)) & 0xFFu;
-  }
-  DEV uint32_t at_rev(uint32_t i) {  // descending access
-    if (!over) return s[i];
-    if (i - base >= 8u) { base = i >= 7u ? i - 7u : 0u; __builtin_memcpy(&w, s + base, 8); }
-    return (uint32_t)(w >> (8 * (i - base))) & 0xFFu;
-  }
-};
-
-DEV void record_error(const DecParams& p, uint32_t frame, uint32_t rank, uint32_t code) {
-  unsigned long long key = ((unsigned long long)frame << 16) | ((unsigned long long)rank << 8) | code;
-  atomicMin(&p.res->first_err, key);
-}
-
-// ETLG_F_ASYNC batches are chained on the device: the transaction state a batch starts from is what the batch before it
-// left in its result block (stream order), not what the host knew when it enqueued this one.
-// Returns false when that batch did not produce a result (an error, a plan that did not hold, a predecessor that failed in turn):
-// this one must not run either — the host decodes both again, in order, when they are synced (DevResult.fused_fail bit 3).
-DEV bool load_carry(DecParams& p) {
-  if (!p.carry) return true;
-  // (bit 1 alone — a fixed-width plan that gave its batch up over a shape it does not cover — is not a reason to stop: that kernel has
-  // published the three words from the Begin / Commit frames it read. The host keeps this batch's result only if the second attempt at
-  // that batch leaves the same words: finish_batch, `spare`; otherwise this batch is decoded again as it always was.)
-  const bool ok = (p.carry->fused_fail & ~2u) == 0 && p.carry->first_err == kNoErr;
-  p.in_txn = p.carry->out_in_txn; p.final_lsn = p.carry->out_final_lsn; p.next_ord = p.carry->out_next_ord;
-  if (!ok && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&p.res->fused_fail, 8u);
-  return ok;
-}
-
-// device slot index -> the slot id the arenas name (DevSlot.host_id); negative values (lookup failures) pass through
-DEV uint32_t slot_host_id(const DecParams& p, int sl) { return sl >= 0 ? p.slots[sl].host_id : (uint32_t)sl; }
-
-// ------------------------------------------------------------- wave scans
-// Inclusive scan over the 64 lanes of a wave with DPP (row_shr 1/2/4/8 inside each row of 16, then
-// row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3): six VALU instructions, no LDS
-// crossbar round trips (a __shfl_up ladder is six dependent ds_bpermute, ~100 cycles each).
-// op(older, newer); `idn` is its left identity (lanes without a source read it).
-#define ETLG_DPP(ctrl, rmask) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp((int)idn, (int)v, ctrl, rmask, 0xF, false); v = op(t_, v); }
-template <class F>
-DEV uint32_t wave_scan_incl(uint32_t v, F op, uint32_t idn) {
-  ETLG_DPP(0x111, 0xF) ETLG_DPP(0x112, 0xF) ETLG_DPP(0x114, 0xF) ETLG_DPP(0x118, 0xF) ETLG_DPP(0x142, 0xA) ETLG_DPP(0x143, 0xC)
-  return v;
-}
-#undef ETLG_DPP
-DEV uint32_t wave_scan_add(uint32_t v) { return wave_scan_incl(v, [](uint32_t a, uint32_t b) { return a + b; }, 0u); }
-DEV uint32_t wave_scan_max(uint32_t v) { return wave_scan_incl(v, [](uint32_t a, uint32_t b) { return a > b ? a : b; }, 0u); }
-DEV uint32_t wave_last(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }  // lane 63 of an inclusive scan = the wave total
-
-// ------------------------------------------------------------- block scans
-DEV uint32_t seg_combine(uint32_t a, uint32_t b) {  // bit31 = "a Begin was seen", low bits = count since
-  return (b & 0x80000000u) ? b : ((a & 0x80000000u) | ((a + b) & 0x7FFFFFFFu));
-}
-
-template <int OP>  // 0 sum, 1 max, 2 segmented count
-DEV uint32_t op_apply(uint32_t a, uint32_t b) {
-  if (OP == 0) return a + b;
-  if (OP == 1) return a > b ? a : b;
-  return seg_combine(a, b);
-}
-
-// Inclusive scan across the 256-lane workgroup. `lds` = 4 words of scratch.
-// Returns the inclusive value; *total = workgroup aggregate.
-template <int OP>
-DEV uint32_t block_scan_incl(uint32_t v, uint32_t* lds, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t t = __shfl_up(v, d, 64);
-    if (lane >= d) v = op_apply<OP>(t, v);
-  }
-  if (lane == 63) lds[wave] = v;
-  __syncthreads();
-  uint32_t pre = 0;
-  bool have = false;
-  for (int w = 0; w < wave; w++) { pre = have ? op_apply<OP>(pre, lds[w]) : lds[w]; have = true; }
-  if (have) v = op_apply<OP>(pre, v);
-  if (total) {
-    uint32_t t = lds[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); w++) t = op_apply<OP>(t, lds[w]);
-    *total = t;
-  }
-  __syncthreads();
-  return v;
-}
-
-DEV uint64_t block_sum64(uint64_t v, uint64_t* lds) {  // returns the workgroup total
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  if (lane == 0) lds[wave] = v;
-  __syncthreads();
-  uint64_t t = 0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += lds[w];
-  __syncthreads();
-  return t;
-}
-
-// Exclusive 64-bit sum scan over the workgroup; *total = aggregate.
-DEV uint64_t block_scan_excl64(uint64_t v, uint64_t* lds, uint64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint64_t t = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  uint64_t pre = 0, tot = 0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); w++) { if (w < wave) pre += lds[w]; tot += lds[w]; }
-  __syncthreads();
-  if (total) *total = tot;
-  return pre + inc - v;
-}
-
-// Exclusive sum scan of three u32 values at once (one LDS exchange, two barriers).
-// lds: 3 * nwaves words. tot[k] = workgroup totals.
-DEV void block_scan3_excl(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t* lds, uint32_t tot[3]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
-  const uint32_t ia = wave_scan_add(a), ib = wave_scan_add(b), ic = wave_scan_add(c);
-  if (lane == 63) { lds[3 * wave] = ia; lds[3 * wave + 1] = ib; lds[3 * wave + 2] = ic; }
-  __syncthreads();
-  uint32_t pa = 0, pb = 0, pc = 0, ta = 0, tb = 0, tc = 0;
-  for (int w = 0; w < nw; w++) {
-    const uint32_t xa = lds[3 * w], xb = lds[3 * w + 1], xc = lds[3 * w + 2];
-    if (w < wave) { pa += xa; pb += xb; pc += xc; }
-    ta += xa; tb += xb; tc += xc;
-  }
-  __syncthreads();
-  a = pa + ia - a; b = pb + ib - b; c = pc + ic - c;
-  tot[0] = ta; tot[1] = tb; tot[2] = tc;
-}
-
-// Transaction scan: inclusive segmented count + EXCLUSIVE running max in one exchange.
-// lds: 2 * nwaves words.
-DEV void block_scan_txn(uint32_t cnt, uint32_t mark, uint32_t* lds, uint32_t& seg_incl, uint32_t& mark_excl,
-                        uint32_t& tot_cnt, uint32_t& tot_mark) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
-  const uint32_t ic = wave_scan_incl(cnt, [](uint32_t a, uint32_t b) { return seg_combine(a, b); }, 0u);
-  const uint32_t im = wave_scan_max(mark);
-  // exclusive running max: the previous lane's inclusive value (wave_shr:1, 0 into lane 0)
-  uint32_t pm = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)im, 0x138, 0xF, 0xF, false);
-  if (lane == 63) { lds[2 * wave] = ic; lds[2 * wave + 1] = im; }
-  __syncthreads();
-  uint32_t pc = 0, pmx = 0, tcn = 0, tmx = 0;
-  for (int w = 0; w < nw; w++) {
-    const uint32_t xc = lds[2 * w], xm = lds[2 * w + 1];
-    if (w < wave) { pc = seg_combine(pc, xc); pmx = pmx > xm ? pmx : xm; }
-    tcn = seg_combine(tcn, xc); tmx = tmx > xm ? tmx : xm;
-  }
-  __syncthreads();
-  seg_incl = seg_combine(pc, ic);
-  mark_excl = pmx > pm ? pmx : pm;
-  tot_cnt = tcn; tot_mark = tmx;
-}
-
-// --------------------------------------------------------- frame geometry
-// CopyData := 'd' Int32-BE(len incl. itself) payload
-// payload  := 'w' u64 wal_start u64 wal_end i64 ts <pgoutput msg> | 'k' u64 i64 u8
-constexpr uint32_t kHdr = 5;        // 'd' + length
-constexpr uint32_t kTagOff = 30;    // offset of the pgoutput tag inside the frame
-constexpr uint32_t kBodyOff = 31;   // first byte after the tag
-
-DEV bool consumes_ordinal(uint32_t tag) {  // apply.rs:2284-2292, 2339, 2377, 2457, 2501, 2545, 2587
-  return tag == 'B' || tag == 'C' || tag == 'R' || tag == 'I' || tag == 'U' || tag == 'D' || tag == 'T';
-}
-
-// ------------------------------------------------------- side-input lookups
-DEV int find_table(const DecParams& p, uint32_t table_id) {
-  int lo = 0, hi = (int)p.n_tables - 1;
-  while (lo <= hi) {
-    int mid = (lo + hi) >> 1;
-    uint32_t v = p.tables[mid].table_id;
-    if (v == table_id) return mid;
-    if (v < table_id) lo = mid + 1; else hi = mid - 1;
-  }
-  return -1;
-}
-
-// should_apply_changes: apply.rs:2626-2639 -> 2836-2867 / 3514-3519
-DEV bool should_apply(const DecParams& p, int ti, uint32_t table_id, uint64_t remote_final_lsn) {
-  if (p.worker_kind == ETLG_WORKER_TABLE_SYNC) return p.sync_table == table_id;
-  if (ti < 0) return false;
-  const DevTable& t = p.tables[ti];
-  if (t.state_kind == ETLG_TS_READY) return true;
-  if (t.state_kind == ETLG_TS_SYNC_DONE) return t.state_lsn <= remote_final_lsn;
-  return false;
-}
-
-// get_replicated_table_schema (apply.rs:3705-3734) at stream position `f`:
-// the shared-table-cache entry in force just before frame f.
-// returns slot >= 0, or -ETLG_E_MISSING_SHARED_STATE / -ETLG_E_WAITING_RELATION
-DEV int cache_slot_before(const DecParams& p, int ti, uint32_t f) {
-  if (ti < 0) return -(int)ETLG_E_MISSING_SHARED_STATE;
-  const DevTable& t = p.tables[ti];
-  uint32_t kind = t.init_kind;
-  int slot = t.init_slot;
-  // epochs are few (one per R / DDL message of this table in the batch)
-  uint32_t lo = t.ep_begin, hi = t.ep_end;  // first epoch with frame >= f
-  while (lo < hi) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (p.epochs[mid].frame < f) lo = mid + 1; else hi = mid;
-  }
-  if (lo > t.ep_begin) { kind = p.epochs[lo - 1].kind; slot = p.epochs[lo - 1].slot; }
-  if (kind == 0) return -(int)ETLG_E_MISSING_SHARED_STATE;
-  if (kind == 1) return -(int)ETLG_E_WAITING_RELATION;
-  return slot;
-}
-
-// The epoch created by the R message at frame f itself (nullptr if the host did not
-// process it, e.g. because it lies behind the host's own error frame).
-DEV const DevEpoch* epoch_at(const DecParams& p, int ti, uint32_t f) {
-  if (ti < 0) return nullptr;
-  const DevTable& t = p.tables[ti];
-  uint32_t lo = t.ep_begin, hi = t.ep_end;
-  while (lo < hi) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (p.epochs[mid].frame < f) lo = mid + 1; else hi = mid;
-  }
-  if (lo < t.ep_end && p.epochs[lo].frame == f && p.epochs[lo].kind == 2) return &p.epochs[lo];
-  return nullptr;
-}
-
-// ---------------------------------------------------------- message shapes
-// Tuple := i16 ncols, ncols x { 'n' | 'u' | 't' i32 len bytes | 'b' i32 len bytes }
-// Structural walk: bounds, tags, value bytes (calculate_tuple_bytes, codec/event.rs:261-271).
-DEV bool walk_tuple(const u8*& c, const u8* e, uint32_t& ncols, uint32_t& vbytes, bool over = false) {
-  if (e - c < 2) return false;
-  const uint32_t n = ld_be16(c);
-  c += 2;
-  if (n & 0x8000u) return false;  // negative count
-  ncols = n;
-  for (uint32_t i = 0; i < n; i++) {
-    if (c >= e) return false;
-    // cell tag and length in one load where the bytes may be over-read (LDS-staged tiles)
-    uint64_t head = 0;
-    if (over) __builtin_memcpy(&head, c, 8);
-    const uint32_t t = over ? (uint32_t)head & 0xFFu : (uint32_t)*c;
-    c++;
-    if (t == 'n' || t == 'u') continue;
-    if (t != 't' && t != 'b') return false;
-    if (e - c < 4) return false;
-    const uint32_t len = over ? __builtin_bswap32((uint32_t)(head >> 8)) : ld_be32(c);
-    c += 4;
-    if ((len & 0x80000000u) || (uint64_t)(e - c) < len) return false;
-    vbytes += len;
-    c += len;
-  }
-  return true;
-}
-
-struct RowMsg {
-  uint32_t rel_id;
-  const u8* old_t;   // at the i16 column count of the old/key tuple (nullptr if none)
-  const u8* new_t;   // likewise for the new tuple (nullptr for D)
-  uint32_t old_kind; // ETLG_OLD_*
-  uint32_t old_n, new_n;
-  uint32_t vbytes;   // payload bytes (A3)
-};
-
-// I := u32 rel 'N' Tuple ; U := u32 rel ['K'|'O' Tuple] 'N' Tuple ; D := u32 rel ('K'|'O') Tuple
-DEV bool parse_row_msg(uint32_t tag, const u8* b, const u8* e, RowMsg& m, bool over = false) {
-  if (e - b < 5) return false;
-  m.rel_id = ld_be32(b);
-  const u8* c = b + 4;
-  m.old_t = nullptr; m.new_t = nullptr; m.old_kind = ETLG_OLD_NONE; m.old_n = m.new_n = 0; m.vbytes = 0;
-  uint32_t t = *c++;
-  if (tag == 'I') {
-    if (t != 'N') return false;
-    m.new_t = c;
-    return walk_tuple(c, e, m.new_n, m.vbytes, over);
-  }
-  if (tag == 'U') {
-    if (t == 'K' || t == 'O') {
-      m.old_kind = t == 'K' ? ETLG_OLD_KEY : ETLG_OLD_FULL;
-      m.old_t = c;
-      if (!walk_tuple(c, e, m.old_n, m.vbytes, over)) return false;
-      if (c >= e) return false;
-      t = *c++;
-    }
-    if (t != 'N') return false;
-    m.new_t = c;
-    return walk_tuple(c, e, m.new_n, m.vbytes, over);
-  }
-  // 'D'
-  if (t != 'K' && t != 'O') return false;
-  m.old_kind = t == 'K' ? ETLG_OLD_KEY : ETLG_OLD_FULL;
-  m.old_t = c;
-  return walk_tuple(c, e, m.old_n, m.vbytes, over);
-}
-
-DEV bool has_cstr(const u8*& c, const u8* e) {
-  while (c < e) if (*c++ == 0) return true;
-  return false;
-}
-
-// Cell iterator over a structurally valid tuple.
-struct CellIt {
-  const u8* c;
-  DEV void begin(const u8* tuple) { c = tuple + 2; }
-  DEV uint32_t next(const u8*& data, uint32_t& len) {
-    const uint32_t t = *c++;
-    data = nullptr; len = 0;
-    if (t == 't' || t == 'b') { len = ld_be32(c); c += 4; data = c; c += len; }
-    return t;
-  }
-};
 
 // ----------------------------------------------------------------- UTF-8
 // core::str::from_utf8 (strict RFC 3629), call site codec/event.rs:976.
@@ -555,13 +134,6 @@ DEV uint32_t digits4(uint32_t w, bool& ok) {
 DEV uint32_t lead_word(const u8* s, uint32_t r) {
   uint32_t w; __builtin_memcpy(&w, s, 4);
   return r == 4 ? w : (w << (8 * (4 - r))) | (0x30303030u >> (8 * r));
-}
-DEV bool swar_digits8(const u8* s, uint32_t n /* 1..8 */, uint32_t& out) {
-  bool ok = true;
-  if (n <= 4) { out = digits4(lead_word(s, n), ok); return ok; }
-  uint32_t lo; __builtin_memcpy(&lo, s + (n - 4), 4);
-  out = digits4(lead_word(s, n - 4), ok) * 10000u + digits4(lo, ok);
-  return ok;
 }
 DEV bool parse_int_swar(const u8* s, uint32_t n, bool is_signed, int bits, int64_t& out) {
   if (n == 0) return false;
@@ -869,11 +441,6 @@ DEV bool iso_timestamp_fast(const u8* s, uint32_t n, int32_t& days, uint32_t& se
   if (n < 19 || s[10] != ' ') return false;
   return iso_date_fast(s, 10, days) && iso_time_fast(s + 11, n - 11, secs, nanos, over);
 }
-// (the register-only temporal parsers below are compiled into the kernels that ask for them — rows.hip; k_cells / k_fused keep the code their
-// register allocation was tuned for: with these inlined k_cells spills 16-21 VGPRs)
-#ifndef ETLG_TEMPORAL_SWAR
-#define ETLG_TEMPORAL_SWAR 0
-#endif
 // parse_iso_timestamp_fast once more, for staged text (the loads may run past the text inside the window's slack): the 19..29 bytes
 // come in as eight dwords, separators are compared in place, every two-digit field is validated and converted with the packed
 // digit test of digits4, the fraction is right-padded with '0' by masks. No byte loads, no character loop. Accepts exactly what
@@ -979,9 +546,6 @@ DEV int32_t split_offset_index(const u8* s, uint32_t n, uint32_t min_index, bool
 // are significant, more are skipped); input left over is an error. Resolution: NaiveDate::from_ymd_opt over years
 // -262143..=262142, hour < 24, minute < 60, second <= 60 with 60 a leap second (second 59, nanos + 10^9). KATs: codec/time.rs:181-269.
 // Rare path (Postgres emits the ISO shapes): out of line, byte loads.
-#ifndef ETLG_CHRONO_CALL
-#define ETLG_CHRONO_CALL static __device__ __attribute__((noinline))
-#endif
 constexpr int32_t kChronoMinDays = -95746129, kChronoMaxDays = 95745399;   // num_days_from_ce of -262143-01-01 and 262142-12-31
 struct ChronoCur {
   const u8* s; uint32_t n, i;
@@ -1032,7 +596,7 @@ struct ChronoCur {
 // paths turned down. `n`: the text without its offset part (timestamptz / timetz: the caller split it off); trailing whitespace
 // is trimmed for those two (`timestamp.trim_end()`, codec/time.rs:67; `time.trim_end()`, etl-postgres/src/time.rs:123).
 // out: days (date classes), secs, nanos. Returns false for chrono's ParseError.
-ETLG_CHRONO_CALL bool chrono_fallback(uint32_t cls, const u8* s, uint32_t n, uint32_t* out3) {
+static __device__ __attribute__((noinline)) bool chrono_fallback(uint32_t cls, const u8* s, uint32_t n, uint32_t* out3) {
   if (cls == ETLG_TC_TIMESTAMPTZ || cls == ETLG_TC_TIMETZ) {
     for (;;) {   // str::trim_end
       if (!n) break;
@@ -1125,10 +689,7 @@ DEV bool parse_uuid(const u8* s, uint32_t n, uint32_t* out4, bool over = false) 
 }
 
 // f32 / f64 `str::parse`: the exact fast path lives in float_fast.h (host-testable); here it reads through ByteWin.
-#ifndef ETLG_FLOAT_CALL   // k_cells calls it out of line: inlined, its two call sites (sizing, decode) cost the kernel ~25 VGPRs, i.e. a workgroup per CU
-#define ETLG_FLOAT_CALL DEV
-#endif
-ETLG_FLOAT_CALL int parse_float_fast(const u8* s, uint32_t n, bool is32, uint64_t& out, bool over) {
+DEV int parse_float_fast(const u8* s, uint32_t n, bool is32, uint64_t& out, bool over) {
   if (over && n <= 24) {  // up to 24 bytes: three loads, then register arithmetic without a per-character loop (float_fast.h, parse_float_swar)
     const uint64_t x0 = ldu64(s), x1 = n > 8 ? ldu64(s + 8) : 0ull, x2 = n > 16 ? ldu64(s + 16) : 0ull;
     const int r = parse_float_swar(x0, x1, x2, n, is32, out);
@@ -1137,6 +698,19 @@ ETLG_FLOAT_CALL int parse_float_fast(const u8* s, uint32_t n, bool is32, uint64_
   ByteWin bw{s, over};
   return parse_float_fast_t([&](uint32_t i) { return bw.at(i); }, n, is32, out);
 }
+// the same out of line (k_cells, k_rows: inlined, its two call sites — sizing, decode — cost k_cells ~25 VGPRs, i.e. a workgroup per CU)
+DEV_NOINLINE int parse_float_fast_call(const u8* s, uint32_t n, bool is32, uint64_t& out, bool over) { return parse_float_fast(s, n, is32, out, over); }
+
+// Variants of the codec a kernel may ask for, as template arguments (VAR, a set of these bits) of decode_text_cell and of everything
+// that reaches it: a variant is an instantiation with a name of its own, never a macro set in front of this header — every unit
+// that includes the header then compiles the same text, and units linked into one image (the SIMT emulator) cannot swap bodies.
+//   CODEC_TEMPORAL_SWAR  timestamps / whole-hour offsets of staged text decided from registers (iso_timestamp_swar, tz_hours_swar):
+//                        k_rows; k_cells / k_fused keep the code their register allocation was tuned for (with these inlined
+//                        k_cells spills 16-21 VGPRs)
+//   CODEC_FLOAT_CALL     floats through parse_float_fast_call
+// (The choice is written out where it is made, as a conditional on a constant: a helper in between is one more inlined frame around
+// `out`, and k_fused came out 44 bytes shorter with it.)
+enum : uint32_t { CODEC_TEMPORAL_SWAR = 1u, CODEC_FLOAT_CALL = 2u };
 
 // Which classes are handed back DEFERRED wholesale (include/etlg.h contract).
 DEV bool class_always_deferred(uint32_t cls) {
@@ -1144,11 +718,12 @@ DEV bool class_always_deferred(uint32_t cls) {
 }
 
 // Heap bytes a text cell will occupy (exact for every non-error outcome).
+template <uint32_t VAR = 0>
 DEV uint32_t cell_heap_bytes(uint32_t cls, const u8* d, uint32_t len, bool over = false) {
   if (class_always_deferred(cls) || cls == ETLG_TC_STRING) return pad4(len);
   switch (cls) {
     case ETLG_TC_BYTEA: return len >= 2 ? pad4((len - 2) >> 1) : 0;
-    case ETLG_TC_F32: case ETLG_TC_F64: { uint64_t b; return parse_float_fast(d, len, cls == ETLG_TC_F32, b, over) == 1 ? pad4(len) : 0; }
+    case ETLG_TC_F32: case ETLG_TC_F64: { uint64_t b; return ((VAR & CODEC_FLOAT_CALL) ? parse_float_fast_call(d, len, cls == ETLG_TC_F32, b, over) : parse_float_fast(d, len, cls == ETLG_TC_F32, b, over)) == 1 ? pad4(len) : 0; }
     case ETLG_TC_NUMERIC: { NumShape s; return ((over && numeric_plain(d, len, s)) || numeric_scan(d, len, s, over)) ? pad4(8 + 2 * s.ngroups) : 0; }
     // date / time / timestamp / timestamptz / timetz: decoded on the device whatever their shape (chrono_fallback): no heap entry
     default: return 0;
@@ -1172,9 +747,10 @@ DEV void heap_copy(u8* dst, const u8* src, uint32_t n) {
 DEV uint32_t slot_bytes(uint32_t cls);
 // COPY_CLASSES = false: the caller moves verbatim text (String cells, wholesale-deferred classes)
 // itself and never passes those classes in (k_cells).
-template <bool COPY_CLASSES = true>
-DEV_DECODE uint32_t decode_text_cell(uint32_t cls, const u8* d, uint32_t len, uint32_t* slot, u8* heap, uint32_t& hcur,
+template <bool COPY_CLASSES = true, uint32_t VAR = 0>
+DEV uint32_t decode_text_cell(uint32_t cls, const u8* d, uint32_t len, uint32_t* slot, u8* heap, uint32_t& hcur,
                               uint32_t& state, bool over = false) {
+  constexpr bool SWAR = (VAR & CODEC_TEMPORAL_SWAR) != 0;
   // str::from_utf8 precedes the type switch (codec/event.rs:976). Every non-text grammar below
   // accepts ASCII only, so for those classes validity is only examined when the parse fails
   // (to pick between the UTF-8 error and the type's own error) or before a cell is deferred.
@@ -1209,7 +785,7 @@ DEV_DECODE uint32_t decode_text_cell(uint32_t cls, const u8* d, uint32_t len, ui
     }
     case ETLG_TC_F32: case ETLG_TC_F64: {
       uint64_t b;
-      const int r = parse_float_fast(d, len, cls == ETLG_TC_F32, b, over);
+      const int r = (VAR & CODEC_FLOAT_CALL) ? parse_float_fast_call(d, len, cls == ETLG_TC_F32, b, over) : parse_float_fast(d, len, cls == ETLG_TC_F32, b, over);
       if (r == 2) return bad(ETLG_E_FLOAT);
       if (r == 1) return defer();
       st64(slot, b);
@@ -1265,7 +841,7 @@ DEV_DECODE uint32_t decode_text_cell(uint32_t cls, const u8* d, uint32_t len, ui
     }
     case ETLG_TC_TIMESTAMP: {
       int32_t x; uint32_t a, b;
-      if ((ETLG_TEMPORAL_SWAR && over && iso_timestamp_swar(d, len, x, a, b)) || iso_timestamp_fast(d, len, x, a, b, over)) { slot[0] = (uint32_t)x; slot[1] = a; slot[2] = b; return 0; }
+      if ((SWAR && over && iso_timestamp_swar(d, len, x, a, b)) || iso_timestamp_fast(d, len, x, a, b, over)) { slot[0] = (uint32_t)x; slot[1] = a; slot[2] = b; return 0; }
       uint32_t o[3];
       if (!chrono_fallback(cls, d, len, o)) return bad(ETLG_E_DATETIME);
       slot[0] = o[0]; slot[1] = o[1]; slot[2] = o[2];
@@ -1275,7 +851,7 @@ DEV_DECODE uint32_t decode_text_cell(uint32_t cls, const u8* d, uint32_t len, ui
       int32_t x; uint32_t a, b;
       int32_t off;
       uint32_t fidx;
-      if (ETLG_TEMPORAL_SWAR && over && tz_hours_swar(d, len, 10, fidx, off) && iso_timestamp_swar(d, fidx, x, a, b)) {
+      if (SWAR && over && tz_hours_swar(d, len, 10, fidx, off) && iso_timestamp_swar(d, fidx, x, a, b)) {
         // (the shape Postgres prints: both halves decided without a byte load)
       } else {
       const int32_t idx = split_offset_index(d, len, 10, over);
@@ -1321,36 +897,6 @@ DEV uint32_t slot_bytes(uint32_t cls) {  // layout rule of include/etlg.h
   }
 }
 
-// ---------------------------------------------------------------- k_size
-// Heap bytes of one tuple decoded against `n` schema columns.
-//   mode 0: full row (convert_tuple_to_row); mode 1: dense key tuple;
-//   mode 2: full-width key tuple (non-identity positions skipped unread);
-//   mode 3: update new tuple (u cells never allocate: alias or Missing)
-DEV uint32_t tuple_heap_bytes(const DecParams& p, const DevSlot& s, const u8* tuple, uint32_t ncells, int mode, bool over = false) {
-  if (!s.has_var) return 0;  // fixed-width schema: no cell can reach the heap
-  const DevCol* cols = p.cols + s.cols_base;
-  CellIt it; it.begin(tuple);
-  uint32_t h = 0, next_ident = 0;
-  for (uint32_t i = 0; i < ncells; i++) {
-    const u8* d; uint32_t len;
-    const uint32_t t = it.next(d, len);
-    uint32_t ci;
-    if (mode == 1) {
-      // i-th identity column
-      ci = 0xFFFFFFFFu;
-      for (uint32_t c = 0, k = 0; c < s.n_cols; c++) if (cols[c].identity) { if (k == i) { ci = c; break; } k++; }
-      if (ci == 0xFFFFFFFFu) break;
-    } else {
-      if (i >= s.n_cols) break;
-      ci = i;
-      if (mode == 2) { if (!cols[ci].identity) continue; next_ident++; }
-    }
-    if (t == 't') h += cell_heap_bytes(cols[ci].cls, d, len, over);
-  }
-  (void)next_ident;
-  return h;
-}
-
 // ---------------------------------------------------------------- k_write
 // Per-cell states are 2 bits, 16 columns per 32-bit word at the head of the row;
 // they are accumulated in a register and stored once per word. Every slot word is
@@ -1367,361 +913,10 @@ DEV void slot_zero(uint32_t* slot, uint32_t cls) {
   for (uint32_t w = 0; w < nw; w++) slot[w] = 0;
 }
 DEV uint32_t get_state(const u8* row, uint32_t i) { return (((const uint32_t*)row)[i >> 4] >> (2 * (i & 15))) & 3u; }
-
-// One row image out of one tuple. `mode`:
-//   ROW_FULL    convert_tuple_to_row (codec/event.rs:554-587), full layout
-//   ROW_KEY     normalize_key_tuple_to_row (codec/event.rs:795-923), key layout (dense or full-width tuple)
-//   ROW_UPDATE  convert_update_tuple_to_updated_table_row + OldRowResolver (codec/event.rs:605-791):
-//               'u' cells alias the aligned old value (Cell::clone) or become MISSING (Partial)
-// A single body (one inlined copy of the value codec) serves all three.
-enum : uint32_t { ROW_FULL = 0, ROW_KEY = 1, ROW_UPDATE = 2 };
-
-// CHECK (ETLG_F_CHECK_CELLS, the multi-pass kernels only: kernels.hip): a json / jsonb / array cell is validated where it is deferred,
-// behind its UTF-8 check, with the code parse_cell_from_postgres_text would raise (cell_text_error, cellparse.hip.h). A compile-time
-// choice: the single-pass kernels instantiate CHECK = false and carry no trace of it.
+// ETLG_F_CHECK_CELLS: would parse_cell_from_postgres_text have failed on this DEFERRED json / array text, and with which code
+// (defined in cellparse.hip.h; declared here for write_row<true>, frames.hip.h)
 DEV_NOINLINE uint32_t cell_text_error(uint32_t cls, uint32_t elem, const u8* s, uint32_t n);
 // element class per DevCol, stored directly behind the DevCol records in GLOBAL memory (build_side_inputs, host_orchestrate.inc)
 DEV const u8* chk_elem_table(const DecParams& p) { return (const u8*)(p.cols + p.n_cols); }
-template <bool CHECK = false>
-DEV uint32_t write_row(const DecParams& p, const DevSlot& s, uint32_t mode, const u8* tuple, uint32_t ncells, u8* row,
-                       uint32_t old_kind, const u8* old_row, uint32_t& hcur, bool& partial, bool over = false) {
-  bool dense = false;
-  if (mode == ROW_KEY) {
-    if (s.n_ident == 0) return ETLG_E_KEY_MISSING_COLS;
-    dense = ncells == s.n_ident;
-    if (!dense && ncells != s.n_cols) return ETLG_E_KEY_SHAPE;
-  } else if (ncells != s.n_cols) {
-    return ETLG_E_TUPLE_WIDTH;
-  }
-  const DevCol* cols = p.cols + s.cols_base;
-  StateAcc sa{(uint32_t*)row};
-  CellIt it; it.begin(tuple);
-  uint32_t ci = 0;  // schema column cursor (dense key tuples walk identity columns only)
-  const uint32_t n_out = mode == ROW_KEY ? s.n_ident : s.n_cols;
-  // A decoded old row always has exactly n_cols (Full) / n_ident (Key) cells, so the
-  // resolver's width checks (codec/event.rs:700-710, 730-740, 772-785) cannot fire here.
-  for (uint32_t i = 0; i < ncells; i++) {
-    const u8* d; uint32_t len;
-    const uint32_t t = it.next(d, len);
-    if (mode == ROW_KEY) {
-      if (dense) { while (ci < s.n_cols && !cols[ci].identity) ci++; }
-      else { ci = i; if (!cols[ci].identity) continue; }  // full-width key tuple: other positions are skipped unread
-    } else {
-      ci = i;
-    }
-    const DevCol col = cols[ci];
-    const uint32_t k = mode == ROW_KEY ? col.key_index : i;  // output cell index
-    uint32_t* slot = (uint32_t*)(row + (mode == ROW_KEY ? col.off_key : col.off_full));
-    uint32_t st = ETLG_CELL_NULL;
-    if (t == 'n') {  // convert_tuple_data_to_cell, codec/event.rs:945-961
-      if (!col.nullable && !(p.flags & 2u)) return ETLG_E_REQUIRED_NULL;
-      slot_zero(slot, col.cls);
-    } else if (t == 'u') {
-      if (mode == ROW_FULL) return ETLG_E_FULL_ROW_MISSING;
-      if (mode == ROW_KEY) return ETLG_E_KEY_MISSING_VALUE;
-      const bool from_full = old_kind == ETLG_OLD_FULL;
-      const bool from_key = old_kind == ETLG_OLD_KEY && col.identity;
-      if (from_full || from_key) {  // Cell::clone of the aligned old value: alias its slot
-        const uint32_t oi = from_full ? i : col.key_index;
-        const uint32_t* src = (const uint32_t*)(old_row + (from_full ? col.off_full : col.off_key));
-        const uint32_t nw = slot_bytes(col.cls) >> 2;
-        for (uint32_t w = 0; w < nw; w++) slot[w] = src[w];
-        st = get_state(old_row, oi);
-      } else {
-        slot_zero(slot, col.cls);
-        st = ETLG_CELL_MISSING;
-        partial = true;
-      }
-    } else if (t == 't') {
-      const uint32_t err = decode_text_cell(col.cls, d, len, slot, p.heap, hcur, st, over);
-      if (err) return err;
-      if constexpr (CHECK) {
-        if (class_always_deferred(col.cls)) {
-          const uint32_t ce = cell_text_error(col.cls, chk_elem_table(p)[s.cols_base + ci], d, len);
-          if (ce && ce < 0x100u) return ce;   // (0x100, ARR_HOST: a lane cannot decide — the cell stays DEFERRED, include/etlg.h)
-        }
-      }
-    } else {
-      return ETLG_E_BINARY_FORMAT;
-    }
-    sa.put(k, st, k + 1 == n_out);
-    if (mode == ROW_KEY && dense) ci++;
-  }
-  return 0;
-}
-
-// convert_tuple_to_row for a wave whose active lanes ALL decode an INSERT of the same
-// schema slot with the same column count (the common case). `slot_u` / `n` are wave-uniform
-// (SGPRs): the column descriptors come through the scalar cache, the loop trip count and
-// the per-column class dispatch are scalar branches, and only the data-dependent work
-// (cell tag, length, characters) stays per lane. `pg` must hold GLOBAL side-table pointers.
-DEV uint32_t write_full_row_uniform(const DecParams& pg, uint32_t slot_u, const u8* tuple, uint32_t n, u8* row,
-                                    uint32_t& hcur, bool over) {
-  // The descriptors are read as whole dwords through constant-address-space pointers: the address is wave-uniform
-  // and the memory is never written by a kernel, so these are s_load (scalar cache, results in SGPRs). As byte /
-  // halfword fields of a plain global struct they compiled to global_load_ubyte / _ushort + s_waitcnt vmcnt(0) +
-  // v_readfirstlane — one dependent vector-memory round trip per column (gfx950 has no sub-dword scalar loads).
-  const ETLG_CONST_AS uint32_t* sw = (const ETLG_CONST_AS uint32_t*)(uintptr_t)(pg.slots + slot_u);
-  static_assert(sizeof(DevSlot) == 44 && sizeof(DevCol) == 12, "descriptor words below");
-  if (n != sw[0]) return ETLG_E_TUPLE_WIDTH;                      // DevSlot.n_cols
-  const ETLG_CONST_AS uint32_t* cw = (const ETLG_CONST_AS uint32_t*)(uintptr_t)(pg.cols + sw[6]);  // DevSlot.cols_base
-  struct { uint32_t cls, nullable, off_full; } col;
-  const u8* c = tuple + 2;
-  uint32_t acc = 0;
-  uint32_t* stw = (uint32_t*)row;
-  for (uint32_t i = 0; i < n; i++) {
-    { const uint32_t w0 = cw[3 * i], w1 = cw[3 * i + 1]; col.cls = w0 & 0xFFu; col.nullable = (w0 >> 8) & 0xFFu; col.off_full = w1 & 0xFFFFu; }
-    const uint32_t cls = col.cls;
-    uint32_t* slot = (uint32_t*)(row + col.off_full);  // always the arena: a pointer that may also name private memory turns every row store into a flat store
-    uint64_t head = 0;
-    if (over) __builtin_memcpy(&head, c, 8);  // tag + length in one load
-    const uint32_t t = over ? (uint32_t)head & 0xFFu : (uint32_t)*c;
-    c++;
-    uint32_t st = ETLG_CELL_NULL;
-    if (t == 't') {
-      const uint32_t len = over ? __builtin_bswap32((uint32_t)(head >> 8)) : ld_be32(c);
-      c += 4;
-      const uint32_t err = decode_text_cell(cls, c, len, slot, pg.heap, hcur, st, over);
-      if (err) return err;
-      c += len;
-    } else if (t == 'n') {
-      if (!col.nullable && !(pg.flags & 2u)) return ETLG_E_REQUIRED_NULL;
-      slot_zero(slot, cls);
-    } else if (t == 'u') {
-      return ETLG_E_FULL_ROW_MISSING;
-    } else {
-      return ETLG_E_BINARY_FORMAT;
-    }
-    acc |= st << (2 * (i & 15));
-    if (((i & 15) == 15 || i + 1 == n) && !(pg.flags & 0x100u)) { stw[i >> 4] = acc; acc = 0; }
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------ per-frame passes
-// Transaction context of one frame (state BEFORE the frame is applied).
-struct TxnCtx {
-  bool in_txn;         // remote_final_lsn.is_some()
-  uint64_t final_lsn;  // valid when in_txn
-  uint64_t ord;        // ordinal this frame takes if it consumes one
-};
-
-struct FrameView {
-  uint32_t f;     // frame index in the batch
-  uint32_t tag;   // pgoutput tag ('k' keepalive, FT_BAD malformed)
-  const u8* fr;   // first byte of the CopyData frame ('d')
-  const u8* e;    // one past its last byte
-};
-
-// Structural validation of the whole message (what the third-party parser does
-// before the reference sees it). For I/U/D fills `m`. Returns false on a wire error.
-DEV bool frame_structure(const FrameView& v, RowMsg& m, bool over = false) {
-  const u8* b = v.fr + kBodyOff;
-  const u8* e = v.e;
-  switch (v.tag) {
-    case FT_BAD: return false;
-    case 'O': { const u8* c = b + 8; return e - b >= 9 && has_cstr(c, e); }              // u64 lsn, cstr name
-    case 'Y': { const u8* c = b + 4; return e - b >= 6 && has_cstr(c, e) && has_cstr(c, e); }  // u32 oid, cstr, cstr
-    case 'R': return e - b >= 4;  // the rest of R is validated by the host control plane
-    case 'I': case 'U': case 'D': return parse_row_msg(v.tag, b, e, m, over);
-    case 'T': {  // i32 nrel, i8 options, nrel x u32
-      if (e - b < 5) return false;
-      const uint32_t nrel = ld_be32(b);
-      return !(nrel & 0x80000000u) && (uint64_t)(e - b - 5) / 4 >= nrel;
-    }
-    default: return true;  // 'k', 'B', 'C' were length-checked by classify; 'M' is the host's
-  }
-}
-
-// Transaction state machine + ownership + exact output sizes of one frame
-// (apply.rs:2279-2617, 2836-2867). `wire_ok`/`m` come from frame_structure.
-// check_txn = false: the transaction context is not known yet (fused kernel, early
-// sizing); the frame is sized as if inside a transaction and txn_check_frame runs later.
-DEV void size_frame(const DecParams& p, const FrameView& v, const TxnCtx& tx, bool wire_ok, const RowMsg& m,
-                    uint32_t& emit, uint32_t& fixed, uint32_t& heap, uint64_t pay[3], int& row_slot,
-                    bool check_txn = true, bool over = false) {
-  const uint32_t f = v.f, tag = v.tag;
-  const u8* b = v.fr + kBodyOff;
-  emit = 0; fixed = 0; heap = 0;
-  if (!wire_ok) { record_error(p, f, RK_WIRE, ETLG_E_WIRE); return; }
-  switch (tag) {
-    case 'B': emit = 1; fixed = 8; break;
-    case 'C':
-      if (check_txn && !tx.in_txn) record_error(p, f, RK_TXN, ETLG_E_TXN_STATE);
-      else if (check_txn && ld_be64(b + 1) != tx.final_lsn) record_error(p, f, RK_TXN, ETLG_E_COMMIT_LSN);
-      else { emit = 1; fixed = 16; }
-      break;
-    case 'M':
-      if (p.flags & 1u) record_error(p, f, RK_WIRE, ETLG_E_CTRL_HINT);
-      break;  // host control plane (apply.rs:2160-2276)
-    case 'R': {  // handle_relation_message: the event is emitted here, the schema work is the host's
-      if (p.flags & 1u) { record_error(p, f, RK_WIRE, ETLG_E_CTRL_HINT); break; }
-      if (check_txn && !tx.in_txn) { record_error(p, f, RK_TXN, ETLG_E_TXN_STATE); break; }
-      const uint32_t rel = ld_be32(b);
-      const DevEpoch* ep = epoch_at(p, find_table(p, rel), f);
-      if (ep && ep->emit) emit = 1;
-      break;
-    }
-    case 'I': case 'U': case 'D': {
-      if (check_txn && !tx.in_txn) { record_error(p, f, RK_TXN, ETLG_E_TXN_STATE); break; }
-      pay[tag == 'I' ? 0 : tag == 'U' ? 1 : 2] = m.vbytes;  // metrics precede the ownership check
-      int slot;
-      if (p.flags & 2u) slot = p.copy_slot;  // table-copy rows: the caller named the schema
-      else {
-        const int ti = find_table(p, m.rel_id);
-        if (!should_apply(p, ti, m.rel_id, tx.final_lsn)) break;
-        slot = cache_slot_before(p, ti, f);
-        if (slot < 0) { record_error(p, f, RK_SCHEMA, (uint32_t)(-slot)); break; }
-      }
-      const DevSlot& s = p.slots[slot];
-      row_slot = slot;
-      emit = 1;
-      for (uint32_t img = (tag == 'I' || m.old_kind == ETLG_OLD_NONE) ? 1u : 0u; img < (tag == 'D' ? 1u : 2u); img++) {
-        const bool is_new = img == 1;
-        int mode;
-        if (is_new) { fixed += s.row_full; mode = tag == 'U' ? 3 : 0; }
-        else if (m.old_kind == ETLG_OLD_FULL) { fixed += s.row_full; mode = 0; }
-        else { fixed += s.row_key; mode = m.old_n == s.n_ident ? 1 : m.old_n == s.n_cols ? 2 : -1; }
-        if (mode >= 0) heap += tuple_heap_bytes(p, s, is_new ? m.new_t : m.old_t, is_new ? m.new_n : m.old_n, mode, over);
-      }
-      break;
-    }
-    case 'T': {
-      if (check_txn && !tx.in_txn) { record_error(p, f, RK_TXN, ETLG_E_TXN_STATE); break; }
-      const uint32_t nrel = ld_be32(b);
-      uint32_t owned = 0;
-      for (uint32_t i = 0; i < nrel; i++) {
-        const uint32_t rel = ld_be32(b + 5 + 4 * i);
-        const int ti = find_table(p, rel);
-        if (!should_apply(p, ti, rel, tx.final_lsn)) continue;
-        const int slot = cache_slot_before(p, ti, f);
-        if (slot < 0) { record_error(p, f, RK_SCHEMA, (uint32_t)(-slot)); owned = 0; break; }
-        owned++;
-      }
-      if (owned) { emit = 1; fixed = 8 * owned; }
-      break;
-    }
-    default: break;  // 'k', 'O', 'Y'
-  }
-}
-
-// The transaction-state checks of size_frame for a frame that was sized early.
-DEV void txn_check_frame(const DecParams& p, const FrameView& v, const TxnCtx& tx) {
-  const uint32_t tag = v.tag;
-  if (tag == 'C') {
-    if (!tx.in_txn) record_error(p, v.f, RK_TXN, ETLG_E_TXN_STATE);
-    else if (ld_be64(v.fr + kBodyOff + 1) != tx.final_lsn) record_error(p, v.f, RK_TXN, ETLG_E_COMMIT_LSN);
-  } else if (tag == 'R' || tag == 'I' || tag == 'U' || tag == 'D' || tag == 'T') {
-    if (!tx.in_txn) record_error(p, v.f, RK_TXN, ETLG_E_TXN_STATE);
-  }
-}
-
-// Decodes one emitting frame into the arena at (ev_idx, fx_off, hp_off).
-// `pu` (optional): the same parameters with GLOBAL side-table pointers, enabling the
-// wave-uniform INSERT path; `over`: the frame bytes may be over-read by up to 7 bytes.
-template <bool CHECK = false>
-DEV void write_frame(const DecParams& p, const FrameView& v, const TxnCtx& tx, const RowMsg& m, int row_slot,
-                     uint64_t ev_idx, uint64_t fx_off, uint64_t hp_off, const DecParams* pu = nullptr, bool over = false) {
-  const uint32_t f = v.f, tag = v.tag;
-  const u8* fr = v.fr;
-  const u8* b = fr + kBodyOff;
-  u8* body = p.fixed + fx_off;
-  uint32_t flags = 0, table = 0, slot_id = 0;
-  uint64_t commit_lsn = tx.final_lsn;
-  switch (tag) {
-    case 'B':  // parse_event_from_begin_message, codec/event.rs:303-316
-      commit_lsn = ld_be64(b);
-      st64((uint32_t*)body, ld_be64(b + 8));
-      table = ld_be32(b + 16);
-      break;
-    case 'C':  // parse_event_from_commit_message, codec/event.rs:322-336
-      flags = b[0];
-      commit_lsn = ld_be64(b + 1);
-      st64((uint32_t*)body, ld_be64(b + 9));
-      st64((uint32_t*)body + 2, ld_be64(b + 17));
-      break;
-    case 'R': {
-      table = ld_be32(b);
-      const DevEpoch* ep = epoch_at(p, find_table(p, table), f);
-      slot_id = ep ? slot_host_id(p, ep->slot) : 0;
-      break;
-    }
-    case 'T': {  // parse_event_from_truncate_message, codec/event.rs:533-547
-      const uint32_t nrel = ld_be32(b);
-      flags = b[4];
-      uint32_t k = 0;
-      for (uint32_t i = 0; i < nrel; i++) {
-        const uint32_t rel = ld_be32(b + 5 + 4 * i);
-        const int ti = find_table(p, rel);
-        if (!should_apply(p, ti, rel, tx.final_lsn)) continue;
-        const int sl = cache_slot_before(p, ti, f);
-        ((uint32_t*)body)[2 * k] = rel; ((uint32_t*)body)[2 * k + 1] = slot_host_id(p, sl);
-        k++;
-      }
-      table = k;
-      break;
-    }
-    default: {  // I / U / D
-      table = m.rel_id;
-      const int sl = row_slot >= 0 ? row_slot : cache_slot_before(p, find_table(p, m.rel_id), f);
-      slot_id = slot_host_id(p, sl);
-      uint32_t hcur = (uint32_t)hp_off;
-      uint32_t err = 0;
-      bool partial = false;
-      const uint32_t sl_u = __builtin_amdgcn_readfirstlane((uint32_t)sl);
-      const uint32_t n_u = __builtin_amdgcn_readfirstlane(m.new_n);
-      if (p.flags & 0x400u) { /* profiling ablation: no row decode at all */ }
-      else if (p.flags & 0x800u) { if (pu && __all(tag == 'I' && (uint32_t)sl == sl_u && m.new_n == n_u)) err = write_full_row_uniform(*pu, sl_u, m.new_t, n_u, body, hcur, over); /* ablation: uniform waves only */ }
-      else if (pu && __all(tag == 'I' && (uint32_t)sl == sl_u && m.new_n == n_u)) {
-        err = write_full_row_uniform(*pu, sl_u, m.new_t, n_u, body, hcur, over);
-      } else {
-        const DevSlot& s = p.slots[sl];
-        const uint32_t old_sz = m.old_kind == ETLG_OLD_FULL ? s.row_full : m.old_kind == ETLG_OLD_KEY ? s.row_key : 0;
-        if (tag != 'I') flags = m.old_kind;
-        // image 0 = old / key tuple (U, D), image 1 = new tuple (I, U): one call site for both
-        for (uint32_t img = (tag == 'I' || m.old_kind == ETLG_OLD_NONE) ? 1u : 0u; img < (tag == 'D' ? 1u : 2u) && !err; img++) {
-          const bool is_new = img == 1;
-          const uint32_t mode = is_new ? (tag == 'U' ? (uint32_t)ROW_UPDATE : (uint32_t)ROW_FULL)
-                                       : (m.old_kind == ETLG_OLD_KEY ? (uint32_t)ROW_KEY : (uint32_t)ROW_FULL);
-          err = write_row<CHECK>(p, s, mode, is_new ? m.new_t : m.old_t, is_new ? m.new_n : m.old_n,
-                          is_new ? body + old_sz : body, m.old_kind, body, hcur, partial, over);
-        }
-      }
-      if (partial) flags |= ETLG_FLAG_PARTIAL;
-      if (err) { record_error(p, f, RK_DECODE, err); return; }
-      break;
-    }
-  }
-  if (p.flags & 0x200u) return;  // profiling ablation (no header stores)
-  p.ev_kind[ev_idx] = (u8)tag;
-  p.ev_flags[ev_idx] = (u8)flags;
-  p.ev_table[ev_idx] = table;
-  p.ev_slot[ev_idx] = slot_id;
-  p.ev_start[ev_idx] = ld_be64(fr + 6);  // wal_start (apply.rs:2039)
-  p.ev_commit[ev_idx] = commit_lsn;
-  p.ev_ord[ev_idx] = tx.ord;
-  p.ev_body[ev_idx] = fx_off;
-}
-
-// classify from a frame pointer (LDS or global) + its sidecar extent
-DEV uint32_t classify_ptr(const u8* fr, uint32_t flen) {
-  if (flen < kHdr + 1 || fr[0] != 'd' || ld_be32(fr + 1) + 1u != flen) return FT_BAD;
-  const uint32_t outer = fr[5];
-  if (outer == 'k') return flen >= kHdr + 18 ? 'k' : FT_BAD;
-  if (outer != 'w' || flen < kBodyOff) return FT_BAD;
-  const uint32_t tag = fr[kTagOff];
-  switch (tag) {
-    case 'B': return flen >= kBodyOff + 20 ? tag : FT_BAD;  // u64 final_lsn, i64 ts, u32 xid
-    case 'C': return flen >= kBodyOff + 25 ? tag : FT_BAD;  // i8 flags, u64, u64, i64
-    case 'O': case 'Y': case 'R': case 'M': case 'I': case 'U': case 'D': case 'T': return tag;
-    default: return FT_BAD;
-  }
-}
-
-DEV uint32_t classify_frame(const DecParams& p, uint32_t f) {
-  const uint32_t o0 = p.offs[f], o1 = p.offs[f + 1];
-  if (o1 <= o0 || o1 > p.in_len) return FT_BAD;
-  return classify_ptr(p.in + o0, o1 - o0);
-}
 
 }  // namespace etlg

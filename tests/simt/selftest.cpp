@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE — self-test of the SIMT emulator: the wave / workgroup primitives of codec.hip.h against scalar loops.
+// TEST INFRASTRUCTURE — self-test of the SIMT emulator: the wave / workgroup primitives of device.hip.h against scalar loops.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 

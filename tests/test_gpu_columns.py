@@ -362,7 +362,7 @@ def test_float_temporal_and_uuid_arrays_on_the_device():
 def test_array_elements_outside_the_fast_paths_hand_the_row_back():
     """An element the scalar decoder would hand back DEFERRED (a float text the device rule does not settle) makes its ROW deferred:
     null in the list column, set in `deferred`, the rest of the column intact. Temporal elements of a shape only chrono parses are
-    decoded like every other (chrono_fallback, codec.hip.h)."""
+    decoded like every other (chrono_fallback, values.hip.h)."""
     rows = [["1", "{1.5}", "{2026-01-02}"], ["2", "{50537618.817359292015891086651596749e82,2}", "{2023-1-01, 2023-12-5}"], ["3", "{2.5}", "{1999-12-31}"]]
     cols3 = [("id", SC.INT8, False, 1), ("f8", 1022, True, 0), ("d", 1182, True, 0)]
     buf, offs = _stream([W.insert(42, r) for r in rows])

@@ -23,7 +23,7 @@ def test_begin_and_commit_frames_have_the_lengths_the_pre_pass_assumes():
     assert _frame_len(W.commit(0x5000, 0x5008, ts=7, flags=0)) == 56
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "etl_amd", "csrc", "plan.hip")).read()
-    body_off = int(re.search(r"constexpr uint32_t kBodyOff = (\d+);", open(os.path.join(root, "etl_amd", "csrc", "codec.hip.h")).read()).group(1))
+    body_off = int(re.search(r"constexpr uint32_t kBodyOff = (\d+);", open(os.path.join(root, "etl_amd", "csrc", "frames.hip.h")).read()).group(1))
     m = re.search(r"kPreBeginLen = kBodyOff \+ (\d+)u, kPreCommitLen = kBodyOff \+ (\d+)u", src)
     assert m and body_off + int(m.group(1)) == 51 and body_off + int(m.group(2)) == 56
 
