@@ -12,6 +12,9 @@
 //! the decode of buffer k-1), the loop fills buffer k+1; a buffer returns to the ring when its batch has been collected
 //! (`GpuDecoder::finish`). The resulting `Vec<Event>` goes through `EventBatch::push` unchanged, so the reference's own size
 //! hints (`TableRow::new`, data/table_row.rs:28-32) still decide where `write_events` batches are cut.
+//! A consumer that takes only the device hand-offs (no `Vec<Event>`) gets the same cuts from the device: `GpuDecoder::cuts`
+//! (etlg_batch_cuts) applies the rule of apply.rs:656-657 / :1932-1945 to the device's size hints, the forced flushes above expressed as
+//! the ends of its ranges, and `etlg_cuts_locate` turns the cuts into row positions of every hand-off object.
 use std::os::raw::c_void;
 use std::time::{Duration, Instant};
 

@@ -276,6 +276,14 @@ pub struct etlg_dl_fp_info {
 }
 
 #[repr(C)]
+pub struct etlg_cuts_info {
+    pub n_cuts: u64,
+    pub stop_event: u64,
+    pub carry_out: u64,
+    pub total: u64,
+}
+
+#[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
     pub arrays_typed: u64,
@@ -485,6 +493,21 @@ extern "C" {
         info: *mut etlg_dl_fp_info,
     ) -> i32;
     pub fn etlg_batch_size_hints(ctx: *mut etlg_ctx, batch: *mut etlg_batch, model: *const etlg_size_model, flags: u32, out: *mut u64) -> i32;
+    pub fn etlg_batch_cuts(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        model: *const etlg_size_model,
+        hints: *const u64,
+        first: u64,
+        end: u64,
+        budget: u64,
+        carry_in: u64,
+        flags: u32,
+        cuts_out: *mut u64,
+        cuts_cap: u64,
+        info: *mut etlg_cuts_info,
+    ) -> i32;
+    pub fn etlg_cuts_locate(ctx: *mut etlg_ctx, cuts: *const u64, n_cuts: u64, cuts_on_device: u32, row_event: *const u64, n_rows: u64, flags: u32, rows_out: *mut u64) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;
     pub fn etlg_ctx_slots(ctx: *const etlg_ctx, n_slots: *mut u32, slots: *mut *const etlg_slot_desc) -> i32;
 

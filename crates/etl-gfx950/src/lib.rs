@@ -283,6 +283,25 @@ impl GpuDecoder {
         let rc = unsafe { etlg_batch_size_hints(self.ctx, batch, &model, 0, out.as_mut_ptr()) };
         if rc == ETLG_OK { Ok(out) } else { Err(self.last_error()) }
     }
+
+    /// The write_events cut points of events `[first, end)` of a device-resident batch, found on the device (etlg_batch_cuts): the
+    /// exclusive ends of the batches the reference's rule closes (apply.rs:656-657, :1932-1945) when it starts with `carry_in` bytes and
+    /// flushes at `budget` — no hint is downloaded. At most `cap` cuts come back; `info.n_cuts` is the full count (resume from the last
+    /// cut with carry 0), `info.stop_event < end` names the first event the host has to size (json / array cells, partial rows), and
+    /// `info.carry_out` is what the next range, or the next decoded batch, starts with.
+    pub fn cuts(&mut self, batch: *mut etlg_batch, first: u64, end: u64, budget: u64, carry_in: u64, cap: usize) -> EtlResult<(Vec<u64>, etlg_cuts_info)> {
+        let model = reference_size_model();
+        let mut out = vec![0u64; cap];
+        let mut info = etlg_cuts_info { n_cuts: 0, stop_event: first, carry_out: carry_in, total: 0 };
+        let rc = unsafe {
+            etlg_batch_cuts(self.ctx, batch, &model, std::ptr::null(), first, end, budget, carry_in, 0, if cap == 0 { std::ptr::null_mut() } else { out.as_mut_ptr() }, cap as u64, &mut info)
+        };
+        if rc != ETLG_OK {
+            return Err(self.last_error());
+        }
+        out.truncate(info.n_cuts.min(cap as u64) as usize);
+        Ok((out, info))
+    }
 }
 
 /// The multi-GPU recipe (one `GpuDecoder` per device, one process or task per GPU — the reference itself has a single

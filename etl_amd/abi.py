@@ -141,6 +141,10 @@ class SizeModel(C.Structure):   # etlg_size_model
                                           "relation_event", "replicated_table_schema", "table_row", "cell")] + [("_reserved", C.c_uint32 * 2)]
 
 
+class CutsInfo(C.Structure):   # etlg_cuts_info
+    _fields_ = [(n, C.c_uint64) for n in ("n_cuts", "stop_event", "carry_out", "total")]
+
+
 class FinishStats(C.Structure):   # etlg_finish_stats
     _fields_ = [(n, C.c_uint64) for n in ("deferred_seen", "arrays_typed", "floats_settled", "left_deferred", "heap_bytes_added")]
 

@@ -300,6 +300,21 @@ struct HintJob {           // Event::size_hint per event (k_size_hints)
   unsigned long long* out;
 };
 
+struct CutJob {            // write_events cut points (etlg_batch_cuts: k_cut_* in finish.hip); k, a, e below are LOCAL indexes, event - first
+  const unsigned long long* hints;   // the batch's hints, n_events entries (k_size_hints' format)
+  uint64_t first, n;                 // the range [first, first + n)
+  uint64_t budget, carry_in;
+  uint32_t tile, n_tiles;            // events per scan tile; ceil(n / tile)
+  unsigned long long* tsum;          // per tile: the sum of its hints; after k_cut_scan the sum of the tiles before it
+  unsigned long long* tinc;          // per tile: the first local index with ETLG_SIZE_HINT_INCOMPLETE, ~0 none
+  unsigned long long* q;             // n + 1 entries: q[0] = 0, q[k + 1] = the hints of [first, first + k] summed
+  unsigned long long* hdr;           // [0] L = stop_event - first, [1] total = q[L], [2] n_cuts, [3] carry_out, [4] the first cut (local)
+  uint32_t* jump;                    // levels x (L + 2): level k maps the start a of a batch to the start 2^k cuts on; L + 1 = no such cut
+  uint64_t L;                        // (the host has read hdr[0] by the time it launches the kernels that take it from here)
+  uint32_t levels;
+  unsigned long long* cuts; uint64_t cuts_cap;
+};
+
 struct FinJob {            // the finish pass (k_fin_count / k_fin_fill, finish.hip)
   const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_body;
   uint8_t* fixed; uint8_t* heap;

@@ -60,6 +60,128 @@ __global__ __launch_bounds__(256) void k_size_hints(HintJob j) {
   j.out[i] = v | (inc ? (1ull << 63) : 0ull);
 }
 
+// ---- write_events cut points (etlg_batch_cuts, include/etlg.h): the apply loop's rule — EventBatch::push adds the event's hint to
+// size_hint_bytes (crates/etl/src/replication/apply.rs:656-657), the loop flushes once size_hint_bytes >= the budget (:1932-1945) and the
+// next batch starts at zero — is a prefix sum that resets, and the reset is not associative. It decomposes: with q the plain prefix sums
+// of the hints, the batch that STARTS at a ends at the smallest e > a with q[e] - q[a] >= budget, whatever came before a. So the cuts are
+// the orbit of the first cut under a -> next(a), and the p-th orbit element is reached through the jump levels next^(2^k) named by the
+// bits of p. Launches, none of which exchanges a word between its workgroups: tile sums + first INCOMPLETE per tile (k_cut_tiles), their
+// scan by one workgroup (k_cut_scan), q (k_cut_write); the host reads L and total and sizes the rest: next by binary search in q
+// (k_cut_next), one squaring per level (k_cut_level), the count and the carry by one thread (k_cut_count), the cuts (k_cut_emit).
+constexpr unsigned long long kHintMask = ~(1ull << 63);
+constexpr unsigned long long kNone64 = ~0ull;
+
+DEV uint64_t block_min64(uint64_t v, uint64_t* lds) {  // returns the workgroup minimum
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) { const uint64_t t = __shfl_xor(v, d, 64); v = t < v ? t : v; }
+  if (lane == 0) lds[wave] = v;
+  __syncthreads();
+  uint64_t m = lds[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); w++) m = lds[w] < m ? lds[w] : m;
+  __syncthreads();
+  return m;
+}
+
+__global__ __launch_bounds__(256) void k_cut_tiles(CutJob j) {
+  __shared__ uint64_t lds[4];
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n) return;
+  const uint64_t k1 = k0 + j.tile < j.n ? k0 + j.tile : j.n;
+  uint64_t sum = 0, inc = kNone64;
+  for (uint64_t k = k0 + threadIdx.x; k < k1; k += 256) {
+    const uint64_t h = j.hints[j.first + k];
+    sum += h & kHintMask;
+    if ((h >> 63) && k < inc) inc = k;
+  }
+  sum = block_sum64(sum, lds);
+  inc = block_min64(inc, lds);
+  if (threadIdx.x == 0) { j.tsum[blockIdx.x] = sum; j.tinc[blockIdx.x] = inc; }
+}
+
+// one workgroup: the tile sums become the sums in front of each tile, the tiles' first INCOMPLETE events their minimum
+__global__ __launch_bounds__(256) void k_cut_scan(CutJob j) {
+  __shared__ uint64_t lds[4];
+  uint64_t carry = 0, inc = kNone64;
+  for (uint32_t t0 = 0; t0 < j.n_tiles; t0 += 256) {
+    const uint32_t t = t0 + threadIdx.x;
+    const bool on = t < j.n_tiles;
+    const uint64_t v = on ? j.tsum[t] : 0;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(v, lds, &tot);
+    if (on) { j.tsum[t] = carry + ex; const uint64_t ti = j.tinc[t]; inc = ti < inc ? ti : inc; }
+    carry += tot;
+  }
+  inc = block_min64(inc, lds);
+  if (threadIdx.x == 0) { j.hdr[0] = inc < j.n ? inc : j.n; j.hdr[1] = 0; j.q[0] = 0; }   // (hdr[1]: k_cut_write, when L > 0)
+}
+
+__global__ __launch_bounds__(256) void k_cut_write(CutJob j) {
+  __shared__ uint64_t lds[4];
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n) return;
+  const uint64_t k1 = k0 + j.tile < j.n ? k0 + j.tile : j.n, L = j.hdr[0];
+  uint64_t carry = j.tsum[blockIdx.x];
+  for (uint64_t kb = k0; kb < k1; kb += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t k = kb + threadIdx.x;
+    const bool on = k < k1;
+    const uint64_t v = on ? j.hints[j.first + k] & kHintMask : 0;
+    uint64_t tot;
+    const uint64_t inc = carry + block_scan_excl64(v, lds, &tot) + v;
+    if (on) { j.q[k + 1] = inc; if (k + 1 == L) j.hdr[1] = inc; }
+    carry += tot;
+  }
+}
+
+// the smallest e in [lo, hi] with q[e] >= want; hi + 1 when there is none (q is ascending)
+DEV uint64_t cut_lower_bound(const unsigned long long* q, uint64_t lo, uint64_t hi, uint64_t want) {
+  uint64_t end = hi + 1;
+  while (lo < end) { const uint64_t mid = lo + ((end - lo) >> 1); if (q[mid] >= want) end = mid; else lo = mid + 1; }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void k_cut_next(CutJob j) {
+  const uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (a > j.L + 1) return;
+  j.jump[a] = a >= j.L ? (uint32_t)(j.L + 1) : (uint32_t)cut_lower_bound(j.q, a + 1, j.L, j.q[a] + j.budget);
+}
+
+__global__ __launch_bounds__(256) void k_cut_level(const uint32_t* src, uint32_t* dst, uint64_t n) {
+  const uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (a < n) dst[a] = src[src[a]];
+}
+
+__global__ __launch_bounds__(64) void k_cut_count(CutJob j) {
+  if (threadIdx.x) return;
+  const uint64_t L = j.L, W = L + 2;
+  // the first batch opens with carry_in (< budget, so the subtraction does not wrap)
+  uint64_t pos = cut_lower_bound(j.q, 1, L, j.budget - j.carry_in), n = 0;
+  j.hdr[4] = pos;
+  if (pos <= L) {
+    n = 1;
+    for (uint32_t k = j.levels; k-- > 0;) { const uint64_t nx = j.jump[(uint64_t)k * W + pos]; if (nx <= L) { pos = nx; n += 1ull << k; } }
+  }
+  j.hdr[2] = n;
+  j.hdr[3] = n ? j.q[L] - j.q[pos] : j.carry_in + j.q[L];
+}
+
+__global__ __launch_bounds__(256) void k_cut_emit(CutJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.hdr[2] || p >= j.cuts_cap) return;
+  const uint64_t W = j.L + 2;
+  uint64_t pos = j.hdr[4];
+  for (uint32_t k = 0; k < j.levels; k++) if ((p >> k) & 1u) pos = j.jump[(uint64_t)k * W + pos];
+  j.cuts[p] = j.first + pos;
+}
+
+// etlg_cuts_locate: per cut the number of rows whose event lies in front of it (row_event is ascending; equal entries stay together)
+__global__ __launch_bounds__(256) void k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows,
+                                                     unsigned long long* rows_out) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n_cuts) return;
+  rows_out[k] = n_rows ? cut_lower_bound(row_event, 0, n_rows - 1, cuts[k]) : 0;
+}
+
 // ---- the finish pass (etlg_batch_finish_cells, include/etlg.h): cells a decode left ETLG_CELL_DEFERRED are settled in the arena itself.
 // Array literals (parse_cell_from_postgres_text_array, crates/etl/src/postgres/codec/text.rs:163-312) become typed heap entries — header,
 // validity bits, element slots or end offsets + bytes (include/etlg.h: etlg_array_hdr) — appended behind the batch's heap; float texts the
@@ -227,6 +349,29 @@ using namespace etlg;
 void etlg_k_size_hints(const void* jv, hipStream_t st) {
   const HintJob j = *(const HintJob*)jv;
   if (j.n_events) hipLaunchKernelGGL(k_size_hints, dim3((uint32_t)((j.n_events + 255) / 256)), dim3(256), 0, st, j);
+}
+
+// etlg_batch_cuts: step 0 = q, L and total (grids from n and the tile), step 1 = the jump levels, the count and the cuts (grids from L
+// and from the host's bound of the cuts, min(cuts_cap, L, (carry_in + total) / budget); threads past the device's count exit)
+void etlg_k_cuts(const void* jv, int step, uint64_t emit_bound, hipStream_t st) {
+  const CutJob j = *(const CutJob*)jv;
+  if (step == 0) {
+    if (j.n_tiles) hipLaunchKernelGGL(k_cut_tiles, dim3(j.n_tiles), dim3(256), 0, st, j);
+    hipLaunchKernelGGL(k_cut_scan, dim3(1), dim3(256), 0, st, j);
+    if (j.n_tiles) hipLaunchKernelGGL(k_cut_write, dim3(j.n_tiles), dim3(256), 0, st, j);
+    return;
+  }
+  const uint64_t W = j.L + 2;
+  const uint32_t nb = (uint32_t)((W + 255) / 256);
+  hipLaunchKernelGGL(k_cut_next, dim3(nb), dim3(256), 0, st, j);
+  for (uint32_t k = 1; k < j.levels; k++) hipLaunchKernelGGL(k_cut_level, dim3(nb), dim3(256), 0, st, j.jump + (uint64_t)(k - 1) * W, j.jump + (uint64_t)k * W, W);
+  hipLaunchKernelGGL(k_cut_count, dim3(1), dim3(64), 0, st, j);
+  if (emit_bound) hipLaunchKernelGGL(k_cut_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
+}
+
+void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows, unsigned long long* rows_out,
+                        hipStream_t st) {
+  if (n_cuts) hipLaunchKernelGGL(k_cuts_locate, dim3((uint32_t)((n_cuts + 255) / 256)), dim3(256), 0, st, cuts, n_cuts, row_event, n_rows, rows_out);
 }
 
 // the finish pass: step 0 = entry sizes of every (event, image, finishable column) + their exclusive scan (blk: (ceil(n / 256) + 1) x u64

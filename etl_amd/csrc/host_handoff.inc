@@ -420,13 +420,13 @@ int32_t etlg_columns_changelog_get(const etlg_columns* cs, etlg_changelog_info* 
   return ETLG_OK;
 }
 
-int32_t etlg_batch_size_hints(etlg_ctx* c, etlg_batch* b, const etlg_size_model* m, uint32_t flags, uint64_t* out) {
-  if (!c || !b || !m || b->ctx != c) return ETLG_InvalidArgument;
-  if (const int32_t rc = batch_ready(c, b, "etlg_batch_size_hints" NEEDS_DEVICE)) return rc;
+// k_size_hints over every event of a ready batch with at least one event, enqueued on the context's stream: the slot / column tables go
+// up into a scratch block taken here, with `extra` bytes behind them (*extra_at); the hints go to `out` (device memory), or `hints_off`
+// bytes into `extra` when out is null.
+static int32_t size_hints_enqueue(etlg_ctx* c, etlg_batch* b, const etlg_size_model* m, ScratchBlk& dblk, size_t extra, size_t hints_off, unsigned long long* out,
+                                  uint8_t** extra_at) {
   const etlg_batch_view& bv = b->v;
   const uint64_t ne = bv.n_events;
-  if (!ne) return ETLG_OK;
-  if (!out) return ETLG_InvalidArgument;
   hipStream_t s = c->stream;
   std::vector<uint32_t> tab;
   const uint32_t ns = (uint32_t)c->slots.size();
@@ -442,11 +442,10 @@ int32_t etlg_batch_size_hints(etlg_ctx* c, etlg_batch* b, const etlg_size_model*
   tab.resize(o_cols + (size_t)ncols * 2);
   for (uint32_t i = 0, k = 0; i < ns; i++)
     for (const etlg_slot_col& col : c->slots[i]->cols) { tab[o_cols + 2 * k] = col.type_class | (col.identity ? 1u << 8 : 0u) | ((uint32_t)col.off_full << 16); tab[o_cols + 2 * k + 1] = col.off_key; k++; }
-  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
   const size_t tab_bytes = (tab.size() * 4 + 63) & ~(size_t)63;
-  ScratchBlk dblk{c};
-  HIPCHK(c, blk_take(c, tab_bytes + (on_dev ? 0 : ne * 8) + 64, false, &dblk.p, &dblk.cap));
+  HIPCHK(c, blk_take(c, tab_bytes + extra + 64, false, &dblk.p, &dblk.cap));
   void* d = dblk.p;
+  *extra_at = (uint8_t*)d + tab_bytes;
   HIPCHK(c, hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
   HintJob j{};
   j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_table = bv.ev_table_id; j.ev_slot = bv.ev_schema_slot; j.ev_body = bv.ev_body_off;
@@ -454,10 +453,103 @@ int32_t etlg_batch_size_hints(etlg_ctx* c, etlg_batch* b, const etlg_size_model*
   j.slots = (const uint32_t*)d; j.cols = (const uint32_t*)d + o_cols; j.n_slots = ns;
   j.m_begin = m->begin_event; j.m_commit = m->commit_event; j.m_insert = m->insert_event; j.m_update = m->update_event; j.m_delete = m->delete_event;
   j.m_truncate = m->truncate_event; j.m_relation = m->relation_event; j.m_rts = m->replicated_table_schema; j.m_row = m->table_row; j.m_cell = m->cell;
-  j.out = on_dev ? (unsigned long long*)out : (unsigned long long*)((uint8_t*)d + tab_bytes);
+  j.out = out ? out : (unsigned long long*)(*extra_at + hints_off);
   etlg_k_size_hints(&j, s);
-  if (!on_dev) HIPCHK(c, hipMemcpyAsync(out, j.out, ne * 8, hipMemcpyDeviceToHost, s));
+  return ETLG_OK;
+}
+
+int32_t etlg_batch_size_hints(etlg_ctx* c, etlg_batch* b, const etlg_size_model* m, uint32_t flags, uint64_t* out) {
+  if (!c || !b || !m || b->ctx != c) return ETLG_InvalidArgument;
+  if (const int32_t rc = batch_ready(c, b, "etlg_batch_size_hints" NEEDS_DEVICE)) return rc;
+  const uint64_t ne = b->v.n_events;
+  if (!ne) return ETLG_OK;
+  if (!out) return ETLG_InvalidArgument;
+  hipStream_t s = c->stream;
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  ScratchBlk dblk{c};
+  uint8_t* staged = nullptr;
+  RC(size_hints_enqueue(c, b, m, dblk, on_dev ? 0 : ne * 8, 0, on_dev ? (unsigned long long*)out : nullptr, &staged));
+  if (!on_dev) HIPCHK(c, hipMemcpyAsync(out, staged, ne * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));   // the tables are freed on return
+  return ETLG_OK;
+}
+
+// write_events cut points (include/etlg.h; k_cut_* in finish.hip). Two stops for the device: the first learns L = stop_event - first
+// and total, from which the host bounds the cuts — every closed batch sums to at least `budget` — and with the bound sizes the jump
+// levels and the launch that writes the cuts; the second brings the counts (and the cuts, for a host caller). A range that cannot hold a
+// cut ends at the first stop.
+int32_t etlg_batch_cuts(etlg_ctx* c, etlg_batch* b, const etlg_size_model* m, const uint64_t* hints, uint64_t first, uint64_t end, uint64_t budget,
+                        uint64_t carry_in, uint32_t flags, uint64_t* cuts_out, uint64_t cuts_cap, etlg_cuts_info* info) {
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  *info = etlg_cuts_info{};
+  if (!m && !hints) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_cuts: without `hints` the library evaluates them and needs the size model");
+  if (budget < 1 || budget > (1ull << 62) || carry_in >= budget) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_cuts: budget in [1, 2^62] and carry_in < budget");
+  if (cuts_cap && !cuts_out) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_cuts: cuts_cap without cuts_out");
+  if (const int32_t rc = batch_ready(c, b, "etlg_batch_cuts" NEEDS_DEVICE)) return rc;
+  const uint64_t ne = b->v.n_events;
+  if (first > end || end > ne) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_cuts: first <= end <= n_events");
+  const uint64_t n = end - first;
+  if (n >= 0xFFFFFFF0ull) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_cuts: the range is beyond what one call cuts (32-bit jump tables)");
+  info->stop_event = first; info->carry_out = carry_in;
+  if (!n) return ETLG_OK;
+  hipStream_t s = c->stream;
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  uint64_t tile = c->cuts_tile_test ? c->cuts_tile_test : 2048u;
+  while ((n + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  const uint64_t n_tiles = (n + tile - 1) / tile;
+  const size_t o_tsum = al64(5 * 8), o_tinc = o_tsum + al64(n_tiles * 8), o_q = o_tinc + al64(n_tiles * 8), o_hints = o_q + al64((n + 1) * 8),
+               total_bytes = o_hints + (hints ? 0 : al64(ne * 8));
+  ScratchBlk ablk{c};
+  uint8_t* d = nullptr;
+  if (hints) { HIPCHK(c, blk_take(c, total_bytes + 64, false, &ablk.p, &ablk.cap)); d = (uint8_t*)ablk.p; }
+  else RC(size_hints_enqueue(c, b, m, ablk, total_bytes, o_hints, nullptr, &d));   // k_size_hints, as etlg_batch_size_hints launches it
+  CutJob j{};
+  j.first = first; j.n = n; j.budget = budget; j.carry_in = carry_in; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles;
+  j.hdr = (unsigned long long*)d; j.tsum = (unsigned long long*)(d + o_tsum); j.tinc = (unsigned long long*)(d + o_tinc); j.q = (unsigned long long*)(d + o_q);
+  j.hints = hints ? (const unsigned long long*)hints : (const unsigned long long*)(d + o_hints);
+  etlg_k_cuts(&j, 0, 0, s);
+  uint64_t head[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // stop 1: L and total
+  const uint64_t L = head[0], total = head[1];
+  info->stop_event = first + L; info->total = total; info->carry_out = carry_in + total;
+  const uint64_t by_sum = (carry_in + total) / budget, max_cuts = by_sum < L ? by_sum : L;
+  if (!max_cuts) return ETLG_OK;
+  uint32_t levels = 0;
+  while ((max_cuts >> levels) != 0) levels++;   // 2^levels > max_cuts >= n_cuts
+  const uint64_t emit = cuts_cap < max_cuts ? cuts_cap : max_cuts;
+  const size_t o_cuts = al64((size_t)levels * (L + 2) * 4);
+  ScratchBlk jblk{c};
+  HIPCHK(c, blk_take(c, o_cuts + (on_dev ? 0 : al64(emit * 8)) + 64, false, &jblk.p, &jblk.cap));
+  j.jump = (uint32_t*)jblk.p; j.L = L; j.levels = levels; j.cuts_cap = emit;
+  j.cuts = on_dev ? (unsigned long long*)cuts_out : (unsigned long long*)((uint8_t*)jblk.p + o_cuts);
+  etlg_k_cuts(&j, 1, emit, s);
+  uint64_t tail[2] = {0, 0};   // n_cuts, carry_out
+  HIPCHK(c, hipMemcpyAsync(tail, j.hdr + 2, sizeof tail, hipMemcpyDeviceToHost, s));
+  std::vector<uint64_t> back;
+  if (!on_dev && emit) { back.resize(emit); HIPCHK(c, hipMemcpyAsync(back.data(), j.cuts, emit * 8, hipMemcpyDeviceToHost, s)); }
+  HIPCHK(c, hipStreamSynchronize(s));   // stop 2
+  info->n_cuts = tail[0]; info->carry_out = tail[1];
+  if (!on_dev && emit) memcpy(cuts_out, back.data(), (size_t)(tail[0] < emit ? tail[0] : emit) * 8);
+  return ETLG_OK;
+}
+
+int32_t etlg_cuts_locate(etlg_ctx* c, const uint64_t* cuts, uint64_t n_cuts, uint32_t cuts_on_device, const uint64_t* row_event, uint64_t n_rows,
+                         uint32_t flags, uint64_t* rows_out) {
+  if (!c) return ETLG_InvalidArgument;
+  if (!n_cuts) return ETLG_OK;
+  if (!cuts || !rows_out || (n_rows && !row_event)) return lib_error(c, ETLG_InvalidArgument, "etlg_cuts_locate: null cuts, rows_out or row_event");
+  hipStream_t s = c->stream;
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  ScratchBlk dblk{c};
+  const size_t o_out = cuts_on_device ? 0 : al64(n_cuts * 8);
+  uint8_t* d = nullptr;
+  if (!cuts_on_device || !on_dev) { HIPCHK(c, blk_take(c, o_out + (on_dev ? 0 : al64(n_cuts * 8)) + 64, false, &dblk.p, &dblk.cap)); d = (uint8_t*)dblk.p; }
+  if (!cuts_on_device) HIPCHK(c, hipMemcpyAsync(d, cuts, n_cuts * 8, hipMemcpyHostToDevice, s));
+  unsigned long long* out_d = on_dev ? (unsigned long long*)rows_out : (unsigned long long*)(d + o_out);
+  etlg_k_cuts_locate(cuts_on_device ? (const unsigned long long*)cuts : (const unsigned long long*)d, n_cuts, (const unsigned long long*)row_event, n_rows, out_d, s);
+  if (!on_dev) HIPCHK(c, hipMemcpyAsync(rows_out, out_d, n_cuts * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop (a device caller's too: the uploaded cuts are freed on return)
   return ETLG_OK;
 }
 

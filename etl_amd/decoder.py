@@ -122,6 +122,40 @@ class Batch:
             raise self.dec.last_error()
         return out
 
+    def cuts(self, model, budget, carry_in=0, first=0, end=None, hints=None, cap=None, on_device=False):
+        """Where the apply loop cuts events [first, end) into write_events batches, found on the device (etlg_batch_cuts): a cut behind
+        the event at which carry_in + the hints since the last cut reach `budget`. `model`: abi.SizeModel, or None with `hints`, the
+        address of a DEVICE array of n_events hints (size_hints' format) that replaces the library's own. `cap`: the cuts to write at most
+        (default: as many as the range has events). on_device: False -> the cuts come back as np.uint64[min(n_cuts, cap)]; the address
+        of a device array of `cap` u64 -> they are written there and the address is returned.
+        Returns (cuts, abi.CutsInfo): n_cuts may exceed cap; stop_event < end names the first INCOMPLETE event."""
+        end = int(self.view().n_events) if end is None else int(end)
+        cap = max(0, end - int(first)) if cap is None else int(cap)
+        info = abi.CutsInfo()
+        out = None if on_device else np.zeros(cap, dtype=np.uint64)
+        ptr = (int(on_device) if cap else None) if on_device else (out.ctypes.data if cap else None)
+        rc = self.dec.L.etlg_batch_cuts(self.dec.h, self.h, C.byref(model) if model is not None else None, hints, int(first), end, int(budget), int(carry_in),
+                                        abi.F_OUTPUT_ON_DEVICE if on_device else 0, ptr, cap, C.byref(info))
+        if rc != abi.OK:
+            raise self.dec.last_error()
+        return (on_device if on_device else out[:min(cap, int(info.n_cuts))]), info
+
+    def locate(self, cuts, row_event, n_rows, n_cuts=None, out=None):
+        """Rows in front of every cut (etlg_cuts_locate): np.uint64[k] = the number of entries of `row_event` below cuts[k]. `row_event`:
+        the address of the DEVICE row_event array (n_rows entries) of a hand-off object built from this batch. `cuts`: a host array, or the
+        address of a device array of `n_cuts` entries. `out`: the address of a device array the counts go to instead (returned as is)."""
+        if isinstance(cuts, (int, np.integer)):
+            cptr, n, dev = int(cuts), int(n_cuts), 1
+        else:
+            cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+            cptr, n, dev = (cuts.ctypes.data if len(cuts) else None), len(cuts), 0
+        res = None if out else np.zeros(n, dtype=np.uint64)
+        rc = self.dec.L.etlg_cuts_locate(self.dec.h, cptr, n, dev, row_event, int(n_rows), abi.F_OUTPUT_ON_DEVICE if out else 0,
+                                         int(out) if out else (res.ctypes.data if n else None))
+        if rc != abi.OK:
+            raise self.dec.last_error()
+        return out if out else res
+
     def rowbinary(self, slot, nullable_flags, engine=abi.CH_MERGE_TREE, on_device=False):
         """ClickHouse RowBinary rows of schema slot `slot`, encoded on the device (etlg_batch_rowbinary). Raises EtlError for
         the reference's ConversionErrors; `RowBinary.status == abi.RB_NEEDS_HOST` when a cell has no device encoding."""

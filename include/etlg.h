@@ -1065,6 +1065,58 @@ typedef struct etlg_size_model {
 int32_t etlg_batch_size_hints(etlg_ctx* ctx, etlg_batch* batch, const etlg_size_model* model, uint32_t flags,
                               uint64_t* out);
 
+/* Where the apply loop cuts the event stream into write_events batches, found on the device: no hint comes back to the host.
+ * The reference's rule: EventBatch::push adds event.size_hint() to a running size_hint_bytes (crates/etl/src/replication/apply.rs:656-657);
+ * after every message the loop flushes when size_hint_bytes >= cached_batch_budget.current_batch_size_bytes() (:1932-1945); the flush takes
+ * the batch and the next one starts at zero. Over the events [first, stop_event) of this batch:
+ *     s = carry_in
+ *     for i in first .. stop_event:
+ *         s += hint[i]
+ *         if s >= budget: emit cut i + 1 (the exclusive end of a write_events batch); s = 0
+ *     carry_out = s
+ * cuts_out receives the cuts, ascending event indexes. When n_cuts > cuts_cap the first cuts_cap cuts are written and n_cuts is the full
+ * count: the caller resumes with first = cuts_out[cuts_cap - 1] and carry_in = 0. That is the contract, not an error. cuts_cap == 0 with
+ * cuts_out == NULL only counts. With ETLG_F_OUTPUT_ON_DEVICE in `flags` cuts_out is device memory, else host memory.
+ * hints == NULL: the library evaluates the hints itself (etlg_batch_size_hints' kernel) into pooled device memory; `model` is required.
+ * hints != NULL: a DEVICE array of n_events entries in etlg_batch_size_hints' format; `model` may be NULL. This form is for tables with
+ * json / array columns and for partial Updates: the host sizes the INCOMPLETE events, writes the completed values — bit 63 cleared —
+ * into its device copy of the hints and calls again; without it every such table would come down to one call per event. The caller's
+ * values are sizes of real events: like the library's, their sum over the range, plus carry_in, plus budget, stays below 2^64.
+ * An event whose hint has ETLG_SIZE_HINT_INCOMPLETE stops the walk: stop_event is the first such event of [first, end) (else `end`), the
+ * cuts are exact up to it, carry_out is the running sum there; the host adds that one event and resumes at stop_event + 1.
+ * What only the host knows it says through the range and the carry: a forced flush after a Commit (end_batch, apply.rs:2337-2353) or at
+ * the deadline ends the range there and starts the next one with carry_in = 0; a change of the budget (CachedBatchBudget refreshes at most
+ * every 100 ms, runtime/batch_budget.rs:123-137) ends the range where it takes effect, and carry_out goes on as the next carry_in; the
+ * sum left open by the previous decoded batch is the first range's carry_in.
+ * Arguments: budget in [1, 2^62]; carry_in < budget (the reference would already have flushed otherwise); first <= end <= n_events; a
+ * model or hints; anything else is ETLG_InvalidArgument. No sum can wrap: carry_in < budget <= 2^62, and a batch's hints are bounded by its
+ * arena bytes plus the model's constants per column (u32 each), far below 2^62 — so the reference's saturating_add never saturates and
+ * plain 64-bit adds are the rule.
+ * Same batch requirements as etlg_batch_columns (device-resident, finished; an ASYNC batch is synced first).
+ * The call stops for the device at most twice: once to learn stop_event and total — the host bounds the cuts by
+ * min(stop_event - first, (carry_in + total) / budget), every closed batch summing to at least budget, and sizes the remaining launches
+ * with that bound — and once at its end. A range that cannot hold a cut (the bound is 0, or first == end) ends at the first stop.
+ * What is tested: the reference's tests state no cut position as a number; tests/batch_cuts.py restates the three lines above. */
+typedef struct etlg_cuts_info {
+  uint64_t n_cuts;      /* cuts the rule makes in [first, stop_event): may exceed cuts_cap */
+  uint64_t stop_event;  /* first event of [first, end) whose hint has ETLG_SIZE_HINT_INCOMPLETE, else `end` */
+  uint64_t carry_out;   /* size_hint_bytes of the batch left open at stop_event (behind the last cut) */
+  uint64_t total;       /* sum of the hints of [first, stop_event) */
+} etlg_cuts_info;
+
+int32_t etlg_batch_cuts(etlg_ctx* ctx, etlg_batch* batch, const etlg_size_model* model, const uint64_t* hints,
+                        uint64_t first, uint64_t end, uint64_t budget, uint64_t carry_in, uint32_t flags,
+                        uint64_t* cuts_out, uint64_t cuts_cap, etlg_cuts_info* info);
+
+/* rows_out[k] = the number of rows whose row_event < cuts[k] (a lower bound), for n_cuts cuts: where a hand-off object's rows are cut so
+ * that every slice holds the rows of one write_events batch, without downloading row_event. row_event: the DEVICE row_event array (n_rows
+ * entries, ascending) of any hand-off object — etlg_columns_view, the iceberg and ducklake-copy results, etlg_rowbinary_view of the
+ * RowBinary / protobuf / NDJSON / DuckLake calls. Consecutive equal entries (BigQuery's DELETE + UPSERT pair of one event) fall on the
+ * same side of a cut. `cuts` is device memory when cuts_on_device != 0, else host memory; rows_out is device memory with
+ * ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory. The call stops for the device once, at its end. */
+int32_t etlg_cuts_locate(etlg_ctx* ctx, const uint64_t* cuts, uint64_t n_cuts, uint32_t cuts_on_device,
+                         const uint64_t* row_event, uint64_t n_rows, uint32_t flags, uint64_t* rows_out);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
