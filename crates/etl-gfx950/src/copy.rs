@@ -7,6 +7,7 @@
 //! ```
 //! The per-row `TableCopyPayloadMetadata` (table_copy.rs:84: the byte length of the text row) stays exact: `CopyStaging` keeps
 //! every row's length, and the batch's `payload_bytes[0]` is their sum over the rows that decoded.
+//! A device-resident copy batch gets the same call as a WAL batch: `etlg_batch_payload` with the rows and their offsets reports them under `ETLG_PK_COPY`.
 use etl::bail;
 use etl::data::TableRow;
 use etl::error::{ErrorKind, EtlResult};

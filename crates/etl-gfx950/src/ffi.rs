@@ -284,6 +284,22 @@ pub struct etlg_cuts_info {
 }
 
 #[repr(C)]
+pub struct etlg_payload_sums {
+    pub bytes: [u64; 4],
+    pub rows: [u64; 4],
+}
+
+#[repr(C)]
+pub struct etlg_payload_info {
+    pub received_bytes: [u64; 4],
+    pub received_rows: [u64; 4],
+    pub n_ranges: u64,
+    pub status: i32,
+    pub _pad: u32,
+    pub mismatch_event: u64,
+}
+
+#[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
     pub arrays_typed: u64,
@@ -320,6 +336,12 @@ pub const ETLG_CH_MERGE_TREE: i32 = 0;
 pub const ETLG_CH_REPLACING_MERGE_TREE: i32 = 1;
 pub const ETLG_RB_OK: u32 = 0;
 pub const ETLG_RB_NEEDS_HOST: u32 = 3;
+pub const ETLG_PK_INSERT: u32 = 0;
+pub const ETLG_PK_UPDATE: u32 = 1;
+pub const ETLG_PK_DELETE: u32 = 2;
+pub const ETLG_PK_COPY: u32 = 3;
+pub const ETLG_PM_OK: u32 = 0;
+pub const ETLG_PM_MISMATCH: u32 = 1;
 pub const ETLG_DL_TUPLES: i32 = 0;
 pub const ETLG_DL_PREDICATES: i32 = 1;
 pub const ETLG_DL_UPDATES: i32 = 3;
@@ -508,6 +530,24 @@ extern "C" {
         info: *mut etlg_cuts_info,
     ) -> i32;
     pub fn etlg_cuts_locate(ctx: *mut etlg_ctx, cuts: *const u64, n_cuts: u64, cuts_on_device: u32, row_event: *const u64, n_rows: u64, flags: u32, rows_out: *mut u64) -> i32;
+    pub fn etlg_batch_payload(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        buf: *const u8,
+        len: usize,
+        frame_offsets: *const u32,
+        nframes: usize,
+        cuts: *const u64,
+        n_cuts: u64,
+        cuts_on_device: u32,
+        hist_bounds: *const u64,
+        n_bounds: u32,
+        flags: u32,
+        ev_bytes_out: *mut u32,
+        sums_out: *mut etlg_payload_sums,
+        hist_out: *mut u64,
+        info: *mut etlg_payload_info,
+    ) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;
     pub fn etlg_ctx_slots(ctx: *const etlg_ctx, n_slots: *mut u32, slots: *mut *const etlg_slot_desc) -> i32;
 

@@ -302,6 +302,44 @@ impl GpuDecoder {
         out.truncate(info.n_cuts.min(cap as u64) as usize);
         Ok((out, info))
     }
+
+    /// Source payload accounting of a device-resident batch, on the device (etlg_batch_payload), as plain values: per event the value
+    /// bytes of its message (what `StreamingPayloadMetadata::{insert,update,delete}` is built from, apply.rs:2459-2463; the kind is the
+    /// event's), per range of `cuts` the merged bytes and rows per kind (what `EventBatch::push` accumulates, apply.rs:656-658; rows == 0
+    /// is `None`), the histogram of `etl_row_size_bytes` over `bounds` and, in the info, what `record_received` counts — every row
+    /// message of the batch, owned or not. Called on a batch in flight, BEFORE `finish` (which downloads the arena and frees the batch):
+    /// the batch is waited for here, and its staged buffer is the input the call reads again. `cuts` as `GpuDecoder::cuts` returns them,
+    /// empty for one range. A batch that ended in a decode error is accounted up to the error (its events are delivered).
+    pub fn payload(&mut self, f: &InFlight, cuts: &[u64], bounds: &[u64]) -> EtlResult<PayloadAccount> {
+        let (batch, staged) = (f.batch, f.staged.as_ref().expect("batch already collected"));
+        let _ = unsafe { etlg_batch_sync(self.ctx, batch) };             // (a decode error is `finish`'s to report)
+        let mut view = std::mem::MaybeUninit::<etlg_batch_view>::uninit();
+        unsafe { etlg_batch_view_get(batch, view.as_mut_ptr()) };
+        let n_events = unsafe { view.assume_init() }.n_events as usize;
+        let mut acc = PayloadAccount {
+            ev_bytes: vec![0u32; n_events],
+            sums: (0..cuts.len() + 1).map(|_| etlg_payload_sums { bytes: [0; 4], rows: [0; 4] }).collect(),
+            hist: vec![0u64; 4 * (bounds.len() + 1)],
+            info: etlg_payload_info { received_bytes: [0; 4], received_rows: [0; 4], n_ranges: 0, status: 0, _pad: 0, mismatch_event: u64::MAX },
+        };
+        let rc = unsafe {
+            etlg_batch_payload(
+                self.ctx, batch, staged.frames_ptr(), staged.len, staged.offsets_ptr(), staged.nframes,
+                if cuts.is_empty() { std::ptr::null() } else { cuts.as_ptr() }, cuts.len() as u64, 0,
+                if bounds.is_empty() { std::ptr::null() } else { bounds.as_ptr() }, bounds.len() as u32, 0,
+                if n_events == 0 { std::ptr::null_mut() } else { acc.ev_bytes.as_mut_ptr() }, acc.sums.as_mut_ptr(), acc.hist.as_mut_ptr(), &mut acc.info,
+            )
+        };
+        if rc == ETLG_OK { Ok(acc) } else { Err(self.last_error()) }
+    }
+}
+
+/// What `GpuDecoder::payload` returns. `hist[k * (bounds + 1) + j]`: messages of kind k (ETLG_PK_*) in bucket j, the last the overflow.
+pub struct PayloadAccount {
+    pub ev_bytes: Vec<u32>,
+    pub sums: Vec<etlg_payload_sums>,
+    pub hist: Vec<u64>,
+    pub info: etlg_payload_info,
 }
 
 /// The multi-GPU recipe (one `GpuDecoder` per device, one process or task per GPU — the reference itself has a single

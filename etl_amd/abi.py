@@ -145,6 +145,15 @@ class CutsInfo(C.Structure):   # etlg_cuts_info
     _fields_ = [(n, C.c_uint64) for n in ("n_cuts", "stop_event", "carry_out", "total")]
 
 
+class PayloadSums(C.Structure):   # etlg_payload_sums
+    _fields_ = [("bytes", C.c_uint64 * 4), ("rows", C.c_uint64 * 4)]
+
+
+class PayloadInfo(C.Structure):   # etlg_payload_info
+    _fields_ = [("received_bytes", C.c_uint64 * 4), ("received_rows", C.c_uint64 * 4), ("n_ranges", C.c_uint64), ("status", C.c_int32), ("_pad", C.c_uint32),
+                ("mismatch_event", C.c_uint64)]
+
+
 class FinishStats(C.Structure):   # etlg_finish_stats
     _fields_ = [(n, C.c_uint64) for n in ("deferred_seen", "arrays_typed", "floats_settled", "left_deferred", "heap_bytes_added")]
 
@@ -152,6 +161,8 @@ class FinishStats(C.Structure):   # etlg_finish_stats
 SIZE_HINT_INCOMPLETE = 1 << 63
 CH_MERGE_TREE, CH_REPLACING_MERGE_TREE = 0, 1
 RB_OK, RB_NEEDS_HOST = 0, 3
+PK_INSERT, PK_UPDATE, PK_DELETE, PK_COPY = range(4)
+PM_OK, PM_MISMATCH = 0, 1
 DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)

@@ -315,6 +315,36 @@ struct CutJob {            // write_events cut points (etlg_batch_cuts: k_cut_* 
   unsigned long long* cuts; uint64_t cuts_cap;
 };
 
+// Source payload accounting (etlg_batch_payload). The frame side (k_payf_* in kernels.hip) measures every row message and lists the
+// frames that take a transaction ordinal; the event side (k_paye_* in finish.hip) joins every event to its frame through that list and
+// sums the ranges. Channels: 0 Insert, 1 Update, 2 Delete; a table-copy batch has channel 0 alone and reports it as ETLG_PK_COPY.
+constexpr uint32_t kPayBad = 0xFFFFFFFFu;   // fbytes of a row message that does not parse, or of a copy row whose offsets do not hold
+constexpr uint32_t kPayBuckets = 65;        // 64 bounds at the most, and the overflow bucket
+enum : uint32_t { PAY_H_BYTES = 0, PAY_H_ROWS = 4, PAY_H_COUNTS = 8, PAY_H_MISMATCH = 9, PAY_H_BAD_CUTS = 10, PAY_H_WORDS = 11 };
+struct PayJob {
+  const uint8_t* in; const uint32_t* offs; const uint8_t* f_tag; uint64_t in_len;   // the input the batch was decoded from, and k_classify's tags
+  uint32_t n_frames;         // frames the batch consumed (view.n_frames): the ordinals and the Begins are counted over them
+  uint32_t n_recv;           // frames the received side measures: n_frames, + 1 when the failing frame had recorded its metrics
+  uint32_t copy;             // table-copy batch: frame f is row f, its bytes offs[f + 1] - offs[f]
+  uint32_t tile, n_tiles;    // frames per tile; ceil(n_recv / tile)
+  const unsigned long long* bounds; uint32_t n_bounds;
+  uint32_t* fbytes;          // per frame of [0, n_recv): the value bytes of a row message, 0 for any other frame, or kPayBad
+  unsigned long long* tcnt;  // per tile: ordinal-taking frames | Begin frames << 32; after k_payf_scan the counts in front of the tile
+  uint32_t* r2f;             // rank among the ordinal-taking frames -> frame
+  uint32_t* brank;           // j-th Begin frame -> its rank
+  unsigned long long* hdr;   // PAY_H_*: received bytes[4], rows[4]; ordinal-taking frames | Begin frames << 32; first mismatching event; bad cuts
+  unsigned long long* hist;  // 4 x (n_bounds + 1) counts
+  const uint8_t* ev_kind; const unsigned long long* ev_ord; uint64_t n_events;
+  uint64_t entry_ord;        // the transaction ordinal the batch started from (events in front of its first Begin)
+  uint32_t etile, n_etiles;  // events per tile; ceil(n_events / etile)
+  unsigned long long* etb;   // per event tile: its 'B' events; after k_paye_scan those in front of it
+  uint32_t* ev_bytes;        // per event: the value bytes of its message
+  unsigned long long* tsum;  // per event tile: bytes[3], rows[3] of the channels; after k_paye_sums those in front of it (null: no range sums)
+  unsigned long long* pb; uint32_t* pr;   // 3 x (n_events + 1) prefix sums of the channels' bytes and rows
+  const unsigned long long* cuts; uint64_t n_cuts;
+  unsigned long long* sums;  // n_cuts + 1 x etlg_payload_sums
+};
+
 struct FinJob {            // the finish pass (k_fin_count / k_fin_fill, finish.hip)
   const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_body;
   uint8_t* fixed; uint8_t* heap;

@@ -182,6 +182,139 @@ __global__ __launch_bounds__(256) void k_cuts_locate(const unsigned long long* c
   rows_out[k] = n_rows ? cut_lower_bound(row_event, 0, n_rows - 1, cuts[k]) : 0;
 }
 
+// ---- source payload accounting, event side (etlg_batch_payload, include/etlg.h): what EventBatch::push merges for the events of one
+// write_events batch (apply.rs:656-658) and record_processed reports. The arena no longer has a message's value bytes (integers, floats
+// and temporals are decoded), so every event is joined to its frame: the frame side (kernels.hip) has listed the frames that take a
+// transaction ordinal (rank -> frame) and the rank of every Begin frame. A Begin always yields an event, so the j-th 'B' event is the
+// j-th Begin frame, and the frame of an event is the (rank of its Begin + ev_tx_ordinal)-th listed frame; in front of the batch's first
+// Begin it is the (ev_tx_ordinal - entry ordinal)-th. The joined frame must carry the event's kind: anything else is a MISMATCH (the
+// caller passed other bytes than the batch was decoded from). Launches, none of which exchanges a word between its workgroups: 'B'
+// events per tile (k_paye_tiles), their scan by one workgroup (k_paye_scan), the join, ev_bytes and the channels' sums per tile
+// (k_paye_join), those scanned (k_paye_sums), the prefix sums of bytes and rows per channel (k_paye_prefix), a lane per range
+// (k_paye_ranges). Sums are plain 64-bit adds: a batch's value bytes are below 2^32 per frame and 2^30 frames, far from 2^64.
+DEV uint32_t pay_channel(uint32_t kind) { return kind == 'I' ? 0u : kind == 'U' ? 1u : kind == 'D' ? 2u : 3u; }
+
+__global__ __launch_bounds__(256) void k_paye_tiles(PayJob j) {
+  __shared__ uint64_t lds[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * j.etile, i1 = i0 + j.etile < j.n_events ? i0 + j.etile : j.n_events;
+  uint64_t n = 0;
+  for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256) n += j.ev_kind[i] == 'B';
+  n = block_sum64(n, lds);
+  if (threadIdx.x == 0) j.etb[blockIdx.x] = n;
+}
+
+__global__ __launch_bounds__(256) void k_paye_scan(PayJob j) {
+  __shared__ uint64_t lds[4];
+  uint64_t carry = 0;
+  for (uint32_t t0 = 0; t0 < j.n_etiles; t0 += 256) {
+    const uint32_t t = t0 + threadIdx.x;
+    const bool on = t < j.n_etiles;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(on ? j.etb[t] : 0, lds, &tot);
+    if (on) j.etb[t] = carry + ex;
+    carry += tot;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_paye_join(PayJob j) {
+  __shared__ uint64_t lds[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * j.etile, i1 = i0 + j.etile < j.n_events ? i0 + j.etile : j.n_events;
+  const uint64_t n_cons = j.hdr[PAY_H_COUNTS] & 0xFFFFFFFFull, n_begin = j.hdr[PAY_H_COUNTS] >> 32;
+  uint64_t carry = j.copy ? 0 : j.etb[blockIdx.x], sb[3] = {0, 0, 0}, sr[3] = {0, 0, 0};
+  for (uint64_t ib = i0; ib < i1; ib += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t i = ib + threadIdx.x;
+    const bool on = i < i1;
+    const uint32_t kind = on ? j.ev_kind[i] : 0;
+    uint64_t begins = 0;   // 'B' events up to and including this one
+    if (!j.copy) {
+      const uint64_t v = kind == 'B';
+      uint64_t tot;
+      begins = carry + block_scan_excl64(v, lds, &tot) + v;
+      carry += tot;
+    }
+    if (on) {
+      uint32_t ch = 3, bytes = kPayBad;
+      if (j.copy) {   // event i is row i
+        ch = 0;
+        if (i < j.n_frames) bytes = j.fbytes[i];
+      } else {
+        const uint64_t ord = j.ev_ord[i];
+        uint64_t rank = ~0ull;
+        if (begins) { if (begins <= n_begin) rank = (uint64_t)j.brank[begins - 1] + ord; }
+        else if (ord >= j.entry_ord) rank = ord - j.entry_ord;
+        if (rank < n_cons) {
+          const uint32_t f = j.r2f[rank];
+          if (j.f_tag[f] == kind) { ch = pay_channel(kind); bytes = j.fbytes[f]; }   // (0 for B / C / R / T, kPayBad for a row message that does not parse)
+        }
+      }
+      if (bytes == kPayBad) { atomicMin(&j.hdr[PAY_H_MISMATCH], (unsigned long long)i); bytes = 0; ch = 3; }
+      j.ev_bytes[i] = bytes;
+      if (ch < 3) { sb[ch] += bytes; sr[ch] += 1; }
+    }
+  }
+  if (!j.tsum) return;
+  for (int k = 0; k < 3; k++) { sb[k] = block_sum64(sb[k], lds); sr[k] = block_sum64(sr[k], lds); }
+  if (threadIdx.x == 0) for (int k = 0; k < 3; k++) { j.tsum[6 * (uint64_t)blockIdx.x + k] = sb[k]; j.tsum[6 * (uint64_t)blockIdx.x + 3 + k] = sr[k]; }
+}
+
+// one workgroup: each of the six sums per tile becomes the sum in front of the tile
+__global__ __launch_bounds__(256) void k_paye_sums(PayJob j) {
+  __shared__ uint64_t lds[4];
+  for (uint32_t k = 0; k < 6; k++) {
+    uint64_t carry = 0;
+    for (uint32_t t0 = 0; t0 < j.n_etiles; t0 += 256) {
+      const uint32_t t = t0 + threadIdx.x;
+      const bool on = t < j.n_etiles;
+      uint64_t tot;
+      const uint64_t ex = block_scan_excl64(on ? j.tsum[6 * (uint64_t)t + k] : 0, lds, &tot);
+      if (on) j.tsum[6 * (uint64_t)t + k] = carry + ex;
+      carry += tot;
+    }
+  }
+  if (threadIdx.x < 3) { j.pb[(uint64_t)threadIdx.x * (j.n_events + 1)] = 0; j.pr[(uint64_t)threadIdx.x * (j.n_events + 1)] = 0; }
+}
+
+// pb[c][i + 1], pr[c][i + 1] = bytes and rows of channel c over the events [0, i]. One scan per channel: a chunk of 256 events holds
+// less than 2^40 bytes, so the rows ride above bit 40 of the same word; the carries are kept apart.
+__global__ __launch_bounds__(256) void k_paye_prefix(PayJob j) {
+  __shared__ uint64_t lds[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * j.etile, i1 = i0 + j.etile < j.n_events ? i0 + j.etile : j.n_events, W = j.n_events + 1;
+  constexpr uint64_t kLow = (1ull << 40) - 1;
+  uint64_t cb[3], cr[3];
+  for (int k = 0; k < 3; k++) { cb[k] = j.tsum[6 * (uint64_t)blockIdx.x + k]; cr[k] = j.tsum[6 * (uint64_t)blockIdx.x + 3 + k]; }
+  for (uint64_t ib = i0; ib < i1; ib += 256) {
+    const uint64_t i = ib + threadIdx.x;
+    const bool on = i < i1;
+    // (an event that did not join counts here with 0 bytes and not in k_paye_join: the call reports MISMATCH and no sum is to be trusted)
+    const uint32_t ch = !on ? 3u : j.copy ? 0u : pay_channel(j.ev_kind[i]);
+    const uint64_t bytes = on ? j.ev_bytes[i] : 0;
+    for (uint32_t k = 0; k < 3; k++) {
+      const uint64_t v = ch == k ? (1ull << 40) | bytes : 0;
+      uint64_t tot;
+      const uint64_t inc = block_scan_excl64(v, lds, &tot) + v;
+      if (on) { j.pb[k * W + i + 1] = cb[k] + (inc & kLow); j.pr[k * W + i + 1] = (uint32_t)(cr[k] + (inc >> 40)); }
+      cb[k] += tot & kLow; cr[k] += tot >> 40;
+    }
+  }
+}
+
+// range k = the events [cuts[k - 1], cuts[k]), the first from 0, the last up to n_events. Cuts that descend or pass n_events read
+// nothing: the range is zero and the call is refused.
+__global__ __launch_bounds__(256) void k_paye_ranges(PayJob j) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k > j.n_cuts) return;
+  const uint64_t lo = k ? j.cuts[k - 1] : 0, hi = k < j.n_cuts ? j.cuts[k] : j.n_events, W = j.n_events + 1;
+  unsigned long long* out = j.sums + 8 * k;
+  for (int c = 0; c < 8; c++) out[c] = 0;
+  if (lo > hi || hi > j.n_events) { j.hdr[PAY_H_BAD_CUTS] = 1; return; }
+  for (uint32_t c = 0; c < 3; c++) {
+    const uint32_t kind = j.copy ? (uint32_t)ETLG_PK_COPY : c;
+    if (j.copy && c) break;
+    out[kind] = j.pb[c * W + hi] - j.pb[c * W + lo];
+    out[4 + kind] = j.pr[c * W + hi] - j.pr[c * W + lo];
+  }
+}
+
 // ---- the finish pass (etlg_batch_finish_cells, include/etlg.h): cells a decode left ETLG_CELL_DEFERRED are settled in the arena itself.
 // Array literals (parse_cell_from_postgres_text_array, crates/etl/src/postgres/codec/text.rs:163-312) become typed heap entries — header,
 // validity bits, element slots or end offsets + bytes (include/etlg.h: etlg_array_hdr) — appended behind the batch's heap; float texts the
@@ -367,6 +500,23 @@ void etlg_k_cuts(const void* jv, int step, uint64_t emit_bound, hipStream_t st) 
   for (uint32_t k = 1; k < j.levels; k++) hipLaunchKernelGGL(k_cut_level, dim3(nb), dim3(256), 0, st, j.jump + (uint64_t)(k - 1) * W, j.jump + (uint64_t)k * W, W);
   hipLaunchKernelGGL(k_cut_count, dim3(1), dim3(64), 0, st, j);
   if (emit_bound) hipLaunchKernelGGL(k_cut_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
+}
+
+// etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the
+// join alone (ev_bytes and the mismatch), no range sums
+void etlg_k_payload_events(const void* jv, hipStream_t st) {
+  const PayJob j = *(const PayJob*)jv;
+  if (j.n_etiles) {
+    if (!j.copy) {
+      hipLaunchKernelGGL(k_paye_tiles, dim3(j.n_etiles), dim3(256), 0, st, j);
+      hipLaunchKernelGGL(k_paye_scan, dim3(1), dim3(256), 0, st, j);
+    }
+    hipLaunchKernelGGL(k_paye_join, dim3(j.n_etiles), dim3(256), 0, st, j);
+  }
+  if (!j.tsum) return;
+  hipLaunchKernelGGL(k_paye_sums, dim3(1), dim3(256), 0, st, j);
+  if (j.n_etiles) hipLaunchKernelGGL(k_paye_prefix, dim3(j.n_etiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_paye_ranges, dim3((uint32_t)((j.n_cuts + 1 + 255) / 256)), dim3(256), 0, st, j);
 }
 
 void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows, unsigned long long* rows_out,

@@ -553,6 +553,94 @@ int32_t etlg_cuts_locate(etlg_ctx* c, const uint64_t* cuts, uint64_t n_cuts, uin
   return ETLG_OK;
 }
 
+// Source payload accounting (include/etlg.h; k_payf_* in kernels.hip, k_paye_* in finish.hip). Everything is sized from what the host
+// knows — the frame and event counts of the view, the cuts' count — and the device's own counts (ordinal-taking frames, Begins) stay on
+// the device, so the launches go out in one piece and the call stops once, for the header, the histogram and a host caller's outputs.
+// The frame side starts from k_classify (classify_begin, as etlg_frame_tags): a frame whose offsets do not lie inside [0, len) is
+// FT_BAD there and no later kernel looks at its bytes.
+int32_t etlg_batch_payload(etlg_ctx* c, etlg_batch* b, const uint8_t* buf, size_t len, const uint32_t* frame_offsets, size_t nframes, const uint64_t* cuts,
+                           uint64_t n_cuts, uint32_t cuts_on_device, const uint64_t* hist_bounds, uint32_t n_bounds, uint32_t flags, uint32_t* ev_bytes_out,
+                           etlg_payload_sums* sums_out, uint64_t* hist_out, etlg_payload_info* info) {
+  (void)flush_deferred(c);
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  clear_error(c);
+  *info = etlg_payload_info{};
+  info->n_ranges = n_cuts + 1; info->mismatch_event = ~0ull;
+  if (b->pending) (void)etlg_batch_sync(c, b);   // (a batch that ended in a decode error is accepted: its events were delivered)
+  if (!b->finished || !b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload needs a finished, device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)");
+  const etlg_batch_view& bv = b->v;
+  const uint64_t ne = bv.n_events, nf = bv.n_frames;
+  if (!frame_offsets) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload: frame_offsets is required (etlg_scan_boundaries returns them for an input without a sidecar)");
+  if (nframes < nf) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload: fewer frames than the batch consumed");
+  if (n_bounds > kPayBuckets - 1 || (n_bounds && !hist_bounds)) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload: at most 64 histogram bounds");
+  for (uint32_t i = 1; i < n_bounds; i++)
+    if (hist_bounds[i] <= hist_bounds[i - 1]) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload: histogram bounds must be strictly ascending");
+  if ((n_cuts && !cuts) || n_cuts >= (1ull << 40)) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload: cuts must be ascending and none above n_events");
+  if (!cuts_on_device)
+    for (uint64_t k = 0; k < n_cuts; k++)
+      if (cuts[k] > ne || (k && cuts[k] < cuts[k - 1])) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload: cuts must be ascending and none above n_events");
+  RC(batch_too_large(c, len, nframes));
+  const bool out_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0, copy = b->copy.active, want_sums = sums_out != nullptr;
+  const uint32_t n_hist = 4 * (n_bounds + 1);
+  // the failing frame had recorded its metrics when the error came after the transaction-state check (k_finalize, kernels.hip: `at_err`)
+  const uint64_t n_recv = nf + (!copy && nf < nframes && b->err_rank != 0xFF && b->err_rank >= RK_SCHEMA ? 1 : 0);
+  hipStream_t s = c->stream;
+  PayJob j{};
+  if (copy) {
+    HIPCHK(c, hipSetDevice(c->device));
+    RC(drain_pending(c));
+    j.in = buf; j.offs = frame_offsets;
+    if (!(flags & ETLG_F_INPUT_ON_DEVICE)) { RC(upload_input(c, buf, 0, frame_offsets, nframes)); j.offs = (const uint32_t*)c->d_offs.p; }   // (the rows' bytes are not read)
+  } else if (nframes) {
+    DecParams p;
+    RC(classify_begin(c, buf, len, frame_offsets, nframes, flags, p));   // k_classify: envelope + tag of every frame
+    j.in = p.in; j.offs = p.offs; j.f_tag = p.f_tag;
+  }
+  j.in_len = len; j.n_frames = (uint32_t)nf; j.n_recv = (uint32_t)n_recv; j.copy = copy ? 1u : 0u;
+  uint64_t tile = c->pay_tile_test ? c->pay_tile_test : 256u, etile = c->pay_tile_test ? c->pay_tile_test : 2048u;
+  while ((n_recv + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  while ((ne + etile - 1) / etile > (1ull << 30)) etile *= 2;
+  j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)((n_recv + tile - 1) / tile); j.etile = (uint32_t)etile; j.n_etiles = (uint32_t)((ne + etile - 1) / etile);
+  j.n_bounds = n_bounds; j.n_events = ne; j.entry_ord = b->entry_ord; j.n_cuts = n_cuts;
+  j.ev_kind = bv.ev_kind; j.ev_ord = (const unsigned long long*)bv.ev_tx_ordinal;
+  const uint64_t n_ranges = n_cuts + 1;
+  const size_t o_hist = al64(PAY_H_WORDS * 8), o_bounds = o_hist + al64((size_t)n_hist * 8), o_fbytes = o_bounds + al64(64 * 8), o_tcnt = o_fbytes + al64(n_recv * 4),
+               o_r2f = o_tcnt + al64((size_t)j.n_tiles * 8), o_brank = o_r2f + al64(nf * 4), o_etb = o_brank + al64(nf * 4), o_evb = o_etb + al64((size_t)j.n_etiles * 8),
+               o_tsum = o_evb + (out_dev && ev_bytes_out ? 0 : al64(ne * 4)), o_pb = o_tsum + (want_sums ? al64((size_t)j.n_etiles * 48) : 0),
+               o_pr = o_pb + (want_sums ? al64(3 * (ne + 1) * 8) : 0), o_cuts = o_pr + (want_sums ? al64(3 * (ne + 1) * 4) : 0),
+               o_sums = o_cuts + (want_sums && !cuts_on_device ? al64(n_cuts * 8) : 0), total = o_sums + (want_sums && !out_dev ? al64(n_ranges * 64) : 0);
+  ScratchBlk blk{c};
+  HIPCHK(c, blk_take(c, total + 64, false, &blk.p, &blk.cap));
+  uint8_t* d = (uint8_t*)blk.p;
+  j.hdr = (unsigned long long*)d; j.hist = (unsigned long long*)(d + o_hist); j.bounds = (const unsigned long long*)(d + o_bounds);
+  j.fbytes = (uint32_t*)(d + o_fbytes); j.tcnt = (unsigned long long*)(d + o_tcnt); j.r2f = (uint32_t*)(d + o_r2f); j.brank = (uint32_t*)(d + o_brank);
+  j.etb = (unsigned long long*)(d + o_etb); j.ev_bytes = out_dev && ev_bytes_out ? ev_bytes_out : (uint32_t*)(d + o_evb);
+  if (want_sums) {
+    j.tsum = (unsigned long long*)(d + o_tsum); j.pb = (unsigned long long*)(d + o_pb); j.pr = (uint32_t*)(d + o_pr);
+    j.cuts = cuts_on_device ? (const unsigned long long*)cuts : (const unsigned long long*)(d + o_cuts);
+    j.sums = out_dev ? (unsigned long long*)sums_out : (unsigned long long*)(d + o_sums);
+    if (!cuts_on_device && n_cuts) HIPCHK(c, hipMemcpyAsync(d + o_cuts, cuts, n_cuts * 8, hipMemcpyHostToDevice, s));
+  }
+  static_assert(sizeof(etlg_payload_sums) == 64, "k_paye_ranges writes 8 words per range");
+  HIPCHK(c, hipMemsetAsync(d, 0, o_bounds, s));   // the header and the histogram
+  const uint64_t none = ~0ull;
+  HIPCHK(c, hipMemcpyAsync(j.hdr + PAY_H_MISMATCH, &none, 8, hipMemcpyHostToDevice, s));
+  if (n_bounds) HIPCHK(c, hipMemcpyAsync(d + o_bounds, hist_bounds, (size_t)n_bounds * 8, hipMemcpyHostToDevice, s));
+  etlg_k_payload_frames(&j, s);
+  etlg_k_payload_events(&j, s);
+  std::vector<uint64_t> back((o_bounds) / 8);
+  HIPCHK(c, hipMemcpyAsync(back.data(), d, o_bounds, hipMemcpyDeviceToHost, s));
+  if (!out_dev && ev_bytes_out && ne) HIPCHK(c, hipMemcpyAsync(ev_bytes_out, j.ev_bytes, ne * 4, hipMemcpyDeviceToHost, s));
+  if (!out_dev && want_sums) HIPCHK(c, hipMemcpyAsync(sums_out, j.sums, n_ranges * 64, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop
+  if (back[PAY_H_BAD_CUTS]) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_payload: cuts must be ascending and none above n_events");
+  for (int k = 0; k < 4; k++) { info->received_bytes[k] = back[PAY_H_BYTES + k]; info->received_rows[k] = back[PAY_H_ROWS + k]; }
+  info->mismatch_event = back[PAY_H_MISMATCH];
+  info->status = back[PAY_H_MISMATCH] != none ? (int32_t)ETLG_PM_MISMATCH : (int32_t)ETLG_PM_OK;
+  if (hist_out) memcpy(hist_out, back.data() + o_hist / 8, (size_t)n_hist * 8);
+  return ETLG_OK;
+}
+
 // The finish pass (include/etlg.h): typed arrays and exact floats in the arena. Tables: one record per host slot, the columns' classes
 // and offsets, and per slot the list of its FINISHABLE columns (arrays of a class the device takes apart, floats) — a thread per
 // (event, row image, finishable column). Two device stops: the entry sizes' total (the heap may have to grow), then the counters.

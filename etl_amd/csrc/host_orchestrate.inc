@@ -979,14 +979,14 @@ void count_path(etlg_ctx* c, const etlg_batch* b, const FinishState& st) {
 }
 
 // First error: device (frame, rank) vs host control plane (frame, rank). Returns the code (0: none) and the failing frame.
-int32_t first_error(const etlg_batch* b, const DevResult& r, int64_t* frame_out) {
+int32_t first_error(const etlg_batch* b, const DevResult& r, int64_t* frame_out, uint32_t* rank_out) {
   int32_t code = 0; int64_t frame = -1; uint32_t rank = 0xFF;
   if (r.first_err != kNoErr) { frame = (int64_t)(r.first_err >> 16); rank = (uint32_t)((r.first_err >> 8) & 0xFF); code = (int32_t)(r.first_err & 0xFF); }
   if (b->host_err_code) {
     const int64_t hf = b->host_err_frame;
     if (frame < 0 || hf < frame || (hf == frame && b->host_err_rank < rank)) { frame = hf; rank = b->host_err_rank; code = b->host_err_code; }
   }
-  *frame_out = frame;
+  *frame_out = frame; *rank_out = rank;
   return code;
 }
 
@@ -1018,6 +1018,7 @@ void carry_state_and_view(etlg_ctx* c, etlg_batch* b, const DevResult& r, int32_
   b->snapshot = ControlState{};
   b->ctrl_raw.clear();
   b->eps_saved.clear();
+  b->entry_ord = c->next_ord;   // batches finish in issue order: what the context holds here is what this batch started from
   c->in_txn = r.out_in_txn != 0; c->final_lsn = r.out_final_lsn; c->next_ord = r.out_next_ord;
   b->copy_span = r.copy_span;
   if (b->scan && !code && r.n_frames) { c->scan_last_nf = r.n_frames; c->scan_last_len = b->len; }   // (sizes the grids of the next batch that is decoded behind its scan)
@@ -1077,7 +1078,7 @@ int32_t finish_batch(etlg_ctx* c, etlg_batch* b) {
   c->res_pool.push_back(b->h_res);
   b->h_res = nullptr;
   int64_t frame = -1;
-  const int32_t code = first_error(b, r, &frame);
+  const int32_t code = first_error(b, r, &frame, &b->err_rank);
   if (code && b->have_snapshot) rollback_control_state(c, b, frame);
   carry_state_and_view(c, b, r, code, frame);
   b->pending = false; b->finished = true;

@@ -67,6 +67,8 @@ extern "C" void etlg_k_scan_lens(const uint32_t* lens, uint64_t n, unsigned long
 extern "C" void etlg_k_col_list(const void* job, unsigned long long* blk, int64_t* offsets, int step, hipStream_t s);
 extern "C" void etlg_k_size_hints(const void* job, hipStream_t s);
 extern "C" void etlg_k_cuts(const void* job, int step, uint64_t emit_bound, hipStream_t s);
+extern "C" void etlg_k_payload_frames(const void* job, hipStream_t s);
+extern "C" void etlg_k_payload_events(const void* job, hipStream_t s);
 extern "C" void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows, unsigned long long* rows_out, hipStream_t s);
 extern "C" void etlg_k_rowbinary(const void* job, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, int step, hipStream_t s);
 extern "C" void etlg_k_col_var(const void* job, unsigned long long* blk, int64_t* offsets, int step, hipStream_t s);
@@ -431,6 +433,7 @@ struct etlg_ctx {
   DevBuf d_colsel;                   // etlg_batch_columns: block counts of the row selection
   uint32_t rb_parts_test = 0;        // ETLG_RB_PARTS (tests)
   uint32_t cuts_tile_test = 0;       // ETLG_CUTS_TILE (tests): events per scan tile of etlg_batch_cuts instead of 2048
+  uint32_t pay_tile_test = 0;        // ETLG_PAY_TILE (tests): frames and events per scan tile of etlg_batch_payload instead of 256 and 2048
   uint64_t dlc_offset_cap_test = 0;  // ETLG_DLC_OFFSET_CAP (tests): the bytes a Utf8 / Binary column of etlg_batch_ducklake_copy may hold, instead of 2^31 - 1
   uint8_t* h_hand = nullptr; size_t h_hand_cap = 0;   // pinned: the row formats' small uploads (initial counters + column words, one copy) and read-backs (row count; totals + counters, one copy each)
   unsigned long long* h_cnt_init = nullptr; size_t h_cnt_init_cols = 0;   // pinned {0, 0, 0, ~0} per column: the hand-off's counters start from it (an asynchronous copy; the content never changes)
@@ -516,6 +519,8 @@ struct etlg_batch {
   size_t n_slots_view = ~(size_t)0;   // schema slots the batch's view lists (fill_view_common)
   // what sync needs to finish the batch
   int32_t host_err_code = 0; int64_t host_err_frame = -1; uint32_t host_err_rank = 0;
+  uint64_t entry_ord = 0;          // the transaction ordinal the batch started from (finish_batch; etlg_batch_payload joins the events in front of the first Begin with it)
+  uint32_t err_rank = 0xFF;        // ... and the RK_* rank of the error that ended it, 0xFF none (from RK_SCHEMA on the failing frame had recorded its payload bytes)
   std::vector<EpochRec> eps_saved; // epochs of the batch's own control frames (a multi-pass redo needs the same side inputs)
   std::vector<CtrlFrame> ctrl;     // processed control frames (for rollback replay)
   std::vector<std::vector<uint8_t>> ctrl_raw;  // their bytes, same order (the input may be device-resident or come without a sidecar)

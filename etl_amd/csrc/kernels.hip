@@ -340,6 +340,93 @@ __global__ __launch_bounds__(kBlock) void k_ctl_gather(const u8* in, const uint3
   for (uint32_t k = threadIdx.x; k < len; k += kBlock) out[pos + k] = in[o0 + k];
 }
 
+// ------------------------------------------------------------ source payload accounting, frame side (etlg_batch_payload, include/etlg.h)
+// What the apply loop records when it RECEIVES a row message (apply.rs:2459-2463, :2503-2507, :2547-2551: the tuple value bytes of
+// calculate_tuple_bytes, codec/event.rs:261-297, before should_apply_changes) over the tags k_classify left, and the list the event side
+// joins through: every B / R / I / U / D / T / C frame takes the transaction's next ordinal whether or not it yields an event
+// (consumes_ordinal), so an event's frame is found by its rank among those frames. Three launches, no word passes between workgroups
+// inside one: per tile the bytes, the counts and the histogram (k_payf_frames), the tile counts scanned by one workgroup (k_payf_scan),
+// rank -> frame and j-th Begin -> rank (k_payf_list). The received totals and the buckets are folded with one atomic add per non-empty
+// bucket of a workgroup; nothing reads them before the kernel boundary.
+__global__ __launch_bounds__(kBlock) void k_payf_frames(PayJob j) {
+  __shared__ uint64_t lds64[4];
+  __shared__ uint32_t hist[4 * kPayBuckets];
+  __shared__ unsigned long long bnd[kPayBuckets - 1];
+  const uint32_t nb1 = j.n_bounds + 1;
+  for (uint32_t i = threadIdx.x; i < 4 * nb1; i += kBlock) hist[i] = 0;
+  for (uint32_t i = threadIdx.x; i < j.n_bounds; i += kBlock) bnd[i] = j.bounds[i];
+  __syncthreads();
+  const uint64_t f0 = (uint64_t)blockIdx.x * j.tile, f1 = f0 + j.tile < j.n_recv ? f0 + j.tile : j.n_recv;
+  uint64_t cnt = 0, by[3] = {0, 0, 0};
+  for (uint64_t f = f0 + threadIdx.x; f < f1; f += kBlock) {
+    uint32_t kind = 4, vb = 0;
+    if (j.copy) {   // TableCopyPayloadMetadata: the row's bytes (table_copy.rs:84)
+      const uint32_t o0 = j.offs[f], o1 = j.offs[f + 1];
+      kind = ETLG_PK_COPY;
+      vb = o1 >= o0 && o1 <= j.in_len ? o1 - o0 : kPayBad;
+    } else {
+      const uint32_t tag = j.f_tag[f];
+      if (f < j.n_frames) {
+        if (consumes_ordinal(tag)) cnt += 1;
+        if (tag == 'B') cnt += 1ull << 32;
+      }
+      if (tag == 'I' || tag == 'U' || tag == 'D') {   // (a tag other than FT_BAD: k_classify has checked offs[f] < offs[f + 1] <= in_len)
+        RowMsg m;
+        if (parse_row_msg(tag, j.in + j.offs[f] + kBodyOff, j.in + j.offs[f + 1], m)) { kind = tag == 'I' ? ETLG_PK_INSERT : tag == 'U' ? ETLG_PK_UPDATE : ETLG_PK_DELETE; vb = m.vbytes; }
+        else vb = kPayBad;
+      }
+    }
+    j.fbytes[f] = vb;
+    if (kind < 4 && vb != kPayBad) {
+      by[kind == ETLG_PK_COPY ? 0 : kind] += vb;
+      uint32_t lo = 0, hi = j.n_bounds;   // the first bound that is >= vb: Prometheus' `le`; n_bounds = the overflow bucket
+      while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (bnd[mid] >= vb) hi = mid; else lo = mid + 1; }
+      atomicAdd(&hist[kind * nb1 + lo], 1u);
+    }
+  }
+  cnt = block_sum64(cnt, lds64);   // (block_sum64 ends in a barrier: the histogram is complete behind it)
+  for (int k = 0; k < 3; k++) by[k] = block_sum64(by[k], lds64);
+  if (threadIdx.x == 0) {
+    j.tcnt[blockIdx.x] = cnt;
+    for (uint32_t k = 0; k < 3; k++) if (by[k]) atomicAdd(&j.hdr[PAY_H_BYTES + (j.copy ? (uint32_t)ETLG_PK_COPY : k)], (unsigned long long)by[k]);
+  }
+  for (uint32_t i = threadIdx.x; i < 4 * nb1; i += kBlock) {
+    const uint32_t n = hist[i];
+    if (n) { atomicAdd(&j.hist[i], (unsigned long long)n); atomicAdd(&j.hdr[PAY_H_ROWS + i / nb1], (unsigned long long)n); }
+  }
+}
+
+// one workgroup: the tiles' counts become the counts in front of each tile (both halves of the word at once: neither reaches 2^30)
+__global__ __launch_bounds__(kBlock) void k_payf_scan(PayJob j) {
+  __shared__ uint64_t lds64[4];
+  uint64_t carry = 0;
+  for (uint32_t t0 = 0; t0 < j.n_tiles; t0 += kBlock) {
+    const uint32_t t = t0 + threadIdx.x;
+    const bool on = t < j.n_tiles;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(on ? j.tcnt[t] : 0, lds64, &tot);
+    if (on) j.tcnt[t] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) j.hdr[PAY_H_COUNTS] = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void k_payf_list(PayJob j) {
+  __shared__ uint64_t lds64[4];
+  const uint64_t f0 = (uint64_t)blockIdx.x * j.tile, f1 = f0 + j.tile < j.n_frames ? f0 + j.tile : j.n_frames;
+  uint64_t carry = j.tcnt[blockIdx.x];
+  for (uint64_t fb = f0; fb < f1; fb += kBlock) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t f = fb + threadIdx.x;
+    const uint32_t tag = f < f1 ? j.f_tag[f] : 0;
+    const bool cons = consumes_ordinal(tag);
+    const uint64_t v = (cons ? 1ull : 0ull) | (tag == 'B' ? 1ull << 32 : 0ull);
+    uint64_t tot;
+    const uint64_t ex = carry + block_scan_excl64(v, lds64, &tot);
+    if (cons) { j.r2f[(uint32_t)ex] = (uint32_t)f; if (tag == 'B') j.brank[ex >> 32] = (uint32_t)ex; }
+    carry += tot;
+  }
+}
+
 // ------------------------------------------------------------------ launch
 }  // namespace etlg
 
@@ -398,6 +485,17 @@ void etlg_k_ctl_span(const uint8_t* tags, uint32_t nframes, const uint32_t* list
 }
 void etlg_k_ctl_gather(const uint8_t* in, const uint32_t* offs, const uint32_t* frames, uint32_t nkeep, uint32_t* lens, const uint32_t* out_offs, uint8_t* out, hipStream_t s) {
   hipLaunchKernelGGL(k_ctl_gather, dim3(nkeep), dim3(kBlock), 0, s, in, offs, frames, lens, out_offs, out);
+}
+
+// etlg_batch_payload, frame side: hdr and hist are zero, f_tag is on its way on the same stream (classify_begin); a table-copy batch has
+// neither ordinals nor Begins and stops behind the first launch
+void etlg_k_payload_frames(const void* jv, hipStream_t s) {
+  const PayJob j = *(const PayJob*)jv;
+  if (!j.n_tiles) return;
+  hipLaunchKernelGGL(k_payf_frames, dim3(j.n_tiles), dim3(kBlock), 0, s, j);
+  if (j.copy) return;
+  hipLaunchKernelGGL(k_payf_scan, dim3(1), dim3(kBlock), 0, s, j);
+  hipLaunchKernelGGL(k_payf_list, dim3(j.n_tiles), dim3(kBlock), 0, s, j);
 }
 
 const char* etlg_k_name(int which) {

@@ -29,6 +29,13 @@ def _ptr(a):
     return a.ctypes.data if a is not None else None
 
 
+class Payload:
+    """What Batch.payload returns: info (abi.PayloadInfo), hist, ev_bytes, sums — arrays, or the device addresses the caller gave."""
+
+    def __init__(self, info, hist, ev_bytes, sums):
+        self.info, self.hist, self.ev_bytes, self.sums = info, hist, ev_bytes, sums
+
+
 class Batch:
     """A decoded batch (etlg_batch). `host()` copies the arena into numpy arrays."""
 
@@ -155,6 +162,46 @@ class Batch:
         if rc != abi.OK:
             raise self.dec.last_error()
         return out if out else res
+
+    def payload(self, buf, offs, cuts=None, bounds=(), on_device=False, nbytes=None, nframes=None, n_cuts=None, sums=True):
+        """Source payload accounting of the batch, on the device (etlg_batch_payload). `buf`, `offs`: the input the batch was decoded
+        from — numpy arrays, or device addresses with `nbytes` / `nframes`; for a table-copy batch the rows and row_offsets. `cuts`: the
+        ends of the write_events ranges, a host array or the address of a device array of `n_cuts` entries (Batch.cuts leaves them so);
+        None: one range. `bounds`: ascending histogram bounds (<= 64). on_device: False -> ev_bytes (np.uint32[n_events]) and sums
+        (np.uint64[n_ranges, 2, 4]: bytes and rows per abi.PK_*) come back as arrays; a pair (ev_bytes address or None, sums address or
+        None) of device arrays -> they are written there. sums=False: no range sums.
+        Returns a Payload: info (abi.PayloadInfo), hist (np.uint64[4, len(bounds) + 1]), ev_bytes, sums."""
+        in_dev = isinstance(buf, (int, np.integer))
+        if in_dev:
+            bptr, blen, optr, nf = int(buf), int(nbytes), int(offs), int(nframes)
+        else:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            offs = None if offs is None else np.ascontiguousarray(offs, dtype=np.uint32)
+            bptr, blen, optr = (buf.ctypes.data if len(buf) else None), len(buf), _ptr(offs)
+            nf = (len(offs) - 1 if offs is not None else 0) if nframes is None else int(nframes)
+        if cuts is None:
+            cptr, nc, cdev = None, 0, 0
+        elif isinstance(cuts, (int, np.integer)):
+            cptr, nc, cdev = int(cuts), int(n_cuts), 1
+        else:
+            cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+            cptr, nc, cdev = (cuts.ctypes.data if len(cuts) else None), len(cuts), 0
+        bnd = np.ascontiguousarray(bounds, dtype=np.uint64)
+        hist = np.zeros((4, len(bnd) + 1), dtype=np.uint64)
+        ne = int(self.view().n_events)
+        flags = (abi.F_INPUT_ON_DEVICE if in_dev else 0) | (abi.F_OUTPUT_ON_DEVICE if on_device else 0)
+        if on_device:
+            ev, sm = on_device
+            eptr, sptr = (int(ev) if ev else None), (int(sm) if sm else None)
+        else:
+            ev, sm = np.zeros(ne, dtype=np.uint32), (np.zeros((nc + 1, 2, 4), dtype=np.uint64) if sums else None)
+            eptr, sptr = (ev.ctypes.data if ne else None), _ptr(sm)
+        info = abi.PayloadInfo()
+        rc = self.dec.L.etlg_batch_payload(self.dec.h, self.h, bptr, blen, optr, nf, cptr, nc, cdev, (bnd.ctypes.data if len(bnd) else None), len(bnd), flags,
+                                           eptr, sptr, hist.ctypes.data, C.byref(info))
+        if rc != abi.OK:
+            raise self.dec.last_error()
+        return Payload(info, hist, ev, sm)
 
     def rowbinary(self, slot, nullable_flags, engine=abi.CH_MERGE_TREE, on_device=False):
         """ClickHouse RowBinary rows of schema slot `slot`, encoded on the device (etlg_batch_rowbinary). Raises EtlError for

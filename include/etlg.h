@@ -1117,6 +1117,67 @@ int32_t etlg_batch_cuts(etlg_ctx* ctx, etlg_batch* batch, const etlg_size_model*
 int32_t etlg_cuts_locate(etlg_ctx* ctx, const uint64_t* cuts, uint64_t n_cuts, uint32_t cuts_on_device,
                          const uint64_t* row_event, uint64_t n_rows, uint32_t flags, uint64_t* rows_out);
 
+/* Source payload accounting on the device: what the apply loop measures per row message and the seam's hand-off has no value for.
+ * The reference builds StreamingPayloadMetadata::{insert,update,delete}(bytes) for every Insert / Update / Delete message it receives
+ * (apply.rs:2459-2463, :2503-2507, :2547-2551) — bytes = the tuple value bytes of calculate_tuple_bytes (codec/event.rs:261-297), the
+ * same number as etlg_batch_view.payload_bytes sums — and calls record_received() and record_row_size() on it BEFORE
+ * should_apply_changes: the received side covers messages that yield no event. EventBatch::push then merges the metadata of the events
+ * of one write_events batch (apply.rs:656-658) and record_processed() reports the merged value per kind once the write is acknowledged
+ * (source_payload_metadata.rs:120-185): the delivered side covers events only. An operation present with 0 bytes is an observation
+ * (Some(0) is not None): every sum comes with its row count, and rows[k] == 0 is the reference's None.
+ *
+ * buf / len / frame_offsets / nframes: the input the batch was decoded from (ETLG_F_INPUT_ON_DEVICE in `flags`: device memory). A
+ * caller that decoded without a sidecar passes the offsets etlg_scan_boundaries returns. For a batch of etlg_copy_decode: the rows and
+ * row_offsets; event i is row i, its bytes are row_offsets[i + 1] - row_offsets[i] (TableCopyPayloadMetadata, table_copy.rs:84), and
+ * everything is reported under ETLG_PK_COPY.
+ * Received side, over the frames [0, view.n_frames): info->received_bytes / received_rows per kind, and hist_out (optional, host
+ * memory): hist_out[k * (n_bounds + 1) + j] = the messages of kind k with hist_bounds[j - 1] < bytes <= hist_bounds[j], the last entry
+ * of each kind being the overflow bucket — Prometheus `le` buckets, not cumulated. The buckets are the exporter's, not the reference's:
+ * hist_bounds is host memory, strictly ascending, n_bounds <= 64. received_bytes[0..3) equals view.payload_bytes in every case: when
+ * the batch ended in an error that was raised after the failing message had recorded its metrics, that message counts here as there.
+ * received_bytes[ETLG_PK_COPY] equals view.payload_bytes[0] of a table-copy batch.
+ * Delivered side, over the batch's events: ev_bytes_out (optional, n_events entries) = the value bytes of each event's message, 0 for
+ * Begin / Commit / Relation / Truncate; sums_out (optional, n_cuts + 1 entries) = bytes and rows per kind of the events
+ * [cuts[k - 1], cuts[k]), the first range from 0, the last up to n_events. `cuts`: as etlg_batch_cuts writes them (device memory when
+ * cuts_on_device != 0, else host memory), ascending, none above n_events; NULL / 0: one range. Both outputs are device memory with
+ * ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory. Sums are plain 64-bit adds: the reference merges with saturating_add, which
+ * cannot differ below 2^64, and a batch holds fewer than 2^32 value bytes per message and fewer than 2^30 messages. Merging the
+ * sums of several decoded batches is the caller's, and there saturating.
+ * How an event finds its message: every Begin / Relation / Insert / Update / Delete / Truncate / Commit frame takes the transaction's
+ * next ordinal, whether or not it yields an event (next_tx_ordinal() runs before the ownership test), and no other frame does. So the
+ * frame of an event is the (r + ev_tx_ordinal)-th such frame of the batch, r being the rank of the Begin frame that opened its
+ * transaction — a Begin always yields an event, so the j-th 'B' event is the j-th Begin frame — and for the events in front of the
+ * batch's first Begin it is the (ev_tx_ordinal - the ordinal the batch started from)-th.
+ * The call never reads outside [buf, buf + len): a frame whose offsets do not lie inside it is not looked at. An event whose frame
+ * does not parse or does not carry the event's kind — other bytes than the batch was decoded from — gives ETLG_OK with info->status
+ * ETLG_PM_MISMATCH and mismatch_event, and then no delivered value is to be trusted.
+ * ETLG_InvalidArgument: a batch of another context, one that is not finished or not device-resident (an ASYNC batch is synced first;
+ * a batch that ended in a decode error is accepted: its events are delivered); frame_offsets == NULL; nframes < view.n_frames;
+ * n_bounds > 64 or bounds that are not strictly ascending; cuts that are not ascending or pass n_events.
+ * The call stops for the device once, at its end. */
+enum { ETLG_PK_INSERT = 0, ETLG_PK_UPDATE = 1, ETLG_PK_DELETE = 2, ETLG_PK_COPY = 3 };
+#define ETLG_PM_OK 0u
+#define ETLG_PM_MISMATCH 1u
+
+typedef struct etlg_payload_sums {
+  uint64_t bytes[4];  /* per ETLG_PK_* */
+  uint64_t rows[4];   /* rows[k] == 0 <=> Option::None */
+} etlg_payload_sums;
+
+typedef struct etlg_payload_info {
+  uint64_t received_bytes[4];  /* every row message of frames [0, view.n_frames), per ETLG_PK_* */
+  uint64_t received_rows[4];
+  uint64_t n_ranges;           /* n_cuts + 1 */
+  int32_t status;              /* ETLG_PM_OK | ETLG_PM_MISMATCH */
+  uint32_t _pad;
+  uint64_t mismatch_event;     /* first event whose joined frame does not carry its kind, ~0 if none */
+} etlg_payload_info;
+
+int32_t etlg_batch_payload(etlg_ctx* ctx, etlg_batch* batch, const uint8_t* buf, size_t len, const uint32_t* frame_offsets,
+                           size_t nframes, const uint64_t* cuts, uint64_t n_cuts, uint32_t cuts_on_device,
+                           const uint64_t* hist_bounds, uint32_t n_bounds, uint32_t flags, uint32_t* ev_bytes_out,
+                           etlg_payload_sums* sums_out, uint64_t* hist_out, etlg_payload_info* info);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
