@@ -1082,15 +1082,13 @@ extern "C" {
 
 using namespace etlg;
 
-void etlg_k_launch_cells(const DecParams* p, const void* qv, hipStream_t s) {
-  const FusedParams* q = (const FusedParams*)qv;
+void etlg_k_launch_cells(const DecParams* p, const FusedParams* q, hipStream_t s) {
   if (q->maxc > (uint32_t)MAXC_NARROW) hipLaunchKernelGGL((k_cells<4, true, false>), dim3(q->ntiles), dim3(256), q->lds_bytes, s, *p, *q);
   else hipLaunchKernelGGL((k_cells<4, false, false>), dim3(q->ntiles), dim3(256), q->lds_bytes, s, *p, *q);
 }
 
 // table-copy rows straight into the arena (p->in / p->offs: the rows and their offsets; q->copy_rel: the table's id)
-void etlg_k_launch_copy_cells(const DecParams* p, const void* qv, hipStream_t s) {
-  const FusedParams* q = (const FusedParams*)qv;
+void etlg_k_launch_copy_cells(const DecParams* p, const FusedParams* q, hipStream_t s) {
   if (q->maxc > (uint32_t)MAXC_NARROW) hipLaunchKernelGGL((k_cells<4, true, true>), dim3(q->ntiles), dim3(256), q->lds_bytes, s, *p, *q);
   else hipLaunchKernelGGL((k_cells<4, false, true>), dim3(q->ntiles), dim3(256), q->lds_bytes, s, *p, *q);
 }
@@ -1104,7 +1102,6 @@ int etlg_k_cells_set_lds(void) {
 }
 
 uint32_t etlg_k_cells_table_bytes(uint32_t maxc) { return 2u * maxc * CF * 4u; }       // next to the window of a staged tile
-uint32_t etlg_k_copy_cells_table_bytes(uint32_t maxc) { return 2u * maxc * CF * 8u; }  // ... of a tile of table-copy rows
 // dynamic LDS of a table-copy tile whose window holds `window` bytes: cell table, window, three bitmaps of the window (k_cells<.., COPYK>)
 uint32_t etlg_k_copy_cells_lds(uint32_t maxc, uint32_t window) { return 2u * maxc * CF * 8u + ((window + 15u) & ~15u) / 8u * 11u + 192u; }
 uint32_t etlg_k_cells_lds_floor(uint32_t maxc) { return 3u * 2u * maxc * CF * 4u; }    // table + window together: what a tile read in place needs

@@ -18,14 +18,14 @@ DEV bool col_selected(const ColSel& s, uint64_t i, uint64_t& base) {
   if (i >= s.n_events || s.ev_slot[i] != s.slot) return false;
   const uint32_t k = s.ev_kind[i], fl = s.ev_flags[i];
   base = s.ev_body[i];
-  if (k == 'I') return (s.kinds & 1u) != 0;
-  if (k == 'U' && (s.kinds & 2u) && !(fl & ETLG_FLAG_PARTIAL)) {
+  if (k == 'I') return (s.kinds & SEL_INSERT) != 0;
+  if (k == 'U' && (s.kinds & SEL_UPDATE_NEW) && !(fl & ETLG_FLAG_PARTIAL)) {
     const uint32_t ok = fl & 3u;
     base += ok == ETLG_OLD_FULL ? s.row_full : ok == ETLG_OLD_KEY ? s.row_key : 0u;
     return true;
   }
-  if (k == 'D' && (s.kinds & 4u) && (fl & 3u) == ETLG_OLD_FULL) return true;
-  if (k == 'D' && (s.kinds & 8u) && (fl & 3u) == ETLG_OLD_KEY) return true;   // the key row: RowBinary expands it into the tombstone (rb_row)
+  if (k == 'D' && (s.kinds & SEL_DELETE_OLD) && (fl & 3u) == ETLG_OLD_FULL) return true;
+  if (k == 'D' && (s.kinds & SEL_DELETE_KEY) && (fl & 3u) == ETLG_OLD_KEY) return true;   // the key row: RowBinary expands it into the tombstone (rb_row)
   return false;
 }
 
@@ -83,26 +83,26 @@ DEV uint32_t pb_selected(const ColSel& s, uint64_t i, unsigned long long* bases)
   return 1;
 }
 
-// ---- DuckLake: what an event becomes for the tuples (dl 1), for the predicates (dl 2; 3: a table-copy batch, every row) and for the
-// partial Updates (dl 4):
-// 0 nothing, 1 a row (bases[0]: the image, | kPbKey when it has the key layout), 2 an event the host has to take (n_host_rows),
-// 3 two rows (dl 4 only).
+// ---- DuckLake: what an event becomes for the tuples (DL_SEL_TUPLES), for the predicates (DL_SEL_PRED_IDENT; DL_SEL_PRED_PK: a table-copy
+// batch, every row) and for the partial Updates (DL_SEL_UPDATES):
+// DLS_NOTHING, DLS_ROW (bases[0]: the image, | kPbKey when it has the key layout), DLS_HOST: an event the host has to take (n_host_rows),
+// DLS_TWO_ROWS (DL_SEL_UPDATES only).
 // Insert -> a tuple; Update -> the new row's tuple unless it is partial, and the predicate of the old image — without one, of the
 // new row's identity columns (TableMutation::Replace) unless that row is partial (key_row_from_updated_partial_row); Delete -> the
 // predicate of the old image, which it must carry ("DuckLake delete requires an old row image").
-// dl 4, a partial Update only (ducklake/core.rs:1846-1913, batches.rs:1179-1190): the SET clause of the partial new row (bases[0]) and
+// DL_SEL_UPDATES, a partial Update only (ducklake/core.rs:1846-1913, batches.rs:1179-1190): the SET clause of the partial new row (bases[0]) and
 // the predicate of the mutation's delete_row (bases[1], | kPbSecond): the old image, else the partial row's own identity cells. The
 // host takes the event when the slot has no identity columns, when no old image came and an identity cell is MISSING (core.rs:896-905)
 // and when no cell is present at all (batches.rs:1337).
 DEV uint32_t dl_selected(const ColSel& s, uint64_t i, unsigned long long* bases) {
-  if (i >= s.n_events || s.ev_slot[i] != s.slot) return 0;
+  if (i >= s.n_events || s.ev_slot[i] != s.slot) return DLS_NOTHING;
   const uint32_t k = s.ev_kind[i], fl = s.ev_flags[i], ok = fl & 3u;
   const bool partial = (fl & ETLG_FLAG_PARTIAL) != 0;
   unsigned long long& base = bases[0];
   base = s.ev_body[i];
-  if (s.dl == 4u) {
-    if (k != 'U' || !partial) return 0;
-    if (!s.dl_ident) return 2;   // "DuckLake update requires a replica identity"
+  if (s.dl == DL_SEL_UPDATES) {
+    if (k != 'U' || !partial) return DLS_NOTHING;
+    if (!s.dl_ident) return DLS_HOST;   // "DuckLake update requires a replica identity"
     const uint64_t oldb = base, newb = oldb + (ok == ETLG_OLD_FULL ? s.row_full : ok == ETLG_OLD_KEY ? s.row_key : 0u);
     bool any = false, key_missing = false;
     for (uint32_t c = 0; c < s.n_cols; c++) {
@@ -110,27 +110,27 @@ DEV uint32_t dl_selected(const ColSel& s, uint64_t i, unsigned long long* bases)
       if (st != ETLG_CELL_MISSING) any = true;
       else if (s.kcols[c] & 1u) key_missing = true;
     }
-    if (!any || (ok == ETLG_OLD_NONE && key_missing)) return 2;
+    if (!any || (ok == ETLG_OLD_NONE && key_missing)) return DLS_HOST;
     bases[0] = newb;
     bases[1] = (ok == ETLG_OLD_NONE ? newb : ok == ETLG_OLD_KEY ? oldb | kPbKey : oldb) | kPbSecond;
-    return 3;
+    return DLS_TWO_ROWS;
   }
-  if (k == 'I') return s.dl != 2u ? 1u : 0u;
-  if (k != 'U' && k != 'D') return 0;
-  if (s.dl == 1u) {
-    if (k == 'D') return 0;
-    if (partial) return 2;
+  if (k == 'I') return s.dl != DL_SEL_PRED_IDENT ? DLS_ROW : DLS_NOTHING;
+  if (k != 'U' && k != 'D') return DLS_NOTHING;
+  if (s.dl == DL_SEL_TUPLES) {
+    if (k == 'D') return DLS_NOTHING;
+    if (partial) return DLS_HOST;
     base += ok == ETLG_OLD_FULL ? s.row_full : ok == ETLG_OLD_KEY ? s.row_key : 0u;
-    return 1;
+    return DLS_ROW;
   }
-  if (!s.dl_ident) return 2;   // "DuckLake delete requires a replica identity"
-  if (ok == ETLG_OLD_FULL) return 1;
-  if (ok == ETLG_OLD_KEY) { base |= kPbKey; return 1; }
-  return k == 'U' && !partial ? 1u : 2u;
+  if (!s.dl_ident) return DLS_HOST;   // "DuckLake delete requires a replica identity"
+  if (ok == ETLG_OLD_FULL) return DLS_ROW;
+  if (ok == ETLG_OLD_KEY) { base |= kPbKey; return DLS_ROW; }
+  return k == 'U' && !partial ? DLS_ROW : DLS_HOST;
 }
-DEV uint32_t dl_rows(uint32_t dls) { return dls == 1u ? 1u : dls == 3u ? 2u : 0u; }
+DEV uint32_t dl_rows(uint32_t dls) { return dls == DLS_ROW ? 1u : dls == DLS_TWO_ROWS ? 2u : 0u; }
 
-// Iceberg changelog: why the sink refuses a row event of the slot that col_selected (kinds 7) left out (iceberg_update_row / iceberg_delete_row,
+// Iceberg changelog: why the sink refuses a row event of the slot that col_selected (inserts, new rows, old rows) left out (iceberg_update_row / iceberg_delete_row,
 // crates/etl-destinations/src/iceberg/core.rs:636-680); 0: not a row event of the slot
 DEV uint32_t ice_refused(const ColSel& s, uint64_t i) {
   if (i >= s.n_events || s.ev_slot[i] != s.slot) return 0u;
@@ -145,10 +145,10 @@ __global__ __launch_bounds__(256) void k_col_count(ColSel s) {
   uint64_t base;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   unsigned long long pbb[2];
-  const uint32_t dls = s.dl ? dl_selected(s, i, pbb) : 0u;
+  const uint32_t dls = s.dl ? dl_selected(s, i, pbb) : (uint32_t)DLS_NOTHING;
   const uint32_t sel = s.dl ? dl_rows(dls) : s.pb ? pb_selected(s, i, pbb) : col_selected(s, i, base) ? 1u : 0u;
   if (s.host_rows) {  // row events of the slot that are not handed off
-    bool left = dls == 2u;
+    bool left = dls == DLS_HOST;
     if (!s.dl && !sel && i < s.n_events && s.ev_slot[i] == s.slot) { const uint32_t k = s.ev_kind[i]; left = k == 'I' || k == 'U' || k == 'D'; }
     const unsigned long long m = __ballot(left);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(s.host_rows, (unsigned long long)__builtin_popcountll(m));
@@ -308,8 +308,6 @@ DEV void col_fixed_body(const ColJob& j, uint32_t bx) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_col_fixed(ColJob j) { col_fixed_body(j, blockIdx.x); }
-
 // Several columns of one hand-off in ONE launch (blockIdx.y = column): a cfg3 batch's Arrow columns were ~30 launches of 3-30 us each,
 // and a third of the call was the gaps between them. The jobs travel in the kernel's argument block (a ColJob is 152 bytes, the
 // block holds 4 KB): tables of more columns take several packs.
@@ -363,11 +361,6 @@ DEV void col_lens_body(const ColJob& j, unsigned long long* blk, uint32_t bx, ui
   if (threadIdx.x == 0) blk[bx] = t;
 }
 template <bool JS>
-__global__ __launch_bounds__(256) void k_col_lens(ColJob j, unsigned long long* blk) {
-  __shared__ uint64_t lds_sum[4];
-  col_lens_body<JS>(j, blk, blockIdx.x, lds_sum);
-}
-template <bool JS>
 __global__ __launch_bounds__(256) void k_col_lens_pack(ColPack p) {
   __shared__ uint64_t lds_sum[4];
   col_lens_body<JS>(p.j[blockIdx.y], p.blk[blockIdx.y], blockIdx.x, lds_sum);
@@ -381,15 +374,8 @@ __global__ __launch_bounds__(256) void k_col_len_blocks(const uint32_t* lens, ui
   if (threadIdx.x == 0) blk[blockIdx.x] = t;
 }
 DEV void col_len_scan_body(unsigned long long* blk, uint32_t n, uint64_t* lds) {
-  uint64_t run = 0;
-  for (uint32_t b0 = 0; b0 < n; b0 += 256) {
-    const uint32_t i = b0 + threadIdx.x;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl64(i < n ? blk[i] : 0ull, lds, &tot);
-    if (i < n) blk[i] = run + ex;
-    run += tot;
-  }
-  if (threadIdx.x == 0) blk[n] = run;
+  const uint64_t total = carry_scan64(blk, n, 1, lds);
+  if (threadIdx.x == 0) blk[n] = total;
 }
 __global__ __launch_bounds__(256) void k_col_len_scan(unsigned long long* blk, uint32_t n) {
   __shared__ uint64_t lds[4];
@@ -446,7 +432,6 @@ DEV void col_copy_body(const ColJob& j, uint32_t bx) {
     }
   }
 }
-__global__ __launch_bounds__(256) void k_col_copy(ColJob j) { col_copy_body(j, blockIdx.x); }
 
 // formatted string columns (numeric, timetz), pass 2: one thread per row writes its Display string at its offset
 template <bool JS, class O = int64_t>
@@ -468,8 +453,6 @@ DEV void col_fmt_body(const ColJob& j, uint32_t bx) {
   }
   w.finish();
 }
-template <bool JS>
-__global__ __launch_bounds__(256) void k_col_fmt(ColJob j) { col_fmt_body<JS>(j, blockIdx.x); }
 // pass 2 of several var-len columns in one launch: a column is copied or formatted by what it is (uniform per blockIdx.y)
 template <bool JS, class O = int64_t>
 __global__ __launch_bounds__(256) void k_col_var2_pack(ColPack p) {
@@ -514,10 +497,10 @@ __global__ __launch_bounds__(256) void k_arr_count(ColJob j) {
       const uint32_t e = j.elem_cls == ETLG_TC_JSON ? arr_json_check(s, n, cnt)
                        : (j.elem_cls == ETLG_TC_STRING || j.elem_cls == ETLG_TC_BYTEA) ? arr_walk<true>(s, n, j.elem_cls, cnt, skip, none) : arr_walk<false>(s, n, j.elem_cls, cnt, skip, none);
       // A row handed back (ARR_HOST) is the host's to finish, and it may turn out to be the batch's first malformed literal. So the call
-      // only fails for a malformed row when no handed-back row precedes it (the host compares the two minima: code 0xFF marks a
+      // only fails for a malformed row when no handed-back row precedes it (the host compares the two minima: code kArrHandBack marks a
       // hand-back); otherwise the malformed rows are handed back as well, and the consumer — finishing deferred rows in event
       // order — meets the first problem first, like parse_cell_from_postgres_text at decode time.
-      if (e == ARR_HOST) { defer = true; cnt = 0; atomicMin(j.err, (unsigned long long)((r << 8) | 0xFFu)); }
+      if (e == ARR_HOST) { defer = true; cnt = 0; atomicMin(j.err, (unsigned long long)((r << 8) | kArrHandBack)); }
       else if (e) { atomicMin(j.err, (unsigned long long)((r << 8) | e)); cnt = 0; defer = true; }
       else valid = true;
     }
@@ -606,7 +589,7 @@ __global__ __launch_bounds__(256) void k_arr_fill(ColJob j) {
     const uint64_t e = o + k;
     if (is_null) { nulls++; }
     else atomicOr(&j.child_validity[e >> 5], 1u << (e & 31));
-    switch (j.kind) {   // child layout: the same conversions as k_col_fixed
+    switch (j.kind) {   // child layout: the same conversions as col_fixed_body
       case AK_BOOL: if (!is_null && w[0]) atomicOr(&((uint32_t*)j.values)[e >> 5], 1u << (e & 31)); break;
       case AK_I32: case AK_F32: ((uint32_t*)j.values)[e] = w[0]; break;
       case AK_DATE32: ((int32_t*)j.values)[e] = is_null ? 0 : (int32_t)w[0] - kCeDays1970; break;
@@ -626,8 +609,8 @@ extern "C" {
 
 using namespace etlg;
 
-void etlg_k_col_select(const void* selv, hipStream_t st) {
-  const ColSel s = *(const ColSel*)selv;
+void etlg_k_col_select(const ColSel* selv, hipStream_t st) {
+  const ColSel s = *selv;
   if (!s.nblocks) return;
   hipLaunchKernelGGL(k_col_count, dim3(s.nblocks), dim3(256), 0, st, s);
   hipLaunchKernelGGL(k_col_scan, dim3(1), dim3(256), 0, st, s.blk, s.nblocks);
@@ -635,17 +618,12 @@ void etlg_k_col_select(const void* selv, hipStream_t st) {
 }
 
 // both CDC columns of a changelog batch in one launch (the job's nb_seq / nb_op are filled in here)
-void etlg_k_col_cdc(const void* jv, hipStream_t st) {
-  CdcJob j = *(const CdcJob*)jv;
+void etlg_k_col_cdc(const CdcJob* jv, hipStream_t st) {
+  CdcJob j = *jv;
   if (!j.n_rows) return;
   j.nb_seq = (uint32_t)((j.n_rows * kCdcSeq + kCdcTile - 1) / kCdcTile);
   j.nb_op = (uint32_t)((j.n_rows * kCdcOp + kCdcTile - 1) / kCdcTile);
   hipLaunchKernelGGL(k_col_cdc, dim3(j.nb_seq + j.nb_op + (uint32_t)((j.n_rows + 256) / 256)), dim3(256), 0, st, j);
-}
-
-void etlg_k_col_fixed(const void* jv, hipStream_t st) {
-  const ColJob j = *(const ColJob*)jv;
-  if (j.n_rows) hipLaunchKernelGGL(k_col_fixed, dim3((uint32_t)((j.n_rows + 255) / 256)), dim3(256), 0, st, j);
 }
 
 // Packed forms (jobs: n <= etlg_k_col_pack_max() ColJob records of ONE hand-off, all with the same n_rows): every fixed-width column /
@@ -654,15 +632,13 @@ uint32_t etlg_k_col_pack_max(void) { return kPack; }
 static void fill_pack(ColPack& p, const ColJob* jobs, uint32_t n, unsigned long long* const* blk, int64_t* const* offs, unsigned long long* const* tot = nullptr) {
   for (uint32_t i = 0; i < n; i++) { p.j[i] = jobs[i]; p.blk[i] = blk ? blk[i] : nullptr; p.offs[i] = offs ? offs[i] : nullptr; p.tot[i] = tot ? tot[i] : nullptr; }
 }
-void etlg_k_col_fixed_pack(const void* jobs, uint32_t n, hipStream_t st) {
-  const ColJob* j = (const ColJob*)jobs;
+void etlg_k_col_fixed_pack(const ColJob* j, uint32_t n, hipStream_t st) {
   if (!n || !j[0].n_rows) return;
   ColPack p; fill_pack(p, j, n, nullptr, nullptr);
   const dim3 grid((uint32_t)((j[0].n_rows + 255) / 256), n);
   if (j[0].off32) hipLaunchKernelGGL(k_col_fixed_pack_dlc, grid, dim3(256), 0, st, p); else hipLaunchKernelGGL(k_col_fixed_pack, grid, dim3(256), 0, st, p);
 }
-void etlg_k_col_var_pack(const void* jobs, uint32_t n, unsigned long long* const* blk, int64_t* const* offs, unsigned long long* const* tot, int step, hipStream_t st) {
-  const ColJob* j = (const ColJob*)jobs;
+void etlg_k_col_var_pack(const ColJob* j, uint32_t n, unsigned long long* const* blk, int64_t* const* offs, unsigned long long* const* tot, int step, hipStream_t st) {
   if (!n || !j[0].n_rows) return;
   const uint32_t nb = (uint32_t)((j[0].n_rows + 255) / 256);
   ColPack p; fill_pack(p, j, n, blk, offs, tot);
@@ -680,7 +656,7 @@ void etlg_k_col_var_pack(const void* jobs, uint32_t n, unsigned long long* const
   }
 }
 
-// block sums of n lens (blk[b]: the sum of lens[256 b ..], left by the caller's own kernel: k_col_lens, k_rb_lens) + lens -> offsets (i64,
+// block sums of n lens (blk[b]: the sum of lens[256 b ..], left by the caller's own kernel: k_rb_lens) + lens -> offsets (i64,
 // n + 1 entries); blk: (ceil(n / 256) + 1) x u64; tot: where the total goes as well, or null
 void etlg_k_scan_blocks(const uint32_t* lens, uint64_t n, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, hipStream_t st) {
   if (!n) return;
@@ -697,24 +673,9 @@ void etlg_k_scan_lens(const uint32_t* lens, uint64_t n, unsigned long long* blk,
   etlg_k_scan_blocks(lens, n, blk, offsets, nullptr, st);
 }
 
-// blk: (nblocks + 1) x u64 scratch
-void etlg_k_col_var(const void* jv, unsigned long long* blk, int64_t* offsets, int step, hipStream_t st) {
-  const ColJob j = *(const ColJob*)jv;
-  if (!j.n_rows) return;
-  const uint32_t nb = (uint32_t)((j.n_rows + 255) / 256);
-  if (step == 0) {
-    if (j.kind == AK_JSON_STR) hipLaunchKernelGGL(k_col_lens<true>, dim3(nb), dim3(256), 0, st, j, blk); else hipLaunchKernelGGL(k_col_lens<false>, dim3(nb), dim3(256), 0, st, j, blk);
-    etlg_k_scan_blocks(j.lens, j.n_rows, blk, offsets, nullptr, st);
-  } else {
-    if (j.kind == AK_JSON_STR) hipLaunchKernelGGL(k_col_fmt<true>, dim3(nb), dim3(256), 0, st, j);
-    else if (j.kind == AK_NUMERIC_STR || j.kind == AK_TIMETZ_STR) hipLaunchKernelGGL(k_col_fmt<false>, dim3(nb), dim3(256), 0, st, j);
-    else hipLaunchKernelGGL(k_col_copy, dim3((uint32_t)((j.n_rows + 255) / 256)), dim3(256), 0, st, j);
-  }
-}
-
 // list columns: step 0 = element counts + list offsets, step 1 = child values / validity
-void etlg_k_col_list(const void* jv, unsigned long long* blk, int64_t* offsets, int step, hipStream_t st) {
-  const ColJob j = *(const ColJob*)jv;
+void etlg_k_col_list(const ColJob* jv, unsigned long long* blk, int64_t* offsets, int step, hipStream_t st) {
+  const ColJob j = *jv;
   if (!j.n_rows) return;
   const uint32_t nb = (uint32_t)((j.n_rows + 255) / 256);
   if (step == 0) {

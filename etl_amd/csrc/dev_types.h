@@ -232,10 +232,31 @@ struct PlanParams {
 };
 
 // ---- columnar hand-off (columns.hip, rowformats.hip, finish.hip)
+// The vocabulary the host (host_handoff.inc) and the kernels share. The fields that hold these stay uint32_t.
+enum : uint32_t { FMT_ROWBINARY = 0, FMT_PROTOBUF = 1, FMT_NDJSON = 2, FMT_DUCKLAKE = 3 };   // RbJob.format: the sink's row format
+// ColSel.kinds bits: inserts, new rows of non-partial updates, full old rows of deletes, key rows of deletes
+enum : uint32_t { SEL_INSERT = 1u, SEL_UPDATE_NEW = 2u, SEL_DELETE_OLD = 4u, SEL_DELETE_KEY = 8u };
+// ColSel.dl (dl_selection, host_handoff.inc): the tuples the sink upserts, the predicates it deletes / matches by over the identity columns,
+// over the primary-key columns (a table-copy batch: every row), the partial Updates. DL_SEL_NONE: not a DuckLake call. RbJob.dl_what holds the
+// same fact one lower (dl_row_what): with one numbering in both fields the code bytes of the six DuckLake kernels moved
+enum : uint32_t { DL_SEL_NONE = 0, DL_SEL_TUPLES = 1, DL_SEL_PRED_IDENT = 2, DL_SEL_PRED_PK = 3, DL_SEL_UPDATES = 4 };
+enum : uint32_t { DL_ROW_TUPLES = 0, DL_ROW_PRED_IDENT = 1, DL_ROW_PRED_PK = 2, DL_ROW_UPDATES = 3 }; constexpr uint32_t dl_row_what(uint32_t sel) { return sel - DL_SEL_TUPLES; }
+enum : uint32_t { DLS_NOTHING = 0, DLS_ROW = 1, DLS_HOST = 2, DLS_TWO_ROWS = 3 };   // dl_selected (columns.hip): what an event becomes
+// A row's error code (rb_row / pb_row / nd_row / dl_row return column << 8 | code). RB_E_BQ_NUMERIC_SCALE: the json integer rule's too. ND_E_*: Error::Encoding of Snowflake
+enum : uint32_t { RB_E_NULL = 1, RB_E_DATE_RANGE = 2, RB_E_HOST_CELL = 3, RB_E_BQ_NUMERIC_SCALE = 4, RB_E_JSON = 5, RB_E_BQ_ARRAY_NULL = 6,
+                  ND_E_FLOAT_NAN = 7, ND_E_FLOAT_INF = 8, ND_E_FLOAT_NINF = 9, ND_E_NUM_NAN = 10, ND_E_NUM_INF = 11, ND_E_FIRST = ND_E_FLOAT_NAN, ND_E_LAST = ND_E_NUM_INF };
+// The report word: rank | row << 24 | column << 8 | code, folded with atomicMin. A json cell that is not JSON ranks first (the reference's
+// decode fails before a sink sees a row), then a date out of range and every report of the other formats, then RowBinary's other reports
+constexpr unsigned long long kRbRankDecode = 0ull, kRbRankEarly = 1ull << 61, kRbRankLate = 1ull << 62;
+struct RbReport { uint64_t row; uint32_t col, code; };
+constexpr unsigned long long rb_report_pack(unsigned long long rank, uint64_t row, uint32_t col_code) { return rank | (unsigned long long)((row << 24) | col_code); }
+constexpr RbReport rb_report_unpack(unsigned long long w) { return RbReport{(w & ~(kRbRankEarly | kRbRankLate)) >> 24, (uint32_t)((w >> 8) & 0xFFFF), (uint32_t)(w & 0xFF)}; }
+// ColJob.err of a list column is min over (row << 8 | code): this code marks a row handed back DEFERRED, not malformed (k_arr_count)
+constexpr uint32_t kArrHandBack = 0xFFu;
 struct ColSel {            // which events are rows of the hand-off
   const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_body;
   uint64_t n_events;
-  uint32_t slot, kinds;    // kinds: bit 0 inserts, bit 1 new rows of non-partial updates, bit 2 full old rows of deletes, bit 3 key rows of deletes
+  uint32_t slot, kinds;    // kinds: SEL_* bits
   unsigned long long* host_rows;  // optional: I/U/D events of the slot the selection leaves out (partial updates, key-only deletes)
   uint32_t row_full, row_key;
   uint32_t* blk;           // per-block counts -> exclusive prefix; blk[nblocks] = total
@@ -249,14 +270,13 @@ struct ColSel {            // which events are rows of the hand-off
   const uint8_t* fixed; const uint8_t* heap;
   const uint32_t* cols;    // per replicated column: cls | .. | off_full << 16 (RbJob.cols)
   const uint32_t* kcols;   // identity | source nullable << 1 | primary key << 2 | key_index << 8 | off_key << 16 (RbJob.kcols)
-  // DuckLake rows (dl != 0; ducklake/core.rs:1824-1945, batches.rs:1128-1226): 1 the tuples the sink upserts, 2 the predicates it deletes /
-  // matches by (a row's base carries kPbKey when the image has the key layout), 3 the predicates of a table-copy batch (every row),
-  // 4 the partial Updates (ETLG_DL_UPDATES): two rows per event, the SET clause of the partial new row, then the predicate of the
-  // old image — without one, of the new row itself (kPbSecond marks the predicate row). That arm reads the new row's cell states
-  // through fixed / kcols / n_cols above.
+  // DuckLake rows (dl: DL_SEL_*; ducklake/core.rs:1824-1945, batches.rs:1128-1226): a predicate row's base carries kPbKey when the image has
+  // the key layout. DL_SEL_UPDATES: two rows per event, the SET clause of the partial new row, then the predicate of the old image — without
+  // one, of the new row itself (kPbSecond marks the predicate row). That arm reads the new row's cell states through fixed / kcols /
+  // n_cols above.
   // dl_ident: the slot has identity columns (without them every predicate candidate of a WAL batch stays with the host)
   uint32_t dl, dl_ident;
-  // Iceberg changelog (etlg_batch_iceberg; kinds = 7): the Update / Delete events of the slot the sink refuses are counted in ice[0],
+  // Iceberg changelog (etlg_batch_iceberg; kinds: inserts, new rows, old rows): the Update / Delete events of the slot the sink refuses are counted in ice[0],
   // and ice[3] takes the minimum of (event << 8 | ETLG_ICE_*) over them, in the counting launch (k_col_count). Null: not asked for
   unsigned long long* ice;
 };
@@ -289,12 +309,25 @@ struct CdcJob {            // the two trailing CDC columns of an Iceberg changel
   unsigned long long* op_validity; unsigned long long* seq_validity; unsigned long long* op_deferred; unsigned long long* seq_deferred;
 };
 
+// A schema slot and a replicated column as the finish pass reads them (slot_table, host_handoff.inc). cols_base: the slot's first ColRec; fin_base / n_fin: its part of FinJob.fin.
+// k_size_hints keeps the narrower packing it had, HintSlotRec / HintColRec, cut from the same table: with the wide records it fell outside the parent's span on cfg3
+struct SlotRec { uint32_t n_cols, n_ident, row_full, row_key, cols_base, fin_base, n_fin; };
+struct ColRec {
+  uint32_t kind, offs, key_index;   // kind: cls | identity << 8 | elem_cls << 16; offs: off_full | off_key << 16
+  constexpr uint32_t cls() const { return kind & 0xFFu; } constexpr uint32_t elem_cls() const { return (kind >> 16) & 0xFFu; }
+  constexpr bool identity() const { return ((kind >> 8) & 1u) != 0; }
+  constexpr uint32_t off_full() const { return offs & 0xFFFFu; } constexpr uint32_t off_key() const { return offs >> 16; }
+};
+struct HintSlotRec { uint32_t n_cols, n_ident, row_full, row_key, cols_base; };
+struct HintColRec {   // kind: cls | identity << 8 | off_full << 16
+  uint32_t kind, off_key;
+  constexpr uint32_t cls() const { return kind & 0xFFu; } constexpr bool identity() const { return ((kind >> 8) & 1u) != 0; } constexpr uint32_t off_full() const { return kind >> 16; }
+};
 struct HintJob {           // Event::size_hint per event (k_size_hints)
   const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_table; const uint32_t* ev_slot; const uint64_t* ev_body;
   const uint8_t* fixed; const uint8_t* heap;
   uint64_t n_events;
-  const uint32_t* slots;   // per slot: n_cols, n_ident, row_full, row_key, cols_base
-  const uint32_t* cols;    // per column: cls | identity << 8 | off_full << 16, then off_key
+  const HintSlotRec* slots; const HintColRec* cols;
   uint32_t n_slots;
   uint32_t m_begin, m_commit, m_insert, m_update, m_delete, m_truncate, m_relation, m_rts, m_row, m_cell;
   unsigned long long* out;
@@ -349,8 +382,7 @@ struct FinJob {            // the finish pass (k_fin_count / k_fin_fill, finish.
   const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_body;
   uint8_t* fixed; uint8_t* heap;
   uint64_t n_events;
-  const uint32_t* slots;   // per host slot: n_cols, n_ident, row_full, row_key, cols_base, fin_base, n_fin
-  const uint32_t* cols;    // per column: cls | identity << 8 | elem_cls << 16, off_full | off_key << 16, key_index
+  const SlotRec* slots; const ColRec* cols;   // per host slot, per column
   const uint32_t* fin;     // the finishable columns of every slot (indexes into the slot's columns)
   uint32_t n_slots, maxfin, what;
   uint32_t* lens; const int64_t* offsets;
@@ -365,28 +397,27 @@ struct RbJob {             // ClickHouse RowBinary rows (k_rb_rows)
   uint64_t n_rows;
   uint32_t n_cols, engine;         // engine: 0 MergeTree, 1 ReplacingMergeTree
   uint32_t cdc_nullable;           // bit 0 / 1: the first / second trailing CDC column is Nullable() in the destination
-  uint32_t format;                 // 0 ClickHouse RowBinary, 1 BigQuery protobuf (prost wire format), 2 Snowflake NDJSON, 3 DuckLake SQL literals
+  uint32_t format;                 // FMT_*: ClickHouse RowBinary, BigQuery protobuf (prost wire format), Snowflake NDJSON, DuckLake SQL literals
   const uint32_t* cols;            // per replicated column: cls | nullable << 8 | off_full << 16
   const uint32_t* kcols;           // per replicated column, for key images: identity | source nullable << 1 | primary key << 2 | key_index << 8 | off_key << 16
   const uint8_t* ev_flags;
   uint32_t* lens; const int64_t* offsets; uint8_t* out;
-  unsigned long long* err;         // min over failing cells of (row << 24 | column << 8 | code); ~0 = none
+  unsigned long long* err;         // min over failing cells of rb_report_pack(); ~0 = none
   uint32_t has_json;               // the table has a json / jsonb column: the kernels that carry json_display
   uint32_t qparts, parts;          // the counting pass notes where the row's qparts pieces begin (4; 2 / 1 for narrow tables); the byte pass writes a row with parts lanes (1, 2, 4 <= qparts)
   uint32_t* part_off;              // [(qparts - 1) x n_rows]: where pieces 1 .. of a row begin, in bytes from the row's start
-  // format 2 (Snowflake NDJSON, nd_row): the escaped `"name":` key of every column (key_off: n_cols + 1 byte offsets into keys), and
+  // FMT_NDJSON (nd_row): the escaped `"name":` key of every column (key_off: n_cols + 1 byte offsets into keys), and
   // whether the batch is a table copy (every row's sequence number is the zero token)
   const uint8_t* nd_keys; const uint32_t* nd_key_off;
   uint32_t nd_zero_token;
-  // formats 0 / 1 on a table-copy batch (etlg_copy_decode): the tail of a copied row, not of a CDC row — RowBinary: the CDC columns of
+  // FMT_ROWBINARY / FMT_PROTOBUF on a table-copy batch (etlg_copy_decode): the tail of a copied row, not of a CDC row — RowBinary: the CDC columns of
   // (Insert, commit_lsn 0, tx_ordinal 0) (clickhouse/core.rs:739-773); protobuf: _CHANGE_TYPE alone, no _CHANGE_SEQUENCE_NUMBER field
   // (bigquery/core.rs:602-649). Uniform over the launch: the counting pass and the byte pass read the same word
   uint32_t copy_tail;
-  // format 3 (DuckLake, dl_row): nd_keys are the quoted identifiers; 0 tuples, 1 predicates over the identity columns, 2 predicates
-  // over the primary-key columns (a table-copy batch), 3 partial Updates: a row whose base carries kPbSecond is a predicate over the
-  // identity columns, any other row the SET clause `"c" = lit, ...` of the cells that are not MISSING
+  // FMT_DUCKLAKE (dl_row): nd_keys are the quoted identifiers; dl_what is DL_ROW_*. DL_ROW_UPDATES: a row whose base carries
+  // kPbSecond is a predicate over the identity columns, any other row the SET clause `"c" = lit, ...` of the cells that are not MISSING
   uint32_t dl_what, _pad;
-  // col_ends (dl_what 3, else null): [n_rows x n_cols] bytes of a record written once a column is done, from the counting pass
+  // col_ends (DL_ROW_UPDATES, else null): [n_rows x n_cols] bytes of a record written once a column is done, from the counting pass
   uint32_t* col_ends;
 };
 

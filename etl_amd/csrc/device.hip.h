@@ -205,4 +205,19 @@ DEV uint64_t block_scan_excl64(uint64_t v, uint64_t* lds, uint64_t* total) {
   return pre + inc - v;
 }
 
+// "The tiles' sums become the sums in front of each tile": an in-place exclusive sum scan of the n 64-bit words v[0], v[stride],
+// v[2 stride], ... by ONE workgroup of 256, in chunks of 256. Returns the total to every lane. `lds` = 4 words of scratch.
+DEV uint64_t carry_scan64(unsigned long long* v, uint32_t n, uint32_t stride, uint64_t* lds) {
+  uint64_t carry = 0;
+  for (uint32_t t0 = 0; t0 < n; t0 += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint32_t t = t0 + threadIdx.x;
+    const bool on = t < n;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(on ? v[(uint64_t)t * stride] : 0ull, lds, &tot);
+    if (on) v[(uint64_t)t * stride] = carry + ex;
+    carry += tot;
+  }
+  return carry;
+}
+
 }  // namespace etlg

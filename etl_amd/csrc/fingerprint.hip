@@ -305,9 +305,9 @@ __global__ __launch_bounds__(256) void k_fp_fold(FpJob j) {
 }  // namespace etlg
 
 // blk: (ceil(n_events / 256) + 1) x u64 scan scratch. n_events and n_ranges are not zero.
-extern "C" void etlg_k_fingerprints(const void* jv, unsigned long long* blk, hipStream_t st) {
+extern "C" void etlg_k_fingerprints(const etlg::FpJob* jv, unsigned long long* blk, hipStream_t st) {
   using namespace etlg;
-  const FpJob j = *(const FpJob*)jv;
+  const FpJob j = *jv;
   const uint32_t rblk = (j.n_ranges + 255) / 256;
   hipLaunchKernelGGL(k_fp_plan, dim3((uint32_t)((j.n_events + 255) / 256)), dim3(256), 0, st, j);
   etlg_k_scan_lens(j.lens, j.n_events, blk, (int64_t*)j.offs, st);

@@ -8,14 +8,14 @@ extern "C" void etlg_k_scan_lens(const uint32_t* lens, uint64_t n, unsigned long
 namespace etlg {
 
 // ---- Event::size_hint (crates/etl/src/event.rs:295-320; data/table_row.rs:248-299)
-DEV uint64_t hint_row(const HintJob& j, const uint32_t* sl, uint64_t base, bool key, bool& incomplete) {
-  const uint32_t n_cols = sl[0], n_ident = sl[1], cb = sl[4];
-  uint64_t total = (uint64_t)j.m_row + (uint64_t)(key ? n_ident : n_cols) * j.m_cell;   // TableRow + Vec<Cell> capacity
+DEV uint64_t hint_row(const HintJob& j, const HintSlotRec& sl, uint64_t base, bool key, bool& incomplete) {
+  uint64_t total = (uint64_t)j.m_row + (uint64_t)(key ? sl.n_ident : sl.n_cols) * j.m_cell;   // TableRow + Vec<Cell> capacity
   uint32_t k = 0;
-  for (uint32_t i = 0; i < n_cols; i++) {
-    const uint32_t cd = j.cols[2 * (cb + i)], cls = cd & 0xFF;
-    if (key && !((cd >> 8) & 1)) continue;
-    const uint32_t pos = key ? k : i, off = key ? j.cols[2 * (cb + i) + 1] : cd >> 16;
+  for (uint32_t i = 0; i < sl.n_cols; i++) {
+    const HintColRec& cd = j.cols[sl.cols_base + i];
+    const uint32_t cls = cd.cls();
+    if (key && !cd.identity()) continue;
+    const uint32_t pos = key ? k : i, off = key ? cd.off_key : cd.off_full();
     k++;
     const uint32_t st = (j.fixed[base + pos / 4] >> (2 * (pos % 4))) & 3u;
     if (st == ETLG_CELL_NULL) continue;
@@ -44,12 +44,12 @@ __global__ __launch_bounds__(256) void k_size_hints(HintJob j) {
     const uint32_t s = j.ev_slot[i];
     if (s >= j.n_slots) { inc = true; }
     else {
-      const uint32_t* sl = j.slots + 5 * s;
+      const HintSlotRec& sl = j.slots[s];
       uint64_t base = j.ev_body[i];
       v = kind == 'I' ? j.m_insert : kind == 'U' ? j.m_update : j.m_delete;
       if (kind != 'I') {
         const uint32_t ok = fl & 3u;
-        if (ok) { v += hint_row(j, sl, base, ok == ETLG_OLD_KEY, inc); base += ok == ETLG_OLD_KEY ? sl[3] : sl[2]; }
+        if (ok) { v += hint_row(j, sl, base, ok == ETLG_OLD_KEY, inc); base += ok == ETLG_OLD_KEY ? sl.row_key : sl.row_full; }
       }
       if (kind != 'D') {
         if (fl & ETLG_FLAG_PARTIAL) inc = true;
@@ -102,16 +102,9 @@ __global__ __launch_bounds__(256) void k_cut_tiles(CutJob j) {
 // one workgroup: the tile sums become the sums in front of each tile, the tiles' first INCOMPLETE events their minimum
 __global__ __launch_bounds__(256) void k_cut_scan(CutJob j) {
   __shared__ uint64_t lds[4];
-  uint64_t carry = 0, inc = kNone64;
-  for (uint32_t t0 = 0; t0 < j.n_tiles; t0 += 256) {
-    const uint32_t t = t0 + threadIdx.x;
-    const bool on = t < j.n_tiles;
-    const uint64_t v = on ? j.tsum[t] : 0;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl64(v, lds, &tot);
-    if (on) { j.tsum[t] = carry + ex; const uint64_t ti = j.tinc[t]; inc = ti < inc ? ti : inc; }
-    carry += tot;
-  }
+  (void)carry_scan64(j.tsum, j.n_tiles, 1, lds);
+  uint64_t inc = kNone64;
+  for (uint32_t t = threadIdx.x; t < j.n_tiles; t += 256) { const uint64_t ti = j.tinc[t]; inc = ti < inc ? ti : inc; }
   inc = block_min64(inc, lds);
   if (threadIdx.x == 0) { j.hdr[0] = inc < j.n ? inc : j.n; j.hdr[1] = 0; j.q[0] = 0; }   // (hdr[1]: k_cut_write, when L > 0)
 }
@@ -205,15 +198,7 @@ __global__ __launch_bounds__(256) void k_paye_tiles(PayJob j) {
 
 __global__ __launch_bounds__(256) void k_paye_scan(PayJob j) {
   __shared__ uint64_t lds[4];
-  uint64_t carry = 0;
-  for (uint32_t t0 = 0; t0 < j.n_etiles; t0 += 256) {
-    const uint32_t t = t0 + threadIdx.x;
-    const bool on = t < j.n_etiles;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl64(on ? j.etb[t] : 0, lds, &tot);
-    if (on) j.etb[t] = carry + ex;
-    carry += tot;
-  }
+  (void)carry_scan64(j.etb, j.n_etiles, 1, lds);
 }
 
 __global__ __launch_bounds__(256) void k_paye_join(PayJob j) {
@@ -260,17 +245,7 @@ __global__ __launch_bounds__(256) void k_paye_join(PayJob j) {
 // one workgroup: each of the six sums per tile becomes the sum in front of the tile
 __global__ __launch_bounds__(256) void k_paye_sums(PayJob j) {
   __shared__ uint64_t lds[4];
-  for (uint32_t k = 0; k < 6; k++) {
-    uint64_t carry = 0;
-    for (uint32_t t0 = 0; t0 < j.n_etiles; t0 += 256) {
-      const uint32_t t = t0 + threadIdx.x;
-      const bool on = t < j.n_etiles;
-      uint64_t tot;
-      const uint64_t ex = block_scan_excl64(on ? j.tsum[6 * (uint64_t)t + k] : 0, lds, &tot);
-      if (on) j.tsum[6 * (uint64_t)t + k] = carry + ex;
-      carry += tot;
-    }
-  }
+  for (uint32_t k = 0; k < 6; k++) (void)carry_scan64(j.tsum + k, j.n_etiles, 6, lds);
   if (threadIdx.x < 3) { j.pb[(uint64_t)threadIdx.x * (j.n_events + 1)] = 0; j.pr[(uint64_t)threadIdx.x * (j.n_events + 1)] = 0; }
 }
 
@@ -334,24 +309,24 @@ DEV FinCell fin_cell(const FinJob& j, uint64_t t) {
   if (!(kind == 'I' || kind == 'U' || kind == 'D')) return c;
   const uint32_t s = j.ev_slot[ev];
   if (s >= j.n_slots) return c;
-  const uint32_t* sl = j.slots + 7 * s;
-  if (q >= sl[6]) return c;
-  const uint32_t col = j.fin[sl[5] + q];
-  const uint32_t* cd = j.cols + 3 * (size_t)(sl[4] + col);
+  const SlotRec& sl = j.slots[s];
+  if (q >= sl.n_fin) return c;
+  const uint32_t col = j.fin[sl.fin_base + q];
+  const ColRec& cd = j.cols[sl.cols_base + col];
   const uint32_t ok = kind == 'I' ? 0u : (uint32_t)j.ev_flags[ev] & 3u;
   uint64_t base = j.ev_body[ev];
-  uint32_t pos = col, off = cd[1] & 0xFFFFu;
+  uint32_t pos = col, off = cd.off_full();
   if (img == 0) {
     if (ok == ETLG_OLD_NONE) return c;
-    if (ok == ETLG_OLD_KEY) { if (!((cd[0] >> 8) & 1u)) return c; pos = cd[2]; off = cd[1] >> 16; }
+    if (ok == ETLG_OLD_KEY) { if (!cd.identity()) return c; pos = cd.key_index; off = cd.off_key(); }
   } else {
     if (kind == 'D') return c;
-    base += ok == ETLG_OLD_KEY ? sl[3] : ok == ETLG_OLD_FULL ? sl[2] : 0u;
+    base += ok == ETLG_OLD_KEY ? sl.row_key : ok == ETLG_OLD_FULL ? sl.row_full : 0u;
   }
   u8* stb = j.fixed + base + pos / 4;
   const uint32_t st = (*stb >> (2 * (pos % 4))) & 3u;
   if (st != ETLG_CELL_DEFERRED) return c;
-  c.on = true; c.cls = cd[0] & 0xFFu; c.elem = (cd[0] >> 16) & 0xFFu;
+  c.on = true; c.cls = cd.cls(); c.elem = cd.elem_cls();
   c.slot = j.fixed + base + off;
   c.stw = (uint32_t*)((uintptr_t)stb & ~(uintptr_t)3);
   c.stsh = 8u * (uint32_t)((uintptr_t)stb & 3u) + 2u * (pos % 4);
@@ -479,15 +454,15 @@ extern "C" {
 
 using namespace etlg;
 
-void etlg_k_size_hints(const void* jv, hipStream_t st) {
-  const HintJob j = *(const HintJob*)jv;
+void etlg_k_size_hints(const HintJob* jv, hipStream_t st) {
+  const HintJob j = *jv;
   if (j.n_events) hipLaunchKernelGGL(k_size_hints, dim3((uint32_t)((j.n_events + 255) / 256)), dim3(256), 0, st, j);
 }
 
 // etlg_batch_cuts: step 0 = q, L and total (grids from n and the tile), step 1 = the jump levels, the count and the cuts (grids from L
 // and from the host's bound of the cuts, min(cuts_cap, L, (carry_in + total) / budget); threads past the device's count exit)
-void etlg_k_cuts(const void* jv, int step, uint64_t emit_bound, hipStream_t st) {
-  const CutJob j = *(const CutJob*)jv;
+void etlg_k_cuts(const CutJob* jv, int step, uint64_t emit_bound, hipStream_t st) {
+  const CutJob j = *jv;
   if (step == 0) {
     if (j.n_tiles) hipLaunchKernelGGL(k_cut_tiles, dim3(j.n_tiles), dim3(256), 0, st, j);
     hipLaunchKernelGGL(k_cut_scan, dim3(1), dim3(256), 0, st, j);
@@ -504,8 +479,8 @@ void etlg_k_cuts(const void* jv, int step, uint64_t emit_bound, hipStream_t st) 
 
 // etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the
 // join alone (ev_bytes and the mismatch), no range sums
-void etlg_k_payload_events(const void* jv, hipStream_t st) {
-  const PayJob j = *(const PayJob*)jv;
+void etlg_k_payload_events(const PayJob* jv, hipStream_t st) {
+  const PayJob j = *jv;
   if (j.n_etiles) {
     if (!j.copy) {
       hipLaunchKernelGGL(k_paye_tiles, dim3(j.n_etiles), dim3(256), 0, st, j);
@@ -526,8 +501,8 @@ void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const u
 
 // the finish pass: step 0 = entry sizes of every (event, image, finishable column) + their exclusive scan (blk: (ceil(n / 256) + 1) x u64
 // scratch, offsets: n + 1 x i64), step 1 = the entries, the slots and the cell states
-void etlg_k_finish(const void* jv, unsigned long long* blk, int64_t* offsets, int step, hipStream_t st) {
-  const FinJob j = *(const FinJob*)jv;
+void etlg_k_finish(const FinJob* jv, unsigned long long* blk, int64_t* offsets, int step, hipStream_t st) {
+  const FinJob j = *jv;
   const uint64_t n = j.n_events * 2ull * j.maxfin;
   if (!n) return;
   const uint32_t nb = (uint32_t)((n + 255) / 256);

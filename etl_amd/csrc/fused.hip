@@ -244,8 +244,7 @@ extern "C" {
 using namespace etlg;
 
 // blk: 256 or 64 frames per tile. lds_bytes = dynamic LDS per workgroup.
-void etlg_k_launch_fused(int blk, const DecParams* p, const void* qv, hipStream_t s) {
-  const FusedParams* q = (const FusedParams*)qv;
+void etlg_k_launch_fused(int blk, const DecParams* p, const FusedParams* q, hipStream_t s) {
   if (blk == 256) hipLaunchKernelGGL(k_fused<256>, dim3(q->ntiles), dim3(256), q->lds_bytes, s, *p, *q);
   else hipLaunchKernelGGL(k_fused<64>, dim3(q->ntiles), dim3(64), q->lds_bytes, s, *p, *q);
 }

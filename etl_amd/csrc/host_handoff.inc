@@ -61,7 +61,7 @@ ColPlan col_plan(uint32_t cls) {
 ColPlan dlc_plan(uint32_t cls) {
   switch (cls) {
     case ETLG_TC_I16: return {ETLG_AK_INT16, 2, false};
-    case ETLG_TC_U32: return {ETLG_AK_UINT64, 8, false, 0, 0, 0, ETLG_AK_INT64};   // (the widening of cell_to_i64: k_col_fixed's I64 arm by class)
+    case ETLG_TC_U32: return {ETLG_AK_UINT64, 8, false, 0, 0, 0, ETLG_AK_INT64};   // (the widening of cell_to_i64: col_fixed_body's I64 arm by class)
     case ETLG_TC_STRING: return {ETLG_AK_UTF8, 0, true, 0, 0, 0, ETLG_AK_LARGE_UTF8};
     case ETLG_TC_BYTEA: return {ETLG_AK_BINARY, 0, true, 0, 0, 0, ETLG_AK_LARGE_BINARY};
     case ETLG_TC_NUMERIC: return {ETLG_AK_UTF8, 0, true, 0, 0, 0, etlg::kAkNumericStr};
@@ -73,8 +73,7 @@ ColPlan dlc_plan(uint32_t cls) {
 }  // namespace
 }  // extern "C++"
 
-// The builder behind etlg_batch_columns and etlg_batch_iceberg. sel_kinds: ColSel.kinds (bit 0 inserts, 1 new rows of non-partial
-// updates, 2 full old rows of deletes); changelog: the Iceberg sink's rows — the refused events are counted in the selection's own
+// The builder behind etlg_batch_columns and etlg_batch_iceberg. sel_kinds: ColSel.kinds (SEL_* bits); changelog: the Iceberg sink's rows — the refused events are counted in the selection's own
 // launches and read back with the row count, and the two CDC columns are written behind the data columns by one more launch
 // (etlg_k_col_cdc), so both calls stop for the device equally often.
 static bool slot_known(const etlg_ctx* c, int32_t slot) { return slot >= 0 && (size_t)slot < c->slots.size(); }
@@ -96,8 +95,9 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   const uint64_t ne = bv.n_events;
   const uint32_t nblk = (uint32_t)((ne + 255) / 256);
   // ---- 1. which events are rows (count -> scan -> scatter); row_event / row_base are sized for every event
-  const size_t o_ice = al64((size_t)(nblk + 1) * 4);   // changelog: {refused events, -, -, min(event << 8 | reason)} behind the block counts
-  HIPCHK(c, c->d_colsel.ensure(o_ice + 64));
+  ScratchLayout sel_lay((size_t)(nblk + 1) * 4);
+  const size_t o_ice = sel_lay.skip(64);   // changelog: {refused events, -, -, min(event << 8 | reason)} behind the block counts
+  HIPCHK(c, c->d_colsel.ensure(sel_lay.total()));
   uint32_t* d_blk = (uint32_t*)c->d_colsel.p;
   cs->m.ctx = c; cs->m.ctx_gen = c->gen;
   cs->changelog = changelog; cs->ci.host_event = ~0ull; cs->ci.n_data_cols = sh.desc.n_cols;
@@ -122,10 +122,10 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
     return ETLG_OK;
   };
   ScratchBlk rows_blk{c};
-  if (ne) HIPCHK(c, blk_take(c, al64(ne * 8) * 2, false, &rows_blk.p, &rows_blk.cap));
-  void* d_rows = rows_blk.p;
-  uint64_t* d_row_event = (uint64_t*)d_rows;
-  uint64_t* d_row_base = (uint64_t*)((uint8_t*)d_rows + al64(ne * 8));
+  ScratchLayout rows_lay(ne * 8); const size_t o_row_base = rows_lay.take(ne * 8);   // row_event | row_base
+  if (ne) HIPCHK(c, blk_take(c, rows_lay.total(), false, &rows_blk.p, &rows_blk.cap));
+  uint64_t* d_row_event = (uint64_t*)rows_blk.p;
+  uint64_t* d_row_base = (uint64_t*)((uint8_t*)rows_blk.p + o_row_base);
   uint32_t n_rows32 = 0;
   if (ne) {
     ColSel q{};
@@ -154,10 +154,10 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   const uint64_t n = n_rows32;
   // ---- 2. block A: row_event | per column {validity, deferred, values or (lens, offsets)} | counters
   const uint32_t nc = sh.desc.n_cols;
-  const size_t bm = al64(((size_t)n + 63) / 64 * 8);
+  const size_t bm = ((size_t)n + 63) / 64 * 8;   // bytes of a bitmap
   struct Lay { ColPlan pl; size_t validity, deferred, values, lens, offsets; };
   std::vector<Lay> lay(nc);
-  size_t off = al64(n * 8);
+  ScratchLayout a_lay(n * 8);   // row_event first
   for (uint32_t i = 0; i < nc; i++) {
     Lay& l = lay[i];
     l.pl = dlc ? dlc_plan(sh.cols[i].type_class) : col_plan(sh.cols[i].type_class);
@@ -165,24 +165,23 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
     if (format_json && sh.cols[i].type_class == ETLG_TC_JSON) l.pl = {ETLG_AK_LARGE_UTF8, 0, true, 0, 0, 0, etlg::kAkJsonStr};   // `j.to_string()` written on the device (AK_JSON_STR)
     l.validity = l.deferred = l.values = l.lens = l.offsets = 0;
     if (l.pl.kind == ETLG_AK_NONE) continue;
-    l.validity = off; off += bm; l.deferred = off; off += bm;
-    if (l.pl.var) { l.offsets = off; off += al64((n + 1) * (dlc ? 4 : 8)); l.lens = off; off += al64(n * 4); }
-    else { l.values = off; off += l.pl.kind == ETLG_AK_BOOLEAN ? bm : al64(n * l.pl.vbytes); }
+    l.validity = a_lay.take(bm); l.deferred = a_lay.take(bm);
+    if (l.pl.var) { l.offsets = a_lay.take((n + 1) * (dlc ? 4 : 8)); l.lens = a_lay.take(n * 4); }
+    else l.values = a_lay.take(l.pl.kind == ETLG_AK_BOOLEAN ? bm : n * l.pl.vbytes);
   }
   // changelog: the two CDC columns — per column validity, deferred, offsets, values (fixed-width strings: sized here, in block A)
   const uint32_t cdc_w[2] = {6u, 33u};
   size_t cdc_validity[2] = {0, 0}, cdc_deferred[2] = {0, 0}, cdc_offsets[2] = {0, 0}, cdc_values[2] = {0, 0};
   if (changelog) for (int k = 0; k < 2; k++) {
-    cdc_validity[k] = off; off += bm; cdc_deferred[k] = off; off += bm;
-    cdc_offsets[k] = off; off += al64((n + 1) * 8); cdc_values[k] = off; off += al64(n * cdc_w[k]);
+    cdc_validity[k] = a_lay.take(bm); cdc_deferred[k] = a_lay.take(bm);
+    cdc_offsets[k] = a_lay.take((n + 1) * 8); cdc_values[k] = a_lay.take(n * cdc_w[k]);
   }
-  const size_t o_cnt = off; off += al64((size_t)nc * 32);   // per column: nulls, deferred, child nulls, first list error
-  const size_t o_tot = off; off += al64((size_t)nc * 8);    // per var-len column: the bytes behind its offsets (one read-back for all)
+  const size_t o_cnt = a_lay.take((size_t)nc * 32);   // per column: nulls, deferred, child nulls, first list error
+  const size_t o_tot = a_lay.take((size_t)nc * 8);    // per var-len column: the bytes behind its offsets (one read-back for all)
   const uint32_t nrb = (uint32_t)((n + 255) / 256);
   const size_t scan_one = al64((size_t)(nrb + 1) * 8);
-  const size_t o_scan = off; off += scan_one * std::max<uint32_t>(nc, 1u);   // a scan scratch per column: the var-len columns' first passes run as ONE launch each (etlg_k_col_var_pack)
-  const size_t a_bytes = off + 64;
-  HIPCHK(c, blk_take(c, a_bytes, false, &cs->m.d_a, &cs->m.cap_a));
+  const size_t o_scan = a_lay.skip(scan_one * std::max<uint32_t>(nc, 1u));   // a scan scratch per column: the var-len columns' first passes run as ONE launch each (etlg_k_col_var_pack)
+  HIPCHK(c, blk_take(c, a_lay.total() + 64, false, &cs->m.d_a, &cs->m.cap_a));
   uint8_t* A = (uint8_t*)cs->m.d_a;
   if (nc) {   // the counters' initial values
     RC(cnt_init(nc));
@@ -264,7 +263,7 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
       const uint64_t k = cnt[(size_t)i * 4 + 3];
       if (k != ~0ull && (first == ~0ull || (k >> 8) < (first >> 8))) first = k;   // strictly earlier row; ties keep the earlier column
     }
-    if (first != ~0ull && (first & 0xFF) != 0xFF) {   // (0xFF: the first row that is not a plain list was handed back DEFERRED, not malformed — k_arr_count)
+    if (first != ~0ull && (first & 0xFF) != kArrHandBack) {   // (kArrHandBack: the first row that is not a plain list was handed back DEFERRED, not malformed — k_arr_count)
       uint64_t ev = 0;
       HIPCHK(c, hipMemcpy(&ev, d_row_event + (first >> 8), 8, hipMemcpyDeviceToHost));
       return set_error(c, (int32_t)(first & 0xFF), (int64_t)ev);
@@ -280,25 +279,25 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   // ---- 3. block B: the bytes of the var-len columns; list columns: child values (or, for lists of strings, child offsets +
   //      lengths) and child validity
   std::vector<size_t> vb(nc, 0);
-  size_t b_bytes = 0;
+  ScratchLayout b_lay;
   std::vector<size_t> cvb(nc, 0), vbytes(nc, 0), clen(nc, 0), cscan(nc, 0);   // list columns: child validity offset; bytes behind `values`; child lens; scan scratch
   bool any_text_list = false;
   for (uint32_t i = 0; i < nc; i++) {
     if (!lay[i].pl.var) continue;
     const size_t tot = (size_t)var_total[i];
-    vb[i] = b_bytes;
     if (lay[i].pl.kind == ETLG_AK_LIST) {
       const size_t bits = (tot + 63) / 64 * 8;
       if (var_child(lay[i].pl)) {   // child offsets first (i64), then lengths, scan scratch, validity
         any_text_list = true;
-        b_bytes += al64((tot + 1) * 8); clen[i] = b_bytes; b_bytes += al64(tot * 4); cscan[i] = b_bytes; b_bytes += al64((tot / 256 + 2) * 8);
-        cvb[i] = b_bytes; b_bytes += al64(bits);
+        vb[i] = b_lay.take((tot + 1) * 8); clen[i] = b_lay.take(tot * 4); cscan[i] = b_lay.take((tot / 256 + 2) * 8);
+        cvb[i] = b_lay.take(bits);
       } else {
         vbytes[i] = lay[i].pl.child == ETLG_AK_BOOLEAN ? bits : tot * lay[i].pl.child_bytes;
-        b_bytes += al64(vbytes[i]); cvb[i] = b_bytes; b_bytes += al64(bits);
+        vb[i] = b_lay.take(vbytes[i]); cvb[i] = b_lay.take(bits);
       }
-    } else { vbytes[i] = tot; b_bytes += al64(tot); }
+    } else { vbytes[i] = tot; vb[i] = b_lay.take(tot); }
   }
+  const size_t b_bytes = b_lay.total();
   if (b_bytes) HIPCHK(c, blk_take(c, b_bytes + 64, false, &cs->m.d_b, &cs->m.cap_b));
   uint8_t* B = (uint8_t*)cs->m.d_b;
   std::vector<int64_t> text_total(nc, 0);
@@ -331,15 +330,15 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   }
   // ---- 3b. block C: the element bytes of lists of strings
   std::vector<size_t> vc(nc, 0);
-  size_t c_bytes = 0;
+  ScratchLayout c_lay;
   if (any_text_list) {
     HIPCHK(c, hipStreamSynchronize(s));
-    for (uint32_t i = 0; i < nc; i++) if (lay[i].pl.kind == ETLG_AK_LIST && var_child(lay[i].pl)) { vc[i] = c_bytes; vbytes[i] = (size_t)text_total[i]; c_bytes += al64((size_t)text_total[i]) + 64; }
-    if (c_bytes) HIPCHK(c, blk_take(c, c_bytes + 64, false, &cs->m.d_c, &cs->m.cap_c));
+    for (uint32_t i = 0; i < nc; i++) if (lay[i].pl.kind == ETLG_AK_LIST && var_child(lay[i].pl)) { vbytes[i] = (size_t)text_total[i]; vc[i] = c_lay.take(vbytes[i]); c_lay.skip(64); }
+    if (c_lay.total()) HIPCHK(c, blk_take(c, c_lay.total() + 64, false, &cs->m.d_c, &cs->m.cap_c));
     for (uint32_t i = 0; i < nc; i++)
       if (lay[i].pl.kind == ETLG_AK_LIST && var_child(lay[i].pl) && var_total[i] > 0) { jobs[i].values = (uint8_t*)cs->m.d_c + vc[i]; etlg_k_col_list(&jobs[i], nullptr, nullptr, 1, s); }
   }
-  uint8_t* Cb = (uint8_t*)cs->m.d_c;
+  uint8_t* Cb = (uint8_t*)cs->m.d_c; const size_t c_bytes = c_lay.total();
   if (nc) HIPCHK(c, hipMemcpyAsync(cnt.data(), A + o_cnt, (size_t)nc * 32, hipMemcpyDeviceToHost, s));   // again: the child null counts
   // ---- 4. the view (device pointers, or a host copy of the blocks)
   const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
@@ -389,23 +388,24 @@ static int32_t build_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t 
   return ETLG_OK;
 }
 
+static_assert(SEL_INSERT == ETLG_ROWS_INSERT && SEL_UPDATE_NEW == ETLG_ROWS_UPDATE, "etlg_batch_columns passes the public row kinds through as ColSel.kinds");
 int32_t etlg_batch_columns(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t row_kinds, uint32_t flags, etlg_columns** out) {
   if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
-  return build_columns(c, b, slot, row_kinds & 3u, row_kinds, flags, ColCaller::Columns, out);
+  return build_columns(c, b, slot, row_kinds & (SEL_INSERT | SEL_UPDATE_NEW), row_kinds, flags, ColCaller::Columns, out);
 }
 
 int32_t etlg_batch_iceberg(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t opts, uint32_t flags, etlg_columns** out) {
   if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
   *out = nullptr;
   if (opts & ~(ETLG_ROWS_PARSE_ARRAYS | ETLG_ROWS_FORMAT_JSON)) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_iceberg: opts takes ETLG_ROWS_PARSE_ARRAYS | ETLG_ROWS_FORMAT_JSON only (the row kinds are fixed)");
-  return build_columns(c, b, slot, 7u, opts, flags, ColCaller::Iceberg, out);
+  return build_columns(c, b, slot, SEL_INSERT | SEL_UPDATE_NEW | SEL_DELETE_OLD, opts, flags, ColCaller::Iceberg, out);
 }
 
 // DuckLake's copy payload for a table arrow_column_kinds accepts (prepare_copy_rows -> copy_rows_to_arrow_record_batch,
 // ducklake/encoding.rs:32-49, :303-340): build_columns' third caller, with a kind table of its own.
 int32_t etlg_batch_ducklake_copy(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t flags, etlg_columns** out) {
   if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
-  return build_columns(c, b, slot, 1u, 1u, flags, ColCaller::DuckLakeCopy, out);
+  return build_columns(c, b, slot, SEL_INSERT, ETLG_ROWS_INSERT, flags, ColCaller::DuckLakeCopy, out);
 }
 
 int32_t etlg_columns_ducklake_get(const etlg_columns* cs, etlg_ducklake_copy_info* out) {
@@ -420,6 +420,33 @@ int32_t etlg_columns_changelog_get(const etlg_columns* cs, etlg_changelog_info* 
   return ETLG_OK;
 }
 
+// The records k_size_hints and the finish pass read (SlotRec / ColRec) for the slots [0, ns): every slot for the size hints, the slots the batch's view
+// lists for the finish pass. `what`: the ETLG_FINISH_* bits whose finishable columns (arrays the device takes apart, floats) `fin` lists; 0 for the hints
+static bool fin_elem_ok(int32_t e) {
+  return e == ETLG_TC_BOOL || e == ETLG_TC_I16 || e == ETLG_TC_I32 || e == ETLG_TC_I64 || e == ETLG_TC_U32 || e == ETLG_TC_F32 || e == ETLG_TC_F64 || e == ETLG_TC_DATE ||
+         e == ETLG_TC_TIME || e == ETLG_TC_TIMETZ || e == ETLG_TC_TIMESTAMP || e == ETLG_TC_TIMESTAMPTZ || e == ETLG_TC_UUID || e == ETLG_TC_NUMERIC || e == ETLG_TC_BYTEA ||
+         e == ETLG_TC_STRING;
+}
+struct SlotTable { std::vector<SlotRec> slots; std::vector<ColRec> cols; std::vector<uint32_t> fin; uint32_t maxfin = 0; bool any_arrays = false; };
+static SlotTable slot_table(const etlg_ctx* c, uint32_t ns, uint32_t what) {
+  SlotTable t; t.slots.resize(ns);
+  for (uint32_t i = 0; i < ns; i++) {
+    const SlotHost& sh = *c->slots[i];
+    SlotRec& r = t.slots[i] = SlotRec{sh.desc.n_cols, sh.desc.n_ident, sh.desc.row_bytes_full, sh.desc.row_bytes_key, (uint32_t)t.cols.size(), (uint32_t)t.fin.size(), 0u};
+    uint32_t k = 0;
+    for (const etlg_slot_col& col : sh.cols) {
+      const int32_t elem = col.type_class == ETLG_TC_ARRAY ? etlg_array_elem_class(col.type_oid) : 0;
+      t.cols.push_back(ColRec{(uint32_t)col.type_class | (col.identity ? 1u << 8 : 0u) | ((uint32_t)elem << 16), (uint32_t)col.off_full | ((uint32_t)col.off_key << 16), (uint32_t)col.key_index});
+      const bool arr = (what & ETLG_FINISH_ARRAYS) && col.type_class == ETLG_TC_ARRAY && fin_elem_ok(elem);
+      const bool flt = (what & ETLG_FINISH_FLOATS) && (col.type_class == ETLG_TC_F32 || col.type_class == ETLG_TC_F64);
+      if (arr || flt) { t.fin.push_back(k); r.n_fin++; t.any_arrays |= arr; }
+      k++;
+    }
+    t.maxfin = std::max(t.maxfin, r.n_fin);
+  }
+  return t;
+}
+
 // k_size_hints over every event of a ready batch with at least one event, enqueued on the context's stream: the slot / column tables go
 // up into a scratch block taken here, with `extra` bytes behind them (*extra_at); the hints go to `out` (device memory), or `hints_off`
 // bytes into `extra` when out is null.
@@ -428,29 +455,23 @@ static int32_t size_hints_enqueue(etlg_ctx* c, etlg_batch* b, const etlg_size_mo
   const etlg_batch_view& bv = b->v;
   const uint64_t ne = bv.n_events;
   hipStream_t s = c->stream;
-  std::vector<uint32_t> tab;
   const uint32_t ns = (uint32_t)c->slots.size();
-  tab.resize((size_t)ns * 5);
-  uint32_t ncols = 0;
-  for (uint32_t i = 0; i < ns; i++) {
-    const SlotHost& sh = *c->slots[i];
-    uint32_t* t = &tab[(size_t)i * 5];
-    t[0] = sh.desc.n_cols; t[1] = sh.desc.n_ident; t[2] = sh.desc.row_bytes_full; t[3] = sh.desc.row_bytes_key; t[4] = ncols;
-    ncols += sh.desc.n_cols;
-  }
-  const size_t o_cols = tab.size();
-  tab.resize(o_cols + (size_t)ncols * 2);
-  for (uint32_t i = 0, k = 0; i < ns; i++)
-    for (const etlg_slot_col& col : c->slots[i]->cols) { tab[o_cols + 2 * k] = col.type_class | (col.identity ? 1u << 8 : 0u) | ((uint32_t)col.off_full << 16); tab[o_cols + 2 * k + 1] = col.off_key; k++; }
-  const size_t tab_bytes = (tab.size() * 4 + 63) & ~(size_t)63;
-  HIPCHK(c, blk_take(c, tab_bytes + extra + 64, false, &dblk.p, &dblk.cap));
-  void* d = dblk.p;
-  *extra_at = (uint8_t*)d + tab_bytes;
-  HIPCHK(c, hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+  const SlotTable t = slot_table(c, ns, 0u);
+  const size_t slot_bytes = t.slots.size() * sizeof(HintSlotRec), col_bytes = t.cols.size() * sizeof(HintColRec);
+  std::vector<uint8_t> tab(slot_bytes + col_bytes + 1);   // the slots, then the columns, in k_size_hints' narrower records: one upload
+  HintSlotRec* hs = (HintSlotRec*)tab.data(); HintColRec* hc = (HintColRec*)(tab.data() + slot_bytes);
+  for (const SlotRec& r : t.slots) *hs++ = HintSlotRec{r.n_cols, r.n_ident, r.row_full, r.row_key, r.cols_base};
+  for (const ColRec& r : t.cols) *hc++ = HintColRec{r.cls() | (r.identity() ? 1u << 8 : 0u) | (r.off_full() << 16), r.off_key()};
+  ScratchLayout lay(slot_bytes + col_bytes);
+  const size_t o_extra = lay.skip(extra + 64);
+  HIPCHK(c, blk_take(c, lay.total(), false, &dblk.p, &dblk.cap));
+  uint8_t* d = (uint8_t*)dblk.p;
+  *extra_at = d + o_extra;
+  HIPCHK(c, hipMemcpyAsync(d, tab.data(), slot_bytes + col_bytes, hipMemcpyHostToDevice, s));
   HintJob j{};
   j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_table = bv.ev_table_id; j.ev_slot = bv.ev_schema_slot; j.ev_body = bv.ev_body_off;
   j.fixed = bv.fixed; j.heap = bv.heap; j.n_events = ne;
-  j.slots = (const uint32_t*)d; j.cols = (const uint32_t*)d + o_cols; j.n_slots = ns;
+  j.slots = (const HintSlotRec*)d; j.cols = (const HintColRec*)(d + slot_bytes); j.n_slots = ns;
   j.m_begin = m->begin_event; j.m_commit = m->commit_event; j.m_insert = m->insert_event; j.m_update = m->update_event; j.m_delete = m->delete_event;
   j.m_truncate = m->truncate_event; j.m_relation = m->relation_event; j.m_rts = m->replicated_table_schema; j.m_row = m->table_row; j.m_cell = m->cell;
   j.out = out ? out : (unsigned long long*)(*extra_at + hints_off);
@@ -497,16 +518,15 @@ int32_t etlg_batch_cuts(etlg_ctx* c, etlg_batch* b, const etlg_size_model* m, co
   uint64_t tile = c->cuts_tile_test ? c->cuts_tile_test : 2048u;
   while ((n + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
   const uint64_t n_tiles = (n + tile - 1) / tile;
-  const size_t o_tsum = al64(5 * 8), o_tinc = o_tsum + al64(n_tiles * 8), o_q = o_tinc + al64(n_tiles * 8), o_hints = o_q + al64((n + 1) * 8),
-               total_bytes = o_hints + (hints ? 0 : al64(ne * 8));
+  const CutsLayout lay = cuts_layout(n, n_tiles, ne, !hints);
   ScratchBlk ablk{c};
   uint8_t* d = nullptr;
-  if (hints) { HIPCHK(c, blk_take(c, total_bytes + 64, false, &ablk.p, &ablk.cap)); d = (uint8_t*)ablk.p; }
-  else RC(size_hints_enqueue(c, b, m, ablk, total_bytes, o_hints, nullptr, &d));   // k_size_hints, as etlg_batch_size_hints launches it
+  if (hints) { HIPCHK(c, blk_take(c, lay.total + 64, false, &ablk.p, &ablk.cap)); d = (uint8_t*)ablk.p; }
+  else RC(size_hints_enqueue(c, b, m, ablk, lay.total, lay.hints, nullptr, &d));   // k_size_hints, as etlg_batch_size_hints launches it
   CutJob j{};
   j.first = first; j.n = n; j.budget = budget; j.carry_in = carry_in; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles;
-  j.hdr = (unsigned long long*)d; j.tsum = (unsigned long long*)(d + o_tsum); j.tinc = (unsigned long long*)(d + o_tinc); j.q = (unsigned long long*)(d + o_q);
-  j.hints = hints ? (const unsigned long long*)hints : (const unsigned long long*)(d + o_hints);
+  j.hdr = (unsigned long long*)(d + lay.hdr); j.tsum = (unsigned long long*)(d + lay.tsum); j.tinc = (unsigned long long*)(d + lay.tinc); j.q = (unsigned long long*)(d + lay.q);
+  j.hints = hints ? (const unsigned long long*)hints : (const unsigned long long*)(d + lay.hints);
   etlg_k_cuts(&j, 0, 0, s);
   uint64_t head[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
@@ -518,9 +538,10 @@ int32_t etlg_batch_cuts(etlg_ctx* c, etlg_batch* b, const etlg_size_model* m, co
   uint32_t levels = 0;
   while ((max_cuts >> levels) != 0) levels++;   // 2^levels > max_cuts >= n_cuts
   const uint64_t emit = cuts_cap < max_cuts ? cuts_cap : max_cuts;
-  const size_t o_cuts = al64((size_t)levels * (L + 2) * 4);
+  ScratchLayout jlay((size_t)levels * (L + 2) * 4);   // the jump levels | the cuts of a host caller
+  const size_t o_cuts = jlay.take(on_dev ? 0 : emit * 8);
   ScratchBlk jblk{c};
-  HIPCHK(c, blk_take(c, o_cuts + (on_dev ? 0 : al64(emit * 8)) + 64, false, &jblk.p, &jblk.cap));
+  HIPCHK(c, blk_take(c, jlay.total() + 64, false, &jblk.p, &jblk.cap));
   j.jump = (uint32_t*)jblk.p; j.L = L; j.levels = levels; j.cuts_cap = emit;
   j.cuts = on_dev ? (unsigned long long*)cuts_out : (unsigned long long*)((uint8_t*)jblk.p + o_cuts);
   etlg_k_cuts(&j, 1, emit, s);
@@ -542,9 +563,10 @@ int32_t etlg_cuts_locate(etlg_ctx* c, const uint64_t* cuts, uint64_t n_cuts, uin
   hipStream_t s = c->stream;
   const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
   ScratchBlk dblk{c};
-  const size_t o_out = cuts_on_device ? 0 : al64(n_cuts * 8);
+  ScratchLayout lay(cuts_on_device ? 0 : n_cuts * 8);   // a host caller's cuts | a host caller's output
+  const size_t o_out = lay.take(on_dev ? 0 : n_cuts * 8);
   uint8_t* d = nullptr;
-  if (!cuts_on_device || !on_dev) { HIPCHK(c, blk_take(c, o_out + (on_dev ? 0 : al64(n_cuts * 8)) + 64, false, &dblk.p, &dblk.cap)); d = (uint8_t*)dblk.p; }
+  if (!cuts_on_device || !on_dev) { HIPCHK(c, blk_take(c, lay.total() + 64, false, &dblk.p, &dblk.cap)); d = (uint8_t*)dblk.p; }
   if (!cuts_on_device) HIPCHK(c, hipMemcpyAsync(d, cuts, n_cuts * 8, hipMemcpyHostToDevice, s));
   unsigned long long* out_d = on_dev ? (unsigned long long*)rows_out : (unsigned long long*)(d + o_out);
   etlg_k_cuts_locate(cuts_on_device ? (const unsigned long long*)cuts : (const unsigned long long*)d, n_cuts, (const unsigned long long*)row_event, n_rows, out_d, s);
@@ -604,22 +626,20 @@ int32_t etlg_batch_payload(etlg_ctx* c, etlg_batch* b, const uint8_t* buf, size_
   j.n_bounds = n_bounds; j.n_events = ne; j.entry_ord = b->entry_ord; j.n_cuts = n_cuts;
   j.ev_kind = bv.ev_kind; j.ev_ord = (const unsigned long long*)bv.ev_tx_ordinal;
   const uint64_t n_ranges = n_cuts + 1;
-  const size_t o_hist = al64(PAY_H_WORDS * 8), o_bounds = o_hist + al64((size_t)n_hist * 8), o_fbytes = o_bounds + al64(64 * 8), o_tcnt = o_fbytes + al64(n_recv * 4),
-               o_r2f = o_tcnt + al64((size_t)j.n_tiles * 8), o_brank = o_r2f + al64(nf * 4), o_etb = o_brank + al64(nf * 4), o_evb = o_etb + al64((size_t)j.n_etiles * 8),
-               o_tsum = o_evb + (out_dev && ev_bytes_out ? 0 : al64(ne * 4)), o_pb = o_tsum + (want_sums ? al64((size_t)j.n_etiles * 48) : 0),
-               o_pr = o_pb + (want_sums ? al64(3 * (ne + 1) * 8) : 0), o_cuts = o_pr + (want_sums ? al64(3 * (ne + 1) * 4) : 0),
-               o_sums = o_cuts + (want_sums && !cuts_on_device ? al64(n_cuts * 8) : 0), total = o_sums + (want_sums && !out_dev ? al64(n_ranges * 64) : 0);
+  const bool evb_here = !(out_dev && ev_bytes_out);
+  const PayLayout lay = payload_layout(PAY_H_WORDS, n_hist, n_recv, nf, ne, j.n_tiles, j.n_etiles, n_cuts, evb_here, want_sums, !cuts_on_device, !out_dev);
+  const size_t o_hist = lay.hist, o_bounds = lay.bounds;
   ScratchBlk blk{c};
-  HIPCHK(c, blk_take(c, total + 64, false, &blk.p, &blk.cap));
+  HIPCHK(c, blk_take(c, lay.total + 64, false, &blk.p, &blk.cap));
   uint8_t* d = (uint8_t*)blk.p;
-  j.hdr = (unsigned long long*)d; j.hist = (unsigned long long*)(d + o_hist); j.bounds = (const unsigned long long*)(d + o_bounds);
-  j.fbytes = (uint32_t*)(d + o_fbytes); j.tcnt = (unsigned long long*)(d + o_tcnt); j.r2f = (uint32_t*)(d + o_r2f); j.brank = (uint32_t*)(d + o_brank);
-  j.etb = (unsigned long long*)(d + o_etb); j.ev_bytes = out_dev && ev_bytes_out ? ev_bytes_out : (uint32_t*)(d + o_evb);
+  j.hdr = (unsigned long long*)(d + lay.hdr); j.hist = (unsigned long long*)(d + o_hist); j.bounds = (const unsigned long long*)(d + o_bounds);
+  j.fbytes = (uint32_t*)(d + lay.fbytes); j.tcnt = (unsigned long long*)(d + lay.tcnt); j.r2f = (uint32_t*)(d + lay.r2f); j.brank = (uint32_t*)(d + lay.brank);
+  j.etb = (unsigned long long*)(d + lay.etb); j.ev_bytes = evb_here ? (uint32_t*)(d + lay.evb) : ev_bytes_out;
   if (want_sums) {
-    j.tsum = (unsigned long long*)(d + o_tsum); j.pb = (unsigned long long*)(d + o_pb); j.pr = (uint32_t*)(d + o_pr);
-    j.cuts = cuts_on_device ? (const unsigned long long*)cuts : (const unsigned long long*)(d + o_cuts);
-    j.sums = out_dev ? (unsigned long long*)sums_out : (unsigned long long*)(d + o_sums);
-    if (!cuts_on_device && n_cuts) HIPCHK(c, hipMemcpyAsync(d + o_cuts, cuts, n_cuts * 8, hipMemcpyHostToDevice, s));
+    j.tsum = (unsigned long long*)(d + lay.tsum); j.pb = (unsigned long long*)(d + lay.pb); j.pr = (uint32_t*)(d + lay.pr);
+    j.cuts = cuts_on_device ? (const unsigned long long*)cuts : (const unsigned long long*)(d + lay.cuts);
+    j.sums = out_dev ? (unsigned long long*)sums_out : (unsigned long long*)(d + lay.sums);
+    if (!cuts_on_device && n_cuts) HIPCHK(c, hipMemcpyAsync(d + lay.cuts, cuts, n_cuts * 8, hipMemcpyHostToDevice, s));
   }
   static_assert(sizeof(etlg_payload_sums) == 64, "k_paye_ranges writes 8 words per range");
   HIPCHK(c, hipMemsetAsync(d, 0, o_bounds, s));   // the header and the histogram
@@ -644,11 +664,6 @@ int32_t etlg_batch_payload(etlg_ctx* c, etlg_batch* b, const uint8_t* buf, size_
 // The finish pass (include/etlg.h): typed arrays and exact floats in the arena. Tables: one record per host slot, the columns' classes
 // and offsets, and per slot the list of its FINISHABLE columns (arrays of a class the device takes apart, floats) — a thread per
 // (event, row image, finishable column). Two device stops: the entry sizes' total (the heap may have to grow), then the counters.
-static bool fin_elem_ok(int32_t e) {
-  return e == ETLG_TC_BOOL || e == ETLG_TC_I16 || e == ETLG_TC_I32 || e == ETLG_TC_I64 || e == ETLG_TC_U32 || e == ETLG_TC_F32 || e == ETLG_TC_F64 || e == ETLG_TC_DATE ||
-         e == ETLG_TC_TIME || e == ETLG_TC_TIMETZ || e == ETLG_TC_TIMESTAMP || e == ETLG_TC_TIMESTAMPTZ || e == ETLG_TC_UUID || e == ETLG_TC_NUMERIC || e == ETLG_TC_BYTEA ||
-         e == ETLG_TC_STRING;
-}
 int32_t finish_cells(etlg_ctx* c, etlg_batch* b, uint32_t what, etlg_finish_stats* stats) {
   etlg_finish_stats st{};
   if (stats) *stats = st;
@@ -658,45 +673,27 @@ int32_t finish_cells(etlg_ctx* c, etlg_batch* b, uint32_t what, etlg_finish_stat
   if (!ne || !what) return ETLG_OK;
   hipStream_t s = c->stream;
   const uint32_t ns = (uint32_t)std::min<size_t>(c->slots.size(), b->n_slots_view == ~(size_t)0 ? c->slots.size() : std::max<size_t>(b->n_slots_view, bv.n_slots));
-  std::vector<uint32_t> tab((size_t)ns * 7), cols, fin;
-  uint32_t maxfin = 0;
-  bool any_arrays = false;
-  for (uint32_t i = 0; i < ns; i++) {
-    const SlotHost& sh = *c->slots[i];
-    uint32_t* t = &tab[(size_t)i * 7];
-    t[0] = sh.desc.n_cols; t[1] = sh.desc.n_ident; t[2] = sh.desc.row_bytes_full; t[3] = sh.desc.row_bytes_key; t[4] = (uint32_t)(cols.size() / 3); t[5] = (uint32_t)fin.size();
-    uint32_t k = 0, nfin = 0;
-    for (const etlg_slot_col& col : sh.cols) {
-      const int32_t elem = col.type_class == ETLG_TC_ARRAY ? etlg_array_elem_class(col.type_oid) : 0;
-      cols.push_back(col.type_class | (col.identity ? 1u << 8 : 0u) | ((uint32_t)elem << 16));
-      cols.push_back((uint32_t)col.off_full | ((uint32_t)col.off_key << 16));
-      cols.push_back(col.key_index);
-      const bool arr = (what & ETLG_FINISH_ARRAYS) && col.type_class == ETLG_TC_ARRAY && fin_elem_ok(elem);
-      const bool flt = (what & ETLG_FINISH_FLOATS) && (col.type_class == ETLG_TC_F32 || col.type_class == ETLG_TC_F64);
-      if (arr || flt) { fin.push_back(k); nfin++; any_arrays |= arr; }
-      k++;
-    }
-    t[6] = nfin;
-    maxfin = std::max(maxfin, nfin);
-  }
+  const SlotTable tab = slot_table(c, ns, what);
+  const std::vector<uint32_t>& fin = tab.fin; const uint32_t maxfin = tab.maxfin; const bool any_arrays = tab.any_arrays;
   if (!maxfin) return ETLG_OK;
   const uint64_t n = ne * 2ull * maxfin;
   const uint32_t nb = (uint32_t)((n + 255) / 256);
-  const size_t o_cols = al64(tab.size() * 4), o_fin = o_cols + al64(cols.size() * 4), o_stats = o_fin + al64(fin.size() * 4 + 4), o_lens = o_stats + 64;
-  const size_t o_cnts = o_lens + (any_arrays ? al64(n * 4) : 0);
-  const size_t o_offs = o_cnts + (any_arrays ? al64(n * 4) : 0), o_blk = o_offs + (any_arrays ? al64((n + 1) * 8) : 0), total = o_blk + (any_arrays ? al64(((size_t)nb + 2) * 8) : 0) + 64;
+  ScratchLayout lay(tab.slots.size() * sizeof(SlotRec));   // slots | columns | finishable columns | stats | with arrays: lens, counts, offsets, scan scratch
+  const size_t o_cols = lay.take(tab.cols.size() * sizeof(ColRec)), o_fin = lay.take(fin.size() * 4 + 4), o_stats = lay.skip(64);
+  const size_t o_lens = lay.take(any_arrays ? n * 4 : 0), o_cnts = lay.take(any_arrays ? n * 4 : 0), o_offs = lay.take(any_arrays ? (n + 1) * 8 : 0),
+               o_blk = lay.take(any_arrays ? ((size_t)nb + 2) * 8 : 0);
   ScratchBlk dblk{c};
-  HIPCHK(c, blk_take(c, total, false, &dblk.p, &dblk.cap));
+  HIPCHK(c, blk_take(c, lay.total() + 64, false, &dblk.p, &dblk.cap));
   uint8_t* d = (uint8_t*)dblk.p;
-  HIPCHK(c, hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d + o_cols, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d, tab.slots.data(), tab.slots.size() * sizeof(SlotRec), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d + o_cols, tab.cols.data(), tab.cols.size() * sizeof(ColRec), hipMemcpyHostToDevice, s));
   if (!fin.empty()) HIPCHK(c, hipMemcpyAsync(d + o_fin, fin.data(), fin.size() * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(d + o_stats, 0, 64, s));
   OutSet* os = b->dev;
   FinJob j{};
   j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot; j.ev_body = bv.ev_body_off;
   j.fixed = (uint8_t*)os->fixed.p; j.heap = (uint8_t*)os->heap.p; j.n_events = ne;
-  j.slots = (const uint32_t*)d; j.cols = (const uint32_t*)(d + o_cols); j.fin = (const uint32_t*)(d + o_fin);
+  j.slots = (const SlotRec*)d; j.cols = (const ColRec*)(d + o_cols); j.fin = (const uint32_t*)(d + o_fin);
   j.n_slots = ns; j.maxfin = maxfin; j.what = what;
   j.stats = (unsigned long long*)(d + o_stats);
   j.heap_base = (bv.heap_bytes + 3) & ~3ull;
@@ -756,7 +753,7 @@ void etlg_columns_free(etlg_columns* cs) {
   delete cs;
 }
 
-struct NdKeys { std::vector<uint32_t> off; std::string bytes; };   // format 2: the escaped `"name":` of every column, back to back
+struct NdKeys { std::vector<uint32_t> off; std::string bytes; };   // FMT_NDJSON: the escaped `"name":` of every column, back to back
 // n NUL-separated names, each as '"' + its characters through esc(bytes, ch) + close; off: where every key begins, and the end
 static NdKeys quoted_names(const char* names, uint32_t n, const char* close, void (*esc)(std::string&, unsigned char)) {
   NdKeys k;
@@ -777,12 +774,12 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
 int32_t etlg_batch_rowbinary(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
                              uint32_t flags, etlg_rowbinary** out) {
   if (!c || !b || !out || b->ctx != c || !nullable_flags) return ETLG_InvalidArgument;
-  return handoff_rows(c, b, slot, nullable_flags, n_flags, engine, flags, 0u, out);
+  return handoff_rows(c, b, slot, nullable_flags, n_flags, engine, flags, FMT_ROWBINARY, out);
 }
 
 int32_t etlg_batch_protobuf(etlg_ctx* c, etlg_batch* b, int32_t slot, uint32_t flags, etlg_rowbinary** out) {
   if (!c || !b || !out || b->ctx != c) return ETLG_InvalidArgument;
-  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags, 1u, out);
+  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags, FMT_PROTOBUF, out);
 }
 
 // Snowflake NDJSON (snowflake/encoding.rs:57-72): the column names are escaped here once — serde_json's table (format_escaped_str) — and
@@ -803,7 +800,7 @@ int32_t etlg_batch_ndjson(etlg_ctx* c, etlg_batch* b, int32_t slot, const char* 
     else if (ch < 0x20) { o += "\\u00"; o.push_back(hexd[ch >> 4]); o.push_back(hexd[ch & 15]); }
     else o.push_back((char)ch);
   });
-  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, 2u, out, &k);
+  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, FMT_NDJSON, out, &k);
 }
 
 // DuckLake SQL literals (ducklake/encoding.rs:366-612, batches.rs:1229-1316): the column names are quoted here once, as
@@ -817,11 +814,15 @@ int32_t etlg_batch_duckdb(etlg_ctx* c, etlg_batch* b, int32_t slot, int32_t what
   if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
   if (n_names != c->slots[(size_t)slot]->desc.n_cols) return lib_error(c, ETLG_InvalidArgument, "DuckLake row width mismatch: one column name per replicated column");
   const NdKeys k = quoted_names(col_names, n_names, "\"", [](std::string& o, unsigned char ch) { if (ch == '"') o.push_back('"'); o.push_back((char)ch); });
-  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, 3u, out, &k, (uint32_t)what);
+  return handoff_rows(c, b, slot, nullptr, 0u, ETLG_CH_MERGE_TREE, flags & ETLG_F_OUTPUT_ON_DEVICE, FMT_DUCKLAKE, out, &k, (uint32_t)what);
 }
 
-// format 0: ClickHouse RowBinary (Insert / Update / Delete rows + the engine's CDC columns); 1: BigQuery protobuf; 2: Snowflake NDJSON;
-// 3: DuckLake SQL literals (dl_what: ETLG_DL_TUPLES / ETLG_DL_PREDICATES / ETLG_DL_UPDATES)
+// ColSel.dl of an etlg_batch_duckdb call, and through dl_row_what RbJob.dl_what (a copied row's predicate is over the primary key: delete_predicate_from_copy_row)
+static uint32_t dl_selection(uint32_t what, bool copy) {
+  return what == ETLG_DL_UPDATES ? DL_SEL_UPDATES : what == ETLG_DL_TUPLES ? DL_SEL_TUPLES : copy ? DL_SEL_PRED_PK : DL_SEL_PRED_IDENT;
+}
+// format (FMT_*): ClickHouse RowBinary (Insert / Update / Delete rows + the engine's CDC columns), BigQuery protobuf, Snowflake NDJSON,
+// DuckLake SQL literals (dl_what: ETLG_DL_TUPLES / ETLG_DL_PREDICATES / ETLG_DL_UPDATES)
 static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint8_t* nullable_flags, uint32_t n_flags, int32_t engine,
                             uint32_t flags, uint32_t format, etlg_rowbinary** out, const NdKeys* nd, uint32_t dl_what) {
   *out = nullptr;
@@ -829,13 +830,14 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   if (!slot_known(c, slot) || (engine != ETLG_CH_MERGE_TREE && engine != ETLG_CH_REPLACING_MERGE_TREE)) return ETLG_InvalidArgument;
   const SlotHost& sh = *c->slots[(size_t)slot];
   const uint32_t nc = sh.desc.n_cols;
-  if (format == 0 && n_flags != nc + 2) return lib_error(c, ETLG_ConversionError, "ClickHouse RowBinary row width mismatch");
+  if (format == FMT_ROWBINARY && n_flags != nc + 2) return lib_error(c, ETLG_ConversionError, "ClickHouse RowBinary row width mismatch");
   std::unique_ptr<etlg_rowbinary, void (*)(etlg_rowbinary*)> rb(new etlg_rowbinary, etlg_rowbinary_free);
   const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
   rb->v.on_device = on_dev ? 1u : 0u; rb->v.host_event = ~0ull;
-  const bool dl_upd = format == 3 && dl_what == ETLG_DL_UPDATES;   // partial Updates: two records per event and the col_ends array
+  const uint32_t dl = format == FMT_DUCKLAKE ? dl_selection(dl_what, b->copy.active) : (uint32_t)DL_SEL_NONE;
+  const bool dl_upd = dl == DL_SEL_UPDATES;   // partial Updates: two records per event and the col_ends array
   rb->updates = dl_upd;
-  if (format == 3) { rb->dl_batch = b; rb->dl_serial = b->serial; rb->dl_slot = slot; rb->dl_what = dl_what; }
+  if (format == FMT_DUCKLAKE) { rb->dl_batch = b; rb->dl_serial = b->serial; rb->dl_slot = slot; rb->dl_what = dl_what; }
   std::vector<uint32_t> cols(2 * (size_t)nc);   // [nc, 2 nc): the key-layout words of the columns (RbJob.kcols)
   // A Delete that carries only the key: the reference expands it into a tombstone row (expand_key_row, clickhouse/core.rs:1437-1472)
   // when the replica identity is the primary key (or Full) — ensure_clickhouse_key_identity_is_primary_key, :1404-1427; identity
@@ -843,7 +845,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   // unless a nullable non-key column has a type outside the value codec's table (a String cell): is_array_type (type_utils.rs:14-18)
   // decides between NULL and an empty array there, and only the host knows every array type — those slots' key-only Deletes stay
   // with the host, like every slot's under another identity (the host raises the reference's SourceReplicaIdentityError).
-  bool key_ok = format == 0 && (sh.identity_type == 1 || sh.identity_type == 2) && sh.desc.n_ident != 0;
+  bool key_ok = format == FMT_ROWBINARY && (sh.identity_type == 1 || sh.identity_type == 2) && sh.desc.n_ident != 0;
   bool pk_comparable = true;
   for (uint32_t i = 0; i < nc; i++) {
     const etlg_slot_col& sc = sh.cols[i];
@@ -865,7 +867,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
       host_class = lp.kind != ETLG_AK_LIST && elem != ETLG_TC_JSON;   // (text-like / numeric / timetz / bytea / json elements are written on the device too)
     }
     // (DuckLake predicates look at the key columns only: the identity columns, for a table-copy batch the primary-key ones)
-    if (format == 3 && dl_what == ETLG_DL_PREDICATES && !(b->copy.active ? sh.pk[i] != 0 : sh.cols[i].identity != 0)) host_class = false;
+    if ((dl == DL_SEL_PRED_PK && !sh.pk[i]) || (dl == DL_SEL_PRED_IDENT && !sh.cols[i].identity)) host_class = false;
     if (host_class) {
       rb->v.status = ETLG_RB_NEEDS_HOST; rb->v.host_column = i;
       *out = rb.release();
@@ -876,14 +878,15 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   hipStream_t s = c->stream;
   const etlg_batch_view& bv = b->v;
   const uint64_t ne = bv.n_events;
-  const uint64_t nr_cap = format ? 2 * ne : ne;   // BigQuery: an update that changes the primary key is two rows
+  const uint64_t nr_cap = format != FMT_ROWBINARY ? 2 * ne : ne;   // BigQuery: an update that changes the primary key is two rows
   const uint32_t nblk = (uint32_t)((ne + 255) / 256);
   // block S (freed on return): block counts | host-row counter | error word | column words | row_base
-  const size_t nd_bytes = nd ? (size_t)(nc + 1) * 4 + nd->bytes.size() : 0;   // (format 2: the keys' offsets and bytes behind the column words)
-  const size_t o_cnt = al64((size_t)(nblk + 1) * 4), o_cols = o_cnt + 64, o_base = o_cols + al64((size_t)nc * 8 + 8 + nd_bytes), s_bytes = o_base + al64(nr_cap * 8) + 64;
+  const size_t nd_bytes = nd ? (size_t)(nc + 1) * 4 + nd->bytes.size() : 0;   // (FMT_NDJSON / FMT_DUCKLAKE: the keys' offsets and bytes behind the column words)
+  ScratchLayout s_lay((size_t)(nblk + 1) * 4);
+  const size_t o_cnt = s_lay.skip(64), o_cols = s_lay.take((size_t)nc * 8 + 8 + nd_bytes), o_base = s_lay.take(nr_cap * 8);
   rb->m.ctx = c; rb->m.ctx_gen = c->gen;
   ScratchBlk sblk{c};
-  HIPCHK(c, blk_take(c, s_bytes, false, &sblk.p, &sblk.cap));
+  HIPCHK(c, blk_take(c, s_lay.total() + 64, false, &sblk.p, &sblk.cap));
   void* d_s = sblk.p;
   uint8_t* S = (uint8_t*)d_s;
   // pinned staging: [host rows = 0 | error word = ~0 | total | pad to 64 | column words] goes up in one copy (S + o_cnt .. lies the same
@@ -908,8 +911,10 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   volatile unsigned long long* down = (volatile unsigned long long*)(c->h_hand + al64(up_bytes));   // [0] row count, [1..3] host rows, error word, total
   // block A: row_event | row_offsets | lens | scan scratch (sized for every event being a row)
   const uint32_t nblk_r = (uint32_t)((nr_cap + 255) / 256);
-  const size_t o_off = al64(nr_cap * 8), o_len = o_off + al64((nr_cap + 1) * 8), o_scan = o_len + al64(nr_cap * 4), o_part = o_scan + al64((size_t)(nblk_r + 1) * 8), a_bytes = o_part + 3 * al64(nr_cap * 4) + 64;   // (o_part: where the parts of a row begin, k_rb_rows)
-  HIPCHK(c, blk_take(c, a_bytes, false, &rb->m.d_a, &rb->m.cap_a));
+  ScratchLayout a_lay(nr_cap * 8);
+  const size_t o_off = a_lay.take((nr_cap + 1) * 8), o_len = a_lay.take(nr_cap * 4), o_scan = a_lay.take((size_t)(nblk_r + 1) * 8);
+  const size_t o_part = a_lay.skip(3 * al64(nr_cap * 4));   // (where the parts of a row begin, k_rb_rows)
+  HIPCHK(c, blk_take(c, a_lay.total() + 64, false, &rb->m.d_a, &rb->m.cap_a));
   uint8_t* A = (uint8_t*)rb->m.d_a;
   uint32_t n32 = 0;
   unsigned long long cnt[2] = {0, ~0ull};
@@ -920,18 +925,20 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     // identity is neither PrimaryKey nor Full (clickhouse_update_row -> ensure_clickhouse_key_identity_is_primary_key,
     // clickhouse/core.rs:1359-1427). Such Updates are not encoded here: they are left to the host (n_host_rows), which raises
     // the reference's SourceReplicaIdentityError when it meets the first of them.
-    const bool upd_ok = format != 0 || engine != ETLG_CH_REPLACING_MERGE_TREE || sh.identity_type == 1 || sh.identity_type == 2;
+    const bool upd_ok = format != FMT_ROWBINARY || engine != ETLG_CH_REPLACING_MERGE_TREE || sh.identity_type == 1 || sh.identity_type == 2;
     // Snowflake: inserts, full updates, deletes with a full old row or a key image (core.rs:345-438, snowflake_update_row /
     // snowflake_delete_row :572-608); partial updates and deletes without an old row stay with the host (SourceReplicaIdentityError)
-    q.n_events = ne; q.slot = (uint32_t)slot; q.kinds = format == 2 ? 15u : format ? 1u : ((upd_ok ? 7u : 5u) | (key_ok ? 8u : 0u)); q.host_rows = (unsigned long long*)(S + o_cnt);
+    q.n_events = ne; q.slot = (uint32_t)slot; q.kinds = format == FMT_NDJSON ? SEL_INSERT | SEL_UPDATE_NEW | SEL_DELETE_OLD | SEL_DELETE_KEY : format != FMT_ROWBINARY ? SEL_INSERT   // (pb_selected / dl_selected pick the rest)
+                      : SEL_INSERT | SEL_DELETE_OLD | (upd_ok ? SEL_UPDATE_NEW : 0u) | (key_ok ? SEL_DELETE_KEY : 0u);
+    q.host_rows = (unsigned long long*)(S + o_cnt);
     q.row_full = sh.desc.row_bytes_full; q.row_key = sh.desc.row_bytes_key;
     q.blk = (uint32_t*)S; q.nblocks = nblk; q.row_event = (uint64_t*)A; q.row_base = (uint64_t*)(S + o_base);
-    if (format == 3) {  // DuckLake: dl_selected (ducklake/core.rs:1824-1945, batches.rs:1128-1226)
-      q.dl = dl_upd ? 4u : dl_what == ETLG_DL_TUPLES ? 1u : b->copy.active ? 3u : 2u;
+    if (format == FMT_DUCKLAKE) {  // dl_selected (ducklake/core.rs:1824-1945, batches.rs:1128-1226)
+      q.dl = dl;
       q.dl_ident = sh.desc.n_ident != 0 ? 1u : 0u;
       if (dl_upd) { q.n_cols = nc; q.fixed = bv.fixed; q.kcols = (const uint32_t*)(S + o_cols) + nc; }   // (the new row's cell states, the identity bits)
     }
-    if (format == 1) {  // BigQuery: inserts, updates (one or two rows) and deletes (bigquery/core.rs:978-1036); the events the reference refuses stay with the host
+    if (format == FMT_PROTOBUF) {  // BigQuery: inserts, updates (one or two rows) and deletes (bigquery/core.rs:978-1036); the events the reference refuses stay with the host
       q.pb = 1; q.n_cols = nc; q.identity_pk = sh.identity_type == 1 ? 1u : 0u; q.pk_comparable = pk_comparable ? 1u : 0u;
       q.fixed = bv.fixed; q.heap = bv.heap; q.cols = (const uint32_t*)(S + o_cols); q.kcols = (const uint32_t*)(S + o_cols) + nc;
     }
@@ -947,8 +954,8 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   j.n_rows = n; j.n_cols = nc; j.engine = (uint32_t)engine;
   j.cdc_nullable = nullable_flags ? (nullable_flags[nc] ? 1u : 0u) | (nullable_flags[nc + 1] ? 2u : 0u) : 0u;
   j.format = format;
-  j.copy_tail = (format <= 1 && b->copy.active) ? 1u : 0u;   // a table-copy batch: write_table_rows' rows (clickhouse/core.rs:739-773, bigquery/core.rs:602-649)
-  j.cols = (const uint32_t*)(S + o_cols); j.kcols = (key_ok || format) ? (const uint32_t*)(S + o_cols) + nc : nullptr; j.ev_flags = bv.ev_flags; j.lens = (uint32_t*)(A + o_len); j.offsets = (const int64_t*)(A + o_off);
+  j.copy_tail = ((format == FMT_ROWBINARY || format == FMT_PROTOBUF) && b->copy.active) ? 1u : 0u;   // a table-copy batch: write_table_rows' rows (clickhouse/core.rs:739-773, bigquery/core.rs:602-649)
+  j.cols = (const uint32_t*)(S + o_cols); j.kcols = (key_ok || format != FMT_ROWBINARY) ? (const uint32_t*)(S + o_cols) + nc : nullptr; j.ev_flags = bv.ev_flags; j.lens = (uint32_t*)(A + o_len); j.offsets = (const int64_t*)(A + o_off);
   j.err = (unsigned long long*)(S + o_cnt) + 1;
   for (uint32_t i = 0; i < nc; i++) if (sh.cols[i].type_class == ETLG_TC_JSON || (sh.cols[i].type_class == ETLG_TC_ARRAY && (uint32_t)etlg_array_elem_class(sh.cols[i].type_oid) == ETLG_TC_JSON)) j.has_json = 1;
   j.qparts = nc >= 4 ? 4u : nc >= 2 ? 2u : 1u; j.parts = 1;
@@ -957,7 +964,7 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
     j.kcols = (const uint32_t*)(S + o_cols) + nc;
     j.nd_key_off = (const uint32_t*)(S + o_cols + (size_t)nc * 8); j.nd_keys = S + o_cols + (size_t)nc * 12 + 4;
     j.nd_zero_token = b->copy.active ? 1u : 0u;   // a table-copy batch (etlg_copy_decode): Insert rows under OffsetToken::zero (core.rs:683-699)
-    j.dl_what = dl_upd ? 3u : dl_what == ETLG_DL_TUPLES ? 0u : b->copy.active ? 2u : 1u;   // (format 3; a copied row's predicate is over the primary key: delete_predicate_from_copy_row)
+    if (dl) j.dl_what = dl_row_what(dl);
     if (dl_upd && n && nc) {  // col_ends: a block of its own, sized by the rows the select pass counted (not by 2 x events x columns)
       HIPCHK(c, blk_take(c, (size_t)n * nc * 4 + 64, false, &rb->m.d_c, &rb->m.cap_c));
       j.col_ends = (uint32_t*)rb->m.d_c;
@@ -974,34 +981,33 @@ static int32_t handoff_rows(etlg_ctx* c, etlg_batch* b, int32_t slot, const uint
   cnt[0] = down[1]; cnt[1] = down[2]; total = (int64_t)down[3];
   rb->v.n_host_rows = cnt[0];
   if (cnt[1] != ~0ull) {  // the first row (event order) with a cell that has no encoding
-    const uint32_t code = (uint32_t)(cnt[1] & 0xFF), col = (uint32_t)((cnt[1] >> 8) & 0xFFFF);
+    const RbReport rep = rb_report_unpack(cnt[1]); const uint32_t code = rep.code, col = rep.col;
     uint64_t ev = 0;
-    HIPCHK(c, hipMemcpy(&ev, A + ((cnt[1] & ~(3ull << 61)) >> 24) * 8, 8, hipMemcpyDeviceToHost));   // (bits 61 / 62: the report's rank, k_rb_lens)
-    if (code == 5) return set_error(c, ETLG_E_JSON, (int64_t)ev);   // a json cell that is not one JSON value: the decode error of codec/text.rs:126-134, as etlg_batch_columns reports it
-    if (code == 3) {
+    HIPCHK(c, hipMemcpy(&ev, A + rep.row * 8, 8, hipMemcpyDeviceToHost));
+    if (code == RB_E_JSON) return set_error(c, ETLG_E_JSON, (int64_t)ev);   // a json cell that is not one JSON value: the decode error of codec/text.rs:126-134, as etlg_batch_columns reports it
+    if (code == RB_E_HOST_CELL) {
       rb->v.status = ETLG_RB_NEEDS_HOST; rb->v.host_event = ev; rb->v.host_column = col;
       blk_give(c, c->gen, rb->m.d_a, rb->m.cap_a, false); blk_give(c, c->gen, rb->m.d_c, rb->m.cap_c, false); rb->m.d_a = rb->m.d_c = nullptr;
       *out = rb.release();
       return ETLG_OK;
     }
-    if (code >= 7 && code <= 11) {  // Error::Encoding of the serde message (snowflake/encoding.rs:162-180, error.rs:25-26, 52)
+    if (code >= ND_E_FIRST && code <= ND_E_LAST) {  // Error::Encoding of the serde message (snowflake/encoding.rs:162-180, error.rs:25-26, 52)
       const int32_t k = lib_error(c, ETLG_InvalidData, "Snowflake encoding error");
-      static const char* const what[] = {"Snowflake does not support NaN/Infinity float values: NaN", "Snowflake does not support NaN/Infinity float values: inf",
-                                         "Snowflake does not support NaN/Infinity float values: -inf", "Snowflake NUMBER does not support NaN",
-                                         "Snowflake NUMBER does not support Infinity"};
-      c->err_detail = std::string("Encoding error: ") + what[code - 7];
+      static const char* const what[ND_E_LAST - ND_E_FIRST + 1] = {"Snowflake does not support NaN/Infinity float values: NaN", "Snowflake does not support NaN/Infinity float values: inf",
+          "Snowflake does not support NaN/Infinity float values: -inf", "Snowflake NUMBER does not support NaN", "Snowflake NUMBER does not support Infinity"};   // ND_E_FLOAT_NAN, _FLOAT_INF, _FLOAT_NINF, _NUM_NAN, _NUM_INF
+      c->err_detail = std::string("Encoding error: ") + what[code - ND_E_FIRST];
       c->err.detail = c->err_detail.c_str();
       c->err.frame_index = (int64_t)ev;
       return k;
     }
-    if (code == 4 || code == 6) {  // BigQueryTableRow::try_from_tagged_cells (bigquery/encoding.rs:37-45) around validate_numeric_for_bigquery (validation.rs:20-35) / reject_nulls (:127-141): the wrapper keeps the kind
-      const int32_t k = lib_error(c, code == 6 ? ETLG_NullValuesNotSupportedInArrayInDestination : ETLG_UnsupportedValueInDestination, "Cell validation failed for BigQuery compatibility");
+    if (code == RB_E_BQ_NUMERIC_SCALE || code == RB_E_BQ_ARRAY_NULL) {  // BigQueryTableRow::try_from_tagged_cells (bigquery/encoding.rs:37-45) around validate_numeric_for_bigquery (validation.rs:20-35) / reject_nulls (:127-141): the wrapper keeps the kind
+      const int32_t k = lib_error(c, code == RB_E_BQ_ARRAY_NULL ? ETLG_NullValuesNotSupportedInArrayInDestination : ETLG_UnsupportedValueInDestination, "Cell validation failed for BigQuery compatibility");
       c->err_detail = "Cell at index " + std::to_string(col) + " failed validation";
       c->err.detail = c->err_detail.c_str();
       c->err.frame_index = (int64_t)ev;
       return k;
     }
-    const int32_t k = lib_error(c, ETLG_ConversionError, code == 1 ? "NULL value for non-nullable ClickHouse column" : "Date out of ClickHouse Date32 range");
+    const int32_t k = lib_error(c, ETLG_ConversionError, code == RB_E_NULL ? "NULL value for non-nullable ClickHouse column" : "Date out of ClickHouse Date32 range");
     c->err.frame_index = (int64_t)ev;
     return k;
   }
@@ -1067,13 +1073,13 @@ int32_t etlg_ducklake_fingerprints(etlg_ctx* c, etlg_batch* b, int32_t slot, con
   const uint64_t n_max = tv.n_bytes + pv.n_bytes + u_bytes + ne * 26 + (u_rows / 2) * (8 + 9 * (uint64_t)nc);
   const uint64_t chunk = etlg_k_fp_chunk_bytes(), n_chunks = n_max / chunk + 1, n_pieces = n_chunks + n_ranges;
   if (n_chunks > 0x7FFFFFFFull) return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_fingerprints: the batch's records are beyond what one call hashes");
-  const size_t o_names = al64(up.size() * 8), o_plan = o_names + al64((size_t)nc * 4 + 4), o_lens = o_plan + al64(ne * 16), o_offs = o_lens + al64(ne * 4),
-               o_blk = o_offs + al64((ne + 1) * 8), o_bounds = o_blk + al64((ne / 256 + 2) * 8), o_result = o_bounds + al64((size_t)n_ranges * 16),
-               o_lin = o_result + al64(((size_t)n_ranges + 1) * 8), o_maps = o_lin + al64(n_pieces), o_perm = o_maps + al64(n_pieces * 16),
-               o_stream = o_perm + al64(n_pieces * 256), total = o_stream + al64(n_max) + 64;
+  ScratchLayout lay(up.size() * 8);   // the ranges first
+  const size_t o_names = lay.take((size_t)nc * 4 + 4), o_plan = lay.take(ne * 16), o_lens = lay.take(ne * 4), o_offs = lay.take((ne + 1) * 8),
+               o_blk = lay.take((ne / 256 + 2) * 8), o_bounds = lay.take((size_t)n_ranges * 16), o_result = lay.take(((size_t)n_ranges + 1) * 8),
+               o_lin = lay.take(n_pieces), o_maps = lay.take(n_pieces * 16), o_perm = lay.take(n_pieces * 256), o_stream = lay.take(n_max);
   hipStream_t s = c->stream;
   ScratchBlk dblk{c};
-  HIPCHK(c, blk_take(c, total, false, &dblk.p, &dblk.cap));
+  HIPCHK(c, blk_take(c, lay.total() + 64, false, &dblk.p, &dblk.cap));
   uint8_t* d = (uint8_t*)dblk.p;
   HIPCHK(c, hipMemcpyAsync(d, up.data(), up.size() * 8, hipMemcpyHostToDevice, s));
   if (nc) HIPCHK(c, hipMemcpyAsync(d + o_names, name_len.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));

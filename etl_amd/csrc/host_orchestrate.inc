@@ -14,9 +14,11 @@ int32_t download_batch(etlg_ctx* c, etlg_batch* b) {
   etlg_batch_view& v = b->v;
   const size_t n = (size_t)v.n_events;
   // layout of the pinned block: 8-byte arrays first, then 4-byte, then bytes (every part 64-byte aligned)
-  const size_t o_start = 0, o_commit = o_start + al64(n * 8), o_ord = o_commit + al64(n * 8), o_body = o_ord + al64(n * 8);
-  const size_t o_table = o_body + al64(n * 8), o_slot = o_table + al64(n * 4), o_kind = o_slot + al64(n * 4), o_flags = o_kind + al64(n);
-  const size_t o_fixed = o_flags + al64(n), o_heap = o_fixed + al64((size_t)v.fixed_bytes), total = o_heap + al64((size_t)v.heap_bytes) + 64;
+  ScratchLayout lay;
+  const size_t o_start = lay.take(n * 8), o_commit = lay.take(n * 8), o_ord = lay.take(n * 8), o_body = lay.take(n * 8);
+  const size_t o_table = lay.take(n * 4), o_slot = lay.take(n * 4), o_kind = lay.take(n), o_flags = lay.take(n);
+  const size_t o_fixed = lay.take((size_t)v.fixed_bytes), o_heap = lay.take((size_t)v.heap_bytes);
+  const size_t total = lay.total() + 64;
   if (b->h_arena_cap < total) {
     if (b->h_arena) { c->harena_pool.emplace_back(b->h_arena, b->h_arena_cap); b->h_arena = nullptr; b->h_arena_cap = 0; }
     // smallest pooled block that fits, else a new one (rounded up so that similar batches can share it)

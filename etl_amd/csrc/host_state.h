@@ -33,6 +33,7 @@
 
 #include "../../include/etlg.h"
 #include "dev_types.h"
+#include "scratch_layout.h"
 
 using namespace etlg;
 
@@ -42,7 +43,7 @@ extern "C" void etlg_k_ctl_pick(const uint8_t* tags, uint32_t nframes, uint32_t*
 extern "C" void etlg_k_shard_cuts(const uint8_t* tags, const uint32_t* offs, uint32_t nframes, uint32_t n_shards, uint32_t* cuts, hipStream_t s);
 extern "C" void etlg_k_ctl_span(const uint8_t* tags, uint32_t nframes, const uint32_t* list, uint32_t n, uint32_t* span, hipStream_t s);
 extern "C" void etlg_k_ctl_gather(const uint8_t* in, const uint32_t* offs, const uint32_t* frames, uint32_t nkeep, uint32_t* lens, const uint32_t* out_offs, uint8_t* out, hipStream_t s);
-extern "C" void etlg_k_launch_fused(int blk, const DecParams* p, const void* q, hipStream_t s);
+extern "C" void etlg_k_launch_fused(int blk, const DecParams* p, const FusedParams* q, hipStream_t s);
 extern "C" int etlg_k_fused_set_lds(void);
 extern "C" void etlg_k_launch_bounds(const uint8_t* in, uint64_t len, uint32_t* offs, uint32_t offs_cap, void* scratch, uint32_t* result, uint32_t* hints, uint32_t* hflag,
                                      int sequential, hipStream_t s);
@@ -52,34 +53,31 @@ extern "C" uint32_t etlg_k_copy_bytes_per_row(uint32_t ncols);
 extern "C" int etlg_k_copy_set_lds(void);
 extern "C" void etlg_k_launch_copy(const uint8_t* rows, const uint32_t* row_offs, uint32_t nrows, uint64_t rows_len, uint32_t ncols,
                                    uint32_t rel_id, uint8_t* out, uint32_t* out_offs, uint32_t lds_bytes, int lane_per_byte, const DecParams* dec, hipStream_t s);
-extern "C" void etlg_k_launch_cells(const DecParams* p, const void* q, hipStream_t s);
-extern "C" void etlg_k_launch_plan(const DecParams* p, const void* q, hipStream_t s);
-extern "C" void etlg_k_launch_plan_pre(const DecParams* p, const void* q, hipStream_t s);
+extern "C" void etlg_k_launch_cells(const DecParams* p, const FusedParams* q, hipStream_t s);
+extern "C" void etlg_k_launch_plan(const DecParams* p, const PlanParams* q, hipStream_t s);
+extern "C" void etlg_k_launch_plan_pre(const DecParams* p, const PlanParams* q, hipStream_t s);
 extern "C" uint32_t etlg_k_plan_pre_group_log(void);
 extern "C" int etlg_k_plan_set_lds(void);
-extern "C" void etlg_k_col_select(const void* sel, hipStream_t s);
-extern "C" void etlg_k_col_cdc(const void* job, hipStream_t s);
-extern "C" void etlg_k_col_fixed(const void* job, hipStream_t s);
+extern "C" void etlg_k_col_select(const ColSel* sel, hipStream_t s);
+extern "C" void etlg_k_col_cdc(const CdcJob* job, hipStream_t s);
 extern "C" uint32_t etlg_k_col_pack_max(void);
-extern "C" void etlg_k_col_fixed_pack(const void* jobs, uint32_t n, hipStream_t s);
-extern "C" void etlg_k_col_var_pack(const void* jobs, uint32_t n, unsigned long long* const* blk, int64_t* const* offs, unsigned long long* const* tot, int step, hipStream_t s);
+extern "C" void etlg_k_col_fixed_pack(const ColJob* jobs, uint32_t n, hipStream_t s);
+extern "C" void etlg_k_col_var_pack(const ColJob* jobs, uint32_t n, unsigned long long* const* blk, int64_t* const* offs, unsigned long long* const* tot, int step, hipStream_t s);
 extern "C" void etlg_k_scan_lens(const uint32_t* lens, uint64_t n, unsigned long long* blk, int64_t* offsets, hipStream_t s);
-extern "C" void etlg_k_col_list(const void* job, unsigned long long* blk, int64_t* offsets, int step, hipStream_t s);
-extern "C" void etlg_k_size_hints(const void* job, hipStream_t s);
-extern "C" void etlg_k_cuts(const void* job, int step, uint64_t emit_bound, hipStream_t s);
-extern "C" void etlg_k_payload_frames(const void* job, hipStream_t s);
-extern "C" void etlg_k_payload_events(const void* job, hipStream_t s);
+extern "C" void etlg_k_col_list(const ColJob* job, unsigned long long* blk, int64_t* offsets, int step, hipStream_t s);
+extern "C" void etlg_k_size_hints(const HintJob* job, hipStream_t s);
+extern "C" void etlg_k_cuts(const CutJob* job, int step, uint64_t emit_bound, hipStream_t s);
+extern "C" void etlg_k_payload_frames(const PayJob* job, hipStream_t s);
+extern "C" void etlg_k_payload_events(const PayJob* job, hipStream_t s);
 extern "C" void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows, unsigned long long* rows_out, hipStream_t s);
-extern "C" void etlg_k_rowbinary(const void* job, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, int step, hipStream_t s);
-extern "C" void etlg_k_col_var(const void* job, unsigned long long* blk, int64_t* offsets, int step, hipStream_t s);
+extern "C" void etlg_k_rowbinary(const RbJob* job, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, int step, hipStream_t s);
 extern "C" int etlg_k_cells_set_lds(void);
 extern "C" uint32_t etlg_k_cells_table_bytes(uint32_t maxc);
-extern "C" uint32_t etlg_k_copy_cells_table_bytes(uint32_t maxc);
 extern "C" uint32_t etlg_k_copy_cells_lds(uint32_t maxc, uint32_t window);
-extern "C" void etlg_k_launch_copy_cells(const DecParams* p, const void* q, hipStream_t s);
+extern "C" void etlg_k_launch_copy_cells(const DecParams* p, const FusedParams* q, hipStream_t s);
 extern "C" uint32_t etlg_k_cells_maxc(void);
-extern "C" void etlg_k_launch_rows(const DecParams* p, const void* q, hipStream_t s);
-extern "C" void etlg_k_finish(const void* job, unsigned long long* blk, int64_t* offsets, int step, hipStream_t st);
+extern "C" void etlg_k_launch_rows(const DecParams* p, const FusedParams* q, hipStream_t s);
+extern "C" void etlg_k_finish(const FinJob* job, unsigned long long* blk, int64_t* offsets, int step, hipStream_t st);
 extern "C" int etlg_k_rows_set_lds(void);
 extern "C" int etlg_k_rows_waves(void);
 extern "C" int etlg_k_rows_waves_per_simd(void);
@@ -92,7 +90,7 @@ extern "C" uint32_t etlg_k_cells_lds_floor(uint32_t maxc);
 extern "C" uint32_t etlg_k_cells_static_lds(uint32_t maxc);
 extern "C" uint32_t etlg_k_copy_cells_static_lds(uint32_t maxc);
 extern "C" void etlg_k_launch_chk_cells(const DecParams* p, uint32_t maxc, uint32_t ev_bound, hipStream_t s);
-extern "C" void etlg_k_fingerprints(const void* job, unsigned long long* blk, hipStream_t s);
+extern "C" void etlg_k_fingerprints(const FpJob* job, unsigned long long* blk, hipStream_t s);
 extern "C" uint32_t etlg_k_fp_chunk_bytes(void);
 
 constexpr int kFused = 7;  // profiling slot of the fused kernel
@@ -231,8 +229,6 @@ struct ControlState {  // everything a failed batch must be able to roll back
   std::map<uint32_t, CacheEntry> cache;
   size_t n_slots = 0;
 };
-
-inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }   // the parts of a shared block start at multiples of 64 bytes
 
 struct DevBuf {
   void* p = nullptr; size_t cap = 0;

@@ -399,16 +399,8 @@ __global__ __launch_bounds__(kBlock) void k_payf_frames(PayJob j) {
 // one workgroup: the tiles' counts become the counts in front of each tile (both halves of the word at once: neither reaches 2^30)
 __global__ __launch_bounds__(kBlock) void k_payf_scan(PayJob j) {
   __shared__ uint64_t lds64[4];
-  uint64_t carry = 0;
-  for (uint32_t t0 = 0; t0 < j.n_tiles; t0 += kBlock) {
-    const uint32_t t = t0 + threadIdx.x;
-    const bool on = t < j.n_tiles;
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl64(on ? j.tcnt[t] : 0, lds64, &tot);
-    if (on) j.tcnt[t] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) j.hdr[PAY_H_COUNTS] = carry;
+  const uint64_t total = carry_scan64(j.tcnt, j.n_tiles, 1, lds64);
+  if (threadIdx.x == 0) j.hdr[PAY_H_COUNTS] = total;
 }
 
 __global__ __launch_bounds__(kBlock) void k_payf_list(PayJob j) {
@@ -489,8 +481,8 @@ void etlg_k_ctl_gather(const uint8_t* in, const uint32_t* offs, const uint32_t* 
 
 // etlg_batch_payload, frame side: hdr and hist are zero, f_tag is on its way on the same stream (classify_begin); a table-copy batch has
 // neither ordinals nor Begins and stops behind the first launch
-void etlg_k_payload_frames(const void* jv, hipStream_t s) {
-  const PayJob j = *(const PayJob*)jv;
+void etlg_k_payload_frames(const PayJob* jv, hipStream_t s) {
+  const PayJob j = *jv;
   if (!j.n_tiles) return;
   hipLaunchKernelGGL(k_payf_frames, dim3(j.n_tiles), dim3(kBlock), 0, s, j);
   if (j.copy) return;

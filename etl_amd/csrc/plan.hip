@@ -926,13 +926,11 @@ extern "C" {
 
 using namespace etlg;
 
-void etlg_k_launch_plan_pre(const DecParams* p, const void* qv, hipStream_t s) {
-  const PlanParams* q = (const PlanParams*)qv;
+void etlg_k_launch_plan_pre(const DecParams* p, const PlanParams* q, hipStream_t s) {
   hipLaunchKernelGGL(k_plan_pre, dim3((q->ntiles + (1u << kPreGroupLog) - 1u) >> kPreGroupLog), dim3(kPreWaves * 64), 0, s, *p, *q);
 }
 
-void etlg_k_launch_plan(const DecParams* p, const void* qv, hipStream_t s) {
-  const PlanParams* q = (const PlanParams*)qv;
+void etlg_k_launch_plan(const DecParams* p, const PlanParams* q, hipStream_t s) {
   // two tiles per wave whenever a row fits 8 dwords (its image then needs no LDS beyond the window); ETLG_PLAN_DBG bit 9 = one tile per wave
   if (q->lds_bytes == q->rows_off && q->max_row_dw <= 8u && !(q->dbg & 512u)) {
     if (q->max_row_dw <= 6u) hipLaunchKernelGGL(k_plan2<6>, dim3((q->ntiles + 1) / 2), dim3(64), q->lds_bytes, s, *p, *q);

@@ -13,7 +13,6 @@ namespace etlg {
 
 // ---- ClickHouse RowBinary (crates/etl-destinations/src/clickhouse/encoding.rs:58-83 which wire type a Cell becomes,
 // :188-283 the byte format; core.rs:96-114 the trailing CDC columns). One thread per row, run twice: lengths, then bytes.
-enum : uint32_t { RB_E_NULL = 1, RB_E_DATE_RANGE = 2, RB_E_HOST_CELL = 3, RB_E_BQ_NUMERIC_SCALE = 4 /* and the json integer rule: one report */, RB_E_JSON = 5, RB_E_BQ_ARRAY_NULL = 6 };
 constexpr int32_t kDate32Min = -25567, kDate32Max = 120529;   // 1900-01-01 .. 2299-12-31 (encoding.rs:147-173)
 
 // A json cell as the sinks' `j.to_string()`: `head(len)` writes what goes in front of the string (its varint length). The text is
@@ -492,7 +491,6 @@ DEV uint32_t typed_array(S& s, const u8* h) {
 // (escaped once by the host: RbJob.nd_keys), its value and a ',' — the trailing CDC pair always follows, so the bytes are serde_json's.
 // Rows: Insert, the new row of a full Update, the old row of a Delete — only the identity columns for a key image (core.rs:345-438,
 // :572-608). Errors are the sink's Error::Encoding (non-finite floats, numeric NaN / Infinity); the host turns the codes into them.
-enum : uint32_t { ND_E_FLOAT_NAN = 7, ND_E_FLOAT_INF = 8, ND_E_FLOAT_NINF = 9, ND_E_NUM_NAN = 10, ND_E_NUM_INF = 11 };
 
 // serde_json's escape table (format_escaped_str): '"' '\\' and the bytes below 0x20 are escaped, everything else is raw
 DEV uint32_t nd_esc_extra(uint32_t c) {
@@ -658,8 +656,8 @@ DEV uint32_t nd_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
 // ---- DuckLake SQL literals (cell_to_sql_literal, crates/etl-destinations/src/ducklake/encoding.rs:366-612): the text every row the
 // DuckLake sink writes goes through — `(lit, lit, ...)` per upserted row (table_row_to_sql_literal_ref, hashed into the batch identity
 // and inserted as VALUES text) and `"col" = lit AND "col" IS NULL` per row image it deletes / matches by (delete_predicate_from_row,
-// batches.rs:1229-1316). RbJob.dl_what says which: 0 tuples, 1 predicates over the identity columns, 2 predicates over the primary-key
-// columns (a table-copy batch). Records carry no separator; the sink itself has no encoding error on this path.
+// batches.rs:1229-1316). RbJob.dl_what says which: DL_ROW_TUPLES, DL_ROW_PRED_IDENT, DL_ROW_PRED_PK (a table-copy
+// batch). Records carry no separator; the sink itself has no encoding error on this path.
 //
 // quote_literal is pg_escape 0.1.1, RESTATED FROM THE CRATE'S DOCUMENTATION (its source is not vendored with the reference and no
 // reference test pins more than the plain arm): `'` is doubled; a text that holds a backslash has every backslash doubled and the
@@ -792,15 +790,15 @@ struct DlArr {
   template <class S> static DEV void json(S& s, const u8* t, uint32_t n) { (void)dl_json(s, t, n, false); }
 };
 
-// UPD: ETLG_DL_UPDATES (dl_what 3, an instantiation of its own so that the tuples and the predicates compile as they did without it): the
+// UPD: ETLG_DL_UPDATES (DL_ROW_UPDATES, an instantiation of its own so that the tuples and the predicates compile as they did without it): the
 // SET clause of a partial new row (update_assignments_from_partial_row joined by ", ": every cell that is not MISSING), and behind it — the
 // row marked kPbSecond — the predicate of the same event
 template <bool JS, bool UPD = false, class S, class M>
 DEV uint32_t dl_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_hi, M&& mark) {   // 0, or column << 8 | code
   const uint64_t rb = j.row_base[r], base = rb & kPbBase;
   const bool set = UPD && !(rb & kPbSecond);
-  const bool pred = j.dl_what != 0 && !set, keyrow = (rb & kPbKey) != 0;   // keyrow: the image has the key layout (the identity cells only)
-  const uint32_t kbit = j.dl_what == 2 ? 4u : 1u;                   // which columns a predicate takes: identity / primary key
+  const bool pred = j.dl_what != DL_ROW_TUPLES && !set, keyrow = (rb & kPbKey) != 0;   // keyrow: the image has the key layout (the identity cells only)
+  const uint32_t kbit = j.dl_what == DL_ROW_PRED_PK ? 4u : 1u;                 // which columns a predicate takes: identity / primary key
   bool first = true;                                                // no predicate / present column in front of this lane's columns?
   if (pred) for (uint32_t i = 0; i < c_lo; i++) if (j.kcols[i] & kbit) first = false;
   if constexpr (UPD) { if (set) for (uint32_t i = 0; i < c_lo; i++) if (((j.fixed[base + i / 4] >> (2 * (i % 4))) & 3u) != ETLG_CELL_MISSING) first = false; }
@@ -854,7 +852,7 @@ DEV uint32_t dl_row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_
 // Arrow columns). A format per sink, so that no kernel carries another sink's arm; RowBinary and protobuf share theirs (j.format).
 template <bool JS> struct RbPbFormat {
   template <class S, class M> static DEV uint32_t row(const RbJob& j, uint64_t r, S& s, uint32_t c_lo, uint32_t c_hi, M&& mark) {
-    return j.format ? pb_row<JS>(j, r, s, c_lo, c_hi, mark) : rb_row<JS>(j, r, s, c_lo, c_hi, mark);
+    return j.format != FMT_ROWBINARY ? pb_row<JS>(j, r, s, c_lo, c_hi, mark) : rb_row<JS>(j, r, s, c_lo, c_hi, mark);
   }
 };
 template <bool JS> struct NdFormat {      // Snowflake NDJSON
@@ -888,8 +886,8 @@ __global__ __launch_bounds__(256) void k_rb_lens(RbJob j, unsigned long long* bl
     // first failing row in event order, rows with a date out of range before all others (bit 62 clear)
     // (and a json cell that is not JSON before those: the reference's decode fails before any sink sees a row)
     if (e) {
-      const unsigned long long rank = (e & 0xFFu) == RB_E_JSON ? 0ull : ((e & 0xFFu) == RB_E_DATE_RANGE || j.format) ? 1ull << 61 : 1ull << 62;
-      atomicMin(j.err, rank | (unsigned long long)((r << 24) | e)); c.n = 0;
+      const unsigned long long rank = (e & 0xFFu) == RB_E_JSON ? kRbRankDecode : ((e & 0xFFu) == RB_E_DATE_RANGE || j.format != FMT_ROWBINARY) ? kRbRankEarly : kRbRankLate;
+      atomicMin(j.err, rb_report_pack(rank, r, e)); c.n = 0;
     }
     j.lens[r] = c.n;
   }

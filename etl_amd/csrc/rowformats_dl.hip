@@ -5,5 +5,5 @@
 
 extern "C" void etlg_k_rows_ducklake(const etlg::RbJob* j, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, int step, hipStream_t st) {
   using namespace etlg;
-  if (j->dl_what == 3u) rb_launch_js<DlUpdFormat>(*j, blk, offsets, tot, step, st); else rb_launch_js<DlFormat>(*j, blk, offsets, tot, step, st);
+  if (j->dl_what == DL_ROW_UPDATES) rb_launch_js<DlUpdFormat>(*j, blk, offsets, tot, step, st); else rb_launch_js<DlFormat>(*j, blk, offsets, tot, step, st);
 }

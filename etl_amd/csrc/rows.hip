@@ -744,8 +744,7 @@ static int rows_nw() {   // waves per tile: ETLG_ROWS_NW = 2 | 4 (experiments; t
   return nw;
 }
 
-void etlg_k_launch_rows(const DecParams* p, const void* qv, hipStream_t s) {
-  const FusedParams* q = (const FusedParams*)qv;
+void etlg_k_launch_rows(const DecParams* p, const FusedParams* q, hipStream_t s) {
   if (rows_nw() == 2) hipLaunchKernelGGL((k_rows<2>), dim3(q->ntiles), dim3(2 * 64), q->lds_bytes, s, *p, *q);
   else hipLaunchKernelGGL((k_rows<4>), dim3(q->ntiles), dim3(4 * 64), q->lds_bytes, s, *p, *q);
 }

@@ -1,0 +1,41 @@
+// How the hand-off calls carve a scratch block: a running offset that hands out 64-byte aligned parts (parts that overlap would be a GPU fault, so no
+// caller adds offsets by hand), and the two layouts with the most links. Plain C++, no HIP: tests/native/scratch_layout_check.cpp includes this header alone.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }   // the parts of a shared block start at multiples of 64 bytes
+
+struct ScratchLayout {
+  size_t off;
+  explicit ScratchLayout(size_t first = 0) : off(al64(first)) {}   // `first`: the bytes of the part at offset 0
+  size_t take(size_t bytes) { const size_t at = off; off += al64(bytes); return at; }   // the next part: where it starts. take(0) takes nothing
+  size_t skip(size_t bytes) { const size_t at = off; off += bytes; return at; }         // the few links that are not al64 (a fixed 64-byte record)
+  size_t total() const { return off; }   // (the callers allocate 64 bytes of slack behind it)
+};
+
+// etlg_batch_cuts, the block of its first stop: hdr (5 words) | tsum | tinc (a word per tile) | q (n + 1 words) | the hints of the whole
+// batch when the library evaluates them itself (own_hints; `hints` is then where k_size_hints writes)
+struct CutsLayout { size_t hdr, tsum, tinc, q, hints, total; };
+inline CutsLayout cuts_layout(uint64_t n, uint64_t n_tiles, uint64_t n_events, bool own_hints) {
+  ScratchLayout l; CutsLayout o{};
+  o.hdr = l.take(5 * 8); o.tsum = l.take(n_tiles * 8); o.tinc = l.take(n_tiles * 8); o.q = l.take((n + 1) * 8);
+  o.hints = own_hints ? l.take(n_events * 8) : l.total();
+  o.total = l.total();
+  return o;
+}
+
+// etlg_batch_payload: hdr | hist | bounds (the three the call reads back and uploads) | the frame side | the event side. ev_bytes and sums
+// live here unless they go straight to the caller's device memory; the range sums' parts exist only when sums are asked for.
+struct PayLayout { size_t hdr, hist, bounds, fbytes, tcnt, r2f, brank, etb, evb, tsum, pb, pr, cuts, sums, total; };
+inline PayLayout payload_layout(uint32_t hdr_words, uint32_t n_hist, uint64_t n_recv, uint64_t nf, uint64_t ne, uint32_t n_tiles, uint32_t n_etiles, uint64_t n_cuts,
+                                bool evb_here, bool want_sums, bool cuts_here, bool sums_here) {
+  ScratchLayout l; PayLayout o{};
+  o.hdr = l.take((size_t)hdr_words * 8); o.hist = l.take((size_t)n_hist * 8); o.bounds = l.take(64 * 8);
+  o.fbytes = l.take(n_recv * 4); o.tcnt = l.take((size_t)n_tiles * 8); o.r2f = l.take(nf * 4); o.brank = l.take(nf * 4); o.etb = l.take((size_t)n_etiles * 8);
+  o.evb = l.take(evb_here ? ne * 4 : 0); o.tsum = l.take(want_sums ? (size_t)n_etiles * 48 : 0);
+  o.pb = l.take(want_sums ? 3 * (ne + 1) * 8 : 0); o.pr = l.take(want_sums ? 3 * (ne + 1) * 4 : 0);
+  o.cuts = l.take(want_sums && cuts_here ? n_cuts * 8 : 0); o.sums = l.take(want_sums && sums_here ? (n_cuts + 1) * 64 : 0);
+  o.total = l.total();
+  return o;
+}
