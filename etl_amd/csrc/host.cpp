@@ -1,9 +1,11 @@
-// Host side of libetl_gfx950.so: the C ABI of include/etlg.h. One translation unit in four files —
+// Host side of libetl_gfx950.so: the C ABI of include/etlg.h. One translation unit in these files —
 //   host_state.h          context, batch and pool structures, kernel launchers
 //   host_control.inc      control plane (schemas, Relation / DDL messages)
 //   host.cpp              this file: error helpers, pools, lifecycle, side inputs, scan / tags / control-stream calls, etlg_decode and the
 //                         ASYNC chain (decode_tail), batch calls
-//   host_handoff.inc      etlg_batch_columns / _rowbinary / _protobuf / _size_hints
+//   host_handoff.inc      what the hand-off calls share; etlg_batch_size_hints / _cuts / _payload / _finish_cells
+//   host_handoff_columns.inc   etlg_batch_columns / _iceberg / _ducklake_copy
+//   host_handoff_rows.inc      etlg_batch_rowbinary / _protobuf / _ndjson / _duckdb
 //   host_orchestrate.inc  side inputs, outputs, kernel ladder, control pre-pass, finish_batch
 #include "host_state.h"
 
@@ -1392,7 +1394,9 @@ void etlg_batch_free(etlg_batch* b) {
   delete b;
 }
 
-#include "host_handoff.inc"   // columnar hand-off: etlg_batch_columns / _rowbinary / _protobuf / _size_hints (columns.hip, rowformats.hip, finish.hip)
+#include "host_handoff.inc"           // hand-off: what the calls share; etlg_batch_size_hints / _cuts / _payload / _finish_cells, etlg_ducklake_fingerprints (finish.hip, fingerprint.hip)
+#include "host_handoff_columns.inc"   // etlg_batch_columns / _iceberg / _ducklake_copy in named steps (columns.hip)
+#include "host_handoff_rows.inc"      // etlg_batch_rowbinary / _protobuf / _ndjson / _duckdb in named steps (rowformats.hip, rowformats_dl.hip)
 
 }  // extern "C"
 

@@ -1,5 +1,5 @@
 // Context / batch / pool structures of the host side of libetl_gfx950.so and the launchers of the kernels (host.cpp and its parts).
-// Part of ONE translation unit: host.cpp includes this header and the three .inc files below it in order; they share the
+// Part of ONE translation unit: host.cpp includes this header and the .inc files below it in order; they share the
 // context structure and the helpers of the anonymous namespace.
 #pragma once
 // Host side of libetl_gfx950.so: the C ABI of include/etlg.h.
@@ -34,6 +34,7 @@
 #include "../../include/etlg.h"
 #include "dev_types.h"
 #include "scratch_layout.h"
+#include "handoff_plan.h"   // SlotHost, and what the hand-off builders plan on the host alone
 
 using namespace etlg;
 
@@ -213,13 +214,6 @@ uint32_t slot_bytes(int32_t cls) {
 struct StoredCol { std::string name; uint32_t type_oid; int32_t typmod; int32_t attnum; bool nullable; bool pk; };
 struct StoredSchema { uint32_t table_id; uint64_t snapshot; std::string nsp, name; std::vector<StoredCol> cols; };
 using SchemaPtr = std::shared_ptr<const StoredSchema>;
-
-struct SlotHost {  // one ReplicatedTableSchema instance
-  etlg_slot_desc desc;
-  std::vector<etlg_slot_col> cols;
-  std::vector<uint8_t> pk;   // per replicated column: a primary-key column of the stored schema (ColumnSchema::primary_key)
-  int identity_type = 0;   // ReplicatedTableSchema::infer_identity_type (schema.rs:686-721): 0 Missing, 1 PrimaryKey, 2 Full, 3 AlternativeKey
-};
 
 struct CacheEntry { uint32_t kind; uint64_t snapshot; int32_t slot; };  // kind: 1 waiting, 2 ready
 struct TState { int32_t kind; uint64_t lsn; };

@@ -553,6 +553,19 @@ void lazy_poll_progress() {
 }
 }  // namespace
 
+// ETLG_SIMT_CALLS (simt.h). launch: a = grid x << 32 | grid y, b = block, c = dynamic LDS bytes; copies: a = bytes, b = hipMemcpyKind; memset: a = bytes, b = value
+void call_log(const char* what, unsigned long long a, unsigned long long b, unsigned long long c, const char* kernel) {
+  static FILE* const f = [] { const char* p = getenv("ETLG_SIMT_CALLS"); return p && *p ? fopen(p, "a") : (FILE*)nullptr; }();
+  if (!f) return;
+  static const char* const dir[] = {"h2h", "h2d", "d2h", "d2d", "default"};
+  if (kernel) fprintf(f, "%s %s grid %llux%llu block %llu lds %llu\n", what, kernel, a >> 32, a & 0xFFFFFFFFull, b, c);
+  else if (what[0] == 'm' && what[3] == 'c') fprintf(f, "%s %llu %s\n", what, a, dir[b < 5 ? b : 4]);   // memcpy, memcpy_async
+  else if (what[0] == 'm' && what[3] == 's') fprintf(f, "%s %llu value %llu\n", what, a, b);           // memset_async
+  else if (a) fprintf(f, "%s %llu\n", what, a);
+  else fprintf(f, "%s\n", what);
+  fflush(f);
+}
+
 bool streams_lazy() { return lazy_mode(); }
 int streams_mode() { return !lazy_mode() ? 0 : g_random_streams ? 2 : 1; }
 

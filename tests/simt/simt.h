@@ -92,12 +92,16 @@ void host_unregister(void* p);
 bool host_is_pinned(const void* p);
 void memcpy_async(void* d, const void* s, size_t n, int kind, void* stream);
 void memset_async(void* d, int v, size_t n, void* stream);
+// ETLG_SIMT_CALLS=<path> (read once, off by default): one line per runtime call the host code makes is appended to the file — the call's name, its
+// byte count or grid x block, a copy's direction, a launch's kernel as the launch site names it; no pointer values, so two builds that make the same calls write the same file
+void call_log(const char* what, unsigned long long a = 0, unsigned long long b = 0, unsigned long long c = 0, const char* kernel = nullptr);
 
 template <class... KArgs, class... Args>
-void launch(void (*k)(KArgs...), dim3 g, dim3 b, size_t lds, void* stream, Args&&... args) {
+void launch(const char* name, void (*k)(KArgs...), dim3 g, dim3 b, size_t lds, void* stream, Args&&... args) {
   using Tup = std::tuple<std::decay_t<KArgs>...>;
   struct Ctx { void (*k)(KArgs...); Tup t; uint32_t grid, block, gx; size_t lds; };
   Ctx* c = new Ctx{k, Tup(std::forward<Args>(args)...), g.x * g.y, b.x, g.x, lds};   // the arguments are captured by value at launch, as on the GPU
+  call_log("launch", (unsigned long long)g.x << 32 | g.y, b.x, lds, name);
   stream_enqueue(stream, [](void* p) { Ctx* c = (Ctx*)p; run_grid(c->grid, c->block, c->lds, [](void* q) { Ctx* c2 = (Ctx*)q; std::apply(c2->k, c2->t); }, c, c->gx); },
                  c, [](void* p) { delete (Ctx*)p; });
 }
@@ -108,7 +112,7 @@ void launch(void (*k)(KArgs...), dim3 g, dim3 b, size_t lds, void* stream, Args&
 #define blockIdx (simt::bidx())
 #define blockDim (simt::bdim())
 #define gridDim (simt::gdim())
-#define hipLaunchKernelGGL(k, g, b, lds, stream, ...) simt::launch(k, g, b, lds, (void*)(stream), __VA_ARGS__)
+#define hipLaunchKernelGGL(k, g, b, lds, stream, ...) simt::launch(#k, k, g, b, lds, (void*)(stream), __VA_ARGS__)
 
 // ---------------------------------------------------------------- collectives
 // Every collective is a function-like macro that stamps its expansion with __COUNTER__: the rendezvous is keyed
@@ -197,23 +201,24 @@ static inline const char* hipGetErrorString(hipError_t e) { return e == hipSucce
 // (ETLG_SIMT_MALLOC_POISON=1: device memory starts as 0xCD bytes instead of zeros — hipMalloc promises nothing, and a pool that hands a block
 // to its second user certainly holds old data)
 static inline hipError_t hipMalloc(void** p, size_t n) {
+  simt::call_log("malloc", n);
   static const bool poison = getenv("ETLG_SIMT_MALLOC_POISON") != nullptr;
   *p = poison ? malloc(n + SIMT_MALLOC_SLACK) : calloc(1, n + SIMT_MALLOC_SLACK);
   if (*p && poison) memset(*p, 0xCD, n + SIMT_MALLOC_SLACK);
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
-static inline hipError_t hipFree(void* p) { simt::device_sync(); free(p); return hipSuccess; }   // (hipFree synchronises the device)
-static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { *p = calloc(1, n + (SIMT_MALLOC_SLACK ? 64 : 0)); if (*p) simt::host_register(*p, n + (SIMT_MALLOC_SLACK ? 64 : 0)); return *p ? hipSuccess : hipErrorOutOfMemory; }
-static inline hipError_t hipHostFree(void* p) { simt::device_sync(); simt::host_unregister(p); free(p); return hipSuccess; }
+static inline hipError_t hipFree(void* p) { simt::call_log("free"); simt::device_sync(); free(p); return hipSuccess; }   // (hipFree synchronises the device)
+static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { simt::call_log("host_malloc", n); *p = calloc(1, n + (SIMT_MALLOC_SLACK ? 64 : 0)); if (*p) simt::host_register(*p, n + (SIMT_MALLOC_SLACK ? 64 : 0)); return *p ? hipSuccess : hipErrorOutOfMemory; }
+static inline hipError_t hipHostFree(void* p) { simt::call_log("host_free"); simt::device_sync(); simt::host_unregister(p); free(p); return hipSuccess; }
 // hipMemcpy: the copy runs on the null stream and the host waits for it (the library's streams are non-blocking: nothing else is waited for)
-static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { simt::memcpy_async(d, s, n, (int)k, nullptr); simt::stream_sync(nullptr); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) { simt::memcpy_async(d, s, n, (int)k, (void*)st); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { simt::memset_async(d, v, n, (void*)st); return hipSuccess; }
+static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { simt::call_log("memcpy", n, k); simt::memcpy_async(d, s, n, (int)k, nullptr); simt::stream_sync(nullptr); return hipSuccess; }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) { simt::call_log("memcpy_async", n, k); simt::memcpy_async(d, s, n, (int)k, (void*)st); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { simt::call_log("memset_async", n, (unsigned)v); simt::memset_async(d, v, n, (void*)st); return hipSuccess; }
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)calloc(1, 8); return hipSuccess; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = 0; return hipSuccess; }
 static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)calloc(1, 8); return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t s) { simt::stream_destroy((void*)s); free(s); return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t s) { simt::stream_sync((void*)s); return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t s) { simt::call_log("stream_sync"); simt::stream_sync((void*)s); return hipSuccess; }
 static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)simt::event_create(); return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s = nullptr) { simt::event_record((void*)e, (void*)s); return hipSuccess; }
 enum { hipEventDisableTiming = 2 };

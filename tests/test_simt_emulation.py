@@ -80,6 +80,8 @@ _JOBS = {
     "finish_pass": _pytest_job(["tests/test_gpu_finish.py"], 600),
     "round6_lazy_streams": _pytest_job(["tests/test_gpu_finish.py", "tests/test_gpu_async.py", "-k", "finish or behind_its_boundary_scan or without_a_sidecar or result_ring"], 900, streams="lazy"),
     "hand_off": _pytest_job(["tests/test_gpu_columns.py", "tests/test_gpu_rowbinary.py", "tests/test_gpu_size_hints.py", "tests/test_gpu_protobuf.py", "tests/test_arrow_kats.py", "tests/test_gpu_json_display.py"], 600),
+    "hand_off_lazy": _pytest_job(["tests/test_gpu_columns.py", "tests/test_gpu_rowbinary.py", "tests/test_gpu_protobuf.py", "tests/test_gpu_ndjson.py", "tests/test_gpu_duckdb.py",
+                                  "tests/test_gpu_duckdb_updates.py", "tests/test_gpu_iceberg.py", "tests/test_gpu_copy_sinks.py", "-k", "not full_size and not synthetic"], 600, streams="lazy"),
     "lane_order": _pytest_job(["tests/test_gpu_copy.py", "tests/test_gpu_rowbinary.py", "tests/test_gpu_protobuf.py",
                                "-k", "not device_resident and not device_input and not 16777216 and not synthetic and not kat_ and not random"], 600, order="shuffle"),
     "plans_shuffled": _pytest_job(["tests/test_gpu_fixed_plan.py", "-k", "prepass or conforming or mix_in_one_launch"], 900, order="shuffle"),
@@ -120,8 +122,8 @@ def _cpus():
 # the longest runs first (alone, on one CPU each: scenarios 310 s, lazy_streams 245, shard_async 187, resident_reverse 138, then 80 s and
 # less): the suite ends soon after its longest run
 _ORDER = ["scenarios", "lazy_streams", "shard_async", "resident_reverse", "plans", "copy_scan", "lane_order", "other_compiler",
-          "round6_lazy_streams", "shim_twin", "resident_shuffle", "plans_shuffled", "finish_pass", "hand_off", "long_chains", "copy_fuzz",
-          "cell_fuzz"]
+          "round6_lazy_streams", "shim_twin", "resident_shuffle", "plans_shuffled", "hand_off_lazy", "finish_pass", "hand_off", "long_chains",
+          "copy_fuzz", "cell_fuzz"]
 assert sorted(_ORDER) == sorted(_JOBS)
 
 
@@ -276,6 +278,14 @@ def test_columnar_hand_off(emu_jobs):
     """etlg_batch_columns / etlg_batch_rowbinary (columns.hip, rowformats.hip): the Arrow-layout buffers built by the emulated kernels against
     the host hand-off of the oracle's arena, the RowBinary bytes against oracle/rowbinary.py."""
     _passed(emu_jobs, "hand_off")
+
+
+def test_hand_off_builders_with_lazy_streams_and_poisoned_memory(emu_jobs):
+    """build_columns and handoff_rows (host_handoff_columns.inc, host_handoff_rows.inc) behind all seven entry points with enqueued work
+    running as late as the HIP ordering rules allow, LDS and device allocations starting as garbage: a scratch block (the select
+    scratch, block S) or a device block given back ahead of the stop that covers it is read after it went to the next taker, and the
+    bytes differ from the oracle's. The columns, row-format, Iceberg and table-copy files, without their full-size cases (50 s alone)."""
+    _passed(emu_jobs, "hand_off_lazy")
 
 
 def test_finish_pass_typed_arrays_and_exact_floats(emu_jobs):
