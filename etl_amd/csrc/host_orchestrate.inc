@@ -9,7 +9,7 @@ int32_t download_batch(etlg_ctx* c, etlg_batch* b) {
   // The batch is complete when this runs (its result block has been read on the host), so the copies need no ordering against
   // the decode streams: they travel on a stream of their own and overlap the upload and decode of the batches issued after this
   // one (PCIe is full duplex: a host-to-host pipeline costs max(upload, download) per batch, not their sum).
-  if (!c->d2h_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
+  RC(ensure_stream(c, &c->d2h_stream));
   hipStream_t s = c->d2h_stream;
   etlg_batch_view& v = b->v;
   const size_t n = (size_t)v.n_events;
@@ -67,104 +67,109 @@ int32_t setup_scratch(etlg_ctx* c, DecParams& p, int set) {
   return ETLG_OK;
 }
 
+// "The side inputs stand": nothing the last upload was built from has changed, and it holds no epochs of some batch's own control frames.
+bool side_inputs_stand(const etlg_ctx* c) { return c->side_valid && !c->side_dirty && !c->slots_dirty && c->last_epochs.empty(); }
+
+// A set that was uploaded on the other decode stream: the first kernels of stream `s` that read it wait for the copy (SideSet::synced,
+// one bit per decode stream).
+uint32_t side_stream_bit(const etlg_ctx* c, hipStream_t s) { return 1u << ((s == c->stream2 && c->stream2) ? 1 : 0); }
+int32_t wait_for_side_upload(etlg_ctx* c, SideSet* ss, hipStream_t s) {
+  const uint32_t bit = side_stream_bit(c, s);
+  if (ss && !(ss->synced & bit)) { HIPCHK(c, hipStreamWaitEvent(s, ss->ready, 0)); ss->synced |= bit; }
+  return ETLG_OK;
+}
+
 // Side inputs of one batch: table states + the shared-table-cache timeline (`eps`: the epochs its own Relation / DDL frames
-// create) + schema slots + the fixed-width plan's tables. Re-uploaded only when they change; a change behind pending ASYNC
-// batches finishes those first (their kernels read the old copy).
-int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec>& eps) {
-  SlowScope slow_scope_build_side_inputs(c, "build_side_inputs");
-  DecParams& p = b->params;
-  hipStream_t s = c->stream;
-  auto point = [&](SideSet* ss, uint32_t n_tables, uint32_t n_epochs) {
-    const uint8_t* d = (const uint8_t*)ss->dev.p;
-    p.tables = (const DevTable*)(d + ss->o_tables); p.epochs = (const DevEpoch*)(d + ss->o_epochs); p.n_tables = n_tables; p.n_epochs = n_epochs;
-    p.slots = (const DevSlot*)(d + ss->o_slots); p.cols = (const DevCol*)(d + ss->o_cols);
-    p.n_slots = ss->n_slots; p.n_cols = ss->n_cols;
+// create) + schema slots + the fixed-width plan's tables. Re-uploaded only when they change, into a set no unfinished batch reads.
+// The steps of build_side_inputs, in its order, and what they hand to each other:
+struct SideBuild {
+  etlg_ctx* c; etlg_batch* b; const std::vector<EpochRec>& eps;
+  hipStream_t s;
+  std::vector<DevTable> tv; std::vector<DevEpoch> ev; std::vector<int32_t> live;   // the records, and the slots a frame of this batch can decode against
+  std::vector<DevSlot> ds; std::vector<DevCol> dc; std::vector<uint8_t> ce;       // slots, columns, one element-class byte per column
+  std::vector<PlanTab> pt; std::vector<uint32_t> pc;                              // the fixed-width plan's tables and column words
+  SideSet* ss = nullptr;
+
+  void point(SideSet* set, uint32_t n_tables, uint32_t n_epochs) {
+    DecParams& p = b->params;
+    const uint8_t* d = (const uint8_t*)set->dev.p;
+    p.tables = (const DevTable*)(d + set->o_tables); p.epochs = (const DevEpoch*)(d + set->o_epochs); p.n_tables = n_tables; p.n_epochs = n_epochs;
+    p.slots = (const DevSlot*)(d + set->o_slots); p.cols = (const DevCol*)(d + set->o_cols);
+    p.n_slots = set->n_slots; p.n_cols = set->n_cols;
     if (p.flags & kDecCopyRows) p.copy_slot = (int32_t)(std::lower_bound(c->last_live.begin(), c->last_live.end(), b->copy.slot) - c->last_live.begin());   // device index of the caller's slot
-    side_use(b, ss);
-  };
-  if (eps.empty() && c->side_valid && !c->side_dirty && !c->slots_dirty && c->last_epochs.empty() && !b->have_snapshot && !b->copy.active) {
-    // nothing the side inputs are built from has changed since the last upload (the common case: one call per batch)
-    point(c->side_cur, (uint32_t)c->last_tables.size(), 0u);
-    b->any_sync_done = c->last_any_sync_done;
-    return ETLG_OK;
+    side_use(b, set);
   }
-  std::map<uint32_t, DevTable> tabs;
-  auto get = [&](uint32_t id) -> DevTable& {
-    auto it = tabs.find(id);
-    if (it == tabs.end()) { DevTable t{}; t.table_id = id; t.init_slot = -1; it = tabs.emplace(id, t).first; }
-    return it->second;
-  };
-  for (auto& kv : c->states) { DevTable& t = get(kv.first); t.state_kind = (uint32_t)kv.second.kind; t.state_lsn = kv.second.lsn; }
-  const ControlState& cs0 = b->have_snapshot ? b->snapshot : c->cs;  // cache as of batch start
-  for (auto& kv : cs0.cache) { DevTable& t = get(kv.first); t.init_kind = kv.second.kind; t.init_slot = kv.second.slot; }
-  for (auto& e : eps) get(e.table_id);
-  std::vector<DevTable> tv;
-  std::vector<DevEpoch> ev;
-  for (auto& kv : tabs) {
-    DevTable t = kv.second;
-    t.ep_begin = (uint32_t)ev.size();
-    for (auto& e : eps) if (e.table_id == t.table_id) ev.push_back(e.ep);  // already in frame order
-    t.ep_end = (uint32_t)ev.size();
-    tv.push_back(t);
-  }
-  std::vector<int32_t> live;   // slots a frame of this batch can decode against
-  for (auto& t : tv) if (t.init_kind == 2u && t.init_slot >= 0) live.push_back(t.init_slot);
-  for (auto& e : ev) if (e.kind == 2u && e.slot >= 0) live.push_back(e.slot);
-  if (b->copy.active && b->copy.slot >= 0) live.push_back(b->copy.slot);
-  std::sort(live.begin(), live.end());
-  live.erase(std::unique(live.begin(), live.end()), live.end());
-  auto dev_index = [&](int32_t host_slot) -> int32_t {   // position in `live`; -1 stays -1
-    if (host_slot < 0) return host_slot;
-    return (int32_t)(std::lower_bound(live.begin(), live.end(), host_slot) - live.begin());
-  };
-  for (auto& t : tv) if (t.init_kind == 2u) t.init_slot = dev_index(t.init_slot);
-  for (auto& e : ev) if (e.kind == 2u) e.slot = dev_index(e.slot);
-  const bool same = c->side_valid && !c->slots_dirty && live == c->last_live && tv.size() == c->last_tables.size() && ev.size() == c->last_epochs.size() &&
-                    (tv.empty() || !memcmp(tv.data(), c->last_tables.data(), tv.size() * sizeof(DevTable))) &&
-                    (ev.empty() || !memcmp(ev.data(), c->last_epochs.data(), ev.size() * sizeof(DevEpoch)));
-  if (!same) {  // table states, the cache timeline or the slots changed: a new upload, into a set no unfinished batch reads
-    std::vector<DevSlot> ds;
-    std::vector<DevCol> dc;
-    build_slots(c, live, ds, dc);
-    // ---- the fixed-width plan (plan.hip): tables the apply worker owns outright, Ready for the whole batch, whose
-    //      replicated columns are all bool / int2 / int4 / int8 / oid
-    std::vector<PlanTab> pt;
-    std::vector<uint32_t> pc;
-    if (ev.empty() && c->worker == ETLG_WORKER_APPLY) {
-      for (const DevTable& t : tv) {  // tv is sorted by table id
-        if (t.state_kind != ETLG_TS_READY || t.init_kind != 2u || t.init_slot < 0 || (size_t)t.init_slot >= live.size()) continue;
-        const int32_t host_slot = live[(size_t)t.init_slot];   // (t.init_slot is the device index by now)
-        if (host_slot < 0 || (size_t)host_slot >= c->slots.size()) continue;
-        const SlotHost& sh = *c->slots[(size_t)host_slot];
-        bool ok = sh.desc.n_cols > 0;
-        for (auto& sc : sh.cols) if (!int_class(sc.type_class)) ok = false;
-        if (!ok) continue;
-        PlanTab e{};
-        e.rel_id = t.table_id; e.slot = (uint32_t)host_slot; e.n_cols = sh.desc.n_cols; e.row_dwords = sh.desc.row_bytes_full / 4;   // (the plan writes the arena's id, it does not index the slot table)
-        e.cols_base = (uint32_t)pc.size();
-        for (auto& sc : sh.cols) pc.push_back((uint32_t)sc.type_class | ((uint32_t)(sc.nullable ? 1 : 0) << 8) | ((uint32_t)sc.off_full << 16));
-        // Deletes by key (round 6): the key-layout row of the table, one key word per column (a key row never outgrows the full
-        // row the tile's LDS is sized by). A table without an identity column, or with more of them than the key word has bits for, keeps key_dwords 0:
-        // its Deletes give the batch up as before.
-        e.n_ident = sh.desc.n_ident; e.key_dwords = sh.desc.n_ident && sh.desc.n_ident < 256 && sh.desc.row_bytes_key <= 255 * 4 ? sh.desc.row_bytes_key / 4 : 0;
-        e.keys_base = (uint32_t)pc.size();
-        for (auto& sc : sh.cols) pc.push_back(sc.identity ? (1u | ((uint32_t)sc.key_index << 8) | ((uint32_t)(sc.off_key / 4) << 24)) : 0u);
-        pt.push_back(e);
-      }
+  // nothing the side inputs are built from has changed since the last upload (the common case: one call per batch)
+  bool unchanged() const { return eps.empty() && side_inputs_stand(c) && !b->have_snapshot && !b->copy.active; }
+  void records() {   // tables (sorted by id) with their epochs in frame order, live slots, host slots -> device indexes
+    std::map<uint32_t, DevTable> tabs;
+    auto get = [&](uint32_t id) -> DevTable& {
+      auto it = tabs.find(id);
+      if (it == tabs.end()) { DevTable t{}; t.table_id = id; t.init_slot = -1; it = tabs.emplace(id, t).first; }
+      return it->second;
+    };
+    for (auto& kv : c->states) { DevTable& t = get(kv.first); t.state_kind = (uint32_t)kv.second.kind; t.state_lsn = kv.second.lsn; }
+    const ControlState& cs0 = b->have_snapshot ? b->snapshot : c->cs;  // cache as of batch start
+    for (auto& kv : cs0.cache) { DevTable& t = get(kv.first); t.init_kind = kv.second.kind; t.init_slot = kv.second.slot; }
+    for (auto& e : eps) get(e.table_id);
+    for (auto& kv : tabs) {
+      DevTable t = kv.second;
+      t.ep_begin = (uint32_t)ev.size();
+      for (auto& e : eps) if (e.table_id == t.table_id) ev.push_back(e.ep);  // already in frame order
+      t.ep_end = (uint32_t)ev.size();
+      tv.push_back(t);
     }
-    SideSet* ss = nullptr;
-    side_release(b);   // (a batch that is decoded again lets go of the set its first attempt read)
+    for (auto& t : tv) if (t.init_kind == 2u && t.init_slot >= 0) live.push_back(t.init_slot);
+    for (auto& e : ev) if (e.kind == 2u && e.slot >= 0) live.push_back(e.slot);
+    if (b->copy.active && b->copy.slot >= 0) live.push_back(b->copy.slot);
+    std::sort(live.begin(), live.end());
+    live.erase(std::unique(live.begin(), live.end()), live.end());
+    auto dev_index = [&](int32_t host_slot) -> int32_t {   // position in `live`; -1 stays -1
+      if (host_slot < 0) return host_slot;
+      return (int32_t)(std::lower_bound(live.begin(), live.end(), host_slot) - live.begin());
+    };
+    for (auto& t : tv) if (t.init_kind == 2u) t.init_slot = dev_index(t.init_slot);
+    for (auto& e : ev) if (e.kind == 2u) e.slot = dev_index(e.slot);
+  }
+  bool same_as_last_upload() const {
+    return c->side_valid && !c->slots_dirty && live == c->last_live && tv.size() == c->last_tables.size() && ev.size() == c->last_epochs.size() &&
+           (tv.empty() || !memcmp(tv.data(), c->last_tables.data(), tv.size() * sizeof(DevTable))) &&
+           (ev.empty() || !memcmp(ev.data(), c->last_epochs.data(), ev.size() * sizeof(DevEpoch)));
+  }
+  // the fixed-width plan (plan.hip): tables the apply worker owns outright, Ready for the whole batch, whose replicated columns are all
+  // bool / int2 / int4 / int8 / oid
+  void plan_tables() {
+    if (!ev.empty() || c->worker != ETLG_WORKER_APPLY) return;
+    for (const DevTable& t : tv) {  // tv is sorted by table id
+      if (t.state_kind != ETLG_TS_READY || t.init_kind != 2u || t.init_slot < 0 || (size_t)t.init_slot >= live.size()) continue;
+      const int32_t host_slot = live[(size_t)t.init_slot];   // (t.init_slot is the device index by now)
+      if (host_slot < 0 || (size_t)host_slot >= c->slots.size()) continue;
+      const SlotHost& sh = *c->slots[(size_t)host_slot];
+      bool ok = sh.desc.n_cols > 0;
+      for (auto& sc : sh.cols) if (!int_class(sc.type_class)) ok = false;
+      if (!ok) continue;
+      PlanTab e{};
+      e.rel_id = t.table_id; e.slot = (uint32_t)host_slot; e.n_cols = sh.desc.n_cols; e.row_dwords = sh.desc.row_bytes_full / 4;   // (the plan writes the arena's id, it does not index the slot table)
+      e.cols_base = (uint32_t)pc.size();
+      for (auto& sc : sh.cols) pc.push_back((uint32_t)sc.type_class | ((uint32_t)(sc.nullable ? 1 : 0) << 8) | ((uint32_t)sc.off_full << 16));
+      // Deletes by key (round 6): the key-layout row of the table, one key word per column (a key row never outgrows the full
+      // row the tile's LDS is sized by). A table without an identity column, or with more of them than the key word has bits for, keeps key_dwords 0:
+      // its Deletes give the batch up as before.
+      e.n_ident = sh.desc.n_ident; e.key_dwords = sh.desc.n_ident && sh.desc.n_ident < 256 && sh.desc.row_bytes_key <= 255 * 4 ? sh.desc.row_bytes_key / 4 : 0;
+      e.keys_base = (uint32_t)pc.size();
+      for (auto& sc : sh.cols) pc.push_back(sc.identity ? (1u | ((uint32_t)sc.key_index << 8) | ((uint32_t)(sc.off_key / 4) << 24)) : 0u);
+      pt.push_back(e);
+    }
+  }
+  int32_t take_free_set() {   // one no unfinished batch reads (a batch that is decoded again lets go of the set its first attempt read)
+    side_release(b);
     for (SideSet* x : c->side_sets) if (x->users == 0) { ss = x; break; }
     if (!ss) { ss = new SideSet(); c->side_sets.push_back(ss); HIPCHK(c, hipEventCreateWithFlags(&ss->ready, hipEventDisableTiming)); }
-    ss->o_tables = 0;
-    ss->o_epochs = al64(tv.size() * sizeof(DevTable) + 16);
-    ss->o_slots = ss->o_epochs + al64(ev.size() * sizeof(DevEpoch) + 16);
-    ss->o_cols = ss->o_slots + al64(ds.size() * sizeof(DevSlot) + 16);
-    ss->o_ptabs = ss->o_cols + al64(dc.size() * (sizeof(DevCol) + 1) + 16);   // (the records, then one element-class byte per record)
-    ss->o_pcols = ss->o_ptabs + al64(pt.size() * sizeof(PlanTab) + 16);
-    // ETLG_F_CHECK_CELLS: the element class of every array column, in DevCol order (build_slots pushes no column for a dead slot),
-    // stored directly behind the DevCol records (chk_elem_table, values.hip.h)
-    std::vector<uint8_t> ce;
+    return ETLG_OK;
+  }
+  // ETLG_F_CHECK_CELLS: the element class of every array column, in DevCol order (build_slots pushes no column for a dead slot),
+  // stored directly behind the DevCol records (chk_elem_table, values.hip.h)
+  int32_t element_classes() {
     ss->chk_any = false; ss->chk_maxc = 0;
     for (int32_t li : live) {
       if (li < 0 || (size_t)li >= c->slots.size()) continue;
@@ -177,68 +182,61 @@ int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec
       if (any) { ss->chk_any = true; ss->chk_maxc = std::max<uint32_t>(ss->chk_maxc, sh.desc.n_cols); }
     }
     if (ce.size() != dc.size()) return lib_error(c, ETLG_InvalidState, "side inputs: element classes and columns differ in number");
-    const size_t total = ss->o_pcols + al64(pc.size() * 4 + 16);
-    if (total > ss->h_cap) {
+    return ETLG_OK;
+  }
+  int32_t upload() {   // ONE copy from the set's pinned block, `ready` recorded behind it
+    const decode_plan::SideLayout lay = decode_plan::side_layout(tv.size(), ev.size(), ds.size(), dc.size(), pt.size(), pc.size());
+    ss->o_tables = lay.tables; ss->o_epochs = lay.epochs; ss->o_slots = lay.slots; ss->o_cols = lay.cols; ss->o_ptabs = lay.ptabs; ss->o_pcols = lay.pcols;
+    if (lay.total > ss->h_cap) {
       if (ss->h) (void)hipHostFree(ss->h);
       ss->h = nullptr; ss->h_cap = 0;
-      const size_t want = total + total / 2 + 4096;
+      const size_t want = lay.total + lay.total / 2 + 4096;
       HIPCHK(c, hipHostMalloc((void**)&ss->h, want, hipHostMallocDefault));
       ss->h_cap = want;
     }
     HIPCHK(c, ss->dev.ensure(ss->h_cap));
-    if (!tv.empty()) memcpy(ss->h + ss->o_tables, tv.data(), tv.size() * sizeof(DevTable));
-    if (!ev.empty()) memcpy(ss->h + ss->o_epochs, ev.data(), ev.size() * sizeof(DevEpoch));
-    if (!ds.empty()) memcpy(ss->h + ss->o_slots, ds.data(), ds.size() * sizeof(DevSlot));
-    if (!dc.empty()) memcpy(ss->h + ss->o_cols, dc.data(), dc.size() * sizeof(DevCol));
-    if (!pt.empty()) memcpy(ss->h + ss->o_ptabs, pt.data(), pt.size() * sizeof(PlanTab));
-    if (!pc.empty()) memcpy(ss->h + ss->o_pcols, pc.data(), pc.size() * 4);
-    if (!ce.empty()) memcpy(ss->h + ss->o_cols + dc.size() * sizeof(DevCol), ce.data(), ce.size());
-    HIPCHK(c, hipMemcpyAsync(ss->dev.p, ss->h, total, hipMemcpyHostToDevice, s));
+    auto put = [&](size_t at, const void* from, size_t bytes) { if (bytes) memcpy(ss->h + at, from, bytes); };
+    put(lay.tables, tv.data(), tv.size() * sizeof(DevTable)); put(lay.epochs, ev.data(), ev.size() * sizeof(DevEpoch));
+    put(lay.slots, ds.data(), ds.size() * sizeof(DevSlot)); put(lay.cols, dc.data(), dc.size() * sizeof(DevCol)); put(lay.elems, ce.data(), ce.size());
+    put(lay.ptabs, pt.data(), pt.size() * sizeof(PlanTab)); put(lay.pcols, pc.data(), pc.size() * 4);
+    HIPCHK(c, hipMemcpyAsync(ss->dev.p, ss->h, lay.total, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(ss->ready, s));
-    ss->synced = 1u << (s == c->stream2 && c->stream2 ? 1 : 0);
+    ss->synced = side_stream_bit(c, s);
     ss->n_slots = (uint32_t)ds.size(); ss->n_cols = (uint32_t)dc.size();
     c->side_cur = ss;
     c->last_tables = tv; c->last_epochs = ev; c->side_valid = true;
     c->slots_dirty = false; c->last_live = live;
-    c->n_plan_tabs = (uint32_t)pt.size();
-    c->plan_max_row = 16;
-    for (auto& e : pt) c->plan_max_row = std::max<uint32_t>(c->plan_max_row, e.row_dwords * 4);
-    c->plan_uniform_dw = pt.empty() ? 0u : pt[0].row_dwords;   // the sidecar pre-pass prices a row without knowing its table
-    for (auto& e : pt) if (e.row_dwords != c->plan_uniform_dw) c->plan_uniform_dw = 0;
-    // (the pre-pass prices a Delete by key by its length too: shorter than any row frame of any planned table. One key-row size for all)
-    c->plan_uniform_key_dw = pt.empty() ? 0u : pt[0].key_dwords;
-    c->plan_key_below = ~0u; c->plan_key_max = 0;
-    for (auto& e : pt) {
-      if (e.key_dwords != c->plan_uniform_key_dw) c->plan_uniform_key_dw = 0;
-      uint32_t shortest = 38;   // CopyData + XLogData head, tag, relation id, 'N', column count
-      for (uint32_t k = 0; k < e.n_cols; k++) shortest += ((pc[e.cols_base + k] >> 8) & 1u) ? 1u : 6u;   // 'n', or 't' len:4 and one character
-      c->plan_key_below = std::min(c->plan_key_below, shortest);
-      uint32_t longest = 38;
-      for (uint32_t k = 0; k < e.n_cols; k++) {
-        const uint32_t cls = pc[e.cols_base + k] & 0xFFu;
-        longest += (pc[e.keys_base + k] & 1u) ? 5u + (cls == ETLG_TC_BOOL ? 1u : cls == ETLG_TC_I16 ? 6u : cls == ETLG_TC_I32 ? 11u : cls == ETLG_TC_U32 ? 10u : 20u) : 1u;
-      }
-      c->plan_key_max = std::max(c->plan_key_max, longest);
-    }
-    if (!c->plan_uniform_key_dw || pt.empty()) { c->plan_key_below = 0; c->plan_key_max = 0; }
-    // every table state the batch can meet must be covered by the plan for it to be worth trying: a table that is not
-    // eligible but owned (a TEXT column, say) would fail every batch that carries its rows
-    c->plan_covers_all = !pt.empty();
-    for (const DevTable& t : tv) if (t.state_kind != ETLG_TS_ABSENT && t.state_kind != ETLG_TS_OTHER) {
-      bool found = false;
-      for (auto& e : pt) if (e.rel_id == t.table_id) found = true;
-      if (!found) c->plan_covers_all = false;
-    }
+    return ETLG_OK;
   }
-  point(c->side_cur, (uint32_t)tv.size(), (uint32_t)ev.size());
-  {  // a set that was uploaded on the other decode stream: this stream's kernels wait for the copy (decode_tail does the same for the
-     // batches whose side inputs are known before their stream is; a control-path batch learns its set here)
-    SideSet* ss = c->side_cur;
-    const uint32_t bit = 1u << ((s == c->stream2 && c->stream2) ? 1 : 0);
-    if (ss && !(ss->synced & bit)) { HIPCHK(c, hipStreamWaitEvent(s, ss->ready, 0)); ss->synced |= bit; }
+  void keep_plan_summary() {
+    const decode_plan::PlanSummary ps = decode_plan::plan_summary(pt, pc, tv);
+    c->n_plan_tabs = ps.n_tabs; c->plan_max_row = ps.max_row; c->plan_uniform_dw = ps.uniform_dw; c->plan_uniform_key_dw = ps.uniform_key_dw;
+    c->plan_key_below = ps.key_below; c->plan_key_max = ps.key_max; c->plan_covers_all = ps.covers_all;
   }
+};
+
+int32_t build_side_inputs(etlg_ctx* c, etlg_batch* b, const std::vector<EpochRec>& eps) {
+  SlowScope slow_scope_build_side_inputs(c, "build_side_inputs");
+  SideBuild sb{c, b, eps, c->stream};
+  if (sb.unchanged()) {
+    sb.point(c->side_cur, (uint32_t)c->last_tables.size(), 0u);
+    b->any_sync_done = c->last_any_sync_done;
+    return ETLG_OK;
+  }
+  sb.records();
+  if (!sb.same_as_last_upload()) {  // table states, the cache timeline or the slots changed: a new upload
+    build_slots(c, sb.live, sb.ds, sb.dc);
+    sb.plan_tables();
+    RC(sb.take_free_set());
+    RC(sb.element_classes());
+    RC(sb.upload());
+    sb.keep_plan_summary();
+  }
+  sb.point(c->side_cur, (uint32_t)sb.tv.size(), (uint32_t)sb.ev.size());
+  // (decode_tail does the same wait for the batches whose side inputs are known before their stream is; a control-path batch learns its set here)
+  RC(wait_for_side_upload(c, c->side_cur, sb.s));
   b->any_sync_done = false;
-  for (auto& t : tv) if (t.state_kind == ETLG_TS_SYNC_DONE) b->any_sync_done = true;
+  for (auto& t : sb.tv) if (t.state_kind == ETLG_TS_SYNC_DONE) b->any_sync_done = true;
   c->last_any_sync_done = b->any_sync_done;
   if (!b->have_snapshot) c->side_dirty = false;   // built from the live control state
   return ETLG_OK;
@@ -251,13 +249,12 @@ int32_t setup_outputs(etlg_ctx* c, etlg_batch* b) {
   DecParams& p = b->params;
   if (!b->dev) b->dev = take_outset(c);
   OutSet* os = b->dev;
-  const uint32_t nf = p.nframes;
-  const size_t evcap = (size_t)nf + 16;
-  // (table-copy rows decoded in place are sized like the Insert frames they would rewrite to: the bounds below count on the five
+  // (table-copy rows decoded in place are sized like the Insert frames they would rewrite to: the bounds count on the five
   // header bytes a frame has per cell)
   const uint64_t blen = b->copy.active ? std::max<uint64_t>(b->len, b->copy.syn_len) : b->len;
-  const uint64_t fixed_cap = (uint64_t)nf * max_row_bytes(c) + 2 * blen + 64;
-  const uint64_t heap_cap = std::min<uint64_t>(0xFFFFFFF0ull, blen * 5 / 2 + 64);
+  const decode_plan::OutCaps caps = decode_plan::out_caps(p.nframes, blen, max_row_bytes(c));
+  const size_t evcap = caps.evcap;
+  const uint64_t fixed_cap = caps.fixed_cap, heap_cap = caps.heap_cap;
   HIPCHK(c, os->kind.ensure(evcap)); HIPCHK(c, os->flags.ensure(evcap));
   HIPCHK(c, os->table.ensure(evcap * 4)); HIPCHK(c, os->slot.ensure(evcap * 4));
   HIPCHK(c, os->start.ensure(evcap * 8)); HIPCHK(c, os->commit.ensure(evcap * 8));
@@ -275,16 +272,31 @@ int32_t setup_outputs(etlg_ctx* c, etlg_batch* b) {
   return ETLG_OK;
 }
 
-// Should this batch try the fixed-width plan first?
+// The fixed-width plan's eligibility by context — everything but the batch's own size and the back-off; no side effect.
+// (copy_rows: table-copy rows; n_epochs: the batch's own control frames changed a table under it)
+bool plan_possible(const etlg_ctx* c, bool copy_rows, uint32_t n_epochs) {
+  if (c->plan_mode == 0 || (c->fused_kernel >= 0 && c->fused_kernel != 3)) return false;  // ETLG_PLAN=0 / a forced generic kernel
+  if (!c->n_plan_tabs || !c->plan_covers_all || n_epochs || copy_rows || c->worker != ETLG_WORKER_APPLY || c->fused_dbg) return false;
+  return c->plan_max_row <= 512;   // 64 rows of the widest table sit in LDS beside the staging window
+}
+// Should this batch try the fixed-width plan first? Consumes a turn of the back-off (plan_skip): once per batch.
 bool plan_wanted(etlg_ctx* c, const etlg_batch* b) {
   const DecParams& p = b->params;
-  if (c->plan_mode == 0 || (c->fused_kernel >= 0 && c->fused_kernel != 3)) return false;  // ETLG_PLAN=0 / a forced generic kernel
-  if (!c->n_plan_tabs || !c->plan_covers_all || p.n_epochs || (p.flags & kDecCopyRows) || c->worker != ETLG_WORKER_APPLY) return false;
-  if (p.nframes >= (1u << 29) || p.fixed_cap >= (1ull << 34) || c->fused_dbg) return false;   // descriptor: mark 30 bits, fixed dwords 32 bits
-  if (c->plan_max_row > 512) return false;   // 64 rows of the widest table sit in LDS beside the staging window
+  if (!plan_possible(c, (p.flags & kDecCopyRows) != 0, p.n_epochs)) return false;
+  if (p.nframes >= (1u << 29) || p.fixed_cap >= (1ull << 34)) return false;   // descriptor: mark 30 bits, fixed dwords 32 bits
   if (c->fused_kernel == 3) return true;
   if (c->plan_skip) { c->plan_skip--; return false; }  // backing off after a batch that did not conform
   return true;
+}
+
+// The optimistic first attempt's preparation: as if the batch held no Relation / DDL frame — side inputs (unchanged: no stream work),
+// outputs, and whether the fixed-width plan goes first (b->plan_decided).
+int32_t prepare_optimistic(etlg_ctx* c, etlg_batch* b) {
+  b->params.flags |= kDecNoControl;
+  RC(build_side_inputs(c, b, std::vector<EpochRec>()));
+  RC(setup_outputs(c, b));
+  b->plan_decided = plan_wanted(c, b) ? 1 : 0;
+  return ETLG_OK;
 }
 
 // Look-back descriptor buffers: four in rotation. The launch of batch k uses buffer k mod 4 and zeroes the head of buffer
@@ -364,188 +376,164 @@ int32_t resolve_scan_count(etlg_ctx* c, etlg_batch* b) {
   return ETLG_OK;
 }
 
-// Enqueues ONE single-pass kernel over the batch: level 0 = the fixed-width plan (plan.hip), level 1 = the generic fused
-// kernel (fused.hip) or, for wide frames, the column-parallel one (cells.hip).
-int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
-  SlowScope slow_scope_enqueue_single(c, "enqueue_single");
-  if (b->scan_chained && level != 0) RC(resolve_scan_count(c, b));   // (only the plan kernels read the count on the device)
-  const DecParams& p = b->params;
-  const uint32_t nf = p.nframes;
-  b->level = level;
-  b->used_rows = false;
-  uint32_t widest = 1;
-  bool cells_ok = false;
-  if (level != 0) {
-    FusedParams& q = c->fq;
-    const uint64_t side = (uint64_t)p.n_tables * sizeof(DevTable) + (uint64_t)p.n_epochs * sizeof(DevEpoch) +
-                          (uint64_t)p.n_slots * sizeof(DevSlot) + (uint64_t)p.n_cols * sizeof(DevCol);
-    q.side_bytes = (side <= 32768 && !(c->fused_dbg & 16)) ? (uint32_t)((side + 15) & ~15ull) : 0u;
-    for (int32_t li : c->last_live) widest = std::max<uint32_t>(widest, c->slots[(size_t)li]->desc.n_cols);
-    cells_ok = widest <= etlg_k_cells_maxc() && q.side_bytes != 0;  // k_cells keeps the side tables in LDS
-    // table-copy rows: the rows -> arena kernel is k_cells with another first phase; where k_cells cannot run (or another kernel is
-    // forced) the rows are rewritten as Insert frames first
-    if (b->copy.active && b->copy.direct && (!cells_ok || c->fused_kernel >= 0)) RC(copy_use_frames(c, b));
+// ---- the single-pass kernels of the ladder: enqueue_single puts ONE of them over the batch — level 0 = the fixed-width plan (plan.hip),
+// level 1 = k_rows (rows.hip) where it may run, else the generic fused kernel (fused.hip) or, for wide frames, the column-parallel one
+// (cells.hip). The numbers of every launch come from decode_plan.h.
+
+// The average frame a launch's LDS windows are sized by (decoded behind its scan: params.nframes is a bound, the stream's estimate counts)
+uint64_t avg_frame_of(const etlg_batch* b) {
+  return decode_plan::avg_frame(b->len, b->scan_chained && b->nf_est ? b->nf_est : b->params.nframes);
+}
+
+// Prefixes of the sidecar pre-pass go to a buffer of their own, four in rotation like the look-back descriptors and for the same reason:
+// batch k + 1 runs beside batch k on the other decode stream, batch k - 2 is complete before k starts. The pre-pass runs on the batch's own
+// decode stream — with two decode streams that is beside the decode of the batch BEFORE. (A stream of its own at the highest priority,
+// eight buffers, the pre-pass up to six batches ahead: 1 355 GB/s against 1 698 on the bench's chain — the events it takes cost
+// the host more than the overlap gains; profiles/r04_plan_development.json.)
+int32_t take_pre_buffer(etlg_ctx* c, size_t pbytes, PlanParams& q) {
+  constexpr uint32_t NB = etlg_ctx::kPreBufs;
+  if (pbytes > c->pre_half) {
+    HIPCHK(c, sync_decode_streams(c));
+    const size_t half = (pbytes * 2 + 4095) & ~(size_t)4095;
+    HIPCHK(c, c->d_pre.ensure(half * NB));
+    HIPCHK(c, hipMemsetAsync(c->d_pre.p, 0, half * NB, c->stream));   // tickets start at zero (every launch leaves its own that way), no word carries a status tag
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pre_half = half;
   }
-  const bool direct = b->copy.active && b->copy.direct;
-  const uint64_t nf_avg = b->scan_chained && b->nf_est ? b->nf_est : nf;   // (decoded behind its scan: nf is a bound)
-  const uint64_t avg = (b->len + nf_avg - 1) / nf_avg;
-  if (level == 0) {
-    PlanParams& q = c->pq;
-    q.ntiles = (nf + 63) / 64;
-    uint64_t cap = 64 * avg * (100 + (uint64_t)c->plan_margin_pct) / 100 + 128;
-    cap = std::min<uint64_t>((cap + 127) & ~127ull, 48 * 1024);
-    q.rows_off = (uint32_t)std::max<uint64_t>(cap, 2048 + 64);        // the staging window (a tile read in place parks 64 x 32-byte bodies there)
-    // rows of up to 8 dwords wait for the look-back inside their own frame's staged head; wider tables get a region of 64 rows
-    q.lds_bytes = q.rows_off + (c->plan_max_row > 32 ? (uint32_t)(64ull * c->plan_max_row + 64) : 0u);
-    q.n_tabs = c->n_plan_tabs; q.tabs = (const PlanTab*)((const uint8_t*)b->side->dev.p + b->side->o_ptabs); q.cols = (const uint32_t*)((const uint8_t*)b->side->dev.p + b->side->o_pcols);
-    q.dbg = c->plan_dbg;
-    q.max_row_dw = (c->plan_max_row + 3) / 4;
-    const size_t gtiles = std::min<size_t>(64, (size_t)1 << etlg_k_plan_pre_group_log());   // (the look-back's groups are 64 tiles, the pre-pass's are what plan.hip makes them)
-    const size_t per = 2 * ((size_t)q.ntiles + ((size_t)q.ntiles + gtiles - 1) / gtiles);   // pairs: {agg, lsn}[ntiles] | {agg, lsn}[ngroups]
-    // the sidecar pre-pass (k_plan_pre, plan.hip) leaves every tile's prefix in memory: the decode kernel
-    // then has no look-back. Needs one row size for all planned tables (a frame is priced by its length alone).
-    const bool pre = c->plan_pre != 0 && c->plan_uniform_dw != 0;
-    const size_t dbytes = per * 8 + 64;
-    q.desc = nullptr; q.d_clear = nullptr; q.clear_words = 0;
-    if (!pre) {   // (behind the pre-pass no kernel reads or writes a look-back word: no buffer is taken, none is cleared)
-      uint8_t *dcur, *doth;
-      RC(take_descriptors(c, dbytes, &dcur, &doth));
-      q.desc = (unsigned long long*)dcur;
-      q.d_clear = (unsigned long long*)doth; q.clear_words = (uint32_t)(dbytes / 8);
-    }
-    q.pre = nullptr; q.pre_out = nullptr; q.pre_ticket = nullptr; q.pre_tag = 0; q.pre_row_dw = c->plan_uniform_dw;
-    q.pre_key_dw = c->plan_uniform_key_dw; q.pre_key_below = c->plan_deletes ? c->plan_key_below : 0u; q.pre_key_max = c->plan_deletes ? c->plan_key_max : 0u;
-    if (pre) {
-      // Prefixes go to a buffer of their own, four in rotation like the look-back descriptors and for the same reason: batch k + 1 runs
-      // beside batch k on the other decode stream, batch k - 2 is complete before k starts. The pre-pass runs on the batch's own decode
-      // stream — with two decode streams that is beside the decode of the batch BEFORE. (A stream of its own at the highest priority,
-      // eight buffers, the pre-pass up to six batches ahead: 1 355 GB/s against 1 698 on the bench's chain — the events it takes cost
-      // the host more than the overlap gains; profiles/r04_plan_development.json.)
-      constexpr uint32_t NB = etlg_ctx::kPreBufs;
-      const size_t pbytes = (64 + per * 8 + 255) & ~(size_t)255;   // ticket (a fixed place, whatever the batch's size: it must read zero) | {prefix inside the group}[ntiles] | {group prefix}[ngroups]
-      if (pbytes > c->pre_half) {
-        HIPCHK(c, sync_decode_streams(c));
-        const size_t half = (pbytes * 2 + 4095) & ~(size_t)4095;
-        HIPCHK(c, c->d_pre.ensure(half * NB));
-        HIPCHK(c, hipMemsetAsync(c->d_pre.p, 0, half * NB, c->stream));   // tickets start at zero (every launch leaves its own that way), no word carries a status tag
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->pre_half = half;
-      }
-      const uint32_t useq = c->pre_seq++, slot = useq % NB;
-      uint8_t* pbuf = (uint8_t*)c->d_pre.p + (size_t)slot * c->pre_half;
-      q.pre_ticket = (uint32_t*)pbuf;
-      q.pre_out = (unsigned long long*)(pbuf + 64);
-      q.pre_tag = 1u + (useq / NB) % 3u;   // differs from the tag of this buffer's last two uses: a stale group word is never taken for this launch's
-      launch(c, kPlanPre, p);
-      q.pre = q.pre_out;
-      if (c->plan_pre == 1) q.dbg |= 512u;   // one tile per wave: without the look-back nothing is gained from a single lock-step round
-    }
-    launch(c, kPlan, p);
-    b->used_fused = true; b->used_cells = false;
+  const decode_plan::PreSlot ps = decode_plan::pre_slot(c->pre_seq++, NB);
+  uint8_t* pbuf = (uint8_t*)c->d_pre.p + (size_t)ps.slot * c->pre_half;
+  q.pre_ticket = (uint32_t*)pbuf;
+  q.pre_out = (unsigned long long*)(pbuf + 64);
+  q.pre_tag = ps.tag;
+  return ETLG_OK;
+}
+
+int32_t enqueue_plan(etlg_ctx* c, etlg_batch* b) {
+  const DecParams& p = b->params;
+  PlanParams& q = c->pq;
+  const decode_plan::PlanGeom g = decode_plan::plan_geom(p.nframes, avg_frame_of(b), c->plan_margin_pct, c->plan_max_row, etlg_k_plan_pre_group_log());
+  q.ntiles = g.ntiles; q.rows_off = g.rows_off; q.lds_bytes = g.lds_bytes; q.max_row_dw = g.max_row_dw;
+  q.n_tabs = c->n_plan_tabs; q.tabs = (const PlanTab*)((const uint8_t*)b->side->dev.p + b->side->o_ptabs); q.cols = (const uint32_t*)((const uint8_t*)b->side->dev.p + b->side->o_pcols);
+  q.dbg = c->plan_dbg;
+  // the sidecar pre-pass (k_plan_pre, plan.hip) leaves every tile's prefix in memory: the decode kernel
+  // then has no look-back. Needs one row size for all planned tables (a frame is priced by its length alone).
+  const bool pre = c->plan_pre != 0 && c->plan_uniform_dw != 0;
+  q.desc = nullptr; q.d_clear = nullptr; q.clear_words = 0;
+  if (!pre) {   // (behind the pre-pass no kernel reads or writes a look-back word: no buffer is taken, none is cleared)
+    uint8_t *dcur, *doth;
+    RC(take_descriptors(c, g.dbytes, &dcur, &doth));
+    q.desc = (unsigned long long*)dcur;
+    q.d_clear = (unsigned long long*)doth; q.clear_words = (uint32_t)(g.dbytes / 8);
+  }
+  q.pre = nullptr; q.pre_out = nullptr; q.pre_ticket = nullptr; q.pre_tag = 0; q.pre_row_dw = c->plan_uniform_dw;
+  q.pre_key_dw = c->plan_uniform_key_dw; q.pre_key_below = c->plan_deletes ? c->plan_key_below : 0u; q.pre_key_max = c->plan_deletes ? c->plan_key_max : 0u;
+  if (pre) {
+    RC(take_pre_buffer(c, g.pbytes, q));
+    launch(c, kPlanPre, p);
+    q.pre = q.pre_out;
+    if (c->plan_pre == 1) q.dbg |= 512u;   // one tile per wave: without the look-back nothing is gained from a single lock-step round
+  }
+  launch(c, kPlan, p);
+  b->used_fused = true; b->used_cells = false;
+  return ETLG_OK;
+}
+
+// What the kernels of level 1 are chosen by: the widest live slot, whether k_cells can run (it keeps the side tables in LDS: FusedParams::
+// side_bytes, set here), the average frame, and whether the batch is table-copy rows decoded in place.
+struct GenericFacts { uint32_t widest = 1; bool cells_ok = false, direct = false; uint64_t avg = 0; };
+int32_t generic_facts(etlg_ctx* c, etlg_batch* b, GenericFacts& f) {
+  const DecParams& p = b->params;
+  FusedParams& q = c->fq;
+  q.side_bytes = decode_plan::side_lds_bytes(p.n_tables, p.n_epochs, p.n_slots, p.n_cols, (c->fused_dbg & 16) != 0);
+  for (int32_t li : c->last_live) f.widest = std::max<uint32_t>(f.widest, c->slots[(size_t)li]->desc.n_cols);
+  f.cells_ok = f.widest <= etlg_k_cells_maxc() && q.side_bytes != 0;
+  // table-copy rows: the rows -> arena kernel is k_cells with another first phase; where k_cells cannot run (or another kernel is
+  // forced) the rows are rewritten as Insert frames first
+  if (b->copy.active && b->copy.direct && (!f.cells_ok || c->fused_kernel >= 0)) RC(copy_use_frames(c, b));
+  f.direct = b->copy.active && b->copy.direct;
+  f.avg = avg_frame_of(b);
+  return ETLG_OK;
+}
+
+// The row-synchronous kernel (rows.hip) takes the batches k_cells / k_fused-64 would: WAL frames (not table-copy rows), no table in SyncDone
+// state (ownership would need the transaction look-back before the slots), tables of up to 64 columns. *taken: it was enqueued.
+int32_t try_enqueue_rows(etlg_ctx* c, etlg_batch* b, const GenericFacts& f, bool* taken) {
+  const DecParams& p = b->params;
+  FusedParams& q = c->fq;
+  uint32_t maxh = 1, maxh_old = 0, maxrow = 16;
+  bool ok = !b->copy.active && !(p.flags & kDecCopyRows) && !b->any_sync_done && !(c->fused_dbg & ~(8u | 32u)) && q.side_bytes != 0 && ((uintptr_t)p.in & 15) == 0 &&
+            f.widest <= etlg_k_rows_max_cols() && !b->no_rows && c->rows_mode != 0 && (c->fused_kernel < 0 || c->fused_kernel == 4);
+  for (int32_t li : c->last_live) {
+    const SlotHost& sh = *c->slots[(size_t)li];
+    uint32_t nh = 0, nhi = 0;
+    for (auto& sc : sh.cols) if (!heapless_class(sc.type_class)) { nh++; if (sc.identity) nhi++; }
+    maxh = std::max(maxh, nh); maxh_old = std::max(maxh_old, nhi);
+    maxrow = std::max<uint32_t>(maxrow, sh.desc.row_bytes_full + std::max<uint32_t>(sh.desc.row_bytes_key, sh.desc.n_ident == sh.desc.n_cols ? sh.desc.row_bytes_full : 0u));
+  }
+  if (maxh > etlg_k_rows_max_heap_cols()) ok = false;
+  if (ok && c->fused_kernel != 4 && c->rows_skip) { c->rows_skip--; ok = false; }   // backing off after a batch that was handed back
+  if (!ok) return ETLG_OK;
+  const uint64_t stat = etlg_k_rows_static_lds();
+  const uint64_t max_wgs = 4ull * (uint64_t)etlg_k_rows_waves_per_simd() / (uint64_t)etlg_k_rows_waves();   // (the register file: ETLG_ROWS_MINBLOCKS waves per SIMD)
+  const decode_plan::RowsChoice r = decode_plan::rows_choice(decode_plan::RowsIn{f.avg, maxrow, maxh, maxh_old, f.widest, q.side_bytes, stat, c->rows_win_min, c->rows_cf, max_wgs},
+                                                             etlg_k_rows_table_bytes);
+  if (!r.taken) {
+    if (c->rows_trace) fprintf(stderr, "[rows] not taken: cf %u need %llu maxrow %u widest %u avg %llu\n", r.cf, (unsigned long long)r.need, maxrow, f.widest, (unsigned long long)f.avg);
     return ETLG_OK;
   }
+  q.blk = r.cf; q.maxc = f.widest; q.rows_maxh_old = maxh_old; q.rows_maxh = maxh;
+  q.lds_bytes = r.lds_bytes;
+  q.seq_lookback = 0; q.in_aligned = 1; q.dbg = c->fused_dbg; q.copy_rel = 0;
+  q.ntiles = (p.nframes + r.cf - 1) / r.cf;
+  RC(take_tile_descriptors(c, q));
+  if (c->rows_lds >= 0) q.lds_bytes = (uint32_t)c->rows_lds;   // (ETLG_ROWS_LDS, experiments)
+  if (c->rows_trace) fprintf(stderr, "[rows] cf %u maxc %u maxh %u lds %u (static %llu) side %u tables %llu need %llu (window min %llu, avg frame %llu) -> %d workgroups per CU by the runtime's count, %llu planned\n", r.cf, f.widest, maxh, q.lds_bytes, (unsigned long long)stat, q.side_bytes, (unsigned long long)r.tabb, (unsigned long long)r.need, (unsigned long long)c->rows_win_min, (unsigned long long)f.avg, etlg_k_rows_occupancy(q.lds_bytes), (unsigned long long)r.wgs);
+  launch(c, kRows, p);
+  launch_chk_cells(c, b);
+  b->used_fused = true; b->used_cells = false; b->used_rows = true;
+  *taken = true;
+  return ETLG_OK;
+}
+
+int32_t enqueue_generic(etlg_ctx* c, etlg_batch* b, const GenericFacts& f, int kernel) {   // k_fused / k_cells / k_copy_cells
+  const DecParams& p = b->params;
   FusedParams& q = c->fq;
-  // kernel choice: narrow frames -> one lane per frame, 256 frames per tile (k_fused); wide frames ->
-  // 64 frames per tile with the waves spread over the columns (k_cells, schemas up to 32 columns: a second instantiation beyond 16)
-  bool any_var = false;   // a table the batch may carry has TEXT / NUMERIC / ... columns: one lane per frame crawls on those
-  for (int32_t li : c->last_live) for (auto& sc : c->slots[(size_t)li]->cols) if (!fixed_class(sc.type_class)) any_var = true;
-  int kernel = (avg <= 192 && !(any_var && cells_ok && avg > 96)) ? 0 : (cells_ok ? 2 : 1);  // 0 fused/256, 1 fused/64, 2 cells
-  if (c->fused_kernel >= 0 && c->fused_kernel <= 2) kernel = c->fused_kernel == 2 && !cells_ok ? 1 : c->fused_kernel;
-  if (direct) kernel = 2;
-  // ---- the row-synchronous kernel (rows.hip) takes the batches k_cells / k_fused-64 would: WAL frames (not table-copy rows), no table in
-  //      SyncDone state (ownership would need the transaction look-back before the slots), tables of up to 64 columns
-  b->used_rows = false;
-  if (kernel != 0 || c->fused_kernel == 4) {
-    uint32_t maxh = 1, maxh_old = 0, maxrow = 16;
-    bool ok = !b->copy.active && !(p.flags & kDecCopyRows) && !b->any_sync_done && !(c->fused_dbg & ~(8u | 32u)) && q.side_bytes != 0 && ((uintptr_t)p.in & 15) == 0 &&
-              widest <= etlg_k_rows_max_cols() && !b->no_rows && c->rows_mode != 0 && (c->fused_kernel < 0 || c->fused_kernel == 4);
-    for (int32_t li : c->last_live) {
-      const SlotHost& sh = *c->slots[(size_t)li];
-      uint32_t nh = 0, nhi = 0;
-      for (auto& sc : sh.cols) if (!heapless_class(sc.type_class)) { nh++; if (sc.identity) nhi++; }
-      maxh = std::max(maxh, nh); maxh_old = std::max(maxh_old, nhi);
-      maxrow = std::max<uint32_t>(maxrow, sh.desc.row_bytes_full + std::max<uint32_t>(sh.desc.row_bytes_key, sh.desc.n_ident == sh.desc.n_cols ? sh.desc.row_bytes_full : 0u));
-    }
-    if (maxh > etlg_k_rows_max_heap_cols()) ok = false;
-    if (ok && c->fused_kernel != 4 && c->rows_skip) { c->rows_skip--; ok = false; }   // backing off after a batch that was handed back
-    if (ok) {
-      // frames per tile x tiles per CU: the pair that keeps the most FRAMES in flight on a CU (a tile is a chain of latencies: what a CU
-      // delivers is frames in flight / a tile's time) — 64 frames at four tiles when that fits; 56 or 48 frames when eight fewer lanes buy
-      // a fourth tile (cfg5 after its window was sized by its largest tile: 64 x 3 = 192 frames against 56 x 4 = 224); 16-frame tiles
-      // for 1.5 KB frames. The window then takes what its share of the LDS leaves.
-      // (LDS is handed out in granules: a workgroup's static + dynamic bytes are rounded up, so the budget per workgroup is rounded DOWN)
-      const uint64_t stat = etlg_k_rows_static_lds();
-      auto budget = [](uint64_t wgs) { return ((160 * 1024) / wgs / 1280) * 1280; };
-      uint32_t cf = 64;
-      uint64_t need = 0, tabb = 0;
-      const uint64_t max_wgs = 4ull * (uint64_t)etlg_k_rows_waves_per_simd() / (uint64_t)etlg_k_rows_waves();   // (the register file: ETLG_ROWS_MINBLOCKS waves per SIMD)
-      const uint32_t cf_forced = c->rows_cf;   // (ETLG_ROWS_CF, experiments / tests: 8 .. 64, a multiple of 8)
-      auto need_of = [&](uint32_t f, uint64_t& tb) {
-        tb = etlg_k_rows_table_bytes(maxh_old, maxh, widest, f);
-        return stat + q.side_bytes + tb + std::max<uint64_t>((uint64_t)f * avg * 9 / 8 + 1024, c->rows_win_min * f / 64 + 64);
-      };
-      auto wgs_of = [&](uint64_t nd) { uint64_t w = 0; for (uint64_t k = 1; k <= max_wgs; k++) if (nd <= budget(k)) w = k; return w; };
-      {
-        uint64_t best = 0;
-        for (uint32_t f = 64; f >= 16; f -= 8) {
-          if (cf_forced >= 8 && cf_forced <= 64 && !(cf_forced & 7u) && f != cf_forced && cf_forced >= 16) continue;
-          uint64_t tb;
-          const uint64_t nd = need_of(f, tb);
-          if ((uint64_t)f * maxrow > 0x3FFFFull || nd > 150 * 1024) continue;
-          const uint64_t w = wgs_of(nd);
-          const uint64_t score = (uint64_t)f * w / (w == 1 ? 2 : 1);   // (one tile per CU is four waves on 256 lanes of SIMD: last resort)
-          if (score >= best && score) { best = score; cf = f; }        // (a tie goes to the smaller tile: more waves per CU)
-        }
-        if (cf_forced >= 8 && cf_forced < 16 && !(cf_forced & 7u)) cf = cf_forced;
-        need = need_of(cf, tabb);
-      }
-      if (c->rows_trace && (need > 150 * 1024 || (uint64_t)cf * maxrow > 0x3FFFFull)) fprintf(stderr, "[rows] not taken: cf %u need %llu maxrow %u widest %u avg %llu\n", cf, (unsigned long long)need, maxrow, widest, (unsigned long long)avg);
-      if (need > 150 * 1024 || (uint64_t)cf * maxrow > 0x3FFFFull) ok = false;   // (a tile's piece of the fixed arena is addressed by 16-bit dword offsets)
-      else {
-        const uint64_t wgs = std::max<uint64_t>(1, wgs_of(need));
-        const uint64_t tot = (budget(wgs) - stat) & ~15ull;
-        q.blk = cf; q.maxc = widest; q.rows_maxh_old = maxh_old; q.rows_maxh = maxh;
-        q.lds_bytes = (uint32_t)std::min<uint64_t>(tot, 150 * 1024);
-        q.seq_lookback = 0; q.in_aligned = 1; q.dbg = c->fused_dbg; q.copy_rel = 0;
-        q.ntiles = (nf + cf - 1) / cf;
-        RC(take_tile_descriptors(c, q));
-        if (c->rows_lds >= 0) q.lds_bytes = (uint32_t)c->rows_lds;   // (ETLG_ROWS_LDS, experiments)
-        if (c->rows_trace) fprintf(stderr, "[rows] cf %u maxc %u maxh %u lds %u (static %llu) side %u tables %llu need %llu (window min %llu, avg frame %llu) -> %d workgroups per CU by the runtime's count, %llu planned\n", cf, widest, maxh, q.lds_bytes, (unsigned long long)stat, q.side_bytes, (unsigned long long)tabb, (unsigned long long)need, (unsigned long long)c->rows_win_min, (unsigned long long)avg, etlg_k_rows_occupancy(q.lds_bytes), (unsigned long long)wgs);
-        launch(c, kRows, p);
-        launch_chk_cells(c, b);
-        b->used_fused = true; b->used_cells = false; b->used_rows = true;
-        return ETLG_OK;
-      }
-    }
-  }
   const bool use_cells = kernel == 2;
   q.blk = kernel == 0 ? 256u : 64u;
-  q.maxc = widest;
-  // LDS window per tile: the average tile plus a margin; a tile that does not fit reads the input in place
-  uint64_t cap = kernel == 1 ? (uint64_t)q.blk * avg * 5 / 4 + 2048 : (uint64_t)q.blk * avg * 9 / 8 + 1024;
-  if (c->lds_margin_pct >= 0) cap = (uint64_t)q.blk * avg * (100 + (uint64_t)c->lds_margin_pct) / 100 + 1024;   // (ETLG_LDS_MARGIN_PCT)
-  cap = (cap + 255) & ~255ull;
-  if (use_cells) {
-    cap = direct ? etlg_k_copy_cells_lds(widest, (uint32_t)cap) : std::max<uint64_t>(cap + etlg_k_cells_table_bytes(widest), etlg_k_cells_lds_floor(widest));
-    // LDS decides how many workgroups share a CU (160 KB; the register file allows four): the window takes whatever the
-    // allocation can grow by without losing one, so fewer tiles overflow it
-    const uint64_t stat = direct ? etlg_k_copy_cells_static_lds(widest) : etlg_k_cells_static_lds(widest);
-    const uint64_t wgs = std::max<uint64_t>(1, std::min<uint64_t>(4, (160 * 1024) / (cap + q.side_bytes + stat)));
-    cap = std::max<uint64_t>(cap, ((160 * 1024) / wgs - 512 - stat - q.side_bytes) & ~255ull);
-  }
-  cap = std::min<uint64_t>(cap + q.side_bytes, 150 * 1024);
-  q.lds_bytes = (uint32_t)cap;
+  q.maxc = f.widest;
+  const uint64_t stat = !use_cells ? 0 : f.direct ? etlg_k_copy_cells_static_lds(f.widest) : etlg_k_cells_static_lds(f.widest);
+  q.lds_bytes = decode_plan::generic_window(kernel, f.avg, c->lds_margin_pct, f.direct, q.side_bytes, use_cells && !f.direct ? etlg_k_cells_table_bytes(f.widest) : 0,
+                                            use_cells && !f.direct ? etlg_k_cells_lds_floor(f.widest) : 0, stat, [&](uint32_t window) { return etlg_k_copy_cells_lds(f.widest, window); });
   q.seq_lookback = (b->any_sync_done || (c->fused_dbg & 32)) ? 1u : 0u;
-  q.ntiles = (nf + q.blk - 1) / q.blk;
+  q.ntiles = (p.nframes + q.blk - 1) / q.blk;
   q.in_aligned = ((uintptr_t)p.in & 15) == 0;
   q.dbg = c->fused_dbg;
   RC(take_tile_descriptors(c, q));
-  q.copy_rel = direct ? b->copy.rel_id : 0u;
-  launch(c, direct ? kCopyCells : use_cells ? kCells : kFused, p);
+  q.copy_rel = f.direct ? b->copy.rel_id : 0u;
+  launch(c, f.direct ? kCopyCells : use_cells ? kCells : kFused, p);
   launch_chk_cells(c, b);
   b->used_fused = true;
   b->used_cells = use_cells;
   return ETLG_OK;
+}
+
+int32_t enqueue_single(etlg_ctx* c, etlg_batch* b, int level) {
+  SlowScope slow_scope_enqueue_single(c, "enqueue_single");
+  if (b->scan_chained && level != 0) RC(resolve_scan_count(c, b));   // (only the plan kernels read the count on the device)
+  b->level = level;
+  b->used_rows = false;
+  if (level == 0) return enqueue_plan(c, b);
+  GenericFacts f;
+  RC(generic_facts(c, b, f));
+  bool any_var = false;   // a table the batch may carry has TEXT / NUMERIC / ... columns: one lane per frame crawls on those
+  for (int32_t li : c->last_live) for (auto& sc : c->slots[(size_t)li]->cols) if (!fixed_class(sc.type_class)) any_var = true;
+  const int kernel = decode_plan::generic_kernel(f.avg, any_var, f.cells_ok, c->fused_kernel, f.direct);
+  if (kernel != 0 || c->fused_kernel == 4) {
+    bool taken = false;
+    RC(try_enqueue_rows(c, b, f, &taken));
+    if (taken) return ETLG_OK;
+  }
+  return enqueue_generic(c, b, f, kernel);
 }
 
 // The control pre-pass, device half: classify + transaction scan + compaction of the R / M frames (k_ctrl_list also gathers their
@@ -686,7 +674,7 @@ int32_t standard_path(etlg_ctx* c, etlg_batch* b) {
   ht_mark(c, 5);
   // (always the generic kernel: the fixed-width plan behind a control pass gave wrong ddl_fixed batches on the MI355X and gained one batch
   // per stream — measured and dropped in round 6, profiles/r06zw_plan_behind_control_dropped.txt)
-  if (nf && !b->host_err_code && !c->force_multipass && b->len < (1ull << 31)) { const int32_t rc = enqueue_single(c, b, 1); ht_mark(c, 6); return rc; }
+  if (nf && !b->host_err_code && single_pass_ok(c, b->len)) { const int32_t rc = enqueue_single(c, b, 1); ht_mark(c, 6); return rc; }
   if (p.carry) {
     // chained to a batch in flight and in need of the multi-pass kernels (the host control plane failed on one of its frames): they
     // take the carried state from the host. The batch is marked "did not run" — the batches behind it stop at that — and is decoded
@@ -920,7 +908,7 @@ int32_t second_attempts(etlg_ctx* c, etlg_batch* b, FinishState& st) {
     st.decoded_again = true;
     DecParams& p = b->params;
     p.carry = nullptr; p.flags &= ~kDecLateCarry;
-    p.in_txn = c->in_txn; p.final_lsn = c->final_lsn; p.next_ord = c->next_ord;
+    carried_from_host(c, p);
     // the batch is decoded against the side inputs of NOW: its view lists the schema slots of now (an optimistic ASYNC batch queued
     // behind one that carried the stream's first Relation frames was enqueued when there were none: its events named slots its view
     // did not list — found by tools/async_fuzz.py). A control pass below (standard_path) sets the count again behind its own frames.

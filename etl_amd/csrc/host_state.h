@@ -35,6 +35,7 @@
 #include "dev_types.h"
 #include "scratch_layout.h"
 #include "handoff_plan.h"   // SlotHost, and what the hand-off builders plan on the host alone
+#include "decode_plan.h"    // what the decode decides before it touches the device: launch geometry, kernel and tile choice, windows, the side set's layout
 
 using namespace etlg;
 

@@ -407,7 +407,7 @@ struct StreamQ {
   uint64_t enq = 0, completed = 0;   // operations enqueued / completed so far
   bool running = false;              // an operation of this stream is executing (or suspended in a poll): the next one must not start
 };
-struct Ev { StreamQ* s = nullptr; uint64_t seq = 0; };
+struct Ev { StreamQ* s = nullptr; uint64_t seq = 0; unsigned no = 0; };   // no: the event's number in the call log
 std::map<void*, StreamQ*> g_streams;   // by hipStream_t (nullptr = the null stream)
 std::vector<StreamQ*> g_all;           // every queue ever made (handles of destroyed streams are forgotten, their queues stay: events point at them)
 std::map<uintptr_t, size_t> g_pinned;  // hipHostMalloc blocks: start -> bytes
@@ -554,15 +554,46 @@ void lazy_poll_progress() {
 }  // namespace
 
 // ETLG_SIMT_CALLS (simt.h). launch: a = grid x << 32 | grid y, b = block, c = dynamic LDS bytes; copies: a = bytes, b = hipMemcpyKind; memset: a = bytes, b = value
-void call_log(const char* what, unsigned long long a, unsigned long long b, unsigned long long c, const char* kernel) {
+const char kNoStream = 0;
+namespace {
+FILE* call_file() {
   static FILE* const f = [] { const char* p = getenv("ETLG_SIMT_CALLS"); return p && *p ? fopen(p, "a") : (FILE*)nullptr; }();
+  return f;
+}
+std::map<const void*, unsigned> g_stream_no;   // by handle; a destroyed stream's handle is forgotten (its address may come back)
+unsigned g_streams_made = 0, g_events_made = 0;
+void put_stream(FILE* f, const void* s) {   // " stream s<n>" | " stream null" | nothing
+  if (s == &kNoStream) return;
+  if (!s) { fputs(" stream null", f); return; }
+  auto it = g_stream_no.find(s);
+  if (it == g_stream_no.end()) it = g_stream_no.emplace(s, ++g_streams_made).first;   // (a stream the library did not create: numbered when it is first seen)
+  fprintf(f, " stream s%u", it->second);
+}
+}  // namespace
+void call_log(const char* what, unsigned long long a, unsigned long long b, unsigned long long c, const char* kernel, const void* stream) {
+  FILE* const f = call_file();
   if (!f) return;
   static const char* const dir[] = {"h2h", "h2d", "d2h", "d2d", "default"};
-  if (kernel) fprintf(f, "%s %s grid %llux%llu block %llu lds %llu\n", what, kernel, a >> 32, a & 0xFFFFFFFFull, b, c);
-  else if (what[0] == 'm' && what[3] == 'c') fprintf(f, "%s %llu %s\n", what, a, dir[b < 5 ? b : 4]);   // memcpy, memcpy_async
-  else if (what[0] == 'm' && what[3] == 's') fprintf(f, "%s %llu value %llu\n", what, a, b);           // memset_async
-  else if (a) fprintf(f, "%s %llu\n", what, a);
-  else fprintf(f, "%s\n", what);
+  if (kernel) fprintf(f, "%s %s grid %llux%llu block %llu lds %llu", what, kernel, a >> 32, a & 0xFFFFFFFFull, b, c);
+  else if (what[0] == 'm' && what[3] == 'c') fprintf(f, "%s %llu %s", what, a, dir[b < 5 ? b : 4]);   // memcpy, memcpy_async
+  else if (what[0] == 'm' && what[3] == 's') fprintf(f, "%s %llu value %llu", what, a, b);           // memset_async
+  else if (a) fprintf(f, "%s %llu", what, a);
+  else fprintf(f, "%s", what);
+  put_stream(f, stream);
+  fputc('\n', f);
+  fflush(f);
+}
+void call_log_stream_created(void* stream) {
+  g_stream_no[stream] = ++g_streams_made;
+  call_log("stream_create", 0, 0, 0, nullptr, stream);
+}
+void call_log_event(const char* what, void* ev, const void* stream) {
+  FILE* const f = call_file();
+  if (!f) return;
+  if (ev && what[6] == 'c') ((Ev*)ev)->no = ++g_events_made;   // event_create
+  if (ev) fprintf(f, "%s e%u", what, ((Ev*)ev)->no); else fprintf(f, "%s e-none", what);
+  put_stream(f, stream);
+  fputc('\n', f);
   fflush(f);
 }
 
@@ -581,6 +612,7 @@ void stream_enqueue(void* stream, void (*fn)(void*), void* arg, void (*drop)(voi
 }
 void stream_sync(void* stream) { if (lazy_mode()) { StreamQ* S = sq(stream); force_or_die(S, S->enq, "hipStreamSynchronize"); } }
 void stream_destroy(void* stream) {
+  g_stream_no.erase(stream);
   if (!lazy_mode()) return;
   auto it = g_streams.find(stream);
   if (it == g_streams.end()) return;

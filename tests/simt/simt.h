@@ -93,15 +93,20 @@ bool host_is_pinned(const void* p);
 void memcpy_async(void* d, const void* s, size_t n, int kind, void* stream);
 void memset_async(void* d, int v, size_t n, void* stream);
 // ETLG_SIMT_CALLS=<path> (read once, off by default): one line per runtime call the host code makes is appended to the file — the call's name, its
-// byte count or grid x block, a copy's direction, a launch's kernel as the launch site names it; no pointer values, so two builds that make the same calls write the same file
-void call_log(const char* what, unsigned long long a = 0, unsigned long long b = 0, unsigned long long c = 0, const char* kernel = nullptr);
+// byte count or grid x block, a copy's direction, a launch's kernel as the launch site names it; no pointer values, so two builds that make the same calls write the same file.
+// Launches, asynchronous copies, memsets and stream syncs name their stream (`stream s<n>`, numbered by order of creation; `stream null`), and
+// stream_create, event_create, event_record, stream_wait_event and event_sync write a line each (events as `e<n>`, by order of creation too).
+extern const char kNoStream;   // (the `stream` of a call that has none)
+void call_log(const char* what, unsigned long long a = 0, unsigned long long b = 0, unsigned long long c = 0, const char* kernel = nullptr, const void* stream = &kNoStream);
+void call_log_stream_created(void* stream);
+void call_log_event(const char* what, void* ev, const void* stream = &kNoStream);
 
 template <class... KArgs, class... Args>
 void launch(const char* name, void (*k)(KArgs...), dim3 g, dim3 b, size_t lds, void* stream, Args&&... args) {
   using Tup = std::tuple<std::decay_t<KArgs>...>;
   struct Ctx { void (*k)(KArgs...); Tup t; uint32_t grid, block, gx; size_t lds; };
   Ctx* c = new Ctx{k, Tup(std::forward<Args>(args)...), g.x * g.y, b.x, g.x, lds};   // the arguments are captured by value at launch, as on the GPU
-  call_log("launch", (unsigned long long)g.x << 32 | g.y, b.x, lds, name);
+  call_log("launch", (unsigned long long)g.x << 32 | g.y, b.x, lds, name, stream);
   stream_enqueue(stream, [](void* p) { Ctx* c = (Ctx*)p; run_grid(c->grid, c->block, c->lds, [](void* q) { Ctx* c2 = (Ctx*)q; std::apply(c2->k, c2->t); }, c, c->gx); },
                  c, [](void* p) { delete (Ctx*)p; });
 }
@@ -212,19 +217,19 @@ static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { simt:
 static inline hipError_t hipHostFree(void* p) { simt::call_log("host_free"); simt::device_sync(); simt::host_unregister(p); free(p); return hipSuccess; }
 // hipMemcpy: the copy runs on the null stream and the host waits for it (the library's streams are non-blocking: nothing else is waited for)
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { simt::call_log("memcpy", n, k); simt::memcpy_async(d, s, n, (int)k, nullptr); simt::stream_sync(nullptr); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) { simt::call_log("memcpy_async", n, k); simt::memcpy_async(d, s, n, (int)k, (void*)st); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { simt::call_log("memset_async", n, (unsigned)v); simt::memset_async(d, v, n, (void*)st); return hipSuccess; }
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)calloc(1, 8); return hipSuccess; }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) { simt::call_log("memcpy_async", n, k, 0, nullptr, (void*)st); simt::memcpy_async(d, s, n, (int)k, (void*)st); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { simt::call_log("memset_async", n, (unsigned)v, 0, nullptr, (void*)st); simt::memset_async(d, v, n, (void*)st); return hipSuccess; }
+static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)calloc(1, 8); simt::call_log_stream_created((void*)*s); return hipSuccess; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = 0; return hipSuccess; }
-static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)calloc(1, 8); return hipSuccess; }
+static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)calloc(1, 8); simt::call_log_stream_created((void*)*s); return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t s) { simt::stream_destroy((void*)s); free(s); return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t s) { simt::call_log("stream_sync"); simt::stream_sync((void*)s); return hipSuccess; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)simt::event_create(); return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s = nullptr) { simt::event_record((void*)e, (void*)s); return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t s) { simt::call_log("stream_sync", 0, 0, 0, nullptr, (void*)s); simt::stream_sync((void*)s); return hipSuccess; }
+static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)simt::event_create(); simt::call_log_event("event_create", (void*)*e); return hipSuccess; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s = nullptr) { simt::call_log_event("event_record", (void*)e, (void*)s); simt::event_record((void*)e, (void*)s); return hipSuccess; }
 enum { hipEventDisableTiming = 2 };
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)simt::event_create(); return hipSuccess; }
-static inline hipError_t hipEventSynchronize(hipEvent_t e) { simt::event_sync((void*)e); return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { simt::stream_wait_event((void*)s, (void*)e); return hipSuccess; }
+static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)simt::event_create(); simt::call_log_event("event_create", (void*)*e); return hipSuccess; }
+static inline hipError_t hipEventSynchronize(hipEvent_t e) { simt::call_log_event("event_sync", (void*)e); simt::event_sync((void*)e); return hipSuccess; }
+static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { simt::call_log_event("stream_wait_event", (void*)e, (void*)s); simt::stream_wait_event((void*)s, (void*)e); return hipSuccess; }
 static inline hipError_t hipEventDestroy(hipEvent_t e) { simt::event_destroy((void*)e); return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.0f; return hipSuccess; }
 static inline hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }

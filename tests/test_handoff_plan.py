@@ -26,7 +26,8 @@ def test_handoff_plan_header_stands_alone():
     assert "etlg_ctx" not in "\n".join(line.split("//")[0] for line in text.split("\n"))
     assert '#include "handoff_plan.h"' in open(os.path.join(CSRC, "host_state.h")).read()
     host = open(os.path.join(CSRC, "host.cpp")).read()
-    assert host.index('#include "host_handoff.inc"') < host.index('#include "host_handoff_columns.inc"') < host.index('#include "host_handoff_rows.inc"')
+    assert (host.index('#include "host_decode.inc"') < host.index('#include "host_handoff.inc"') < host.index('#include "host_handoff_columns.inc"')
+            < host.index('#include "host_handoff_rows.inc"') < host.index('#include "host_orchestrate.inc"'))
 
 
 def test_builder_bodies_stay_short():

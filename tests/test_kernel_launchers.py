@@ -15,7 +15,7 @@ from etl_amd import build  # noqa: E402
 
 CSRC = os.path.join(ROOT, "etl_amd", "csrc")
 HANDOFF_UNITS = ["columns.hip", "rowformats.hip", "rowformats_dl.hip", "finish.hip", "check.hip", "fingerprint.hip"]
-HOST_FILES = ["host.cpp", "host_control.inc", "host_handoff.inc", "host_handoff_columns.inc", "host_handoff_rows.inc", "host_orchestrate.inc"]
+HOST_FILES = ["host.cpp", "host_control.inc", "host_decode.inc", "host_handoff.inc", "host_handoff_columns.inc", "host_handoff_rows.inc", "host_orchestrate.inc"]
 
 
 def _read(csrc, name):
