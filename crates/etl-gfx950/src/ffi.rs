@@ -299,6 +299,46 @@ pub struct etlg_payload_info {
     pub mismatch_event: u64,
 }
 
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_outline_pass {
+    pub first_event: u64,
+    pub data_end: u64,
+    pub rel_end: u64,
+    pub end_event: u64,
+    pub range: u64,
+    pub trunc_first: u64,
+    pub n_trunc: u64,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_outline_trunc {
+    pub table_id: u32,
+    pub schema_slot: u32,
+    pub event: u64,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_outline_slot {
+    pub rows: [u64; 6],
+    pub first: [u64; 6],
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_outline_info {
+    pub n_passes: u64,
+    pub n_trunc: u64,
+    pub n_relations: u64,
+    pub n_rows: u64,
+    pub n_ranges: u64,
+    pub bad_cut: u64,
+    pub status: u32,
+    pub _pad: u32,
+}
+
 #[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
@@ -342,6 +382,9 @@ pub const ETLG_PK_DELETE: u32 = 2;
 pub const ETLG_PK_COPY: u32 = 3;
 pub const ETLG_PM_OK: u32 = 0;
 pub const ETLG_PM_MISMATCH: u32 = 1;
+pub const ETLG_OL_RELATIONS_INLINE: u32 = 1;
+pub const ETLG_OL_OK: u32 = 0;
+pub const ETLG_OL_BAD_CUTS: u32 = 1;
 pub const ETLG_DL_TUPLES: i32 = 0;
 pub const ETLG_DL_PREDICATES: i32 = 1;
 pub const ETLG_DL_UPDATES: i32 = 3;
@@ -547,6 +590,25 @@ extern "C" {
         sums_out: *mut etlg_payload_sums,
         hist_out: *mut u64,
         info: *mut etlg_payload_info,
+    ) -> i32;
+    pub fn etlg_batch_outline(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        first: u64,
+        end: u64,
+        cuts: *const u64,
+        n_cuts: u64,
+        cuts_on_device: u32,
+        opts: u32,
+        flags: u32,
+        passes_out: *mut etlg_outline_pass,
+        ends_out: *mut u64,
+        touched_out: *mut u64,
+        passes_cap: u64,
+        trunc_out: *mut etlg_outline_trunc,
+        trunc_cap: u64,
+        slots_out: *mut etlg_outline_slot,
+        info: *mut etlg_outline_info,
     ) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;
     pub fn etlg_ctx_slots(ctx: *const etlg_ctx, n_slots: *mut u32, slots: *mut *const etlg_slot_desc) -> i32;

@@ -303,6 +303,44 @@ impl GpuDecoder {
         Ok((out, info))
     }
 
+    /// The pass plan of a sink's `write_events` loop over events `[first, end)` of a device-resident batch, built on the device
+    /// (etlg_batch_outline): where the passes of the loop all five destinations share end (clickhouse/core.rs:1063-1164), which slots
+    /// each pass holds rows of, where its Relation events `[data_end, rel_end)` and its Truncates are, and what every slot holds by kind.
+    /// `cuts`: the range ends `GpuDecoder::cuts` returned, empty for one range; `opts`: `ETLG_OL_RELATIONS_INLINE` for Iceberg's loop. At
+    /// most `passes_cap` passes and `trunc_cap` truncate entries come back; `info.n_passes` / `info.n_trunc` are the full counts — call
+    /// again with larger caps. `info.status == ETLG_OL_BAD_CUTS` comes with nothing but `info.bad_cut`.
+    pub fn outline(&mut self, batch: *mut etlg_batch, first: u64, end: u64, cuts: &[u64], opts: u32, passes_cap: usize, trunc_cap: usize) -> EtlResult<Outline> {
+        let mut view = std::mem::MaybeUninit::<etlg_batch_view>::uninit();
+        unsafe { etlg_batch_view_get(batch, view.as_mut_ptr()) };
+        let n_slots = unsafe { view.assume_init() }.n_slots as usize;
+        let words = (n_slots + 63) / 64;
+        let mut out = Outline {
+            passes: vec![etlg_outline_pass { first_event: 0, data_end: 0, rel_end: 0, end_event: 0, range: 0, trunc_first: 0, n_trunc: 0 }; passes_cap],
+            ends: vec![0u64; passes_cap],
+            touched: vec![0u64; passes_cap * words],
+            words,
+            truncates: vec![etlg_outline_trunc { table_id: 0, schema_slot: 0, event: 0 }; trunc_cap],
+            slots: vec![etlg_outline_slot { rows: [0; 6], first: [u64::MAX; 6] }; n_slots],
+            info: etlg_outline_info { n_passes: 0, n_trunc: 0, n_relations: 0, n_rows: 0, n_ranges: 0, bad_cut: 0, status: 0, _pad: 0 },
+        };
+        fn ptr<T>(v: &mut Vec<T>) -> *mut T { if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() } }
+        let rc = unsafe {
+            etlg_batch_outline(
+                self.ctx, batch, first, end, if cuts.is_empty() { std::ptr::null() } else { cuts.as_ptr() }, cuts.len() as u64, 0, opts, 0,
+                ptr(&mut out.passes), ptr(&mut out.ends), ptr(&mut out.touched), passes_cap as u64, ptr(&mut out.truncates), trunc_cap as u64, ptr(&mut out.slots), &mut out.info,
+            )
+        };
+        if rc != ETLG_OK {
+            return Err(self.last_error());
+        }
+        let (p, k) = (out.info.n_passes.min(passes_cap as u64) as usize, out.info.n_trunc.min(trunc_cap as u64) as usize);
+        out.passes.truncate(p);
+        out.ends.truncate(p);
+        out.touched.truncate(p * words);
+        out.truncates.truncate(k);
+        Ok(out)
+    }
+
     /// Source payload accounting of a device-resident batch, on the device (etlg_batch_payload), as plain values: per event the value
     /// bytes of its message (what `StreamingPayloadMetadata::{insert,update,delete}` is built from, apply.rs:2459-2463; the kind is the
     /// event's), per range of `cuts` the merged bytes and rows per kind (what `EventBatch::push` accumulates, apply.rs:656-658; rows == 0
@@ -331,6 +369,32 @@ impl GpuDecoder {
             )
         };
         if rc == ETLG_OK { Ok(acc) } else { Err(self.last_error()) }
+    }
+}
+
+/// What `GpuDecoder::outline` returns. `touched[p * words + s / 64]` holds bit `s % 64` when pass `p` has rows of slot `s`.
+pub struct Outline {
+    pub passes: Vec<etlg_outline_pass>,
+    pub ends: Vec<u64>,
+    pub touched: Vec<u64>,
+    pub words: usize,
+    pub truncates: Vec<etlg_outline_trunc>,
+    pub slots: Vec<etlg_outline_slot>,
+    pub info: etlg_outline_info,
+}
+
+impl Outline {
+    /// The truncate entries pass `p` acts on: the first entry per table, as `truncate_schemas.entry(id).or_insert(schema)` keeps it
+    /// (clickhouse/core.rs:1148-1155). Entries beyond `trunc_cap` are not there to be looked at.
+    pub fn truncated_tables(&self, p: usize) -> Vec<etlg_outline_trunc> {
+        let (lo, n) = (self.passes[p].trunc_first as usize, self.passes[p].n_trunc as usize);
+        let mut out: Vec<etlg_outline_trunc> = Vec::new();
+        for t in self.truncates.iter().skip(lo).take(n) {
+            if !out.iter().any(|o| o.table_id == t.table_id) {
+                out.push(*t);
+            }
+        }
+        out
     }
 }
 

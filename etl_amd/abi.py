@@ -154,6 +154,22 @@ class PayloadInfo(C.Structure):   # etlg_payload_info
                 ("mismatch_event", C.c_uint64)]
 
 
+class OutlinePass(C.Structure):   # etlg_outline_pass
+    _fields_ = [(n, C.c_uint64) for n in ("first_event", "data_end", "rel_end", "end_event", "range", "trunc_first", "n_trunc")]
+
+
+class OutlineTrunc(C.Structure):   # etlg_outline_trunc
+    _fields_ = [("table_id", C.c_uint32), ("schema_slot", C.c_uint32), ("event", C.c_uint64)]
+
+
+class OutlineSlot(C.Structure):   # etlg_outline_slot
+    _fields_ = [("rows", C.c_uint64 * 6), ("first", C.c_uint64 * 6)]
+
+
+class OutlineInfo(C.Structure):   # etlg_outline_info
+    _fields_ = [(n, C.c_uint64) for n in ("n_passes", "n_trunc", "n_relations", "n_rows", "n_ranges", "bad_cut")] + [("status", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class FinishStats(C.Structure):   # etlg_finish_stats
     _fields_ = [(n, C.c_uint64) for n in ("deferred_seen", "arrays_typed", "floats_settled", "left_deferred", "heap_bytes_added")]
 
@@ -163,6 +179,8 @@ CH_MERGE_TREE, CH_REPLACING_MERGE_TREE = 0, 1
 RB_OK, RB_NEEDS_HOST = 0, 3
 PK_INSERT, PK_UPDATE, PK_DELETE, PK_COPY = range(4)
 PM_OK, PM_MISMATCH = 0, 1
+OL_RELATIONS_INLINE = 1
+OL_OK, OL_BAD_CUTS = 0, 1
 DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)

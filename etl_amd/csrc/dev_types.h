@@ -348,6 +348,31 @@ struct CutJob {            // write_events cut points (etlg_batch_cuts: k_cut_* 
   unsigned long long* cuts; uint64_t cuts_cap;
 };
 
+// The write_events pass plan (etlg_batch_outline: k_ol_* in finish.hip). k below is a LOCAL index, event - first. The host has set the
+// scratch parts up: bitmap, crow, touched and hdr zero; bad, cfirst, de and re all ones. Nothing leaves the scratch before k_ol_fix, and
+// no kernel behind k_ol_mark writes anything once *bad names a cut.
+enum : uint32_t { OL_H_PASSES = 0, OL_H_TRUNC = 1, OL_H_REL = 2, OL_H_ROWS = 3, OL_H_RANGES = 4, OL_H_WORDS = 5 };
+constexpr uint32_t kOlLdsSlots = 64;   // distinct slots a tile's census aggregates in LDS; the rest goes to global atomics one by one
+struct OutlineJob {
+  const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint32_t* ev_table; const uint64_t* ev_body; const uint8_t* fixed;
+  uint64_t first, n;                  // the window [first, first + n)
+  const unsigned long long* cuts; uint64_t n_cuts;
+  uint32_t inline_rel;                // ETLG_OL_RELATIONS_INLINE: 'R' is class 0
+  uint32_t n_slots, W;                // slots the census covers; touched words per pass
+  uint32_t tile, n_tiles;             // events per tile; ceil(n / tile)
+  unsigned long long* hdr;            // OL_H_*
+  unsigned long long* bad;            // the lowest index of a bad cut, ~0 none
+  uint32_t* bitmap;                   // bit k: a write_events range starts at local event k (n / 32 + 1 words)
+  unsigned long long* tsum;           // per tile: pass starts, truncate entries, Relations, rows; after k_ol_scan those in front of the tile
+  unsigned long long* crow; unsigned long long* cfirst;   // the census, n_slots x 6 each
+  unsigned long long* de; unsigned long long* re;   // per written pass: data_end / rel_end where a lane raised the class, else ~0 (null without passes_out)
+  unsigned long long* tf;             // passes_cap + 1: truncate entries in front of the pass (null without passes_out)
+  unsigned long long* touched;        // passes_cap x W, k_ol_fix copies the written passes out (null without touched_out)
+  unsigned long long* passes_out; unsigned long long* ends_out; unsigned long long* touched_out; uint64_t passes_cap;   // 7 words per pass
+  unsigned long long* trunc_out; uint64_t trunc_cap;                                                                    // 2 words per entry
+  unsigned long long* slots_out;      // 12 words per slot
+};
+
 // Source payload accounting (etlg_batch_payload). The frame side (k_payf_* in kernels.hip) measures every row message and lists the
 // frames that take a transaction ordinal; the event side (k_paye_* in finish.hip) joins every event to its frame through that list and
 // sums the ranges. Channels: 0 Insert, 1 Update, 2 Delete; a table-copy batch has channel 0 alone and reports it as ETLG_PK_COPY.

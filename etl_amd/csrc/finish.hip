@@ -175,6 +175,248 @@ __global__ __launch_bounds__(256) void k_cuts_locate(const unsigned long long* c
   rows_out[k] = n_rows ? cut_lower_bound(row_event, 0, n_rows - 1, cuts[k]) : 0;
 }
 
+// ---- the write_events pass plan (etlg_batch_outline, include/etlg.h: the pass rule is stated there). The sequential loop of the sinks —
+// rows until a Relation or Truncate, the Relation run, the Truncate run, again — becomes a flag per event: a pass starts where a
+// write_events range starts (a bitmap of the cuts, k_ol_mark) and where the class falls against the event before, which global memory
+// holds, so no tile needs a carry. Launches, none of which exchanges a word between its workgroups: the cuts checked and marked
+// (k_ol_mark), per tile the starts, truncate entries, Relations and rows plus the slot census (k_ol_tiles), their scan by one workgroup
+// (k_ol_scan), a pass index and a truncate position per event (k_ol_write), a thread per written pass for what no single event knows
+// (k_ol_fix). The caps are the caller's, so nothing is read back in between; every output is written from scratch by k_ol_write and
+// k_ol_fix, which do nothing once a cut is bad. Every loop runs to a launch parameter: tile / 256 chunks, 64 table entries, log2(n_cuts)
+// steps of a search, W words, at most trunc_cap entries of a body.
+constexpr uint32_t kOlFree = ~0u;
+constexpr uint32_t kOlTouchWords = 16;          // touched words of the pass a tile continues that k_ol_write gathers in LDS (1 024 slots)
+constexpr uint64_t kOlLow = (1ull << 48) - 1;  // a chunk's truncate entries (256 x u32) ride below its starts in one scanned word
+
+DEV uint32_t ol_class(uint32_t kind, uint32_t inline_rel) { return kind == 'T' ? 2u : (kind == 'R' && !inline_rel) ? 1u : 0u; }
+DEV bool ol_is_row(uint32_t kind) { return kind == 'I' || kind == 'U' || kind == 'D'; }
+DEV uint32_t ol_category(uint32_t kind, uint32_t fl) {
+  if (kind == 'I') return 0u;
+  if (kind == 'U') return (fl & ETLG_FLAG_PARTIAL) ? 2u : 1u;
+  const uint32_t ok = fl & 3u;
+  return ok == ETLG_OLD_FULL ? 3u : ok == ETLG_OLD_KEY ? 4u : 5u;
+}
+
+// local event k < n: its kind and class, whether a pass starts at it, and the class it follows inside its pass (0 at a start)
+struct OlEvent { uint32_t kind, cls, after; bool start; };
+DEV OlEvent ol_event(const OutlineJob& j, uint64_t k) {
+  OlEvent e;
+  e.kind = j.ev_kind[j.first + k];
+  e.cls = ol_class(e.kind, j.inline_rel);
+  e.after = k ? ol_class(j.ev_kind[j.first + k - 1], j.inline_rel) : 0u;   // (ev_kind[first - 1] is never read)
+  e.start = k == 0 || ((j.bitmap[k >> 5] >> (k & 31)) & 1u) || e.cls < e.after;
+  if (e.start) e.after = 0u;
+  return e;
+}
+
+__global__ __launch_bounds__(256) void k_ol_mark(OutlineJob j) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= j.n_cuts) return;
+  const uint64_t c = j.cuts[k], end = j.first + j.n;
+  if (c < j.first || c > end || (k && c < j.cuts[k - 1])) { atomicMin(j.bad, (unsigned long long)k); return; }
+  if (c < end) atomicOr(&j.bitmap[(c - j.first) >> 5], 1u << ((c - j.first) & 31));
+  if (k + 1 == j.n_cuts) j.hdr[OL_H_RANGES] = j.n_cuts + (c < end ? 1u : 0u);   // a last range runs to `end`
+}
+
+// The tile's slot table: kOlLdsSlots keys, claimed by atomicMin alone. A lane walks from its slot's home and leaves the smaller key in
+// every entry it meets, carrying the larger one on; entries are never freed, so whoever looks a slot up later walks from the same home
+// until it meets the slot or a free entry. With more distinct slots than entries the largest keys fall off the end and are counted in
+// global memory directly. A claim MOVES keys that were placed before it, and the counters belong to positions: so the tile claims the
+// slots of ALL its events first, and counts, behind a barrier, in a table that no longer changes.
+DEV void ol_claim(uint32_t* keys, uint32_t s) {
+  uint32_t cur = s, pos = s % kOlLdsSlots;
+  for (uint32_t t = 0; t < kOlLdsSlots; t++) {
+    const uint32_t old = atomicMin(&keys[pos], cur);
+    if (old == kOlFree || old == cur) return;
+    if (old > cur) cur = old;
+    pos = (pos + 1) % kOlLdsSlots;
+  }
+}
+DEV uint32_t ol_find(const uint32_t* keys, uint32_t s) {
+  uint32_t pos = s % kOlLdsSlots;
+  for (uint32_t t = 0; t < kOlLdsSlots; t++) {
+    const uint32_t k = keys[pos];
+    if (k == s) return pos;
+    if (k == kOlFree) break;
+    pos = (pos + 1) % kOlLdsSlots;
+  }
+  return kOlLdsSlots;
+}
+
+// A lane's part in the census: its event is a row of slot s (< n_slots) and category cat; `mine`: the lane claims and counts — every
+// row lane, or the first lane alone (cnt = 64) of a wave whose 64 events are rows of one slot and category, which is every wave of a
+// single-table stream. Holds wave collectives: every lane of the workgroup calls it, `on` or not.
+struct OlRow { uint32_t s, cat, cnt; bool mine; };
+DEV OlRow ol_row(const OutlineJob& j, uint64_t k, bool on, uint32_t kind) {
+  OlRow r{0, 0, 1, false};
+  bool row = false;
+  if (on && ol_is_row(kind)) {
+    r.s = j.ev_slot[j.first + k];
+    r.cat = ol_category(kind, j.ev_flags[j.first + k]);
+    row = r.s < j.n_slots;
+  }
+  const uint32_t key = row ? r.s * 8u + r.cat : kOlFree, key0 = __shfl(key, 0, 64);
+  const bool uni = __all(key == key0) && key0 != kOlFree;
+  r.mine = row && (!uni || (threadIdx.x & 63) == 0);
+  if (uni) r.cnt = 64;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void k_ol_tiles(OutlineJob j) {
+  __shared__ uint64_t lds[4];
+  __shared__ uint32_t keys[kOlLdsSlots], rows[kOlLdsSlots * 6];
+  __shared__ unsigned long long firsts[kOlLdsSlots * 6];
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n) return;
+  const uint64_t k1 = k0 + j.tile < j.n ? k0 + j.tile : j.n;
+  if (threadIdx.x < kOlLdsSlots) keys[threadIdx.x] = kOlFree;
+  for (uint32_t t = threadIdx.x; t < kOlLdsSlots * 6; t += 256) { rows[t] = 0; firsts[t] = kNone64; }
+  __syncthreads();
+  uint64_t starts = 0, truncs = 0, rels = 0, nrows = 0;
+  for (uint64_t kb = k0; kb < k1; kb += 256) {   // the tile's sums, and every slot claimed (uniform trip count: every lane takes part in every collective)
+    const uint64_t k = kb + threadIdx.x;
+    const bool on = k < k1;
+    uint32_t kind = 0;
+    if (on) {
+      const OlEvent e = ol_event(j, k);
+      kind = e.kind;
+      starts += e.start;
+      rels += e.kind == 'R';
+      nrows += ol_is_row(e.kind);
+      if (e.kind == 'T') truncs += j.ev_table[j.first + k];
+    }
+    const OlRow r = ol_row(j, k, on, kind);
+    if (r.mine) ol_claim(keys, r.s);
+  }
+  __syncthreads();
+  for (uint64_t kb = k0; kb < k1; kb += 256) {   // the census, in the table as it now stands
+    const uint64_t k = kb + threadIdx.x;
+    const bool on = k < k1;
+    const OlRow r = ol_row(j, k, on, on ? (uint32_t)j.ev_kind[j.first + k] : 0u);
+    if (!r.mine) continue;
+    const uint32_t at = ol_find(keys, r.s);
+    if (at < kOlLdsSlots) { atomicAdd(&rows[at * 6 + r.cat], r.cnt); atomicMin(&firsts[at * 6 + r.cat], (unsigned long long)(j.first + k)); }
+    else { atomicAdd(&j.crow[(uint64_t)r.s * 6 + r.cat], (unsigned long long)r.cnt); atomicMin(&j.cfirst[(uint64_t)r.s * 6 + r.cat], (unsigned long long)(j.first + k)); }
+  }
+  __syncthreads();
+  if (threadIdx.x < kOlLdsSlots && keys[threadIdx.x] != kOlFree) {   // one global atomic per slot and category of the tile
+    const uint64_t s = keys[threadIdx.x];
+    for (uint32_t c = 0; c < 6; c++) {
+      const uint32_t r = rows[threadIdx.x * 6 + c];
+      if (r) { atomicAdd(&j.crow[s * 6 + c], (unsigned long long)r); atomicMin(&j.cfirst[s * 6 + c], firsts[threadIdx.x * 6 + c]); }
+    }
+  }
+  starts = block_sum64(starts, lds); truncs = block_sum64(truncs, lds); rels = block_sum64(rels, lds); nrows = block_sum64(nrows, lds);
+  if (threadIdx.x == 0) { unsigned long long* t = j.tsum + 4 * (uint64_t)blockIdx.x; t[0] = starts; t[1] = truncs; t[2] = rels; t[3] = nrows; }
+}
+
+// one workgroup: each of the four sums per tile becomes the sum in front of the tile; the totals are the call's counts
+__global__ __launch_bounds__(256) void k_ol_scan(OutlineJob j) {
+  __shared__ uint64_t lds[4];
+  if (*j.bad != kNone64) return;
+  for (uint32_t k = 0; k < 4; k++) {
+    const uint64_t tot = carry_scan64(j.tsum + k, j.n_tiles, 4, lds);
+    if (threadIdx.x == 0) j.hdr[k] = tot;   // OL_H_PASSES, _TRUNC, _REL, _ROWS
+  }
+}
+
+// the number of cuts <= ev: the index of the write_events range that holds event ev
+DEV uint64_t ol_range_of(const unsigned long long* cuts, uint64_t n_cuts, uint64_t ev) {
+  uint64_t lo = 0, hi = n_cuts;
+  while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (cuts[mid] <= ev) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void k_ol_write(OutlineJob j) {
+  __shared__ uint64_t lds[4];
+  if (*j.bad != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n) return;
+  const uint64_t k1 = k0 + j.tile < j.n ? k0 + j.tile : j.n;
+  const int lane = threadIdx.x & 63;
+  uint64_t carry_p = j.tsum[4 * (uint64_t)blockIdx.x], carry_t = j.tsum[4 * (uint64_t)blockIdx.x + 1];
+  // The pass in progress where the tile begins (~0, which no event has, in front of the window's first tile) may span thousands of tiles
+  // — one range of a single-table stream is one pass —, and every tile would send its bits to the same words: the tile gathers the
+  // first kOlTouchWords words of that pass in LDS and ends with one atomicOr per word. Passes that start inside the tile go direct.
+  __shared__ unsigned long long tw[kOlTouchWords];
+  const uint64_t p_in = carry_p - 1;
+  if (threadIdx.x < kOlTouchWords) tw[threadIdx.x] = 0;
+  __syncthreads();
+  for (uint64_t kb = k0; kb < k1; kb += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t k = kb + threadIdx.x, i = j.first + k;
+    const bool on = k < k1;
+    OlEvent e{0, 0, 0, false};
+    if (on) e = ol_event(j, k);
+    const uint64_t tcnt = on && e.kind == 'T' ? j.ev_table[i] : 0ull, v = ((uint64_t)e.start << 48) | tcnt;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(v, lds, &tot);
+    // the event's pass (the window's first event is a start, so every event has one) and its first truncate entry
+    const uint64_t p = carry_p + (ex >> 48) + e.start - 1, tpos = carry_t + (ex & kOlLow);
+    carry_p += tot >> 48; carry_t += tot & kOlLow;
+    if (on && e.start) {
+      if (j.passes_out && p < j.passes_cap) { j.passes_out[7 * p] = i; j.passes_out[7 * p + 4] = ol_range_of(j.cuts, j.n_cuts, i); }
+      if (j.tf && p <= j.passes_cap) j.tf[p] = tpos;
+      if (p >= 1 && p - 1 < j.passes_cap) {   // the pass before ends here
+        if (j.passes_out) j.passes_out[7 * (p - 1) + 3] = i;
+        if (j.ends_out) j.ends_out[p - 1] = i;
+      }
+    }
+    if (on && j.de && p < j.passes_cap && e.cls > e.after) {   // the class rises: the data run ends, the Truncate run begins
+      if (e.after == 0) j.de[p] = i;
+      if (e.cls == 2) j.re[p] = i;
+    }
+    if (on && e.kind == 'T' && j.trunc_out && tpos < j.trunc_cap) {
+      const uint64_t room = j.trunc_cap - tpos, cnt = tcnt < room ? tcnt : room;
+      const u8* body = j.fixed + j.ev_body[i];
+      for (uint64_t t = 0; t < cnt; t++) {
+        j.trunc_out[2 * (tpos + t)] = (uint64_t)ld32a(body + 8 * t) | ((uint64_t)ld32a(body + 8 * t + 4) << 32);   // table_id, schema_slot
+        j.trunc_out[2 * (tpos + t) + 1] = i;
+      }
+    }
+    // touched: neighbouring lanes with the same (pass, word) fold their bits into the first of them, which issues the one atomicOr
+    uint32_t s = 0;
+    bool row = on && j.touched && p < j.passes_cap && ol_is_row(e.kind);
+    if (row) { s = j.ev_slot[i]; row = s < j.n_slots; }
+    const uint64_t key = row ? p * j.W + (s >> 6) : kNone64;
+    uint64_t bits = row ? 1ull << (s & 63) : 0ull;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t ok = __shfl(key, (lane + d) & 63, 64), ob = __shfl(bits, (lane + d) & 63, 64);
+      if (lane + d < 64 && ok == key) bits |= ob;
+    }
+    const uint64_t before = __shfl_up(key, 1, 64);
+    if (row && (lane == 0 || before != key)) {
+      if (p == p_in && (s >> 6) < kOlTouchWords) atomicOr(&tw[s >> 6], (unsigned long long)bits);
+      else atomicOr(&j.touched[key], (unsigned long long)bits);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kOlTouchWords && tw[threadIdx.x]) atomicOr(&j.touched[p_in * j.W + threadIdx.x], tw[threadIdx.x]);   // (set bits: a row of p_in, p_in < passes_cap)
+}
+
+// a thread per written pass: what no event of the pass knows — the ends no lane set, the last pass's end, the truncate entries' count —
+// and the copy of its touched words; the grid's first threads also copy the census out
+__global__ __launch_bounds__(256) void k_ol_fix(OutlineJob j) {
+  if (*j.bad != kNone64) return;
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t np = j.hdr[OL_H_PASSES], nt = j.hdr[OL_H_TRUNC], P = np < j.passes_cap ? np : j.passes_cap, end = j.first + j.n;
+  if (t < P) {
+    const bool last = t + 1 == np;
+    if (j.passes_out) {
+      unsigned long long* po = j.passes_out + 7 * t;
+      const uint64_t pe = last ? end : po[3], d = j.de[t], r = j.re[t], tf = j.tf[t];
+      po[1] = d == kNone64 ? pe : d; po[2] = r == kNone64 ? pe : r; po[3] = pe;
+      po[5] = tf; po[6] = (last ? nt : j.tf[t + 1]) - tf;
+    }
+    if (j.ends_out && last) j.ends_out[t] = end;
+    if (j.touched_out) for (uint32_t w = 0; w < j.W; w++) j.touched_out[t * j.W + w] = j.touched[t * j.W + w];
+  }
+  if (j.slots_out && t < (uint64_t)j.n_slots * 12) {
+    const uint64_t s = t / 12, c = t % 12;
+    j.slots_out[t] = c < 6 ? j.crow[s * 6 + c] : j.cfirst[s * 6 + c - 6];
+  }
+}
+
 // ---- source payload accounting, event side (etlg_batch_payload, include/etlg.h): what EventBatch::push merges for the events of one
 // write_events batch (apply.rs:656-658) and record_processed reports. The arena no longer has a message's value bytes (integers, floats
 // and temporals are decoded), so every event is joined to its frame: the frame side (kernels.hip) has listed the frames that take a
@@ -475,6 +717,18 @@ void etlg_k_cuts(const CutJob* jv, int step, uint64_t emit_bound, hipStream_t st
   for (uint32_t k = 1; k < j.levels; k++) hipLaunchKernelGGL(k_cut_level, dim3(nb), dim3(256), 0, st, j.jump + (uint64_t)(k - 1) * W, j.jump + (uint64_t)k * W, W);
   hipLaunchKernelGGL(k_cut_count, dim3(1), dim3(64), 0, st, j);
   if (emit_bound) hipLaunchKernelGGL(k_cut_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
+}
+
+// etlg_batch_outline: every launch in one piece (the grids come from n, the tile, n_cuts and the caller's caps; threads past the device's
+// counts exit). passes_cap is the host's bound of the passes that can be written, min(the caller's cap, n)
+void etlg_k_outline(const OutlineJob* jv, hipStream_t st) {
+  const OutlineJob j = *jv;
+  if (j.n_cuts) hipLaunchKernelGGL(k_ol_mark, dim3((uint32_t)((j.n_cuts + 255) / 256)), dim3(256), 0, st, j);
+  if (j.n_tiles) hipLaunchKernelGGL(k_ol_tiles, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_ol_scan, dim3(1), dim3(256), 0, st, j);
+  if (j.n_tiles) hipLaunchKernelGGL(k_ol_write, dim3(j.n_tiles), dim3(256), 0, st, j);
+  const uint64_t census = j.slots_out ? (uint64_t)j.n_slots * 12 : 0, fix = j.passes_cap > census ? j.passes_cap : census;
+  if (fix) hipLaunchKernelGGL(k_ol_fix, dim3((uint32_t)((fix + 255) / 256)), dim3(256), 0, st, j);
 }
 
 // etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the

@@ -305,6 +305,7 @@ void read_knobs(etlg_ctx* c) {
   integer("ETLG_DLC_OFFSET_CAP", c->dlc_offset_cap_test, 0);      // tests: the int32 offsets' byte cap of etlg_batch_ducklake_copy, so that the overflow report is reachable at test size
   integer("ETLG_RB_PARTS", c->rb_parts_test, 0);                  // tests: lanes per row in k_rb_rows (1-4) instead of the choice by row count
   integer("ETLG_CUTS_TILE", c->cuts_tile_test, 0);                // tests: events per scan tile of etlg_batch_cuts, so that a small batch crosses every level of its scan
+  integer("ETLG_OL_TILE", c->ol_tile_test, 0);                    // tests: events per tile of etlg_batch_outline, so that a small batch crosses every level of its scan
   integer("ETLG_PAY_TILE", c->pay_tile_test, 0);                  // tests: frames / events per scan tile of etlg_batch_payload, so that a small batch crosses every level of its scans
   integer("ETLG_FUSED_DBG", c->fused_dbg, 0);                     // ablation bits, profiling only (results are wrong)
   integer("ETLG_FUSED_KERNEL", c->fused_kernel, -1);              // 0 k_fused/256, 1 k_fused/64, 2 k_cells, 3 k_plan, 4 k_rows whenever eligible

@@ -8,9 +8,10 @@ extern "C++" {
 // (fail-fast, as the reference), not a hand-off of the prefix — and a batch that is not device-resident is refused. `refusal`: the
 // entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
 #define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
-static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal) {
+// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, whose contract lists the batch among its arguments.
+static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal, int32_t code = ETLG_InvalidState) {
   if (b->pending) RC(etlg_batch_sync(c, b));
-  if (!b->v.on_device || !b->dev) return lib_error(c, ETLG_InvalidState, refusal);
+  if (!b->v.on_device || !b->dev) return lib_error(c, code, refusal);
   return ETLG_OK;
 }
 static bool slot_known(const etlg_ctx* c, int32_t slot) { return slot >= 0 && (size_t)slot < c->slots.size(); }
@@ -206,6 +207,75 @@ int32_t etlg_cuts_locate(etlg_ctx* c, const uint64_t* cuts, uint64_t n_cuts, uin
   etlg_k_cuts_locate(cuts_on_device ? (const unsigned long long*)cuts : (const unsigned long long*)d, n_cuts, (const unsigned long long*)row_event, n_rows, out_d, s);
   if (!on_dev) HIPCHK(c, hipMemcpyAsync(rows_out, out_d, n_cuts * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));   // the one stop (a device caller's too: the uploaded cuts are freed on return)
+  return ETLG_OK;
+}
+
+// The write_events pass plan (include/etlg.h; k_ol_* in finish.hip). Everything is sized from what the host knows — the window, the
+// cuts' count, the caller's caps — so the launches go out in one piece and the call stops once: for the header and, for a host caller,
+// the staged outputs, of which the written parts are then copied to the caller. A device caller's memory is written by the last two
+// kernels alone, and by neither when a cut is bad.
+int32_t etlg_batch_outline(etlg_ctx* c, etlg_batch* b, uint64_t first, uint64_t end, const uint64_t* cuts, uint64_t n_cuts, uint32_t cuts_on_device, uint32_t opts,
+                           uint32_t flags, etlg_outline_pass* passes_out, uint64_t* ends_out, uint64_t* touched_out, uint64_t passes_cap, etlg_outline_trunc* trunc_out,
+                           uint64_t trunc_cap, etlg_outline_slot* slots_out, etlg_outline_info* info) {
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  *info = etlg_outline_info{};
+  if (const int32_t rc = batch_ready(c, b, "etlg_batch_outline" NEEDS_DEVICE, ETLG_InvalidArgument)) return rc;   // (etlg_batch_cuts' rule; the code is this call's)
+  if (b->copy.active) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_outline: a table-copy batch has no write_events passes");
+  const etlg_batch_view& bv = b->v;
+  if (first > end || end > bv.n_events) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_outline: first <= end <= n_events");
+  if (n_cuts && !cuts) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_outline: n_cuts without cuts");
+  if (n_cuts > (1ull << 38)) return lib_error(c, ETLG_InvalidArgument, "etlg_batch_outline: more cuts than one call takes (2^38: a grid of 2^30 workgroups marks them)");
+  static_assert(sizeof(etlg_outline_pass) == 56 && sizeof(etlg_outline_trunc) == 16 && sizeof(etlg_outline_slot) == 96, "k_ol_write / k_ol_fix write 7, 2 and 12 words");
+  const uint64_t n = end - first, ns = bv.n_slots, W = (ns + 63) / 64;
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  if (!trunc_out) trunc_cap = 0;
+  if (!passes_out && !ends_out && !touched_out) passes_cap = 0;
+  const uint64_t P = passes_cap < n ? passes_cap : n, T = trunc_cap < bv.fixed_bytes / 8 ? trunc_cap : bv.fixed_bytes / 8;   // what can be written at the most
+  uint64_t tile = c->ol_tile_test ? c->ol_tile_test : 2048u;
+  while ((n + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  const uint64_t n_tiles = (n + tile - 1) / tile;
+  const OutlineLayout lay = outline_layout(n, n_tiles, ns, W, P, T, n_cuts, passes_out != nullptr, ends_out != nullptr, touched_out != nullptr, slots_out != nullptr,
+                                           !cuts_on_device, !on_dev);
+  hipStream_t s = c->stream;
+  ScratchBlk blk{c};
+  HIPCHK(c, blk_take(c, lay.total + 64, false, &blk.p, &blk.cap));
+  uint8_t* d = (uint8_t*)blk.p;
+  HIPCHK(c, hipMemsetAsync(d + lay.zero_at, 0, lay.ones_at - lay.zero_at, s));
+  HIPCHK(c, hipMemsetAsync(d + lay.ones_at, 0xFF, lay.ones_end - lay.ones_at, s));
+  if (!cuts_on_device && n_cuts) HIPCHK(c, hipMemcpyAsync(d + lay.cuts, cuts, n_cuts * 8, hipMemcpyHostToDevice, s));
+  typedef unsigned long long* W64;
+  OutlineJob j{};
+  j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot; j.ev_table = bv.ev_table_id; j.ev_body = bv.ev_body_off; j.fixed = bv.fixed;
+  j.first = first; j.n = n; j.n_cuts = n_cuts; j.cuts = cuts_on_device ? (const unsigned long long*)cuts : (const unsigned long long*)(d + lay.cuts);
+  j.inline_rel = (opts & ETLG_OL_RELATIONS_INLINE) ? 1u : 0u; j.n_slots = (uint32_t)ns; j.W = (uint32_t)W; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles;
+  j.hdr = (W64)(d + lay.hdr); j.bad = (W64)(d + lay.bad); j.bitmap = (uint32_t*)(d + lay.bitmap); j.tsum = (W64)(d + lay.tsum);
+  j.crow = (W64)(d + lay.crow); j.cfirst = (W64)(d + lay.cfirst);
+  if (passes_out) { j.de = (W64)(d + lay.de); j.re = (W64)(d + lay.re); j.tf = (W64)(d + lay.tf); }
+  if (touched_out) j.touched = (W64)(d + lay.touched);
+  j.passes_cap = P; j.trunc_cap = T;
+  j.passes_out = !passes_out ? nullptr : on_dev ? (W64)passes_out : (W64)(d + lay.s_passes);
+  j.ends_out = !ends_out ? nullptr : on_dev ? (W64)ends_out : (W64)(d + lay.s_ends);
+  j.touched_out = !touched_out ? nullptr : on_dev ? (W64)touched_out : (W64)(d + lay.s_touched);
+  j.trunc_out = !trunc_out ? nullptr : on_dev ? (W64)trunc_out : (W64)(d + lay.s_trunc);
+  j.slots_out = !slots_out ? nullptr : on_dev ? (W64)slots_out : (W64)(d + lay.s_slots);
+  etlg_k_outline(&j, s);
+  uint64_t head[9] = {};   // hdr, and `bad` 64 bytes behind it
+  HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> back;
+  if (!on_dev && lay.total > lay.stage_at) { back.resize(lay.total - lay.stage_at); HIPCHK(c, hipMemcpyAsync(back.data(), d + lay.stage_at, back.size(), hipMemcpyDeviceToHost, s)); }
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop
+  if (head[8] != ~0ull) { info->status = ETLG_OL_BAD_CUTS; info->bad_cut = head[8]; return ETLG_OK; }
+  info->n_passes = head[OL_H_PASSES]; info->n_trunc = head[OL_H_TRUNC]; info->n_relations = head[OL_H_REL]; info->n_rows = head[OL_H_ROWS];
+  info->n_ranges = n_cuts ? head[OL_H_RANGES] : 1; info->status = ETLG_OL_OK;
+  if (!on_dev) {
+    const uint64_t np = info->n_passes < P ? info->n_passes : P, nt = info->n_trunc < T ? info->n_trunc : T;
+    const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
+    if (passes_out && np) memcpy(passes_out, staged(lay.s_passes), np * 56);
+    if (ends_out && np) memcpy(ends_out, staged(lay.s_ends), np * 8);
+    if (touched_out && np && W) memcpy(touched_out, staged(lay.s_touched), np * W * 8);
+    if (trunc_out && nt) memcpy(trunc_out, staged(lay.s_trunc), nt * 16);
+    if (slots_out && ns) memcpy(slots_out, staged(lay.s_slots), ns * 96);
+  }
   return ETLG_OK;
 }
 

@@ -25,6 +25,26 @@ inline CutsLayout cuts_layout(uint64_t n, uint64_t n_tiles, uint64_t n_events, b
   return o;
 }
 
+// etlg_batch_outline, its one block. What starts as zeros lies together ([zero_at, ones_at): the range-start bitmap, the census' rows, the
+// touched words of the passes that can be written, hdr), then what starts as all ones ([ones_at, ones_end): bad, the census' firsts, de,
+// re), then what is written before it is read (tsum, tf), a host caller's cuts, and the staging of a host caller's outputs in one piece
+// ([stage_at, total): passes | ends | touched | truncates | slots). hdr and bad are neighbours: one read-back of 72 bytes brings both.
+// P: the passes that can be written, min(passes_cap, n); T: the truncate entries that can be; a part nobody asked for takes nothing.
+struct OutlineLayout { size_t zero_at, bitmap, crow, touched, hdr, ones_at, bad, cfirst, de, re, ones_end, tsum, tf, cuts, stage_at, s_passes, s_ends, s_touched, s_trunc, s_slots, total; };
+inline OutlineLayout outline_layout(uint64_t n, uint64_t n_tiles, uint64_t n_slots, uint64_t W, uint64_t P, uint64_t T, uint64_t n_cuts, bool want_passes, bool want_ends,
+                                    bool want_touched, bool want_slots, bool cuts_here, bool stage) {
+  ScratchLayout l; OutlineLayout o{};
+  o.zero_at = o.bitmap = l.take((n / 32 + 1) * 4); o.crow = l.take(n_slots * 48); o.touched = l.take(want_touched ? P * W * 8 : 0); o.hdr = l.take(64);
+  o.ones_at = o.bad = l.take(64); o.cfirst = l.take(n_slots * 48); o.de = l.take(want_passes ? P * 8 : 0); o.re = l.take(want_passes ? P * 8 : 0);
+  o.ones_end = l.total();
+  o.tsum = l.take(n_tiles * 32); o.tf = l.take(want_passes ? (P + 1) * 8 : 0); o.cuts = l.take(cuts_here ? n_cuts * 8 : 0);
+  o.stage_at = l.total();
+  o.s_passes = l.take(stage && want_passes ? P * 56 : 0); o.s_ends = l.take(stage && want_ends ? P * 8 : 0); o.s_touched = l.take(stage && want_touched ? P * W * 8 : 0);
+  o.s_trunc = l.take(stage ? T * 16 : 0); o.s_slots = l.take(stage && want_slots ? n_slots * 96 : 0);
+  o.total = l.total();
+  return o;
+}
+
 // etlg_batch_payload: hdr | hist | bounds (the three the call reads back and uploads) | the frame side | the event side. ev_bytes and sums
 // live here unless they go straight to the caller's device memory; the range sums' parts exist only when sums are asked for.
 struct PayLayout { size_t hdr, hist, bounds, fbytes, tcnt, r2f, brank, etb, evb, tsum, pb, pr, cuts, sums, total; };

@@ -36,6 +36,32 @@ class Payload:
         self.info, self.hist, self.ev_bytes, self.sums = info, hist, ev_bytes, sums
 
 
+TRUNC_DTYPE = np.dtype([("table_id", np.uint32), ("schema_slot", np.uint32), ("event", np.uint64)])   # etlg_outline_trunc
+PASS_FIELDS = ("first_event", "data_end", "rel_end", "end_event", "range", "trunc_first", "n_trunc")    # etlg_outline_pass
+
+
+class Outline:
+    """What Batch.outline returns: info (abi.OutlineInfo) and, as arrays cut to what was written — or as the device addresses the caller
+    gave —, passes (np.uint64[P, 7], columns PASS_FIELDS), ends (np.uint64[P]), touched (np.uint64[P, W]), truncates (TRUNC_DTYPE[K])
+    and slots (np.uint64[n_slots, 2, 6]: rows and first per category)."""
+
+    def __init__(self, info, passes, ends, touched, truncates, slots):
+        self.info, self.passes, self.ends, self.touched, self.truncates, self.slots = info, passes, ends, touched, truncates, slots
+
+    def touched_slots(self, p):
+        """The slots pass p holds rows of (host arrays only)."""
+        return [64 * w + b for w, word in enumerate(self.touched[p].tolist()) for b in range(64) if (word >> b) & 1]
+
+    def truncated_tables(self, p):
+        """[(table_id, schema_slot, event)] pass p truncates: the first entry per table_id, as truncate_schemas.entry(id).or_insert(schema)
+        keeps it (clickhouse/core.rs:1148-1155). Host arrays only; entries beyond trunc_cap are not there to be looked at."""
+        lo, n = int(self.passes[p][5]), int(self.passes[p][6])
+        seen = {}
+        for t, s, e in self.truncates[lo:lo + n].tolist():
+            seen.setdefault(t, (t, s, e))
+        return list(seen.values())
+
+
 class Batch:
     """A decoded batch (etlg_batch). `host()` copies the arena into numpy arrays."""
 
@@ -162,6 +188,52 @@ class Batch:
         if rc != abi.OK:
             raise self.dec.last_error()
         return out if out else res
+
+    def outline(self, cuts=None, n_cuts=None, first=0, end=None, relations_inline=False, passes_cap=None, trunc_cap=None, on_device=False):
+        """The pass plan of a sink's write_events loop over events [first, end), built on the device (etlg_batch_outline). `cuts`: the
+        ends of the write_events ranges, a host array or the address of a device array of `n_cuts` entries (Batch.cuts leaves them so);
+        None: one range. relations_inline: Iceberg's loop (abi.OL_RELATIONS_INLINE). on_device: False -> arrays; a dict of device
+        addresses under "passes", "ends", "touched", "truncates", "slots" (absent: that part is skipped) -> written there, with
+        passes_cap / trunc_cap saying what they hold. Host caps left None: one call counts, a second one fills arrays of exactly that size.
+        Returns an Outline; with info.status == abi.OL_BAD_CUTS nothing but info.bad_cut is set."""
+        v = self.view()
+        end = int(v.n_events) if end is None else int(end)
+        ns, W = int(v.n_slots), (int(v.n_slots) + 63) // 64
+        if cuts is None:
+            cptr, nc, cdev = None, 0, 0
+        elif isinstance(cuts, (int, np.integer)):
+            cptr, nc, cdev = int(cuts), int(n_cuts), 1
+        else:
+            cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+            cptr, nc, cdev = (cuts.ctypes.data if len(cuts) else None), len(cuts), 0
+        opts = abi.OL_RELATIONS_INLINE if relations_inline else 0
+
+        def call(flags, pp, ep, tp, pcap, kp, kcap, sp):
+            info = abi.OutlineInfo()
+            rc = self.dec.L.etlg_batch_outline(self.dec.h, self.h, int(first), end, cptr, nc, cdev, opts, flags, pp, ep, tp, pcap, kp, kcap, sp, C.byref(info))
+            if rc != abi.OK:
+                raise self.dec.last_error()
+            return info
+
+        if on_device:
+            g = lambda k: int(on_device[k]) if on_device.get(k) else None
+            info = call(abi.F_OUTPUT_ON_DEVICE, g("passes"), g("ends"), g("touched"), int(passes_cap or 0), g("truncates"), int(trunc_cap or 0), g("slots"))
+            return Outline(info, g("passes"), g("ends"), g("touched"), g("truncates"), g("slots"))
+        if passes_cap is None or trunc_cap is None:
+            info = call(0, None, None, None, 0, None, 0, None)
+            if info.status != abi.OL_OK:
+                return Outline(info, None, None, None, None, None)
+            passes_cap = int(info.n_passes) if passes_cap is None else int(passes_cap)
+            trunc_cap = int(info.n_trunc) if trunc_cap is None else int(trunc_cap)
+        pc, kc = int(passes_cap), int(trunc_cap)
+        passes, ends, touched = np.zeros((pc, 7), dtype=np.uint64), np.zeros(pc, dtype=np.uint64), np.zeros((pc, W), dtype=np.uint64)
+        trunc, slots = np.zeros(kc, dtype=TRUNC_DTYPE), np.zeros((ns, 2, 6), dtype=np.uint64)
+        info = call(0, passes.ctypes.data if pc else None, ends.ctypes.data if pc else None, touched.ctypes.data if pc and W else None, pc,
+                    trunc.ctypes.data if kc else None, kc, slots.ctypes.data if ns else None)
+        if info.status != abi.OL_OK:
+            return Outline(info, None, None, None, None, None)
+        P, K = min(pc, int(info.n_passes)), min(kc, int(info.n_trunc))
+        return Outline(info, passes[:P], ends[:P], touched[:P], trunc[:K], slots)
 
     def payload(self, buf, offs, cuts=None, bounds=(), on_device=False, nbytes=None, nframes=None, n_cuts=None, sums=True):
         """Source payload accounting of the batch, on the device (etlg_batch_payload). `buf`, `offs`: the input the batch was decoded

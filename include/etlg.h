@@ -1178,6 +1178,89 @@ int32_t etlg_batch_payload(etlg_ctx* ctx, etlg_batch* batch, const uint8_t* buf,
                            const uint64_t* hist_bounds, uint32_t n_bounds, uint32_t flags, uint32_t* ev_bytes_out,
                            etlg_payload_sums* sums_out, uint64_t* hist_out, etlg_payload_info* info);
 
+/* The pass plan of a destination's write_events loop, built on the device: what a driver that holds only device hand-offs needs to run
+ * the loop all five sinks share (etl-destinations: clickhouse/core.rs:1063-1164, bigquery/core.rs:956-1100, snowflake/core.rs:262-335,
+ * ducklake/core.rs:1815-2060, iceberg/core.rs:300-430) without downloading ev_kind / ev_flags / ev_schema_slot / ev_table_id. One pass of
+ * that loop collects Insert / Update / Delete rows per table until the next Relation or Truncate event, writes those tables, handles the
+ * run of Relation events, then the run of Truncate events, and starts over while events are left.
+ * Window and ranges: events [first, end), first <= end <= n_events. `cuts` (n_cuts entries; device memory when cuts_on_device != 0,
+ * else host memory) are the exclusive range ends etlg_batch_cuts wrote: ascending, each in [first, end]. Every cut closes one
+ * write_events range; a last range runs to `end` when the last cut is below `end`; n_cuts == 0 is one range. Equal neighbouring cuts,
+ * or a cut equal to `first`, make an empty range: it is counted (in `range` and n_ranges) and has no pass — the reference's
+ * `while event_iter.peek().is_some()` does nothing for it. The device checks the cuts: one outside [first, end] or below its
+ * predecessor gives ETLG_OK with info->status = ETLG_OL_BAD_CUTS, info->bad_cut = the index of the first such cut, and nothing else
+ * written anywhere.
+ * THE PASS RULE. The class of an event is 2 for 'T', 1 for 'R' — 0 with ETLG_OL_RELATIONS_INLINE in `opts`: Iceberg's loop breaks at
+ * Truncate only and meets Relation events inside the data run (iceberg/core.rs:310-312, :360) —, and 0 for everything else (B, C, I,
+ * U, D). A pass starts at the first event of every non-empty range and at every event whose class is lower than its predecessor's.
+ * Inside a pass the classes therefore never fall: data_end is the pass's first event of class >= 1 (the pass end if it has none) and
+ * rel_end its first event of class 2 (the pass end if it has none): rows are the I / U / D events of [first_event, data_end), the
+ * Relation run is [data_end, rel_end), the Truncate run [rel_end, end_event).
+ * Outputs: device memory with ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory, filled before the call returns; any of them may
+ * be NULL and its part is skipped. With P = min(n_passes, passes_cap) and W = (view.n_slots + 63) / 64:
+ *   passes_out[p], p < P   the pass; `range` = the index of its write_events range (empty ranges counted); trunc_first / n_trunc = its
+ *                          entries of trunc_out, counted over all entries, those beyond trunc_cap included.
+ *   ends_out[p], p < P     end_event again, as plain words: the shape etlg_cuts_locate takes as `cuts`, so that the passes become row
+ *                          positions of any hand-off object's row_event.
+ *   touched_out[p * W + s / 64], p < P   bit s % 64 is set iff pass p holds at least one I / U / D event of slot s — the keys of the
+ *                          loop's `pending` map. Every word of the P passes is written, zero when no bit is set.
+ *   trunc_out[k], k < min(n_trunc, trunc_cap)   one entry per {table_id, schema_slot} pair in the body of every Truncate event of the
+ *                          window, in event order, then body order. Not de-duplicated: the host keeps the first entry per table_id of a
+ *                          pass, as truncate_schemas.entry(id).or_insert(schema) does (clickhouse/core.rs:1148-1155). A Truncate that
+ *                          names no table this worker owns has no entry.
+ *   slots_out[s], s < view.n_slots   the census of the whole window per category: 0 Insert, 1 Update with a full new row, 2 Update
+ *                          with ETLG_FLAG_PARTIAL, 3 Delete ETLG_OLD_FULL, 4 Delete ETLG_OLD_KEY, 5 Delete ETLG_OLD_NONE. rows[k] =
+ *                          events of the category, first[k] = the lowest event index of it, ~0 when there is none. It tells which
+ *                          slots to hand off at all, and the lowest event over all tables that a sink refuses, before anything is
+ *                          written.
+ * The caps are the caller's: n_passes and n_trunc are the full counts and may exceed them; nothing is written at or beyond a cap, and
+ * the caller calls again with larger buffers. passes_cap counts passes for passes_out, ends_out and touched_out alike.
+ * Same batch requirements as etlg_batch_cuts (device-resident, finished; an ASYNC batch is synced first, and one that ended in a decode
+ * error gives that error).
+ * ETLG_InvalidArgument: a batch that is not device-resident, a batch of etlg_copy_decode (write_table_rows has no passes), first > end
+ * or end > n_events, n_cuts without cuts or above 2^38. The call stops for the device once, at its end.
+ * What is tested: the reference's tests state no pass boundary as a number; tests/batch_outline.py restates the loop above. */
+#define ETLG_OL_RELATIONS_INLINE 1u
+#define ETLG_OL_OK 0u
+#define ETLG_OL_BAD_CUTS 1u
+
+typedef struct etlg_outline_pass {
+  uint64_t first_event;
+  uint64_t data_end;     /* first event of class >= 1, else end_event */
+  uint64_t rel_end;      /* first event of class 2, else end_event */
+  uint64_t end_event;    /* exclusive */
+  uint64_t range;        /* index of the write_events range */
+  uint64_t trunc_first;  /* first entry of trunc_out */
+  uint64_t n_trunc;
+} etlg_outline_pass;
+
+typedef struct etlg_outline_trunc {
+  uint32_t table_id;
+  uint32_t schema_slot;
+  uint64_t event;
+} etlg_outline_trunc;
+
+typedef struct etlg_outline_slot {
+  uint64_t rows[6];
+  uint64_t first[6];     /* ~0: none */
+} etlg_outline_slot;
+
+typedef struct etlg_outline_info {
+  uint64_t n_passes;     /* may exceed passes_cap */
+  uint64_t n_trunc;      /* may exceed trunc_cap */
+  uint64_t n_relations;  /* 'R' events of the window */
+  uint64_t n_rows;       /* I / U / D events of the window */
+  uint64_t n_ranges;     /* write_events ranges, empty ones included */
+  uint64_t bad_cut;      /* ETLG_OL_BAD_CUTS: index of the first bad cut */
+  uint32_t status;       /* ETLG_OL_OK | ETLG_OL_BAD_CUTS */
+  uint32_t _pad;
+} etlg_outline_info;
+
+int32_t etlg_batch_outline(etlg_ctx* ctx, etlg_batch* batch, uint64_t first, uint64_t end, const uint64_t* cuts, uint64_t n_cuts,
+                           uint32_t cuts_on_device, uint32_t opts, uint32_t flags, etlg_outline_pass* passes_out, uint64_t* ends_out,
+                           uint64_t* touched_out, uint64_t passes_cap, etlg_outline_trunc* trunc_out, uint64_t trunc_cap,
+                           etlg_outline_slot* slots_out, etlg_outline_info* info);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
