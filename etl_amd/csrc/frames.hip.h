@@ -23,12 +23,14 @@ DEV void record_error(const DecParams& p, uint32_t frame, uint32_t rank, uint32_
 // left in its result block (stream order), not what the host knew when it enqueued this one.
 // Returns false when that batch did not produce a result (an error, a plan that did not hold, a predecessor that failed in turn):
 // this one must not run either — the host decodes both again, in order, when they are synced (DevResult.fused_fail bit 3).
+// (bit 1 alone — a fixed-width plan that gave its batch up over a shape it does not cover — is not a reason to stop: that kernel has
+// published the three words from the Begin / Commit frames it read. The host keeps this batch's result only if the second attempt at
+// that batch leaves the same words: finish_batch, `spare`; otherwise this batch is decoded again as it always was.)
+// The rule on its own, for a kernel that fetches the block's words itself (plan.hip: with everything else its prologue loads).
+DEV bool carry_usable(uint32_t fused_fail, unsigned long long first_err) { return (fused_fail & ~2u) == 0 && first_err == kNoErr; }
 DEV bool load_carry(DecParams& p) {
   if (!p.carry) return true;
-  // (bit 1 alone — a fixed-width plan that gave its batch up over a shape it does not cover — is not a reason to stop: that kernel has
-  // published the three words from the Begin / Commit frames it read. The host keeps this batch's result only if the second attempt at
-  // that batch leaves the same words: finish_batch, `spare`; otherwise this batch is decoded again as it always was.)
-  const bool ok = (p.carry->fused_fail & ~2u) == 0 && p.carry->first_err == kNoErr;
+  const bool ok = carry_usable(p.carry->fused_fail, p.carry->first_err);
   p.in_txn = p.carry->out_in_txn; p.final_lsn = p.carry->out_final_lsn; p.next_ord = p.carry->out_next_ord;
   if (!ok && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&p.res->fused_fail, 8u);
   return ok;

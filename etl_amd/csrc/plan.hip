@@ -131,11 +131,16 @@ DEV int plan_find(const PlanParams& q, uint32_t rel_u) {
   return -1;
 }
 
-// ETLG_PLAN_DBG bit 5: per-phase shader-clock sums of one tile in 16 (lane 0), in DevResult.dbg_t[k]
+// The profiling hooks live in a DEBUG instantiation of the decode kernel (template argument DBG of plan_kernel and of everything it
+// calls that stamps or tests PlanParams.dbg; the launcher picks it when ETLG_PLAN_DBG has any bit but bit 9). The production
+// instantiation carries no trace of them: no clock reads and no branches on q.dbg between its loads, no registers kept for either.
+template <bool DBG> DEV bool plan_dbg(const PlanParams& q, uint32_t bits) {
+  if constexpr (DBG) return (q.dbg & bits) != 0u; else return false;
+}
 // ETLG_PLAN_DBG bit 6: wall-clock (100 MHz, chip-wide) timeline of EVERY tile into the (otherwise unused) heap arena: 8 x u64 per tile
-#define WSTAMP(k) do { if ((q.dbg & 64u) && threadIdx.x == 0) ((unsigned long long*)p.heap)[(size_t)blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
+#define WSTAMP(k) do { if constexpr (DBG) { if ((q.dbg & 64u) && threadIdx.x == 0) ((unsigned long long*)p.heap)[(size_t)blockIdx.x * 8 + (k)] = wall_clock64(); } } while (0)
 // ETLG_PLAN_DBG bit 5: per-phase shader-clock sums of one tile in 16 (lane 0), in DevResult.dbg_t[k]
-#define PSTAMP(k) do { if ((q.dbg & 32u) && threadIdx.x == 0 && (blockIdx.x & 15u) == 3u) { const unsigned long long t_ = clock64(); atomicAdd(&p.res->dbg_t[k], t_ - tprev); tprev = t_; } } while (0)
+#define PSTAMP(k) do { if constexpr (DBG) { if ((q.dbg & 32u) && threadIdx.x == 0 && (blockIdx.x & 15u) == 3u) { const unsigned long long t_ = clock64(); atomicAdd(&p.res->dbg_t[k], t_ - tprev); tprev = t_; } } } while (0)
 
 // ---- the plan's look-back --------------------------------------------------------------------------------------------
 // What a tile needs from the tiles before it: the sum of their fixed-arena dwords, the last Begin / Commit mark, and the LSN
@@ -274,8 +279,8 @@ struct PlanLocal {
   bool early, done;
 };
 
-template <class M, int RD>
-DEV void plan_local(const DecParams& p, const PlanParams& q, const M& m, u8* rows, bool stage_own, uint32_t a0, uint32_t tile, uint32_t nt, uint32_t my_o,
+template <bool DBG, class M, int RD>
+DEV void plan_local(const DecParams& p, const PlanParams& q, uint32_t ntiles, const M& m, u8* rows, bool stage_own, uint32_t a0, uint32_t tile, uint32_t nt, uint32_t my_o,
                     uint32_t span0, uint32_t span1, unsigned long long& tprev, PlanLocal<RD>& L, bool keep) {
   L.done = true;   // until the local phase has run to its end
   const uint32_t lane = threadIdx.x;
@@ -344,7 +349,9 @@ DEV void plan_local(const DecParams& p, const PlanParams& q, const M& m, u8* row
   }
   PSTAMP(2);
   WSTAMP(2);
-  if (q.dbg & 4u) { if (tot_mark + tot_fx == 0xFFFFFFF1u) atomicOr(failp, 2u); return; }  // profiling: stop after the message heads
+  // profiling: stop after the message heads. The batch is given up (the host decodes it again with the generic kernels: what a caller gets is
+  // right, what the kernel's own time shows is the ablation); the totals feed the word so that the work in front of the exit stays
+  if (plan_dbg<DBG>(q, 4u)) { if (lane == 0) atomicOr(failp, tot_mark + tot_fx == 0xFFFFFFF1u ? 3u : 2u); return; }
 
   // ---- (2) publish, and while the predecessors' words travel: envelope checks, the rest of the heads, the rows into LDS
   //      (a row only needs the tile-local offset x_fx; where the tile's block goes in the arena is the look-back's answer)
@@ -360,7 +367,7 @@ DEV void plan_local(const DecParams& p, const PlanParams& q, const M& m, u8* row
   if (q.pre) bad |= (uint32_t)((isB && flen != kPreBeginLen) || (isC && flen != kPreCommitLen) || (isI && ti >= 0 && (row_dw != q.pre_row_dw || flen < q.pre_key_below)) ||
                                (isD && ti >= 0 && (key_dw != q.pre_key_dw || (flen >= q.pre_key_below && flen > q.pre_key_max))));
   else plan_publish2(q.desc, tile, agg, tile_lsn);
-  if (early && !q.pre) plan_resolve2(q.desc, q.desc + 2 * (size_t)q.ntiles, tile, agg, tile_lsn, failp, PlanPre2(), ex, ex_lsn);
+  if (early && !q.pre) plan_resolve2(q.desc, q.desc + 2 * (size_t)ntiles, tile, agg, tile_lsn, failp, PlanPre2(), ex, ex_lsn);
   {
     const uint64_t h0 = rd64(m, fr);        // 'd' | len:4 | 'w' | 2 bytes of wal_start
     const uint32_t len = __builtin_bswap32((uint32_t)(h0 >> 8));
@@ -382,7 +389,7 @@ DEV void plan_local(const DecParams& p, const PlanParams& q, const M& m, u8* row
   if (isB && !bad) { rimg[0] = (uint32_t)b_ts; rimg[1] = (uint32_t)(b_ts >> 32); }
   if (isC && !bad) { rimg[0] = (uint32_t)c_end; rimg[1] = (uint32_t)(c_end >> 32); rimg[2] = (uint32_t)b_ts; rimg[3] = (uint32_t)(b_ts >> 32); }
   uint32_t vbytes = 0;
-  if (!(q.dbg & 8u)) {  // profiling: bit 3 skips the cell decode
+  if (!plan_dbg<DBG>(q, 8u)) {  // profiling: bit 3 skips the cell decode
     unsigned long long todo = __ballot(isI && !bad);
     while (todo) {  // one pass per distinct table of the wave (one, normally): column descriptors in SGPRs
       const int leader = __builtin_ctzll(todo);
@@ -504,37 +511,58 @@ DEV void plan_local(const DecParams& p, const PlanParams& q, const M& m, u8* row
 // The transaction state a batch starts from when the batch before it may still be running (DecParams.flags bit 4, set by the
 // host for batches it puts on the second stream): wait for that batch's last tile to have written its totals, then read them.
 // Wave-uniform; once per wave. No poison check here: when a batch of a chain fails, the host decodes its successors again.
-DEV void plan_late_carry(DecParams& p, uint32_t* failp) {
-  if (!(p.flags & 16u) || !p.carry) return;
+// What a wave knows about its batch once the prologue's loads are in: the frame and tile counts (kernel arguments, or read from the device:
+// DecParams.nframes_dev) and the transaction state the batch starts from (kernel arguments, the carry block of the batch before it, or —
+// `late` — still to be fetched by the few tiles that need it). The kernel arguments themselves are never written.
+struct PlanBatch {
+  uint32_t nframes, ntiles, in_txn;
+  uint64_t final_lsn, next_ord;
+  const DevResult* carry;
+  bool late;
+};
+DEV void plan_late_carry(PlanBatch& b, uint32_t* failp) {
+  if (!b.late) return;
   for (uint32_t polls = 0;; polls++) {
-    if (__hip_atomic_load(&p.carry->carry_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) break;
+    if (__hip_atomic_load(&b.carry->carry_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) break;
     if (polls > kPlanMaxPolls) { if (threadIdx.x == 0) atomicOr(failp, 1u); break; }
     __builtin_amdgcn_s_sleep(8);
   }
-  p.in_txn = __hip_atomic_load(&p.carry->out_in_txn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  p.final_lsn = __hip_atomic_load(&p.carry->out_final_lsn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  p.next_ord = __hip_atomic_load(&p.carry->out_next_ord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  p.flags &= ~16u;
+  b.in_txn = __hip_atomic_load(&b.carry->out_in_txn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  b.final_lsn = __hip_atomic_load(&b.carry->out_final_lsn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  b.next_ord = __hip_atomic_load(&b.carry->out_next_ord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  b.late = false;
 }
 
 // Finish, part 1: everything that LOADS — the look-back's answer, with it the open Begin's LSN — and the transaction context. A wave
 // runs this for both of its tiles before it stores anything: memory operations of a wave return in order, so a descriptor load issued
 // behind a tile's row / header stores waits for those stores to be acknowledged first.
-// The two words the sidecar pre-pass left for a tile — its prefix inside its group of 1 << kPreGroupLog tiles, the group's prefix — through scalar loads
-// (one address per wave; written by the kernels before this one on the stream), requested before the tile's bytes are.
+// The two words the sidecar pre-pass left for a tile — its prefix inside its group of 1 << kPreGroupLog tiles, the group's prefix: written
+// by the kernels before this one on the stream — are requested before the tile's bytes are.
+// They are first used when the tile's bytes have long landed, so they travel as ONE vector load into ONE register — lane 4 k + d holds dword d
+// of the tile's pair (k = 0) and of its group's (k = 1); lanes 8-15 the same for the wave's second tile — and wait with the staging
+// pieces. (As scalar loads their eight registers were spilled where they were loaded: a wait of its own in front of the staging.)
 struct PlanPreWords { unsigned long long g0 = 0, g1 = 0, t0 = 0, t1 = 0; };
-DEV PlanPreWords plan_pre_load(const PlanParams& q, uint32_t tile) {
-  PlanPreWords w;
-  if (q.pre && tile < q.ntiles) {
-    const ETLG_CONST_AS unsigned long long* dt = (const ETLG_CONST_AS unsigned long long*)(uintptr_t)(q.pre + 2 * (size_t)tile);
-    const ETLG_CONST_AS unsigned long long* dg = (const ETLG_CONST_AS unsigned long long*)(uintptr_t)(q.pre + 2 * ((size_t)q.ntiles + (tile >> kPreGroupLog)));
-    w.t0 = dt[0]; w.t1 = dt[1]; w.g0 = dg[0]; w.g1 = dg[1];
+DEV uint32_t plan_pre_load(const unsigned long long* pre, uint32_t ntiles, uint32_t tile0) {
+  const uint32_t lane = threadIdx.x, tile = tile0 + (lane >> 3);
+  uint32_t v = 0;
+  if (pre && lane < 16u && tile < ntiles) {
+    const unsigned long long* w = pre + 2 * ((lane & 4u) ? (size_t)ntiles + (tile >> kPreGroupLog) : (size_t)tile);
+    v = ((const uint32_t*)w)[lane & 3u];
   }
+  return v;
+}
+DEV PlanPreWords plan_pre_words(uint32_t v, int which) {   // which: 0 the wave's first tile, 1 its second
+  uint32_t d[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) d[i] = (uint32_t)__builtin_amdgcn_readlane((int)v, 8 * which + i);
+  PlanPreWords w;
+  w.t0 = ((unsigned long long)d[1] << 32) | d[0]; w.t1 = ((unsigned long long)d[3] << 32) | d[2];
+  w.g0 = ((unsigned long long)d[5] << 32) | d[4]; w.g1 = ((unsigned long long)d[7] << 32) | d[6];
   return w;
 }
 
-template <int RD>
-DEV void plan_resolve(DecParams& p, const PlanParams& q, uint32_t tile, PlanLocal<RD>& L, unsigned long long& tprev, const PlanPre2& pre = PlanPre2(), const PlanPreWords& pw = PlanPreWords()) {
+template <bool DBG, int RD>
+DEV void plan_resolve(const DecParams& p, const PlanParams& q, PlanBatch& b, uint32_t tile, PlanLocal<RD>& L, unsigned long long& tprev, const PlanPre2& pre, uint32_t pre_v, int which) {
   if (L.done) return;
   const uint32_t lane = threadIdx.x;
   const uint32_t f = tile * 64u + lane;
@@ -547,18 +575,19 @@ DEV void plan_resolve(DecParams& p, const PlanParams& q, uint32_t tile, PlanLoca
 
   // ---- (3) the look-back's answer
   if (q.pre) {   // the pre-pass left the tile's prefix inside its group and the group's prefix: asked for at the kernel's start (plan_pre_load)
+    const PlanPreWords pw = plan_pre_words(pre_v, which);
     const PlanFold r = fold_f(fold_of(pw.g0, pw.g1), fold_of(pw.t0, pw.t1));
     ex = fold_agg(r); ex_lsn = fold_lsn(r);
   }
-  else if (!L.early) plan_resolve2(q.desc, q.desc + 2 * (size_t)q.ntiles, tile, L.agg, L.tile_lsn, failp, pre, ex, ex_lsn);
+  else if (!L.early) plan_resolve2(q.desc, q.desc + 2 * (size_t)b.ntiles, tile, L.agg, L.tile_lsn, failp, pre, ex, ex_lsn);
   PSTAMP(7);
   uint32_t pre_mark = (uint32_t)(ex >> 32);
   if (pre_mark == 0) {   // no Begin / Commit before this tile in the batch: the state the batch started from decides (virtual Begin before frame 0)
-    plan_late_carry(p, failp);
-    if (p.in_txn) { pre_mark = 1u; ex |= 1ull << 32; }
+    plan_late_carry(b, failp);
+    if (b.in_txn) { pre_mark = 1u; ex |= 1ull << 32; }
   }
   // LSN of the Begin that is open when this tile starts: carried in, or (it lives in an earlier tile) it came with the fold
-  const uint64_t pre_lsn = (pre_mark & 1u) && (pre_mark >> 1) != 0 ? ex_lsn : p.final_lsn;
+  const uint64_t pre_lsn = (pre_mark & 1u) && (pre_mark >> 1) != 0 ? ex_lsn : b.final_lsn;
   PSTAMP(4);
   WSTAMP(4);
 
@@ -575,7 +604,7 @@ DEV void plan_resolve(DecParams& p, const PlanParams& q, uint32_t tile, PlanLoca
     if (in_txn) final_lsn = here ? (((uint64_t)hi << 32) | lo) : pre_lsn;
   }
   uint64_t ord = 0;
-  if (!isB && in_txn) ord = fb1 == 0 ? p.next_ord + f : (uint64_t)(f - (fb1 - 1));
+  if (!isB && in_txn) ord = fb1 == 0 ? b.next_ord + f : (uint64_t)(f - (fb1 - 1));
   bad |= (uint32_t)((isI || isC) && !in_txn);               // "Invalid transaction state"
   bad |= (uint32_t)(isC && in_txn && b_lsn != final_lsn);   // "Invalid commit LSN"
   L.bad = bad; L.ex = ex; L.tile_pre_lsn = pre_lsn;
@@ -584,8 +613,8 @@ DEV void plan_resolve(DecParams& p, const PlanParams& q, uint32_t tile, PlanLoca
 }
 
 // Finish, part 2: everything that STORES.
-template <bool REGS, int RD>
-DEV void plan_store(DecParams& p, const PlanParams& q, uint32_t tile, const PlanLocal<RD>& L, unsigned long long& tprev) {
+template <bool DBG, bool REGS, int RD>
+DEV void plan_store(const DecParams& p, const PlanParams& q, const PlanBatch& b, uint32_t tile, const PlanLocal<RD>& L, unsigned long long& tprev) {
   if (L.done) return;
   const uint32_t lane = threadIdx.x;
   const uint32_t f = tile * 64u + lane;
@@ -599,9 +628,9 @@ DEV void plan_store(DecParams& p, const PlanParams& q, uint32_t tile, const Plan
   const uint64_t pre_fx = (uint64_t)(uint32_t)L.ex << 2;  // bytes
 
   // ---- totals and the carried transaction state (last tile)
-  if (tile == q.ntiles - 1 && lane == 0) {
+  if (tile == b.ntiles - 1 && lane == 0) {
     DevResult* r = p.res;
-    r->n_events = p.nframes; r->fixed_bytes = pre_fx + ((uint64_t)tot_fx << 2); r->heap_bytes = 0; r->n_frames = p.nframes;
+    r->n_events = b.nframes; r->fixed_bytes = pre_fx + ((uint64_t)tot_fx << 2); r->heap_bytes = 0; r->n_frames = b.nframes;
     const uint32_t lm = pre_mark > tot_mark ? pre_mark : tot_mark;
     const bool it = (lm & 1u) != 0;
     r->out_in_txn = it;
@@ -609,7 +638,7 @@ DEV void plan_store(DecParams& p, const PlanParams& q, uint32_t tile, const Plan
     if (it) {
       const uint32_t lb1 = lm >> 1;
       fl = tot_mark ? tile_lsn : pre_lsn;   // marks grow with the frame index: a mark of this tile is the last one
-      no = lb1 == 0 ? p.next_ord + p.nframes : (uint64_t)(p.nframes - (lb1 - 1));
+      no = lb1 == 0 ? b.next_ord + b.nframes : (uint64_t)(b.nframes - (lb1 - 1));
     }
     r->out_final_lsn = fl; r->out_next_ord = no;
     __hip_atomic_store(&r->carry_ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);   // the batch behind this one may be waiting for exactly these three words (plan_late_carry)
@@ -619,7 +648,7 @@ DEV void plan_store(DecParams& p, const PlanParams& q, uint32_t tile, const Plan
   const uint64_t fx_off = pre_fx + ((uint64_t)x_fx << 2);
   const uint32_t any_bad = __any(bad != 0u) ? 1u : 0u;
   const bool cap_ok = pre_fx + ((uint64_t)tot_fx << 2) <= p.fixed_cap;
-  if (!any_bad && cap_ok && !(q.dbg & 8u)) {
+  if (!any_bad && cap_ok && !plan_dbg<DBG>(q, 8u)) {
     uint32_t* dst = (uint32_t*)(p.fixed + fx_off);
     if (REGS) {
 #pragma unroll
@@ -631,7 +660,7 @@ DEV void plan_store(DecParams& p, const PlanParams& q, uint32_t tile, const Plan
   }
   PSTAMP(5);
   // ---- event headers (A13/A15)
-  if (live && !any_bad && cap_ok && !(q.dbg & 16u)) {  // profiling: bit 4 skips the event header stores
+  if (live && !any_bad && cap_ok && !plan_dbg<DBG>(q, 16u)) {  // profiling: bit 4 skips the event header stores
     p.ev_kind[f] = (u8)tag;
     p.ev_flags[f] = (u8)c_flags;
     p.ev_table[f] = L.tbl;
@@ -658,113 +687,231 @@ DEV void plan_store(DecParams& p, const PlanParams& q, uint32_t tile, const Plan
   if ((any_bad || !cap_ok) && lane == 0) atomicOr(failp, 2u);
 }
 
-// A tile's frames: their count, the byte span (two scalar loads) and this lane's offset
+// ---- the prologue's loads --------------------------------------------------------------------------------------------------------
+// Everything a tile reads before its bytes can be asked for has an address that follows from the kernel arguments and blockIdx.x alone:
+// the span's two ends and the lane's offset (both tiles' of a two-tile wave), the pre-pass's prefix words, the carry block of a batch
+// chained on the same stream. A wave therefore makes TWO trips in front of its first LDS-DMA — the arguments, then all of these at
+// once — and decides what hangs on them (a failed predecessor, a tile past the count) once, on what has arrived. Scalar loads return out
+// of order, so every wait for one is a wait for all that are in flight: a load issued behind a wait, or behind a branch on a loaded value,
+// is one more full trip (1.5-2 us where another kernel wrote the word). The loaders below only issue; nothing in them looks at a value.
+
+// A tile's frames: their count, the byte span (two scalar loads) and this lane's offset — a lane past the tile's last frame reads the
+// span's end, so that its address needs no loaded value either
 struct TileSpan { uint32_t nt, span0, span1, my_o; };
-DEV TileSpan plan_span(const DecParams& p, uint32_t tile) {
+DEV TileSpan plan_span(const uint32_t* offs, uint32_t nframes, uint32_t tile) {
   const uint32_t lane = threadIdx.x;
   TileSpan t;
   const uint32_t f0 = tile * 64u;
-  t.nt = p.nframes - f0 < 64u ? p.nframes - f0 : 64u;
-  const ETLG_CONST_AS uint32_t* offs_c = (const ETLG_CONST_AS uint32_t*)(uintptr_t)p.offs;
+  t.nt = nframes - f0 < 64u ? nframes - f0 : 64u;
+  const ETLG_CONST_AS uint32_t* offs_c = (const ETLG_CONST_AS uint32_t*)(uintptr_t)offs;
   t.span0 = offs_c[f0]; t.span1 = offs_c[f0 + t.nt];
-  t.my_o = lane < t.nt ? p.offs[f0 + lane] : t.span1;
+  t.my_o = offs[f0 + (lane < t.nt ? lane : t.nt)];
   return t;
 }
+// The second tile of a two-tile wave looks at its span when the first tile's local phase is over: its two ends travel in lanes 0 and 1 of
+// a vector register and land with the first tile's staging pieces — no scalar registers held, or spilled with a wait, across that phase
+struct TileSpanB { uint32_t nt, ends, my_o; };
+DEV TileSpanB plan_span_b(const uint32_t* offs, uint32_t nframes, uint32_t tile) {
+  const uint32_t lane = threadIdx.x;
+  TileSpanB t;
+  const uint32_t f0 = tile * 64u;
+  t.nt = nframes - f0 < 64u ? nframes - f0 : 64u;
+  t.ends = offs[f0 + (lane ? t.nt : 0u)];
+  t.my_o = offs[f0 + (lane < t.nt ? lane : t.nt)];
+  return t;
+}
+DEV TileSpan plan_span_of(const TileSpanB& s) {
+  return TileSpan{s.nt, (uint32_t)__builtin_amdgcn_readlane((int)s.ends, 0), (uint32_t)__builtin_amdgcn_readlane((int)s.ends, 1), s.my_o};
+}
 
-// Stages one tile (LDS-DMA) and runs its local phase.
-template <int RD>
-DEV void plan_stage_local(DecParams& p, const PlanParams& q, u8* smem, uint32_t tile, const TileSpan& ts, unsigned long long& tprev, PlanLocal<RD>& L, bool keep) {
+// The carry block of the batch before this one on the SAME stream (load_carry, frames.hip.h: that batch is complete, its words were
+// written by a kernel before this one) as one batch of scalar loads. The default is "no predecessor": usable, nothing carried.
+struct PlanCarry { unsigned long long first_err = kNoErr; uint32_t fused_fail = 0, in_txn = 0; uint64_t final_lsn = 0, next_ord = 0; };
+DEV PlanCarry plan_carry_load(const DevResult* carry) {
+  const ETLG_CONST_AS DevResult* c = (const ETLG_CONST_AS DevResult*)(uintptr_t)carry;
+  PlanCarry w;
+  w.first_err = c->first_err; w.fused_fail = c->fused_fail; w.in_txn = c->out_in_txn; w.final_lsn = c->out_final_lsn; w.next_ord = c->out_next_ord;
+  return w;
+}
+DEV void plan_carry_failed(DevResult* res) { if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&res->fused_fail, 8u); }
+
+// A batch whose record-boundary scan was still running when this launch was enqueued (DecParams.nframes_dev): the frame count is read from
+// the device now; p.nframes / q.ntiles were the bound the grid was sized by. There is nothing to do here when the scan did not hold, the
+// batch is empty or larger than the bound (DevResult.fused_fail bit 5: the host collects the scan and decodes the batch again with the
+// count in hand) — after letting a batch that may be polling for this one's carried state go on (it is decoded again as well).
+struct PlanDevCount { uint32_t nf = 0, flags = 0; };
+DEV PlanDevCount plan_count_load(const uint32_t* nframes_dev) {
+  const ETLG_CONST_AS uint32_t* r = (const ETLG_CONST_AS uint32_t*)(uintptr_t)nframes_dev;
+  PlanDevCount c;
+  c.nf = r[0]; c.flags = r[1] | r[2];   // ([2]: tiles of the scan whose guess did not hold — the boundaries are not the chain's)
+  return c;
+}
+DEV bool plan_count_ok(const PlanDevCount& c, uint32_t bound) { return c.flags == 0 && c.nf != 0 && c.nf <= bound; }
+DEV void plan_count_failed(DevResult* res) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    atomicOr(&res->fused_fail, 32u);
+    __hip_atomic_store(&res->carry_ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// (the pre-pass: it takes the count the same way; what it leaves undone the decode kernel behind it reports)
+DEV bool plan_frames_from_device(DecParams& p, PlanParams& q) {
+  if (!p.nframes_dev) return true;
+  const PlanDevCount c = plan_count_load(p.nframes_dev);
+  if (!plan_count_ok(c, p.nframes)) { plan_count_failed(p.res); return false; }
+  p.nframes = c.nf;
+  q.ntiles = (c.nf + 63u) >> 6;
+  return true;
+}
+
+// Staging, part 1: the tile's LDS-DMA pieces are issued (nothing is waited for).
+struct PlanStage { uint32_t a0; bool staged; };
+template <bool DBG>
+DEV PlanStage plan_stage_issue(const DecParams& p, const PlanParams& q, const u8* in, uint64_t in_len, u8* smem, const TileSpan& ts, unsigned long long& tprev) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t span0 = ts.span0, span1 = ts.span1;
+  PSTAMP(0);
+  PlanStage g;
+  g.a0 = span0 & ~15u;
+  g.staged = span1 > span0 && span1 <= in_len && (uint64_t)(span1 - g.a0) + 64 <= q.rows_off && !plan_dbg<DBG>(q, 1u);
+  if (g.staged) {
+    // LDS-DMA: piece k of the window = 1 KiB, lane l moves bytes [a0 + 1024 k + 16 l, +16) to LDS offset 1024 k + 16 l.
+    // A 16-byte piece that would cross the end of the input is moved bytewise by the first lanes instead.
+    const uint32_t a0 = g.a0, npieces = (span1 - a0 + 1023u) >> 10;
+    for (uint32_t k = 0; k < npieces; k++) {
+      const uint32_t c = a0 + (k << 10) + (lane << 4);
+      if (c < span1 && (uint64_t)c + 16 <= in_len) ETLG_GLDS16(in + c, smem + (k << 10));
+    }
+    const uint32_t tail = a0 + (((uint32_t)in_len - a0) & ~15u);  // the piece holding the last input byte, if partial
+    if (tail < span1 && (uint64_t)tail + 16 > in_len && tail + lane < in_len && lane < 16) smem[tail - a0 + lane] = in[tail + lane];
+  }
+  return g;
+}
+
+// Staging, part 2: the pieces have landed; the tile's local phase.
+template <bool DBG, int RD>
+DEV void plan_stage_local(const DecParams& p, const PlanParams& q, uint32_t ntiles, const u8* in, uint64_t in_len, u8* smem, uint32_t tile, const TileSpan& ts,
+                          const PlanStage& g, unsigned long long& tprev, PlanLocal<RD>& L, bool keep) {
   const uint32_t lane = threadIdx.x;
   L.done = true;
   const uint32_t nt = ts.nt, span0 = ts.span0, span1 = ts.span1, my_o = ts.my_o;
-  PSTAMP(0);
-  const uint32_t a0 = span0 & ~15u;
-  const bool staged = span1 > span0 && span1 <= p.in_len && (uint64_t)(span1 - a0) + 64 <= q.rows_off && !(q.dbg & 1u);
-  if (staged) {
-    // LDS-DMA: piece k of the window = 1 KiB, lane l moves bytes [a0 + 1024 k + 16 l, +16) to LDS offset 1024 k + 16 l.
-    // A 16-byte piece that would cross the end of the input is moved bytewise by the first lanes instead.
-    const uint32_t npieces = (span1 - a0 + 1023u) >> 10;
-    for (uint32_t k = 0; k < npieces; k++) {
-      const uint32_t c = a0 + (k << 10) + (lane << 4);
-      if (c < span1 && (uint64_t)c + 16 <= p.in_len) ETLG_GLDS16(p.in + c, smem + (k << 10));
-    }
-    const uint32_t tail = a0 + (((uint32_t)p.in_len - a0) & ~15u);  // the piece holding the last input byte, if partial
-    if (tail < span1 && (uint64_t)tail + 16 > p.in_len && tail + lane < p.in_len && lane < 16) smem[tail - a0 + lane] = p.in[tail + lane];
+  if (g.staged) {
     ETLG_VMEM_WAIT();
     PSTAMP(1);
     WSTAMP(1);
-    if (q.dbg & 2u) { if (smem[lane * 97u] == 0xEE && smem[lane * 13u + 5u] == 0xEF && my_o == 0xFFFFFFF1u) atomicOr(&p.res->fused_fail, 2u); return; }  // profiling: staging only
+    if (plan_dbg<DBG>(q, 2u)) {   // profiling: staging only (the batch is given up, as behind the message heads; every lane's read of the window stays)
+      const bool odd = smem[lane * 97u] == 0xEE && smem[lane * 13u + 5u] == 0xEF && my_o == 0xFFFFFFF1u;
+      if (__any(odd) || lane == 0) atomicOr(&p.res->fused_fail, 2u);
+      return;
+    }
     const WinLds m{(const ETLG_LDS_AS u8*)smem};
-    plan_local(p, q, m, smem, true, a0, tile, nt, my_o, span0, span1, tprev, L, keep);
+    plan_local<DBG>(p, q, ntiles, m, smem, true, g.a0, tile, nt, my_o, span0, span1, tprev, L, keep);
   } else {
-    const WinGlb m{p.in, (uint32_t)p.in_len};
-    plan_local(p, q, m, smem, false, 0u, tile, nt, my_o, span0, span1, tprev, L, keep);
+    const WinGlb m{in, (uint32_t)in_len};
+    plan_local<DBG>(p, q, ntiles, m, smem, false, 0u, tile, nt, my_o, span0, span1, tprev, L, keep);
   }
 }
 
-// A batch whose record-boundary scan was still running when this launch was enqueued (DecParams.nframes_dev): the frame count is read from
-// the device now; p.nframes / q.ntiles were the bound the grid was sized by. Returns false when there is nothing to do here — the scan did
-// not hold, the batch is empty or larger than the bound (DevResult.fused_fail bit 5: the host collects the scan and decodes the batch again
-// with the count in hand) — after letting a batch that may be polling for this one's carried state go on (it is decoded again as well).
-DEV bool plan_frames_from_device(DecParams& p, PlanParams& q) {
-  if (!p.nframes_dev) return true;
-  const ETLG_CONST_AS uint32_t* r = (const ETLG_CONST_AS uint32_t*)(uintptr_t)p.nframes_dev;
-  const uint32_t nf = r[0], flags = r[1] | r[2];   // ([2]: tiles of the scan whose guess did not hold — the boundaries are not the chain's)
-  if (flags != 0 || nf == 0 || nf > p.nframes) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      atomicOr(&p.res->fused_fail, 32u);
-      __hip_atomic_store(&p.res->carry_ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return false;
-  }
-  p.nframes = nf;
-  q.ntiles = (nf + 63u) >> 6;
-  return true;
-}
+// The prologue's two waits, pinned: an empty statement that needs the named wave-uniform values in scalar registers where it stands. The
+// loads behind them are issued above it, in one block, and waited for once; nothing of them sinks towards a later use. (The emulator has
+// no scalar registers: nothing to hold.)
+#ifdef ETLG_SIMT
+#define PLAN_HOLD_ARGS(...) ((void)0)
+#define PLAN_HOLD_DATA(a0, a1, cw) ((void)0)
+#define PLAN_HOLD_COUNT(dc) ((void)0)
+#else
+#define PLAN_HOLD_ARGS(in, offs, in_len, nf_dev, pre, carry, res, flags, nframes, ntiles, rows_off, n_tabs, in_txn, final_lsn, next_ord, tabs, cols, pre_row_dw, \
+                       pre_key_dw, pre_key_below, pre_key_max, fixed, fixed_cap) \
+  asm volatile("" :: "s"(in), "s"(offs), "s"(in_len), "s"(nf_dev), "s"(pre), "s"(carry), "s"(res), "s"(flags), "s"(nframes), "s"(ntiles), "s"(rows_off), "s"(n_tabs), \
+               "s"(in_txn), "s"(final_lsn), "s"(next_ord), "s"(tabs), "s"(cols), "s"(pre_row_dw), "s"(pre_key_dw), "s"(pre_key_below), "s"(pre_key_max), "s"(fixed), "s"(fixed_cap))
+#define PLAN_HOLD_DATA(a0, a1, cw) \
+  asm volatile("" :: "s"(a0), "s"(a1), "s"(cw.first_err), "s"(cw.fused_fail), "s"(cw.in_txn), "s"(cw.final_lsn), "s"(cw.next_ord))
+#define PLAN_HOLD_COUNT(dc) asm volatile("" :: "s"(dc.nf), "s"(dc.flags))
+#endif
 
 // TWO: a wave takes two consecutive tiles through ONE LDS window — local(A), local(B), finish(A), finish(B): half as many waves
 // as tiles (a 64 MiB cfg2 batch is 4 645 waves: one round of the chip's ~5 100 slots instead of 1.8), and A's look-back is resolved
 // a whole tile's work after it was published. Only for rows of up to 8 dwords (A's image waits in registers).
-template <bool TWO, int RD>
-DEV void plan_kernel(DecParams& p, const PlanParams& q_in, u8* smem) {
-  PlanParams q = q_in;
+// DBG: the instantiation with the profiling hooks (PSTAMP / WSTAMP / plan_dbg above).
+template <bool TWO, int RD, bool DBG>
+DEV void plan_kernel(const DecParams& p, const PlanParams& q, u8* smem) {
   const uint32_t lane = threadIdx.x;
-  unsigned long long tprev = (q.dbg & 32u) ? clock64() : 0ull;
-  const uint32_t tile = blockIdx.x;   // (the timeline's slot)
-  WSTAMP(0);
-  clear_next_descriptors<64>(q.d_clear, q.clear_words, lane);
+  // ---- trip 1: the kernel arguments the prologue works with, as values of its own (the argument blocks are never written), all of
+  // them in scalar registers HERE: left alone, the compiler loads an argument in front of its first use — the input pointer in front of
+  // the staging loop, behind the data's wait — and every such load is a wait of its own
+  const u8* const in = p.in;
+  const uint32_t* const offs = p.offs;
+  const uint64_t in_len = p.in_len;
+  const uint32_t* const nf_dev = p.nframes_dev;
+  const unsigned long long* const pre = q.pre;
+  const DevResult* const carry = p.carry;
+  DevResult* const res = p.res;
+  const uint32_t flags = p.flags, nframes = p.nframes, ntiles = q.ntiles, rows_off = q.rows_off, n_tabs = q.n_tabs, in_txn = p.in_txn;
+  const uint64_t final_lsn = p.final_lsn, next_ord = p.next_ord;
+  // (... and what the local phase and the stores read from the argument blocks: loaded where they are used, each was a wait in the middle of the tile)
+  PLAN_HOLD_ARGS(in, offs, in_len, nf_dev, pre, carry, res, flags, nframes, ntiles, rows_off, n_tabs, in_txn, final_lsn, next_ord, q.tabs, q.cols, q.pre_row_dw,
+                 q.pre_key_dw, q.pre_key_below, q.pre_key_max, p.fixed, p.fixed_cap);
   // ASYNC chain: the state the batch before this one left on the device — read now (that batch has finished: same stream), or, for
   // a batch the host put on the second stream, by the few tiles that need it, when they need it (plan_late_carry)
-  if (!(p.flags & 16u) && !load_carry(p)) return;
-  if (!plan_frames_from_device(p, q)) return;
+  const bool carry_now = !(flags & 16u) && carry != nullptr;
+  PlanBatch b{nframes, ntiles, in_txn, final_lsn, next_ord, carry, (flags & 16u) != 0u && carry != nullptr};
+  unsigned long long tprev = 0ull;
+  if constexpr (DBG) tprev = (q.dbg & 32u) ? clock64() : 0ull;
+  WSTAMP(0);
   const uint32_t t0 = TWO ? 2u * blockIdx.x : blockIdx.x;
-  if (t0 >= q.ntiles) return;   // (a grid sized by a bound)
-  const TileSpan sa = plan_span(p, t0);
-  const PlanPreWords pwa = plan_pre_load(q, t0), pwb = TWO ? plan_pre_load(q, t0 + 1u) : PlanPreWords();
-  TileSpan sb = sa;
-  if (TWO && t0 + 1u < q.ntiles) sb = plan_span(p, t0 + 1u);   // B's offsets travel while A is worked on
+  // A wave that leaves early stores nothing of the batch — but still clears its share of the NEXT batch's look-back words, as every
+  // wave of the launch does: the share is a function of the grid, and nobody else would.
+  if (nf_dev) {   // the count is on the device: one trip more, on this (wave-uniform) path only; a failed predecessor is reported first
+    const PlanDevCount dc = plan_count_load(nf_dev);
+    PlanCarry cw;
+    if (carry_now) cw = plan_carry_load(carry);
+    PLAN_HOLD_COUNT(dc);   // (the wait stays on this path: none is left for where the two paths meet)
+    if (carry_now && !carry_usable(cw.fused_fail, cw.first_err)) { plan_carry_failed(res); clear_next_descriptors<64>(q.d_clear, q.clear_words, lane); return; }
+    if (!plan_count_ok(dc, b.nframes)) { plan_count_failed(res); clear_next_descriptors<64>(q.d_clear, q.clear_words, lane); return; }
+    b.nframes = dc.nf;
+    b.ntiles = (dc.nf + 63u) >> 6;
+  }
+  if (t0 >= b.ntiles) { clear_next_descriptors<64>(q.d_clear, q.clear_words, lane); return; }   // (a grid sized by a bound; nothing was loaded: its addresses would lie past the sidecar)
+  // ---- trip 2: every load in front of the staging, issued before the first of them is looked at (a two-tile wave without a second tile
+  // asks for its first again: what comes back is not used)
+  const bool two = TWO && t0 + 1u < b.ntiles;
+  const TileSpan sa = plan_span(offs, b.nframes, t0);
+  TileSpanB sbv{};
+  if constexpr (TWO) sbv = plan_span_b(offs, b.nframes, two ? t0 + 1u : t0);   // B's offsets travel with A's
+  const uint32_t pre_v = plan_pre_load(pre, b.ntiles, t0);
+  PlanCarry cw;
+  if (carry_now) cw = plan_carry_load(carry);
+  PLAN_HOLD_DATA(sa.span0, sa.span1, cw);
+  // ---- the decisions, on what has arrived
+  if (carry_now) {
+    if (!carry_usable(cw.fused_fail, cw.first_err)) { plan_carry_failed(res); clear_next_descriptors<64>(q.d_clear, q.clear_words, lane); return; }
+    b.in_txn = cw.in_txn; b.final_lsn = cw.final_lsn; b.next_ord = cw.next_ord;
+  }
   PlanLocal<RD> A;
-  plan_stage_local(p, q, smem, t0, sa, tprev, A, TWO);
+  const PlanStage ga = plan_stage_issue<DBG>(p, q, in, in_len, smem, sa, tprev);
+  clear_next_descriptors<64>(q.d_clear, q.clear_words, lane);   // behind the pieces: stores of a wave queue in front of what it issues after them
+  plan_stage_local<DBG>(p, q, b.ntiles, in, in_len, smem, t0, sa, ga, tprev, A, TWO);
   if (TWO) {
     const uint32_t t1 = t0 + 1u;
     PlanLocal<RD> B;
     B.done = true;
-    if (t1 < q.ntiles) {
+    if (two) {
       __threadfence_block();
       __syncthreads();   // every read of A's window has returned before B's bytes land in it
-      plan_stage_local(p, q, smem, t1, sb, tprev, B, false);
+      const TileSpan sb = plan_span_of(sbv);
+      const PlanStage gb = plan_stage_issue<DBG>(p, q, in, in_len, smem, sb, tprev);
+      plan_stage_local<DBG>(p, q, b.ntiles, in, in_len, smem, t1, sb, gb, tprev, B, false);
     }
     // both tiles' first look-back words are requested before the first wait: one round trip instead of two
     PlanPre2 preA, preB;
-    if (!A.done && !A.early && !q.pre) preA = plan_prefetch2(q.desc, q.desc + 2 * (size_t)q.ntiles, t0);
-    if (!B.done && !B.early && !q.pre) preB = plan_prefetch2(q.desc, q.desc + 2 * (size_t)q.ntiles, t1);
-    plan_resolve(p, q, t0, A, tprev, preA, pwa);
-    plan_resolve(p, q, t1, B, tprev, preB, pwb);
-    plan_store<true>(p, q, t0, A, tprev);
-    plan_store<false>(p, q, t1, B, tprev);
+    if (!A.done && !A.early && !pre) preA = plan_prefetch2(q.desc, q.desc + 2 * (size_t)b.ntiles, t0);
+    if (!B.done && !B.early && !pre) preB = plan_prefetch2(q.desc, q.desc + 2 * (size_t)b.ntiles, t1);
+    plan_resolve<DBG>(p, q, b, t0, A, tprev, preA, pre_v, 0);
+    plan_resolve<DBG>(p, q, b, t1, B, tprev, preB, pre_v, 1);
+    plan_store<DBG, true>(p, q, b, t0, A, tprev);
+    plan_store<DBG, false>(p, q, b, t1, B, tprev);
   } else {
-    plan_resolve(p, q, t0, A, tprev, PlanPre2(), pwa);
-    plan_store<false>(p, q, t0, A, tprev);
+    plan_resolve<DBG>(p, q, b, t0, A, tprev, PlanPre2(), pre_v, 0);
+    plan_store<DBG, false>(p, q, b, t0, A, tprev);
   }
 }
 
@@ -911,13 +1058,25 @@ __global__ __launch_bounds__(kPreWaves * 64) void k_plan_pre(DecParams p, PlanPa
 
 __global__ __launch_bounds__(64, ETLG_PLAN_MINWAVES) void k_plan(DecParams p, PlanParams q) {
   ETLG_DYNAMIC_LDS(smem);
-  plan_kernel<false, 1>(p, q, smem);
+  plan_kernel<false, 1, false>(p, q, smem);
 }
 
 template <int RD>
 __global__ __launch_bounds__(64, ETLG_PLAN_MINWAVES) void k_plan2(DecParams p, PlanParams q) {
   ETLG_DYNAMIC_LDS(smem);
-  plan_kernel<true, RD>(p, q, smem);
+  plan_kernel<true, RD, false>(p, q, smem);
+}
+
+// the same kernels with the profiling hooks (ETLG_PLAN_DBG: tools/plan_phases.py, tools/plan_timeline.py, the ablation bits, bit 0 of the tests)
+__global__ __launch_bounds__(64, ETLG_PLAN_MINWAVES) void k_plan_dbg(DecParams p, PlanParams q) {
+  ETLG_DYNAMIC_LDS(smem);
+  plan_kernel<false, 1, true>(p, q, smem);
+}
+
+template <int RD>
+__global__ __launch_bounds__(64, ETLG_PLAN_MINWAVES) void k_plan2_dbg(DecParams p, PlanParams q) {
+  ETLG_DYNAMIC_LDS(smem);
+  plan_kernel<true, RD, true>(p, q, smem);
 }
 
 }  // namespace etlg
@@ -931,20 +1090,29 @@ void etlg_k_launch_plan_pre(const DecParams* p, const PlanParams* q, hipStream_t
 }
 
 void etlg_k_launch_plan(const DecParams* p, const PlanParams* q, hipStream_t s) {
-  // two tiles per wave whenever a row fits 8 dwords (its image then needs no LDS beyond the window); ETLG_PLAN_DBG bit 9 = one tile per wave
-  if (q->lds_bytes == q->rows_off && q->max_row_dw <= 8u && !(q->dbg & 512u)) {
-    if (q->max_row_dw <= 6u) hipLaunchKernelGGL(k_plan2<6>, dim3((q->ntiles + 1) / 2), dim3(64), q->lds_bytes, s, *p, *q);
-    else hipLaunchKernelGGL(k_plan2<8>, dim3((q->ntiles + 1) / 2), dim3(64), q->lds_bytes, s, *p, *q);
-  } else hipLaunchKernelGGL(k_plan, dim3(q->ntiles), dim3(64), q->lds_bytes, s, *p, *q);
+  // two tiles per wave whenever a row fits 8 dwords (its image then needs no LDS beyond the window); ETLG_PLAN_DBG bit 9 = one tile per wave.
+  // Any other bit of ETLG_PLAN_DBG asks for something only the debug instantiation has.
+  const bool two = q->lds_bytes == q->rows_off && q->max_row_dw <= 8u && !(q->dbg & 512u), dbg = (q->dbg & ~512u) != 0u;
+  const dim3 grid(two ? (q->ntiles + 1) / 2 : q->ntiles);
+  if (!dbg) {
+    if (!two) hipLaunchKernelGGL(k_plan, grid, dim3(64), q->lds_bytes, s, *p, *q);
+    else if (q->max_row_dw <= 6u) hipLaunchKernelGGL(k_plan2<6>, grid, dim3(64), q->lds_bytes, s, *p, *q);
+    else hipLaunchKernelGGL(k_plan2<8>, grid, dim3(64), q->lds_bytes, s, *p, *q);
+  } else {
+    if (!two) hipLaunchKernelGGL(k_plan_dbg, grid, dim3(64), q->lds_bytes, s, *p, *q);
+    else if (q->max_row_dw <= 6u) hipLaunchKernelGGL(k_plan2_dbg<6>, grid, dim3(64), q->lds_bytes, s, *p, *q);
+    else hipLaunchKernelGGL(k_plan2_dbg<8>, grid, dim3(64), q->lds_bytes, s, *p, *q);
+  }
 }
 
 uint32_t etlg_k_plan_pre_group_log(void) { return kPreGroupLog; }   // tiles per group of the pre-pass, log 2: the host sizes the prefix buffers by it
 
 int etlg_k_plan_set_lds(void) {
-  const int a = hipFuncSetAttribute((const void*)k_plan, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess ? 0 : 1;
-  const int b = hipFuncSetAttribute((const void*)k_plan2<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess ? 0 : 1;
-  const int c = hipFuncSetAttribute((const void*)k_plan2<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess ? 0 : 1;
-  return a | b | c;
+  const void* const kernels[] = {(const void*)k_plan, (const void*)k_plan2<6>, (const void*)k_plan2<8>,
+                                 (const void*)k_plan_dbg, (const void*)k_plan2_dbg<6>, (const void*)k_plan2_dbg<8>};
+  int bad = 0;
+  for (const void* k : kernels) bad |= hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess ? 0 : 1;
+  return bad;
 }
 
 }  // extern "C"
