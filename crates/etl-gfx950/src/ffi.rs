@@ -339,6 +339,48 @@ pub struct etlg_outline_info {
     pub _pad: u32,
 }
 
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_dl_batch {
+    pub first_event: u64,
+    pub end_event: u64,
+    pub first_start_lsn: u64,
+    pub last_commit_lsn: u64,
+    pub first_commit_lsn: u64,
+    pub first_tx_ordinal: u64,
+    pub last_tx_ordinal: u64,
+    pub window: u64,
+    pub op_first: u64,
+    pub n_members: u32,
+    pub n_ops: u32,
+    pub n_cat: [u32; 5],
+    pub _pad: u32,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_dl_op {
+    pub kind: u32,
+    pub origin: u32,
+    pub first_event: u64,
+    pub n: u64,
+    pub rec_first: u64,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_dl_plan_info {
+    pub n_batches: u64,
+    pub n_ops: u64,
+    pub n_members: u64,
+    pub n_retained: u64,
+    pub n_dropped: u64,
+    pub event: u64,
+    pub bad_pass: u64,
+    pub status: u32,
+    pub reason: u32,
+}
+
 #[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
@@ -385,6 +427,26 @@ pub const ETLG_PM_MISMATCH: u32 = 1;
 pub const ETLG_OL_RELATIONS_INLINE: u32 = 1;
 pub const ETLG_OL_OK: u32 = 0;
 pub const ETLG_OL_BAD_CUTS: u32 = 1;
+pub const ETLG_DLP_OK: u32 = 0;
+pub const ETLG_DLP_BAD_PASSES: u32 = 1;
+pub const ETLG_DLP_REFUSED: u32 = 2;
+pub const ETLG_DLP_NOT_PREFIX: u32 = 3;
+pub const ETLG_DLP_NEEDS_HOST: u32 = 4;
+pub const ETLG_DLP_R_UPDATE_IDENTITY: u32 = 1;
+pub const ETLG_DLP_R_DELETE_IDENTITY: u32 = 2;
+pub const ETLG_DLP_R_DELETE_NO_OLD: u32 = 3;
+pub const ETLG_DLP_CAT_INSERT: u32 = 0;
+pub const ETLG_DLP_CAT_UPDATE_FULL: u32 = 1;
+pub const ETLG_DLP_CAT_REPLACE: u32 = 2;
+pub const ETLG_DLP_CAT_UPDATE_PARTIAL: u32 = 3;
+pub const ETLG_DLP_CAT_DELETE: u32 = 4;
+pub const ETLG_DLP_OP_UPSERT: u32 = 0;
+pub const ETLG_DLP_OP_DELETE: u32 = 1;
+pub const ETLG_DLP_OP_UPDATE: u32 = 2;
+pub const ETLG_DLP_ORIGIN_NONE: u32 = 0;
+pub const ETLG_DLP_ORIGIN_DELETE: u32 = 1;
+pub const ETLG_DLP_ORIGIN_UPDATE: u32 = 2;
+pub const ETLG_DLP_ORIGIN_REPLACE: u32 = 3;
 pub const ETLG_DL_TUPLES: i32 = 0;
 pub const ETLG_DL_PREDICATES: i32 = 1;
 pub const ETLG_DL_UPDATES: i32 = 3;
@@ -609,6 +671,28 @@ extern "C" {
         trunc_cap: u64,
         slots_out: *mut etlg_outline_slot,
         info: *mut etlg_outline_info,
+    ) -> i32;
+    pub fn etlg_ducklake_plan(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        schema_slot: i32,
+        passes: *const etlg_outline_pass,
+        n_passes: u64,
+        passes_on_device: u32,
+        has_watermark: u32,
+        wm_commit_lsn: u64,
+        wm_tx_ordinal: u64,
+        seed: u64,
+        tuples: *const etlg_rowbinary,
+        predicates: *const etlg_rowbinary,
+        updates: *const etlg_rowbinary,
+        flags: u32,
+        ranges_out: *mut etlg_dl_range,
+        batches_out: *mut etlg_dl_batch,
+        batches_cap: u64,
+        ops_out: *mut etlg_dl_op,
+        ops_cap: u64,
+        info: *mut etlg_dl_plan_info,
     ) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;
     pub fn etlg_ctx_slots(ctx: *const etlg_ctx, n_slots: *mut u32, slots: *mut *const etlg_slot_desc) -> i32;

@@ -341,6 +341,49 @@ impl GpuDecoder {
         Ok(out)
     }
 
+    /// The DuckLake sink's atomic batches of one schema slot of a device-resident batch, cut on the device (etlg_ducklake_plan): the
+    /// replay filter (`retain_mutations_after_sequence_key`, ducklake/batches.rs:932-946), the groups of 16 with their identity fields
+    /// (`prepare_mutation_table_batches` :727-758) and each group's DuckDB operations (`prepare_table_mutations` :1128-1226).
+    /// `passes`: what `GpuDecoder::outline` returned — only `[first_event, data_end)` is read. `watermark`: the sequence key already
+    /// applied. `tuples` / `predicates` / `updates`: the device-resident `etlg_batch_duckdb` objects of this batch and slot, or null.
+    /// At most `batches_cap` groups and `ops_cap` ops come back; `info.n_batches` / `info.n_ops` are the full counts — call again with
+    /// larger caps. With `info.status != ETLG_DLP_OK` nothing but `info` is set. `ranges` is what `etlg_ducklake_fingerprints` takes.
+    #[allow(clippy::too_many_arguments)]
+    pub fn ducklake_plan(
+        &mut self, batch: *mut etlg_batch, schema_slot: i32, passes: &[etlg_outline_pass], watermark: Option<(u64, u64)>, seed: u64, tuples: *const etlg_rowbinary,
+        predicates: *const etlg_rowbinary, updates: *const etlg_rowbinary, batches_cap: usize, ops_cap: usize,
+    ) -> EtlResult<DuckLakePlan> {
+        let mut out = DuckLakePlan {
+            ranges: (0..batches_cap).map(|_| etlg_dl_range { first_event: 0, end_event: 0, seed: 0 }).collect(),
+            batches: vec![
+                etlg_dl_batch {
+                    first_event: 0, end_event: 0, first_start_lsn: 0, last_commit_lsn: 0, first_commit_lsn: 0, first_tx_ordinal: 0, last_tx_ordinal: 0, window: 0, op_first: 0,
+                    n_members: 0, n_ops: 0, n_cat: [0; 5], _pad: 0,
+                };
+                batches_cap
+            ],
+            ops: vec![etlg_dl_op { kind: 0, origin: 0, first_event: 0, n: 0, rec_first: 0 }; ops_cap],
+            info: etlg_dl_plan_info { n_batches: 0, n_ops: 0, n_members: 0, n_retained: 0, n_dropped: 0, event: 0, bad_pass: 0, status: 0, reason: 0 },
+        };
+        fn ptr<T>(v: &mut Vec<T>) -> *mut T { if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() } }
+        let (has_wm, wm_lsn, wm_ord) = match watermark { Some((l, o)) => (1, l, o), None => (0, 0, 0) };
+        let rc = unsafe {
+            etlg_ducklake_plan(
+                self.ctx, batch, schema_slot, if passes.is_empty() { std::ptr::null() } else { passes.as_ptr() }, passes.len() as u64, 0, has_wm, wm_lsn, wm_ord, seed,
+                tuples, predicates, updates, 0, ptr(&mut out.ranges), ptr(&mut out.batches), batches_cap as u64, ptr(&mut out.ops), ops_cap as u64, &mut out.info,
+            )
+        };
+        if rc != ETLG_OK {
+            return Err(self.last_error());
+        }
+        let ok = out.info.status == ETLG_DLP_OK;
+        let (b, k) = if ok { (out.info.n_batches.min(batches_cap as u64) as usize, out.info.n_ops.min(ops_cap as u64) as usize) } else { (0, 0) };
+        out.ranges.truncate(b);
+        out.batches.truncate(b);
+        out.ops.truncate(k);
+        Ok(out)
+    }
+
     /// Source payload accounting of a device-resident batch, on the device (etlg_batch_payload), as plain values: per event the value
     /// bytes of its message (what `StreamingPayloadMetadata::{insert,update,delete}` is built from, apply.rs:2459-2463; the kind is the
     /// event's), per range of `cuts` the merged bytes and rows per kind (what `EventBatch::push` accumulates, apply.rs:656-658; rows == 0
@@ -395,6 +438,23 @@ impl Outline {
             }
         }
         out
+    }
+}
+
+/// What `GpuDecoder::ducklake_plan` returns.
+pub struct DuckLakePlan {
+    pub ranges: Vec<etlg_dl_range>,
+    pub batches: Vec<etlg_dl_batch>,
+    pub ops: Vec<etlg_dl_op>,
+    pub info: etlg_dl_plan_info,
+}
+
+impl DuckLakePlan {
+    /// The ops of group `b` that were written (those beyond `ops_cap` are not there to be looked at).
+    pub fn ops_of(&self, b: usize) -> &[etlg_dl_op] {
+        let (lo, n) = (self.batches[b].op_first as usize, self.batches[b].n_ops as usize);
+        let hi = (lo + n).min(self.ops.len());
+        &self.ops[lo.min(hi)..hi]
     }
 }
 

@@ -170,6 +170,21 @@ class OutlineInfo(C.Structure):   # etlg_outline_info
     _fields_ = [(n, C.c_uint64) for n in ("n_passes", "n_trunc", "n_relations", "n_rows", "n_ranges", "bad_cut")] + [("status", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class DlBatch(C.Structure):   # etlg_dl_batch
+    _fields_ = ([(n, C.c_uint64) for n in ("first_event", "end_event", "first_start_lsn", "last_commit_lsn", "first_commit_lsn", "first_tx_ordinal",
+                                            "last_tx_ordinal", "window", "op_first")]
+                + [("n_members", C.c_uint32), ("n_ops", C.c_uint32), ("n_cat", C.c_uint32 * 5), ("_pad", C.c_uint32)])
+
+
+class DlOp(C.Structure):   # etlg_dl_op
+    _fields_ = [("kind", C.c_uint32), ("origin", C.c_uint32), ("first_event", C.c_uint64), ("n", C.c_uint64), ("rec_first", C.c_uint64)]
+
+
+class DlPlanInfo(C.Structure):   # etlg_dl_plan_info
+    _fields_ = ([(n, C.c_uint64) for n in ("n_batches", "n_ops", "n_members", "n_retained", "n_dropped", "event", "bad_pass")]
+                + [("status", C.c_uint32), ("reason", C.c_uint32)])
+
+
 class FinishStats(C.Structure):   # etlg_finish_stats
     _fields_ = [(n, C.c_uint64) for n in ("deferred_seen", "arrays_typed", "floats_settled", "left_deferred", "heap_bytes_added")]
 
@@ -181,6 +196,11 @@ PK_INSERT, PK_UPDATE, PK_DELETE, PK_COPY = range(4)
 PM_OK, PM_MISMATCH = 0, 1
 OL_RELATIONS_INLINE = 1
 OL_OK, OL_BAD_CUTS = 0, 1
+DLP_OK, DLP_BAD_PASSES, DLP_REFUSED, DLP_NOT_PREFIX, DLP_NEEDS_HOST = range(5)
+DLP_R_UPDATE_IDENTITY, DLP_R_DELETE_IDENTITY, DLP_R_DELETE_NO_OLD = 1, 2, 3
+DLP_CAT_INSERT, DLP_CAT_UPDATE_FULL, DLP_CAT_REPLACE, DLP_CAT_UPDATE_PARTIAL, DLP_CAT_DELETE = range(5)
+DLP_OP_UPSERT, DLP_OP_DELETE, DLP_OP_UPDATE = range(3)
+DLP_ORIGIN_NONE, DLP_ORIGIN_DELETE, DLP_ORIGIN_UPDATE, DLP_ORIGIN_REPLACE = range(4)
 DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)

@@ -373,6 +373,35 @@ struct OutlineJob {
   unsigned long long* slots_out;      // 12 words per slot
 };
 
+// The DuckLake atomic-batch plan (etlg_ducklake_plan: k_dlp_* in finish.hip). hdr: the four counts start as zeros, the four status
+// words — the lowest bad pass, the lowest refused event * 4 + its reason, the lowest not-prefix event, the lowest event without a record —
+// as all ones. No kernel behind the one that sets a status word writes an output once one of them is set.
+enum : uint32_t { DLP_H_MEMBERS = 0, DLP_H_RETAINED = 1, DLP_H_BATCHES = 2, DLP_H_OPS = 3, DLP_H_BAD = 4, DLP_H_REFUSED = 5, DLP_H_NOTPREFIX = 6, DLP_H_NEEDSHOST = 7, DLP_H_WORDS = 8 };
+constexpr uint32_t kDlpGroup = 16;        // CDC_MUTATION_BATCH_SIZE (ducklake/batches.rs:79)
+constexpr uint32_t kDlpBatchWords = 13;   // etlg_dl_batch
+constexpr uint32_t kDlpOpWords = 4;       // etlg_dl_op
+struct DlpRecs { const unsigned long long* row_event; uint64_t n_rows; uint32_t given, _pad; };   // one etlg_batch_duckdb object's row_event
+struct DlpJob {
+  const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_start; const uint64_t* ev_commit; const uint64_t* ev_ord;
+  uint64_t n_events;
+  const unsigned long long* passes; uint64_t n_passes;   // etlg_outline_pass: 7 words, the window is words 0 and 1
+  uint32_t slot, no_ident;            // no_ident: the slot has no identity column, every Update / Delete is refused
+  uint32_t has_wm, tile, n_tiles, _pad;
+  uint64_t wm_lsn, wm_ord, seed;
+  DlpRecs t, p, u;                    // ETLG_DL_TUPLES / _PREDICATES / _UPDATES
+  unsigned long long* hdr;            // DLP_H_*
+  unsigned long long* tsum;           // per tile: members, retained; after k_dlp_scan those in front of the tile
+  uint8_t* code;                      // per event: 1 member | 2 retained | category << 2
+  unsigned long long* rpre;           // n_events + 1: retained members in front of the event
+  uint32_t* glens; const int64_t* gpre;   // per pass: its groups, and (n_passes + 1) the groups in front of it
+  unsigned long long* dense;          // the retained members' events, in order
+  unsigned long long* gstart;         // per group, and one more: where its members begin in `dense`
+  unsigned long long* mpos;           // per retained member: its record in tuples (updates: the SET record), its record in predicates; ~0 none
+  uint32_t* oplens; const int64_t* opre;  // per group (n_events entries, 0 behind the last group): its ops, and the ops in front of it
+  unsigned long long* ranges_out; unsigned long long* batches_out; uint64_t batches_cap;   // 3 and kDlpBatchWords words per group
+  unsigned long long* ops_out; uint64_t ops_cap;                                           // kDlpOpWords words per op
+};
+
 // Source payload accounting (etlg_batch_payload). The frame side (k_payf_* in kernels.hip) measures every row message and lists the
 // frames that take a transaction ordinal; the event side (k_paye_* in finish.hip) joins every event to its frame through that list and
 // sums the ranges. Channels: 0 Insert, 1 Update, 2 Delete; a table-copy batch has channel 0 alone and reports it as ETLG_PK_COPY.

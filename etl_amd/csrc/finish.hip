@@ -417,6 +417,213 @@ __global__ __launch_bounds__(256) void k_ol_fix(OutlineJob j) {
   }
 }
 
+// ---- the DuckLake atomic-batch plan (etlg_ducklake_plan, include/etlg.h: the rule is stated there). Replay filter, the cut into groups
+// of 16 and the grouping into operations are a selection, a rank that restarts at every window and run boundaries inside a group: with
+// rpre[i] the retained members in front of event i, a member's rank in its window w is rpre[i] - rpre[first_event of w], the groups of w
+// are ceil(retained of w / 16), and the retained members in event order are one dense list that the groups cut without a gap — a group
+// is the stretch between two neighbouring starts of that list. Launches, none of which exchanges a word between its workgroups: the
+// windows checked (k_dlp_mark), per tile the members and the retained ones plus a code byte per event (k_dlp_tiles), their scan by one
+// workgroup (k_dlp_scan), rpre (k_dlp_write), the groups per window (k_dlp_pass) and their scan (etlg_k_scan_lens), per member its place
+// in the dense list, its group's start and its records (k_dlp_members), per group its fields and the count of its ops (k_dlp_groups),
+// their scan, and the ops (k_dlp_ops). The caps are the caller's, so nothing is read back in between; the outputs are written from
+// scratch by the last two kernels, which do nothing once a status word is set. Every loop runs to a launch parameter: tile / 256
+// chunks, log2(n_passes) and log2(records) steps of a search, 16 members.
+DEV bool dlp_any_status(const DlpJob& j) {
+  return j.hdr[DLP_H_BAD] != kNone64 || j.hdr[DLP_H_REFUSED] != kNone64 || j.hdr[DLP_H_NOTPREFIX] != kNone64 || j.hdr[DLP_H_NEEDSHOST] != kNone64;
+}
+// the window that can hold event i: the last one that starts at or in front of it (every earlier one has ended by then); ~0 none
+DEV uint64_t dlp_window(const DlpJob& j, uint64_t i) {
+  uint64_t lo = 0, hi = j.n_passes;
+  while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (j.passes[7 * mid] <= i) lo = mid + 1; else hi = mid; }
+  if (!lo || i >= j.passes[7 * (lo - 1) + 1]) return kNone64;
+  return lo - 1;
+}
+// event i as the code byte of a member inside a window, 0 otherwise; *refused: the reason the sink refuses it, 0 none
+DEV uint32_t dlp_code(const DlpJob& j, uint64_t i, uint32_t* refused) {
+  *refused = 0;
+  const uint32_t kind = j.ev_kind[i];
+  if (!ol_is_row(kind) || j.ev_slot[i] != j.slot || dlp_window(j, i) == kNone64) return 0u;
+  const uint32_t fl = j.ev_flags[i], old = fl & 3u;
+  uint32_t cat = ETLG_DLP_CAT_INSERT;
+  if (kind == 'U') {
+    cat = (fl & ETLG_FLAG_PARTIAL) ? ETLG_DLP_CAT_UPDATE_PARTIAL : old == ETLG_OLD_NONE ? ETLG_DLP_CAT_REPLACE : ETLG_DLP_CAT_UPDATE_FULL;
+    if (j.no_ident) *refused = ETLG_DLP_R_UPDATE_IDENTITY;
+  } else if (kind == 'D') {
+    cat = ETLG_DLP_CAT_DELETE;
+    if (j.no_ident) *refused = ETLG_DLP_R_DELETE_IDENTITY;
+    else if (old == ETLG_OLD_NONE) *refused = ETLG_DLP_R_DELETE_NO_OLD;
+  }
+  const uint64_t lsn = j.ev_commit[i];
+  const bool keep = !j.has_wm || lsn > j.wm_lsn || (lsn == j.wm_lsn && j.ev_ord[i] > j.wm_ord);   // compare_sequence_keys: lexicographic
+  return 1u | (keep ? 2u : 0u) | (cat << 2);
+}
+
+__global__ __launch_bounds__(256) void k_dlp_mark(DlpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes) return;
+  const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1];
+  if (fe > de || de > j.n_events || (p && fe < j.passes[7 * (p - 1) + 1])) atomicMin(&j.hdr[DLP_H_BAD], (unsigned long long)p);
+}
+
+__global__ __launch_bounds__(256) void k_dlp_tiles(DlpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[DLP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t members = 0, kept = 0, refused = kNone64;
+  for (uint64_t i = k0 + threadIdx.x; i < k1; i += 256) {
+    uint32_t why;
+    const uint32_t code = dlp_code(j, i, &why);
+    j.code[i] = (uint8_t)code;
+    members += code & 1u;
+    kept += (code >> 1) & 1u;
+    if (why && i * 4 + why < refused) refused = i * 4 + why;
+  }
+  members = block_sum64(members, lds); kept = block_sum64(kept, lds); refused = block_min64(refused, lds);
+  if (threadIdx.x == 0) {
+    j.tsum[2 * (uint64_t)blockIdx.x] = members; j.tsum[2 * (uint64_t)blockIdx.x + 1] = kept;
+    if (refused != kNone64) atomicMin(&j.hdr[DLP_H_REFUSED], (unsigned long long)refused);
+  }
+}
+
+// one workgroup: both sums per tile become the sums in front of the tile; the totals are the call's counts
+__global__ __launch_bounds__(256) void k_dlp_scan(DlpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[DLP_H_BAD] != kNone64) return;
+  const uint64_t members = carry_scan64(j.tsum, j.n_tiles, 2, lds), kept = carry_scan64(j.tsum + 1, j.n_tiles, 2, lds);
+  if (threadIdx.x == 0) { j.hdr[DLP_H_MEMBERS] = members; j.hdr[DLP_H_RETAINED] = kept; j.rpre[j.n_events] = kept; }
+}
+
+__global__ __launch_bounds__(256) void k_dlp_write(DlpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[DLP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t carry = j.tsum[2 * (uint64_t)blockIdx.x + 1];
+  for (uint64_t kb = k0; kb < k1; kb += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t i = kb + threadIdx.x;
+    const bool on = i < k1;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(on ? (j.code[i] >> 1) & 1u : 0u, lds, &tot);
+    if (on) j.rpre[i] = carry + ex;
+    carry += tot;
+  }
+}
+
+// a thread per window: its groups (the windows were checked: data_end <= n_events)
+__global__ __launch_bounds__(256) void k_dlp_pass(DlpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes || j.hdr[DLP_H_BAD] != kNone64) return;
+  const uint64_t kept = j.rpre[j.passes[7 * p + 1]] - j.rpre[j.passes[7 * p]];
+  j.glens[p] = (uint32_t)((kept + kDlpGroup - 1) / kDlpGroup);
+}
+
+// the record of event i in an object: its lower bound in row_event when that entry is the event's, ~0 when the event has none
+DEV uint64_t dlp_record(const DlpRecs& r, uint64_t i) {
+  if (!r.n_rows) return kNone64;
+  const uint64_t at = cut_lower_bound(r.row_event, 0, r.n_rows - 1, i);
+  return at < r.n_rows && r.row_event[at] == i ? at : kNone64;
+}
+
+// a thread per event: a retained member takes its place in the dense list, opens its group when its rank in the window is a multiple
+// of 16, and finds its records; a dropped member behind a retained one of its window is the not-prefix case
+__global__ __launch_bounds__(256) void k_dlp_members(DlpJob j) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= j.n_events || j.hdr[DLP_H_BAD] != kNone64) return;
+  if (i == 0) j.gstart[j.gpre[j.n_passes]] = j.rpre[j.n_events];   // the end of the last group
+  const uint32_t code = j.code[i];
+  if (!(code & 1u)) return;
+  const uint64_t w = dlp_window(j, i), m = j.rpre[i], rank = m - j.rpre[j.passes[7 * w]];
+  if (!(code & 2u)) { if (rank) atomicMin(&j.hdr[DLP_H_NOTPREFIX], (unsigned long long)i); return; }
+  j.dense[m] = i;
+  if (rank % kDlpGroup == 0) j.gstart[(uint64_t)j.gpre[w] + rank / kDlpGroup] = m;
+  const uint32_t cat = code >> 2;
+  uint64_t a = kNone64, b = kNone64;
+  bool missing = false;
+  if (cat == ETLG_DLP_CAT_UPDATE_PARTIAL) {
+    if (j.u.given) { a = dlp_record(j.u, i); missing = a == kNone64; }
+  } else {
+    if (cat != ETLG_DLP_CAT_DELETE && j.t.given) { a = dlp_record(j.t, i); missing = a == kNone64; }
+    if (cat != ETLG_DLP_CAT_INSERT && j.p.given) { b = dlp_record(j.p, i); missing = missing || b == kNone64; }
+  }
+  j.mpos[2 * m] = a; j.mpos[2 * m + 1] = b;
+  if (missing) atomicMin(&j.hdr[DLP_H_NEEDSHOST], (unsigned long long)i);
+}
+
+// a thread per group: its fields but op_first, its range for etlg_ducklake_fingerprints, and the count of its ops — a maximal run of
+// Inserts or of Deletes is one op, a full Update or a Replace two, a partial Update one (prepare_table_mutations)
+__global__ __launch_bounds__(256) void k_dlp_groups(DlpJob j) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= j.n_events || dlp_any_status(j)) return;
+  if (g >= (uint64_t)j.gpre[j.n_passes]) { j.oplens[g] = 0; return; }
+  const uint64_t m0 = j.gstart[g], cnt = j.gstart[g + 1] - m0, first = j.dense[m0], last = j.dense[m0 + cnt - 1];
+  uint32_t cats[5] = {0, 0, 0, 0, 0}, ops = 0, before = ~0u;
+#pragma unroll
+  for (uint32_t k = 0; k < kDlpGroup; k++) {
+    if (k >= cnt) break;
+    const uint32_t cat = j.code[j.dense[m0 + k]] >> 2;
+#pragma unroll
+    for (uint32_t c = 0; c < 5; c++) cats[c] += cat == c;
+    if (cat == ETLG_DLP_CAT_INSERT || cat == ETLG_DLP_CAT_DELETE) ops += cat != before;
+    else ops += cat == ETLG_DLP_CAT_UPDATE_PARTIAL ? 1u : 2u;
+    before = cat;
+  }
+  j.oplens[g] = ops;
+  if (g >= j.batches_cap) return;
+  if (j.ranges_out) { j.ranges_out[3 * g] = first; j.ranges_out[3 * g + 1] = last + 1; j.ranges_out[3 * g + 2] = j.seed; }
+  if (j.batches_out) {
+    unsigned long long* o = j.batches_out + kDlpBatchWords * g;
+    o[0] = first; o[1] = last + 1; o[2] = j.ev_start[first]; o[3] = j.ev_commit[last];
+    o[4] = j.ev_commit[first]; o[5] = j.ev_ord[first]; o[6] = j.ev_ord[last]; o[7] = dlp_window(j, first);
+    o[9] = cnt | ((uint64_t)ops << 32);
+    o[10] = cats[0] | ((uint64_t)cats[1] << 32); o[11] = cats[2] | ((uint64_t)cats[3] << 32); o[12] = cats[4];
+  }
+}
+
+DEV void dlp_emit(const DlpJob& j, uint64_t k, uint32_t kind, uint32_t origin, uint64_t first, uint64_t n, uint64_t rec) {
+  if (!j.ops_out || k >= j.ops_cap) return;
+  unsigned long long* o = j.ops_out + kDlpOpWords * k;
+  o[0] = kind | ((uint64_t)origin << 32); o[1] = first; o[2] = n; o[3] = rec;
+}
+
+// a thread per group: op_first, and its ops behind those of the groups in front; the grid's first thread leaves the two counts
+__global__ __launch_bounds__(256) void k_dlp_ops(DlpJob j) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= j.n_events || dlp_any_status(j)) return;
+  const uint64_t G = (uint64_t)j.gpre[j.n_passes];
+  if (g == 0) { j.hdr[DLP_H_BATCHES] = G; j.hdr[DLP_H_OPS] = (uint64_t)j.opre[j.n_events]; }
+  if (g >= G) return;
+  const uint64_t m0 = j.gstart[g], cnt = j.gstart[g + 1] - m0;
+  uint64_t k = (uint64_t)j.opre[g];
+  if (j.batches_out && g < j.batches_cap) j.batches_out[kDlpBatchWords * g + 8] = k;
+  if (!j.ops_out || k >= j.ops_cap) return;
+  uint64_t run_first = 0, run_n = 0, run_rec = 0;
+  uint32_t run_cat = ~0u;
+  for (uint32_t t = 0; t <= kDlpGroup; t++) {   // one step past the last member closes the run in progress
+    const bool on = t < cnt;
+    const uint64_t i = on ? j.dense[m0 + t] : 0;
+    const uint32_t cat = on ? j.code[i] >> 2 : ~0u;
+    if (run_n && cat != run_cat) {
+      const bool ins = run_cat == ETLG_DLP_CAT_INSERT;
+      dlp_emit(j, k++, ins ? ETLG_DLP_OP_UPSERT : ETLG_DLP_OP_DELETE, ins ? ETLG_DLP_ORIGIN_NONE : ETLG_DLP_ORIGIN_DELETE, run_first, run_n, run_rec);
+      run_n = 0;
+    }
+    if (!on) break;
+    const uint64_t a = j.mpos[2 * (m0 + t)], b = j.mpos[2 * (m0 + t) + 1];
+    if (cat == ETLG_DLP_CAT_INSERT || cat == ETLG_DLP_CAT_DELETE) {
+      if (!run_n) { run_first = i; run_cat = cat; run_rec = cat == ETLG_DLP_CAT_INSERT ? a : b; }
+      run_n++;
+    } else if (cat == ETLG_DLP_CAT_UPDATE_PARTIAL) {
+      dlp_emit(j, k++, ETLG_DLP_OP_UPDATE, ETLG_DLP_ORIGIN_NONE, i, 1, a);
+    } else {
+      dlp_emit(j, k++, ETLG_DLP_OP_DELETE, cat == ETLG_DLP_CAT_UPDATE_FULL ? ETLG_DLP_ORIGIN_UPDATE : ETLG_DLP_ORIGIN_REPLACE, i, 1, b);
+      dlp_emit(j, k++, ETLG_DLP_OP_UPSERT, ETLG_DLP_ORIGIN_NONE, i, 1, a);
+    }
+  }
+}
+
 // ---- source payload accounting, event side (etlg_batch_payload, include/etlg.h): what EventBatch::push merges for the events of one
 // write_events batch (apply.rs:656-658) and record_processed reports. The arena no longer has a message's value bytes (integers, floats
 // and temporals are decoded), so every event is joined to its frame: the frame side (kernels.hip) has listed the frames that take a
@@ -729,6 +936,23 @@ void etlg_k_outline(const OutlineJob* jv, hipStream_t st) {
   if (j.n_tiles) hipLaunchKernelGGL(k_ol_write, dim3(j.n_tiles), dim3(256), 0, st, j);
   const uint64_t census = j.slots_out ? (uint64_t)j.n_slots * 12 : 0, fix = j.passes_cap > census ? j.passes_cap : census;
   if (fix) hipLaunchKernelGGL(k_ol_fix, dim3((uint32_t)((fix + 255) / 256)), dim3(256), 0, st, j);
+}
+
+// etlg_ducklake_plan: every launch in one piece (the grids come from n_events, the tile and n_passes, both > 0; threads past the
+// device's counts exit). gblk / oblk: the block sums of the two offset scans ((ceil(n / 256) + 1) words each)
+void etlg_k_ducklake_plan(const DlpJob* jv, unsigned long long* gblk, unsigned long long* oblk, hipStream_t st) {
+  const DlpJob j = *jv;
+  const dim3 per_pass((uint32_t)((j.n_passes + 255) / 256)), per_event((uint32_t)((j.n_events + 255) / 256));
+  hipLaunchKernelGGL(k_dlp_mark, per_pass, dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_dlp_tiles, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_dlp_scan, dim3(1), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_dlp_write, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_dlp_pass, per_pass, dim3(256), 0, st, j);
+  etlg_k_scan_lens(j.glens, j.n_passes, gblk, (int64_t*)j.gpre, st);
+  hipLaunchKernelGGL(k_dlp_members, per_event, dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_dlp_groups, per_event, dim3(256), 0, st, j);
+  etlg_k_scan_lens(j.oplens, j.n_events, oblk, (int64_t*)j.opre, st);
+  hipLaunchKernelGGL(k_dlp_ops, per_event, dim3(256), 0, st, j);
 }
 
 // etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the

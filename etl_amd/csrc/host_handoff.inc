@@ -1,5 +1,5 @@
 // Part of host.cpp (included there, one translation unit): what the hand-off calls over a decoded, device-resident batch share, and the calls
-// that build neither columns nor rows — size hints, cuts, locate, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
+// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
 // fingerprint.hip). The two builders follow in host_handoff_columns.inc and host_handoff_rows.inc.
 
 extern "C++" {
@@ -8,7 +8,7 @@ extern "C++" {
 // (fail-fast, as the reference), not a hand-off of the prefix — and a batch that is not device-resident is refused. `refusal`: the
 // entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
 #define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
-// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, whose contract lists the batch among its arguments.
+// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline and etlg_ducklake_plan, whose contracts list the batch among their arguments.
 static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal, int32_t code = ETLG_InvalidState) {
   if (b->pending) RC(etlg_batch_sync(c, b));
   if (!b->v.on_device || !b->dev) return lib_error(c, code, refusal);
@@ -275,6 +275,82 @@ int32_t etlg_batch_outline(etlg_ctx* c, etlg_batch* b, uint64_t first, uint64_t 
     if (touched_out && np && W) memcpy(touched_out, staged(lay.s_touched), np * W * 8);
     if (trunc_out && nt) memcpy(trunc_out, staged(lay.s_trunc), nt * 16);
     if (slots_out && ns) memcpy(slots_out, staged(lay.s_slots), ns * 96);
+  }
+  return ETLG_OK;
+}
+
+// The DuckLake atomic-batch plan (include/etlg.h; k_dlp_* in finish.hip). Everything is sized from what the host knows — the events,
+// the passes' count, the caller's caps — so the launches go out in one piece and the call stops once: for the header and, for a host
+// caller, the staged outputs, of which the written parts are then copied to the caller. A device caller's memory is written by the last
+// two kernels alone, and by neither when a status word is set.
+int32_t etlg_ducklake_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_outline_pass* passes, uint64_t n_passes, uint32_t passes_on_device,
+                           uint32_t has_watermark, uint64_t wm_commit_lsn, uint64_t wm_tx_ordinal, uint64_t seed, const etlg_rowbinary* tuples,
+                           const etlg_rowbinary* predicates, const etlg_rowbinary* updates, uint32_t flags, etlg_dl_range* ranges_out, etlg_dl_batch* batches_out,
+                           uint64_t batches_cap, etlg_dl_op* ops_out, uint64_t ops_cap, etlg_dl_plan_info* info) {
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  *info = etlg_dl_plan_info{};
+  info->event = info->bad_pass = ~0ull;
+  if (const int32_t rc = batch_ready(c, b, "etlg_ducklake_plan" NEEDS_DEVICE, ETLG_InvalidArgument)) return rc;
+  if (b->copy.active) return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_plan: a table-copy batch is one batch of all its rows, there is nothing to plan");
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (n_passes && !passes) return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_plan: n_passes without passes");
+  const etlg_batch_view& bv = b->v;
+  const uint64_t n = bv.n_events;
+  if (n_passes > (1ull << 38) || n > (1ull << 38)) return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_plan: more passes or events than one call takes (2^38: a grid of 2^30 workgroups walks them)");
+  auto mine = [&](const etlg_rowbinary* r, uint32_t what) { return !r || (r->dl_batch == b && r->dl_serial == b->serial && r->dl_slot == slot && r->dl_what == what && r->v.on_device && r->v.status == ETLG_RB_OK); };
+  if (!mine(tuples, ETLG_DL_TUPLES) || !mine(predicates, ETLG_DL_PREDICATES) || !mine(updates, ETLG_DL_UPDATES))
+    return lib_error(c, ETLG_InvalidArgument, "etlg_ducklake_plan takes the ETLG_DL_TUPLES, ETLG_DL_PREDICATES and ETLG_DL_UPDATES objects etlg_batch_duckdb built for this batch and slot, on the device (ETLG_F_OUTPUT_ON_DEVICE) and with status ETLG_RB_OK");
+  static_assert(sizeof(etlg_dl_range) == 24 && sizeof(etlg_dl_batch) == 8 * kDlpBatchWords && sizeof(etlg_dl_op) == 8 * kDlpOpWords && sizeof(etlg_outline_pass) == 56,
+                "k_dlp_groups / k_dlp_ops write 3, 13 and 4 words; the windows are words 0 and 1 of 7");
+  if (!n_passes || !n) return ETLG_OK;   // no window, or no event a window could hold: no member, no group
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  if (!ranges_out && !batches_out) batches_cap = 0;
+  if (!ops_out) ops_cap = 0;
+  const uint64_t B = batches_cap < n ? batches_cap : n, K = ops_cap < 2 * n ? ops_cap : 2 * n;   // what can be written at the most
+  uint64_t tile = c->dlp_tile_test ? c->dlp_tile_test : 2048u;
+  while ((n + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  const uint64_t n_tiles = (n + tile - 1) / tile;
+  const DlpLayout lay = dlp_layout(n, n_tiles, n_passes, B, K, ranges_out != nullptr, batches_out != nullptr, !passes_on_device, !on_dev);
+  hipStream_t s = c->stream;
+  ScratchBlk blk{c};
+  HIPCHK(c, blk_take(c, lay.total + 64, false, &blk.p, &blk.cap));
+  uint8_t* d = (uint8_t*)blk.p;
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr, 0, 32, s));
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr + 32, 0xFF, 32, s));
+  if (!passes_on_device) HIPCHK(c, hipMemcpyAsync(d + lay.passes, passes, n_passes * 56, hipMemcpyHostToDevice, s));
+  typedef unsigned long long* W64;
+  DlpJob j{};
+  j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot; j.ev_start = bv.ev_start_lsn; j.ev_commit = bv.ev_commit_lsn; j.ev_ord = bv.ev_tx_ordinal;
+  j.n_events = n; j.passes = passes_on_device ? (const unsigned long long*)passes : (const unsigned long long*)(d + lay.passes); j.n_passes = n_passes;
+  j.slot = (uint32_t)slot; j.no_ident = c->slots[(size_t)slot]->desc.n_ident == 0 ? 1u : 0u;
+  j.has_wm = has_watermark ? 1u : 0u; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles; j.wm_lsn = wm_commit_lsn; j.wm_ord = wm_tx_ordinal; j.seed = seed;
+  const auto recs = [](const etlg_rowbinary* r) { return r ? DlpRecs{(const unsigned long long*)r->v.row_event, r->v.n_rows, 1u, 0u} : DlpRecs{nullptr, 0, 0u, 0u}; };
+  j.t = recs(tuples); j.p = recs(predicates); j.u = recs(updates);
+  j.hdr = (W64)(d + lay.hdr); j.tsum = (W64)(d + lay.tsum); j.code = d + lay.code; j.rpre = (W64)(d + lay.rpre);
+  j.glens = (uint32_t*)(d + lay.glens); j.gpre = (const int64_t*)(d + lay.gpre); j.dense = (W64)(d + lay.dense); j.gstart = (W64)(d + lay.gstart);
+  j.mpos = (W64)(d + lay.mpos); j.oplens = (uint32_t*)(d + lay.oplens); j.opre = (const int64_t*)(d + lay.opre);
+  j.batches_cap = B; j.ops_cap = K;
+  j.ranges_out = !ranges_out ? nullptr : on_dev ? (W64)ranges_out : (W64)(d + lay.s_ranges);
+  j.batches_out = !batches_out ? nullptr : on_dev ? (W64)batches_out : (W64)(d + lay.s_batches);
+  j.ops_out = !ops_out ? nullptr : on_dev ? (W64)ops_out : (W64)(d + lay.s_ops);
+  etlg_k_ducklake_plan(&j, (W64)(d + lay.gblk), (W64)(d + lay.oblk), s);
+  uint64_t head[DLP_H_WORDS] = {};
+  HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> back;
+  if (!on_dev && lay.total > lay.stage_at) { back.resize(lay.total - lay.stage_at); HIPCHK(c, hipMemcpyAsync(back.data(), d + lay.stage_at, back.size(), hipMemcpyDeviceToHost, s)); }
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop
+  if (head[DLP_H_BAD] != ~0ull) { info->status = ETLG_DLP_BAD_PASSES; info->bad_pass = head[DLP_H_BAD]; return ETLG_OK; }
+  if (head[DLP_H_REFUSED] != ~0ull) { info->status = ETLG_DLP_REFUSED; info->event = head[DLP_H_REFUSED] >> 2; info->reason = (uint32_t)(head[DLP_H_REFUSED] & 3u); return ETLG_OK; }
+  if (head[DLP_H_NOTPREFIX] != ~0ull) { info->status = ETLG_DLP_NOT_PREFIX; info->event = head[DLP_H_NOTPREFIX]; return ETLG_OK; }
+  if (head[DLP_H_NEEDSHOST] != ~0ull) { info->status = ETLG_DLP_NEEDS_HOST; info->event = head[DLP_H_NEEDSHOST]; return ETLG_OK; }
+  info->n_batches = head[DLP_H_BATCHES]; info->n_ops = head[DLP_H_OPS]; info->n_members = head[DLP_H_MEMBERS]; info->n_retained = head[DLP_H_RETAINED];
+  info->n_dropped = info->n_members - info->n_retained;
+  if (!on_dev) {
+    const uint64_t nb = info->n_batches < B ? info->n_batches : B, nk = info->n_ops < K ? info->n_ops : K;
+    const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
+    if (ranges_out && nb) memcpy(ranges_out, staged(lay.s_ranges), nb * 24);
+    if (batches_out && nb) memcpy(batches_out, staged(lay.s_batches), nb * 104);
+    if (ops_out && nk) memcpy(ops_out, staged(lay.s_ops), nk * 32);
   }
   return ETLG_OK;
 }

@@ -45,6 +45,24 @@ inline OutlineLayout outline_layout(uint64_t n, uint64_t n_tiles, uint64_t n_slo
   return o;
 }
 
+// etlg_ducklake_plan, its one block: hdr (4 words of zeros, then 4 of all ones) | what is written before it is read — the tile sums, a
+// code byte and rpre per event, the groups per window with their scan, the dense list, the groups' starts, two record positions per
+// member, the ops per group with their scan — | a host caller's passes | the staging of a host caller's outputs in one piece
+// ([stage_at, total): ranges | batches | ops). B, K: the groups and ops that can be written; a part nobody asked for takes nothing.
+struct DlpLayout { size_t hdr, tsum, code, rpre, glens, gblk, gpre, dense, gstart, mpos, oplens, oblk, opre, passes, stage_at, s_ranges, s_batches, s_ops, total; };
+inline DlpLayout dlp_layout(uint64_t n, uint64_t n_tiles, uint64_t n_passes, uint64_t B, uint64_t K, bool want_ranges, bool want_batches, bool passes_here, bool stage) {
+  ScratchLayout l; DlpLayout o{};
+  o.hdr = l.take(64); o.tsum = l.take(n_tiles * 16); o.code = l.take(n); o.rpre = l.take((n + 1) * 8);
+  o.glens = l.take(n_passes * 4); o.gblk = l.take((n_passes / 256 + 2) * 8); o.gpre = l.take((n_passes + 1) * 8);
+  o.dense = l.take(n * 8); o.gstart = l.take((n + 1) * 8); o.mpos = l.take(n * 16);
+  o.oplens = l.take(n * 4); o.oblk = l.take((n / 256 + 2) * 8); o.opre = l.take((n + 1) * 8);
+  o.passes = l.take(passes_here ? n_passes * 56 : 0);
+  o.stage_at = l.total();
+  o.s_ranges = l.take(stage && want_ranges ? B * 24 : 0); o.s_batches = l.take(stage && want_batches ? B * 104 : 0); o.s_ops = l.take(stage ? K * 32 : 0);
+  o.total = l.total();
+  return o;
+}
+
 // etlg_batch_payload: hdr | hist | bounds (the three the call reads back and uploads) | the frame side | the event side. ev_bytes and sums
 // live here unless they go straight to the caller's device memory; the range sums' parts exist only when sums are asked for.
 struct PayLayout { size_t hdr, hist, bounds, fbytes, tcnt, r2f, brank, etb, evb, tsum, pb, pr, cuts, sums, total; };

@@ -62,6 +62,18 @@ class Outline:
         return list(seen.values())
 
 
+class DuckLakePlan:
+    """What Batch.ducklake_plan returns: info (abi.DlPlanInfo) and, cut to what was written — or as the device addresses the caller
+    gave —, ranges (abi.DlRange per group: what ducklake_fingerprints takes), batches (abi.DlBatch) and ops (abi.DlOp)."""
+
+    def __init__(self, info, ranges, batches, ops):
+        self.info, self.ranges, self.batches, self.ops = info, ranges, batches, ops
+
+    def fingerprint_ranges(self):
+        """[(first_event, end_event, seed)] for Batch.ducklake_fingerprints (host arrays only)."""
+        return [(int(r.first_event), int(r.end_event), int(r.seed)) for r in self.ranges]
+
+
 class Batch:
     """A decoded batch (etlg_batch). `host()` copies the arena into numpy arrays."""
 
@@ -340,6 +352,49 @@ class Batch:
         if rc != abi.OK:
             raise self.dec.last_error()
         return out, info
+
+    def ducklake_plan(self, slot, passes, n_passes=None, watermark=None, seed=0, tuples=None, predicates=None, updates=None,
+                      batches_cap=None, ops_cap=None, on_device=False):
+        """The DuckLake sink's atomic batches of schema slot `slot`, cut on the device (etlg_ducklake_plan). `passes`: what
+        Batch.outline gave — np.uint64[P, 7], or the address of a device array of `n_passes` etlg_outline_pass; only first_event and
+        data_end are read. watermark: None or (commit_lsn, tx_ordinal), the sequence key already applied. seed: the table's hasher state,
+        copied into every range. tuples / predicates / updates: the device-resident duckdb() results of this batch and slot, or None.
+        on_device: False -> arrays; a dict of device addresses under "ranges", "batches", "ops" (absent: that part is skipped) ->
+        written there, with batches_cap / ops_cap saying what they hold. Host caps left None: one call counts, a second one fills arrays
+        of exactly that size. Returns a DuckLakePlan; with info.status != abi.DLP_OK nothing but info is set."""
+        if isinstance(passes, (int, np.integer)):
+            pptr, npass, pdev = int(passes), int(n_passes), 1
+        else:
+            passes = np.ascontiguousarray(passes, dtype=np.uint64).reshape(-1, 7)
+            pptr, npass, pdev = (passes.ctypes.data if len(passes) else None), len(passes), 0
+        has_wm, wl, wo = (0, 0, 0) if watermark is None else (1, int(watermark[0]), int(watermark[1]))
+        h = lambda r: r.h if r is not None else None
+
+        def call(flags, rp, bp, bcap, op, ocap):
+            info = abi.DlPlanInfo()
+            rc = self.dec.L.etlg_ducklake_plan(self.dec.h, self.h, slot, pptr, npass, pdev, has_wm, wl, wo, int(seed), h(tuples), h(predicates), h(updates),
+                                               flags, rp, bp, bcap, op, ocap, C.byref(info))
+            if rc != abi.OK:
+                raise self.dec.last_error()
+            return info
+
+        if on_device:
+            g = lambda k: int(on_device[k]) if on_device.get(k) else None
+            info = call(abi.F_OUTPUT_ON_DEVICE, g("ranges"), g("batches"), int(batches_cap or 0), g("ops"), int(ops_cap or 0))
+            return DuckLakePlan(info, g("ranges"), g("batches"), g("ops"))
+        if batches_cap is None or ops_cap is None:
+            info = call(0, None, None, 0, None, 0)
+            if info.status != abi.DLP_OK:
+                return DuckLakePlan(info, None, None, None)
+            batches_cap = int(info.n_batches) if batches_cap is None else int(batches_cap)
+            ops_cap = int(info.n_ops) if ops_cap is None else int(ops_cap)
+        bc, oc = int(batches_cap), int(ops_cap)
+        ranges, batches, ops = (abi.DlRange * max(1, bc))(), (abi.DlBatch * max(1, bc))(), (abi.DlOp * max(1, oc))()
+        info = call(0, C.addressof(ranges) if bc else None, C.addressof(batches) if bc else None, bc, C.addressof(ops) if oc else None, oc)
+        if info.status != abi.DLP_OK:
+            return DuckLakePlan(info, None, None, None)
+        B, K = min(bc, int(info.n_batches)), min(oc, int(info.n_ops))
+        return DuckLakePlan(info, [ranges[i] for i in range(B)], [batches[i] for i in range(B)], [ops[i] for i in range(K)])
 
     def close(self):
         if self.h:

@@ -1261,6 +1261,121 @@ int32_t etlg_batch_outline(etlg_ctx* ctx, etlg_batch* batch, uint64_t first, uin
                            uint64_t* touched_out, uint64_t passes_cap, etlg_outline_trunc* trunc_out, uint64_t trunc_cap,
                            etlg_outline_slot* slots_out, etlg_outline_info* info);
 
+/* The DuckLake sink's atomic batches of ONE schema slot, cut on the device: the step between etlg_batch_outline and
+ * etlg_ducklake_fingerprints — the replay filter (retain_mutations_after_sequence_key, etl-destinations ducklake/batches.rs:932-946), the
+ * cut into atomic batches with their identity fields (prepare_mutation_table_batches :727-758, push_prepared_mutation_batch :1091-1125)
+ * and the grouping of a batch's mutations into the DuckDB operations the sink executes (prepare_table_mutations :1128-1226) — without
+ * downloading ev_kind / ev_flags / ev_schema_slot / ev_start_lsn / ev_commit_lsn / ev_tx_ordinal.
+ * Windows: `passes` (n_passes entries; device memory when passes_on_device != 0, else host memory) are the passes etlg_batch_outline
+ * wrote, of which only [first_event, data_end) is read: one window is one segment of the reference, the rows write_events_inner
+ * (ducklake/core.rs:1815-1947) collects per table before a Relation or Truncate. Windows ascend and do not overlap; an empty window is
+ * allowed.
+ * MEMBERS of a window: its Insert / Update / Delete events with ev_schema_slot == schema_slot. Category (ETLG_DLP_CAT_*): Insert;
+ * UPDATE_FULL = Update with ETLG_OLD_FULL / _KEY and a full new row; REPLACE = Update with ETLG_OLD_NONE and a full new row;
+ * UPDATE_PARTIAL = Update with ETLG_FLAG_PARTIAL, any old image; DELETE = Delete.
+ * REFUSED members (before the replay filter, as in the reference): an Update / Delete of a slot with n_ident == 0
+ * (ETLG_DLP_R_UPDATE_IDENTITY "DuckLake update requires a replica identity", ETLG_DLP_R_DELETE_IDENTITY "DuckLake delete requires a
+ * replica identity"; core.rs:371-392), else a Delete with ETLG_OLD_NONE (ETLG_DLP_R_DELETE_NO_OLD "DuckLake delete requires an old row
+ * image", :1919-1929).
+ * REPLAY FILTER: with has_watermark != 0 a member is retained iff (ev_commit_lsn, ev_tx_ordinal) > (wm_commit_lsn, wm_tx_ordinal),
+ * lexicographically (compare_sequence_keys :1012-1015); otherwise every member is retained.
+ * ATOMIC BATCHES: per window the retained members in event order, in consecutive groups of 16 (CDC_MUTATION_BATCH_SIZE, :79); the last
+ * group of a window may be shorter; no group spans two windows.
+ * OPERATIONS of a group, in member order: a maximal run of INSERTs is one UPSERT op of n rows; a maximal run of DELETEs one DELETE op
+ * of n predicates, origin "delete"; every UPDATE_FULL a DELETE op (origin "update", 1 predicate) then an UPSERT op of 1 row; every
+ * REPLACE the same with origin "replace"; every UPDATE_PARTIAL one UPDATE op. An Insert directly behind an Update's own UPSERT op
+ * starts a new UPSERT op (the reference does not merge them, :3168-3233). A group has at most 32 ops.
+ * `tuples` / `predicates` / `updates`: the objects etlg_batch_duckdb built for this batch and slot, checked as
+ * etlg_ducklake_fingerprints checks them (ETLG_InvalidArgument otherwise); each may be NULL.
+ * Outputs: device memory with ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory; any may be NULL and its part is skipped.
+ *   ranges_out[b], b < min(n_batches, batches_cap)    {first_event, end_event, seed}: what etlg_ducklake_fingerprints takes as `ranges`.
+ *   batches_out[b], same b                            the group; op_first / n_ops index ops_out, counted over all ops, those beyond
+ *                                                     ops_cap included.
+ *   ops_out[k], k < min(n_ops, ops_cap)               the op. rec_first is the index of its first record in the object of its kind — an
+ *                                                     UPSERT op's in `tuples`, a DELETE op's in `predicates`, an UPDATE op's in `updates`
+ *                                                     (its SET record 2k; 2k + 1 is its predicate) —, the lower bound of first_event in
+ *                                                     that object's row_event; the op's n records follow it without a gap. ~0 when the
+ *                                                     object is NULL.
+ * info gives the full n_batches, n_ops, n_members, n_retained and n_dropped; nothing is written at or beyond a cap, caps of 0 only count.
+ * info->status, the first that applies; for every status but ETLG_DLP_OK NO output array is touched and the counts are 0:
+ *   ETLG_DLP_BAD_PASSES  a window with first_event > data_end, data_end > n_events, or first_event below its predecessor's data_end;
+ *                        info->bad_pass = the lowest such index.
+ *   ETLG_DLP_REFUSED     info->event = the lowest refused member inside a window, info->reason = ETLG_DLP_R_*. The reference fails the
+ *                        whole write_events at the first such event over all tables: the host takes the minimum over the slots it plans.
+ *   ETLG_DLP_NOT_PREFIX  info->event = the lowest dropped member that follows a retained member of its window. Keys ascend in a
+ *                        replication stream, so this should not occur; a range [first_event, end_event) would otherwise cover an event
+ *                        the fingerprint must not absorb.
+ *   ETLG_DLP_NEEDS_HOST  info->event = the lowest retained member whose record is missing from an object that was given (the events the
+ *                        hand-off calls counted in n_host_rows). A NULL object is no error; a partial Update with updates == NULL is
+ *                        reported by etlg_ducklake_fingerprints.
+ * ETLG_InvalidArgument: a batch of etlg_copy_decode (prepare_copy_table_batch makes one batch of all rows), a batch that is not
+ * device-resident (an ASYNC batch is synced first; one that ended in a decode error gives that error), an unknown slot, n_passes > 0
+ * without passes, n_passes or n_events above 2^38. The call stops for the device once, at its end.
+ * What is tested: tests/golden/ducklake_plan_kats.json transcribes the reference's own vectors (batches.rs:2893-3272);
+ * tests/ducklake_plan.py restates the three loops. */
+#define ETLG_DLP_OK 0u
+#define ETLG_DLP_BAD_PASSES 1u
+#define ETLG_DLP_REFUSED 2u
+#define ETLG_DLP_NOT_PREFIX 3u
+#define ETLG_DLP_NEEDS_HOST 4u
+#define ETLG_DLP_R_UPDATE_IDENTITY 1u
+#define ETLG_DLP_R_DELETE_IDENTITY 2u
+#define ETLG_DLP_R_DELETE_NO_OLD 3u
+#define ETLG_DLP_CAT_INSERT 0u
+#define ETLG_DLP_CAT_UPDATE_FULL 1u
+#define ETLG_DLP_CAT_REPLACE 2u
+#define ETLG_DLP_CAT_UPDATE_PARTIAL 3u
+#define ETLG_DLP_CAT_DELETE 4u
+#define ETLG_DLP_OP_UPSERT 0u
+#define ETLG_DLP_OP_DELETE 1u
+#define ETLG_DLP_OP_UPDATE 2u
+#define ETLG_DLP_ORIGIN_NONE 0u
+#define ETLG_DLP_ORIGIN_DELETE 1u
+#define ETLG_DLP_ORIGIN_UPDATE 2u
+#define ETLG_DLP_ORIGIN_REPLACE 3u
+
+typedef struct etlg_dl_batch {
+  uint64_t first_event;       /* the first member */
+  uint64_t end_event;         /* the last member + 1 */
+  uint64_t first_start_lsn;   /* the first member's ev_start_lsn */
+  uint64_t last_commit_lsn;   /* the last member's ev_commit_lsn: with last_tx_ordinal the last sequence key */
+  uint64_t first_commit_lsn;  /* with first_tx_ordinal the first sequence key */
+  uint64_t first_tx_ordinal;
+  uint64_t last_tx_ordinal;
+  uint64_t window;            /* index into `passes` */
+  uint64_t op_first;          /* first entry of ops_out */
+  uint32_t n_members;         /* 1 .. 16 */
+  uint32_t n_ops;             /* 1 .. 32 */
+  uint32_t n_cat[5];          /* members per ETLG_DLP_CAT_* */
+  uint32_t _pad;
+} etlg_dl_batch;
+
+typedef struct etlg_dl_op {
+  uint32_t kind;              /* ETLG_DLP_OP_* */
+  uint32_t origin;            /* ETLG_DLP_ORIGIN_*: of a DELETE op */
+  uint64_t first_event;       /* the op's first member */
+  uint64_t n;                 /* rows / predicates; 1 for UPDATE */
+  uint64_t rec_first;         /* ~0: the object is NULL */
+} etlg_dl_op;
+
+typedef struct etlg_dl_plan_info {
+  uint64_t n_batches;         /* may exceed batches_cap */
+  uint64_t n_ops;             /* may exceed ops_cap */
+  uint64_t n_members;
+  uint64_t n_retained;
+  uint64_t n_dropped;         /* n_members - n_retained */
+  uint64_t event;             /* REFUSED / NOT_PREFIX / NEEDS_HOST: the lowest such event */
+  uint64_t bad_pass;          /* BAD_PASSES: the lowest such window */
+  uint32_t status;            /* ETLG_DLP_* */
+  uint32_t reason;            /* REFUSED: ETLG_DLP_R_* */
+} etlg_dl_plan_info;
+
+int32_t etlg_ducklake_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const etlg_outline_pass* passes, uint64_t n_passes,
+                           uint32_t passes_on_device, uint32_t has_watermark, uint64_t wm_commit_lsn, uint64_t wm_tx_ordinal, uint64_t seed,
+                           const etlg_rowbinary* tuples, const etlg_rowbinary* predicates, const etlg_rowbinary* updates, uint32_t flags,
+                           etlg_dl_range* ranges_out, etlg_dl_batch* batches_out, uint64_t batches_cap, etlg_dl_op* ops_out,
+                           uint64_t ops_cap, etlg_dl_plan_info* info);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
