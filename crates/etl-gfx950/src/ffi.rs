@@ -381,6 +381,53 @@ pub struct etlg_dl_plan_info {
     pub reason: u32,
 }
 
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_sf_segment {
+    pub window: u64,
+    pub first_row: u64,
+    pub end_row: u64,
+    pub first_event: u64,
+    pub last_event: u64,
+    pub byte_first: u64,
+    pub byte_end: u64,
+    pub first_row_bytes: u64,
+    pub first_commit_lsn: u64,
+    pub first_tx_ordinal: u64,
+    pub last_commit_lsn: u64,
+    pub last_tx_ordinal: u64,
+    pub flush_before: u32,
+    pub _pad: u32,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_sf_window {
+    pub seg_first: u64,
+    pub n_segs: u64,
+    pub first_row: u64,
+    pub end_row: u64,
+    pub n_members: u64,
+    pub n_retained: u64,
+    pub n_bytes: u64,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_sf_plan_info {
+    pub n_segs: u64,
+    pub n_members: u64,
+    pub n_retained: u64,
+    pub n_dropped: u64,
+    pub n_rows: u64,
+    pub n_bytes: u64,
+    pub event: u64,
+    pub row_bytes: u64,
+    pub bad_pass: u64,
+    pub status: u32,
+    pub reason: u32,
+}
+
 #[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
@@ -447,6 +494,16 @@ pub const ETLG_DLP_ORIGIN_NONE: u32 = 0;
 pub const ETLG_DLP_ORIGIN_DELETE: u32 = 1;
 pub const ETLG_DLP_ORIGIN_UPDATE: u32 = 2;
 pub const ETLG_DLP_ORIGIN_REPLACE: u32 = 3;
+pub const ETLG_SF_MAX_UNFLUSHED_BYTES: u64 = 131072;
+pub const ETLG_SF_MAX_ROW_BYTES: u64 = 2097152;
+pub const ETLG_SFP_OK: u32 = 0;
+pub const ETLG_SFP_BAD_PASSES: u32 = 1;
+pub const ETLG_SFP_FAILED: u32 = 2;
+pub const ETLG_SFP_NOT_PREFIX: u32 = 3;
+pub const ETLG_SFP_NEEDS_HOST: u32 = 4;
+pub const ETLG_SFP_R_PARTIAL_UPDATE: u32 = 1;
+pub const ETLG_SFP_R_DELETE_NO_OLD: u32 = 2;
+pub const ETLG_SFP_R_ROW_TOO_LARGE: u32 = 3;
 pub const ETLG_DL_TUPLES: i32 = 0;
 pub const ETLG_DL_PREDICATES: i32 = 1;
 pub const ETLG_DL_UPDATES: i32 = 3;
@@ -693,6 +750,25 @@ extern "C" {
         ops_out: *mut etlg_dl_op,
         ops_cap: u64,
         info: *mut etlg_dl_plan_info,
+    ) -> i32;
+    pub fn etlg_snowflake_plan(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        schema_slot: i32,
+        passes: *const etlg_outline_pass,
+        n_passes: u64,
+        passes_on_device: u32,
+        has_committed: u32,
+        c_commit_lsn: u64,
+        c_tx_ordinal: u64,
+        ndjson: *const etlg_rowbinary,
+        flush_bytes: u64,
+        max_row_bytes: u64,
+        flags: u32,
+        segs_out: *mut etlg_sf_segment,
+        segs_cap: u64,
+        windows_out: *mut etlg_sf_window,
+        info: *mut etlg_sf_plan_info,
     ) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;
     pub fn etlg_ctx_slots(ctx: *const etlg_ctx, n_slots: *mut u32, slots: *mut *const etlg_slot_desc) -> i32;

@@ -384,6 +384,51 @@ impl GpuDecoder {
         Ok(out)
     }
 
+    /// The Snowflake sink's row batches of one schema slot of a device-resident batch, planned on the device (etlg_snowflake_plan): what
+    /// `encode_insert` / `encode_update` / `encode_delete` (snowflake/core.rs:345-438) and `RowBatchBuilder::push_row`
+    /// (snowflake/streaming/batch.rs:150-189) decide per row — the committed-offset test, the three refusals and where the encoder is
+    /// flushed — as segments of consecutive rows of `ndjson`, the device-resident `etlg_batch_ndjson` object of this batch and slot.
+    /// `passes`: what `GpuDecoder::outline` returned — only `[first_event, data_end)` is read; empty on a table-copy batch (one window
+    /// over all rows). `committed`: the channel's committed offset. The reference's thresholds are `ETLG_SF_MAX_UNFLUSHED_BYTES` and
+    /// `ETLG_SF_MAX_ROW_BYTES`. At most `segs_cap` segments come back; `info.n_segs` is the full count — call again with a larger cap.
+    /// With `info.status != ETLG_SFP_OK` nothing but `info` is set. Per segment the host flushes when `flush_before != 0`, checks the
+    /// compressed size with `first_row_bytes`, writes `bytes[byte_first..byte_end]` in one `write_all` and extends the offset range.
+    #[allow(clippy::too_many_arguments)]
+    pub fn snowflake_plan(
+        &mut self, batch: *mut etlg_batch, schema_slot: i32, passes: &[etlg_outline_pass], committed: Option<(u64, u64)>, ndjson: *const etlg_rowbinary, flush_bytes: u64,
+        max_row_bytes: u64, segs_cap: usize,
+    ) -> EtlResult<SnowflakePlan> {
+        let n_windows = if passes.is_empty() { 1 } else { passes.len() };
+        let mut out = SnowflakePlan {
+            segments: vec![
+                etlg_sf_segment {
+                    window: 0, first_row: 0, end_row: 0, first_event: 0, last_event: 0, byte_first: 0, byte_end: 0, first_row_bytes: 0, first_commit_lsn: 0, first_tx_ordinal: 0,
+                    last_commit_lsn: 0, last_tx_ordinal: 0, flush_before: 0, _pad: 0,
+                };
+                segs_cap
+            ],
+            windows: vec![etlg_sf_window { seg_first: 0, n_segs: 0, first_row: 0, end_row: 0, n_members: 0, n_retained: 0, n_bytes: 0 }; n_windows],
+            info: etlg_sf_plan_info { n_segs: 0, n_members: 0, n_retained: 0, n_dropped: 0, n_rows: 0, n_bytes: 0, event: 0, row_bytes: 0, bad_pass: 0, status: 0, reason: 0 },
+        };
+        let (has_c, c_lsn, c_ord) = match committed { Some((l, o)) => (1, l, o), None => (0, 0, 0) };
+        let rc = unsafe {
+            etlg_snowflake_plan(
+                self.ctx, batch, schema_slot, if passes.is_empty() { std::ptr::null() } else { passes.as_ptr() }, passes.len() as u64, 0, has_c, c_lsn, c_ord, ndjson,
+                flush_bytes, max_row_bytes, 0, if segs_cap == 0 { std::ptr::null_mut() } else { out.segments.as_mut_ptr() }, segs_cap as u64, out.windows.as_mut_ptr(),
+                &mut out.info,
+            )
+        };
+        if rc != ETLG_OK {
+            return Err(self.last_error());
+        }
+        let ok = out.info.status == ETLG_SFP_OK;
+        out.segments.truncate(if ok { out.info.n_segs.min(segs_cap as u64) as usize } else { 0 });
+        if !ok {
+            out.windows.clear();
+        }
+        Ok(out) // (no passes: `windows` has one entry, the whole-batch window of a table-copy batch; all zeros for any other batch)
+    }
+
     /// Source payload accounting of a device-resident batch, on the device (etlg_batch_payload), as plain values: per event the value
     /// bytes of its message (what `StreamingPayloadMetadata::{insert,update,delete}` is built from, apply.rs:2459-2463; the kind is the
     /// event's), per range of `cuts` the merged bytes and rows per kind (what `EventBatch::push` accumulates, apply.rs:656-658; rows == 0
@@ -455,6 +500,22 @@ impl DuckLakePlan {
         let (lo, n) = (self.batches[b].op_first as usize, self.batches[b].n_ops as usize);
         let hi = (lo + n).min(self.ops.len());
         &self.ops[lo.min(hi)..hi]
+    }
+}
+
+/// What `GpuDecoder::snowflake_plan` returns.
+pub struct SnowflakePlan {
+    pub segments: Vec<etlg_sf_segment>,
+    pub windows: Vec<etlg_sf_window>,
+    pub info: etlg_sf_plan_info,
+}
+
+impl SnowflakePlan {
+    /// The segments of window `w` that were written (those beyond `segs_cap` are not there to be looked at).
+    pub fn segments_of(&self, w: usize) -> &[etlg_sf_segment] {
+        let (lo, n) = (self.windows[w].seg_first as usize, self.windows[w].n_segs as usize);
+        let hi = (lo + n).min(self.segments.len());
+        &self.segments[lo.min(hi)..hi]
     }
 }
 

@@ -185,6 +185,21 @@ class DlPlanInfo(C.Structure):   # etlg_dl_plan_info
                 + [("status", C.c_uint32), ("reason", C.c_uint32)])
 
 
+class SfSegment(C.Structure):   # etlg_sf_segment
+    _fields_ = ([(n, C.c_uint64) for n in ("window", "first_row", "end_row", "first_event", "last_event", "byte_first", "byte_end", "first_row_bytes",
+                                            "first_commit_lsn", "first_tx_ordinal", "last_commit_lsn", "last_tx_ordinal")]
+                + [("flush_before", C.c_uint32), ("_pad", C.c_uint32)])
+
+
+class SfWindow(C.Structure):   # etlg_sf_window
+    _fields_ = [(n, C.c_uint64) for n in ("seg_first", "n_segs", "first_row", "end_row", "n_members", "n_retained", "n_bytes")]
+
+
+class SfPlanInfo(C.Structure):   # etlg_sf_plan_info
+    _fields_ = ([(n, C.c_uint64) for n in ("n_segs", "n_members", "n_retained", "n_dropped", "n_rows", "n_bytes", "event", "row_bytes", "bad_pass")]
+                + [("status", C.c_uint32), ("reason", C.c_uint32)])
+
+
 class FinishStats(C.Structure):   # etlg_finish_stats
     _fields_ = [(n, C.c_uint64) for n in ("deferred_seen", "arrays_typed", "floats_settled", "left_deferred", "heap_bytes_added")]
 
@@ -201,6 +216,9 @@ DLP_R_UPDATE_IDENTITY, DLP_R_DELETE_IDENTITY, DLP_R_DELETE_NO_OLD = 1, 2, 3
 DLP_CAT_INSERT, DLP_CAT_UPDATE_FULL, DLP_CAT_REPLACE, DLP_CAT_UPDATE_PARTIAL, DLP_CAT_DELETE = range(5)
 DLP_OP_UPSERT, DLP_OP_DELETE, DLP_OP_UPDATE = range(3)
 DLP_ORIGIN_NONE, DLP_ORIGIN_DELETE, DLP_ORIGIN_UPDATE, DLP_ORIGIN_REPLACE = range(4)
+SF_MAX_UNFLUSHED_BYTES, SF_MAX_ROW_BYTES = 131072, 2097152
+SFP_OK, SFP_BAD_PASSES, SFP_FAILED, SFP_NOT_PREFIX, SFP_NEEDS_HOST = range(5)
+SFP_R_PARTIAL_UPDATE, SFP_R_DELETE_NO_OLD, SFP_R_ROW_TOO_LARGE = 1, 2, 3
 DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)

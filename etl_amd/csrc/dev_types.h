@@ -402,6 +402,31 @@ struct DlpJob {
   unsigned long long* ops_out; uint64_t ops_cap;                                           // kDlpOpWords words per op
 };
 
+// The Snowflake row-batch plan (etlg_snowflake_plan: k_sfp_* in finish.hip). hdr: four counts and the ROW_TOO_LARGE length start as
+// zeros, the four status words — the lowest bad pass, the lowest failing event * 4 + its reason, the lowest not-prefix event, the lowest
+// retained event without a row — as all ones. No kernel behind the one that sets a status word writes an output once one of them is set.
+enum : uint32_t { SFP_H_MEMBERS = 0, SFP_H_RETAINED = 1, SFP_H_SEGS = 2, SFP_H_BYTES = 3, SFP_H_BAD = 4, SFP_H_FAILED = 5, SFP_H_NOTPREFIX = 6, SFP_H_NEEDSHOST = 7,
+                  SFP_H_ROWBYTES = 8, SFP_H_WORDS = 16 };
+constexpr uint32_t kSfpSegWords = 13;     // etlg_sf_segment
+constexpr uint32_t kSfpWinWords = 7;      // etlg_sf_window
+struct SfpJob {
+  const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint64_t* ev_commit; const uint64_t* ev_ord;
+  uint64_t n_events;
+  const unsigned long long* passes; uint64_t n_passes;   // etlg_outline_pass: 7 words, the window is words 0 and 1
+  const unsigned long long* row_event; const unsigned long long* q;   // the NDJSON object: n_rows events, n_rows + 1 offsets (the prefix sums of the row lengths)
+  uint64_t n_rows;
+  uint32_t slot, has_c, zero_keys, tile, n_tiles, levels;   // zero_keys: a table-copy batch, every key is (0, 0)
+  uint64_t c_lsn, c_ord, flush, max_row;
+  unsigned long long* hdr;            // SFP_H_*
+  unsigned long long* tsum;           // per tile: members, retained; after k_sfp_scan those in front of the tile
+  uint8_t* code;                      // per event: 1 member | 2 retained
+  unsigned long long* pre;            // 2 x (n_events + 1): members and retained members in front of the event
+  unsigned long long* wrow;           // per window: first_row, end_row
+  uint32_t* slens; const int64_t* spre;   // per window: its segments, and (n_passes + 1) the segments in front of it
+  uint32_t* jump;                     // levels x (n_rows + 2): next^(2^k) of every row; n_rows + 1 is the end
+  unsigned long long* segs_out; uint64_t segs_cap; unsigned long long* windows_out;
+};
+
 // Source payload accounting (etlg_batch_payload). The frame side (k_payf_* in kernels.hip) measures every row message and lists the
 // frames that take a transaction ordinal; the event side (k_paye_* in finish.hip) joins every event to its frame through that list and
 // sums the ranges. Channels: 0 Insert, 1 Update, 2 Delete; a table-copy batch has channel 0 alone and reports it as ETLG_PK_COPY.

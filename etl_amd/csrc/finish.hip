@@ -624,6 +624,191 @@ __global__ __launch_bounds__(256) void k_dlp_ops(DlpJob j) {
   }
 }
 
+// ---- the Snowflake row-batch plan (etlg_snowflake_plan, include/etlg.h: the rule is stated there). What encode_insert / _update /
+// _delete and RowBatchBuilder::push_row decide per row is a selection, three refusals and a byte counter that resets at every flush;
+// like the apply loop's budget rule above, the reset is not associative, and it decomposes the same way: the NDJSON object's
+// row_offsets q ARE the prefix sums of the row lengths, and the segment that STARTS at row a of a window whose retained rows end at
+// win_end ends at next(a) = min(win_end, max(a + 1, the smallest e with q[e + 1] - q[a] >= flush)), whatever came before a. A window's
+// segments are the orbit of its first retained row under next, cut where it reaches win_end, and the p-th is reached through the jump
+// levels next^(2^k) named by the bits of p. With no status set the retained members of a window are a suffix of its members and each
+// has a row, so they are the last `retained` rows in front of the lower bound of data_end in row_event. Launches, none of which
+// exchanges a word between its workgroups: the windows checked (k_sfp_mark), per tile the members and the retained ones, a code byte per
+// event and the lowest failing event and event without a row (k_sfp_tiles), the scan by one workgroup (k_sfp_scan), both prefixes per
+// event (k_sfp_write), the not-prefix test (k_sfp_members), next per row (k_sfp_next), a squaring per level (k_cut_level), per window
+// its rows and the count of its segments through the levels (k_sfp_pass), their scan (etlg_k_scan_lens), the windows (k_sfp_windows)
+// and the segments (k_sfp_emit). The host sizes the levels and the emit grid from the object's n_rows and n_bytes — two neighbouring
+// segments of a window hold at least `flush` bytes — so nothing is read back in between. Every loop runs to a launch parameter: tile /
+// 256 chunks, log2(n_passes) and log2(n_rows) steps of a search, `levels` jumps.
+DEV bool sfp_any_status(const SfpJob& j) {
+  return j.hdr[SFP_H_BAD] != kNone64 || j.hdr[SFP_H_FAILED] != kNone64 || j.hdr[SFP_H_NOTPREFIX] != kNone64 || j.hdr[SFP_H_NEEDSHOST] != kNone64;
+}
+// the window that can hold event i: the last one that starts at or in front of it (every earlier one has ended by then); ~0 none
+DEV uint64_t sfp_window(const SfpJob& j, uint64_t i) {
+  uint64_t lo = 0, hi = j.n_passes;
+  while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (j.passes[7 * mid] <= i) lo = mid + 1; else hi = mid; }
+  if (!lo || i >= j.passes[7 * (lo - 1) + 1]) return kNone64;
+  return lo - 1;
+}
+// the rows of the object whose event lies in front of event i
+DEV uint64_t sfp_rows_before(const SfpJob& j, uint64_t i) { return j.n_rows ? cut_lower_bound(j.row_event, 0, j.n_rows - 1, i) : 0; }
+
+__global__ __launch_bounds__(256) void k_sfp_mark(SfpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes) return;
+  const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1];
+  if (fe > de || de > j.n_events || (p && fe < j.passes[7 * (p - 1) + 1])) atomicMin(&j.hdr[SFP_H_BAD], (unsigned long long)p);
+}
+
+// a code byte per event, the tile's members and retained members, and the two minima: the lowest failing event (with its reason in the
+// low bits) and the lowest retained, non-failing member without a row. row_event == null: the object has no rows to look at (NEEDS_HOST)
+__global__ __launch_bounds__(256) void k_sfp_tiles(SfpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[SFP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t members = 0, kept = 0, failed = kNone64, norow = kNone64;
+  for (uint64_t i = k0 + threadIdx.x; i < k1; i += 256) {
+    const uint32_t kind = j.ev_kind[i];
+    uint32_t code = 0, why = 0;
+    if (ol_is_row(kind) && j.ev_slot[i] == j.slot && sfp_window(j, i) != kNone64) {
+      const uint32_t fl = j.ev_flags[i];
+      const uint64_t lsn = j.zero_keys ? 0 : j.ev_commit[i], ord = j.zero_keys ? 0 : j.ev_ord[i];
+      const bool keep = !j.has_c || lsn > j.c_lsn || (lsn == j.c_lsn && ord > j.c_ord);   // committed_offset >= offset drops it
+      code = 1u | (keep ? 2u : 0u);
+      if (kind == 'U' && (fl & ETLG_FLAG_PARTIAL)) why = ETLG_SFP_R_PARTIAL_UPDATE;          // refused in front of the filter
+      else if (keep && kind == 'D' && (fl & 3u) == ETLG_OLD_NONE) why = ETLG_SFP_R_DELETE_NO_OLD;
+      else if (keep && j.row_event) {
+        const uint64_t r = sfp_rows_before(j, i);
+        if (r >= j.n_rows || j.row_event[r] != i) { if (i < norow) norow = i; }
+        else if (j.q[r + 1] - j.q[r] > j.max_row) why = ETLG_SFP_R_ROW_TOO_LARGE;
+      }
+    }
+    j.code[i] = (uint8_t)code;
+    members += code & 1u;
+    kept += (code >> 1) & 1u;
+    if (why && i * 4 + why < failed) failed = i * 4 + why;
+  }
+  members = block_sum64(members, lds); kept = block_sum64(kept, lds); failed = block_min64(failed, lds); norow = block_min64(norow, lds);
+  if (threadIdx.x == 0) {
+    j.tsum[2 * (uint64_t)blockIdx.x] = members; j.tsum[2 * (uint64_t)blockIdx.x + 1] = kept;
+    if (failed != kNone64) atomicMin(&j.hdr[SFP_H_FAILED], (unsigned long long)failed);
+    if (norow != kNone64) atomicMin(&j.hdr[SFP_H_NEEDSHOST], (unsigned long long)norow);
+  }
+}
+
+// one workgroup: both sums per tile become the sums in front of the tile; the totals are the call's counts; the length of the row
+// that is too large, for the reference's message
+__global__ __launch_bounds__(256) void k_sfp_scan(SfpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[SFP_H_BAD] != kNone64) return;
+  const uint64_t members = carry_scan64(j.tsum, j.n_tiles, 2, lds), kept = carry_scan64(j.tsum + 1, j.n_tiles, 2, lds);
+  if (threadIdx.x == 0) {
+    j.hdr[SFP_H_MEMBERS] = members; j.hdr[SFP_H_RETAINED] = kept; j.pre[2 * j.n_events] = members; j.pre[2 * j.n_events + 1] = kept;
+    const uint64_t failed = j.hdr[SFP_H_FAILED];
+    if (failed != kNone64 && (failed & 3u) == ETLG_SFP_R_ROW_TOO_LARGE) { const uint64_t r = sfp_rows_before(j, failed >> 2); j.hdr[SFP_H_ROWBYTES] = j.q[r + 1] - j.q[r]; }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_sfp_write(SfpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[SFP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t cm = j.tsum[2 * (uint64_t)blockIdx.x], cr = j.tsum[2 * (uint64_t)blockIdx.x + 1];
+  for (uint64_t kb = k0; kb < k1; kb += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t i = kb + threadIdx.x;
+    const bool on = i < k1;
+    const uint32_t code = on ? j.code[i] : 0u;
+    uint64_t tot;   // members in the high half, retained members in the low half: a chunk has at most 256 of each
+    const uint64_t ex = block_scan_excl64(((uint64_t)(code & 1u) << 32) | ((code >> 1) & 1u), lds, &tot);
+    if (on) { j.pre[2 * i] = cm + (ex >> 32); j.pre[2 * i + 1] = cr + (ex & 0xFFFFFFFFull); }
+    cm += tot >> 32; cr += tot & 0xFFFFFFFFull;
+  }
+}
+
+// a thread per event: a dropped member behind a retained one of its window is the not-prefix case
+__global__ __launch_bounds__(256) void k_sfp_members(SfpJob j) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= j.n_events || j.hdr[SFP_H_BAD] != kNone64) return;
+  if ((j.code[i] & 3u) != 1u) return;
+  const uint64_t w = sfp_window(j, i);
+  if (j.pre[2 * i + 1] != j.pre[2 * j.passes[7 * w] + 1]) atomicMin(&j.hdr[SFP_H_NOTPREFIX], (unsigned long long)i);
+}
+
+// a thread per row, and two more: where the segment that starts at the row ends. Rows n_rows and n_rows + 1 are the end of every orbit.
+__global__ __launch_bounds__(256) void k_sfp_next(SfpJob j) {
+  const uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (a > j.n_rows + 1) return;   // (no status test: the squarings behind this launch index with what it writes, which is a row or the end whatever the passes hold)
+  uint64_t nx = j.n_rows + 1;
+  if (a < j.n_rows && j.row_event) {
+    nx = a + 1;
+    const uint64_t w = sfp_window(j, j.row_event[a]);
+    if (w != kNone64) {
+      const uint64_t win_end = sfp_rows_before(j, j.passes[7 * w + 1]);                   // > a: the row's event lies in front of data_end
+      const uint64_t k = cut_lower_bound(j.q, a + 1, j.n_rows, j.q[a] + j.flush);         // q[k] - q[a] >= flush first holds at k (n_rows + 1: never)
+      if (k - 1 > nx) nx = k - 1;
+      if (win_end < nx) nx = win_end;
+    }
+  }
+  j.jump[a] = (uint32_t)nx;
+}
+
+// a thread per window: its retained rows and the count of its segments; a workgroup's bytes go into the call's total in one add
+__global__ __launch_bounds__(256) void k_sfp_pass(SfpJob j) {
+  __shared__ uint64_t lds[4];
+  if (sfp_any_status(j)) return;
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint64_t bytes = 0;
+  if (p < j.n_passes) {
+    const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1], kept = j.pre[2 * de + 1] - j.pre[2 * fe + 1];
+    const uint64_t end_row = sfp_rows_before(j, de), first_row = end_row - kept, W = j.n_rows + 2;
+    uint64_t n = 0;
+    if (kept) {
+      uint64_t pos = first_row;
+      n = 1;
+      for (uint32_t k = j.levels; k-- > 0;) { const uint64_t nx = j.jump[(uint64_t)k * W + pos]; if (nx < end_row) { pos = nx; n += 1ull << k; } }
+      bytes = j.q[end_row] - j.q[first_row];
+    }
+    j.wrow[2 * p] = first_row; j.wrow[2 * p + 1] = end_row;
+    j.slens[p] = (uint32_t)n;
+  }
+  bytes = block_sum64(bytes, lds);
+  if (threadIdx.x == 0 && bytes) atomicAdd(&j.hdr[SFP_H_BYTES], (unsigned long long)bytes);
+}
+
+// a thread per window: its entry; the grid's first thread leaves the count of all segments
+__global__ __launch_bounds__(256) void k_sfp_windows(SfpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes || sfp_any_status(j)) return;
+  if (p == 0) j.hdr[SFP_H_SEGS] = (uint64_t)j.spre[j.n_passes];
+  if (!j.windows_out) return;
+  const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1], first_row = j.wrow[2 * p], end_row = j.wrow[2 * p + 1];
+  unsigned long long* o = j.windows_out + kSfpWinWords * p;
+  o[0] = (uint64_t)j.spre[p]; o[1] = j.slens[p]; o[2] = first_row; o[3] = end_row;
+  o[4] = j.pre[2 * de] - j.pre[2 * fe]; o[5] = j.pre[2 * de + 1] - j.pre[2 * fe + 1];
+  o[6] = end_row > first_row ? j.q[end_row] - j.q[first_row] : 0;
+}
+
+// a thread per segment that can be written: its window by a search in the windows' offsets (of equal offsets the last: the windows in
+// front of it are empty), its first row through the levels named by the bits of its index in the window
+__global__ __launch_bounds__(256) void k_sfp_emit(SfpJob j) {
+  const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= j.segs_cap || sfp_any_status(j) || s >= (uint64_t)j.spre[j.n_passes]) return;
+  uint64_t lo = 0, hi = j.n_passes;
+  while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if ((uint64_t)j.spre[mid] <= s) lo = mid + 1; else hi = mid; }
+  const uint64_t w = lo - 1, p = s - (uint64_t)j.spre[w], W = j.n_rows + 2;
+  uint64_t pos = j.wrow[2 * w];
+  for (uint32_t k = 0; k < j.levels; k++) if ((p >> k) & 1u) pos = j.jump[(uint64_t)k * W + pos];
+  const uint64_t end = j.jump[pos], first = j.row_event[pos], last = j.row_event[end - 1], len0 = j.q[pos + 1] - j.q[pos];
+  unsigned long long* o = j.segs_out + kSfpSegWords * s;
+  o[0] = w; o[1] = pos; o[2] = end; o[3] = first; o[4] = last; o[5] = j.q[pos]; o[6] = j.q[end]; o[7] = len0;
+  o[8] = j.zero_keys ? 0 : j.ev_commit[first]; o[9] = j.zero_keys ? 0 : j.ev_ord[first];
+  o[10] = j.zero_keys ? 0 : j.ev_commit[last]; o[11] = j.zero_keys ? 0 : j.ev_ord[last];
+  o[12] = (p || len0 >= j.flush) ? 1u : 0u;
+}
+
 // ---- source payload accounting, event side (etlg_batch_payload, include/etlg.h): what EventBatch::push merges for the events of one
 // write_events batch (apply.rs:656-658) and record_processed reports. The arena no longer has a message's value bytes (integers, floats
 // and temporals are decoded), so every event is joined to its frame: the frame side (kernels.hip) has listed the frames that take a
@@ -953,6 +1138,28 @@ void etlg_k_ducklake_plan(const DlpJob* jv, unsigned long long* gblk, unsigned l
   hipLaunchKernelGGL(k_dlp_groups, per_event, dim3(256), 0, st, j);
   etlg_k_scan_lens(j.oplens, j.n_events, oblk, (int64_t*)j.opre, st);
   hipLaunchKernelGGL(k_dlp_ops, per_event, dim3(256), 0, st, j);
+}
+
+// etlg_snowflake_plan: every launch in one piece (the grids come from n_events, the tile, n_passes — all > 0 —, n_rows and the host's
+// bound on the segments that can be written; threads past the device's counts exit). rows == false: the object has no rows (its
+// status is NEEDS_HOST), only the statuses in front of that one are worked out. sblk: the block sums of the offset scan
+void etlg_k_snowflake_plan(const SfpJob* jv, unsigned long long* sblk, uint64_t emit_bound, bool rows, hipStream_t st) {
+  const SfpJob j = *jv;
+  const dim3 per_pass((uint32_t)((j.n_passes + 255) / 256)), per_event((uint32_t)((j.n_events + 255) / 256));
+  hipLaunchKernelGGL(k_sfp_mark, per_pass, dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_sfp_tiles, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_sfp_scan, dim3(1), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_sfp_write, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_sfp_members, per_event, dim3(256), 0, st, j);
+  if (!rows) return;
+  const uint64_t W = j.n_rows + 2;
+  const uint32_t nb = (uint32_t)((W + 255) / 256);
+  hipLaunchKernelGGL(k_sfp_next, dim3(nb), dim3(256), 0, st, j);
+  for (uint32_t k = 1; k < j.levels; k++) hipLaunchKernelGGL(k_cut_level, dim3(nb), dim3(256), 0, st, j.jump + (uint64_t)(k - 1) * W, j.jump + (uint64_t)k * W, W);
+  hipLaunchKernelGGL(k_sfp_pass, per_pass, dim3(256), 0, st, j);
+  etlg_k_scan_lens(j.slens, j.n_passes, sblk, (int64_t*)j.spre, st);
+  hipLaunchKernelGGL(k_sfp_windows, per_pass, dim3(256), 0, st, j);
+  if (emit_bound) hipLaunchKernelGGL(k_sfp_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
 }
 
 // etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the

@@ -1,5 +1,5 @@
 // Part of host.cpp (included there, one translation unit): what the hand-off calls over a decoded, device-resident batch share, and the calls
-// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
+// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, Snowflake plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
 // fingerprint.hip). The two builders follow in host_handoff_columns.inc and host_handoff_rows.inc.
 
 extern "C++" {
@@ -8,7 +8,7 @@ extern "C++" {
 // (fail-fast, as the reference), not a hand-off of the prefix — and a batch that is not device-resident is refused. `refusal`: the
 // entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
 #define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
-// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline and etlg_ducklake_plan, whose contracts list the batch among their arguments.
+// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, etlg_ducklake_plan and etlg_snowflake_plan, whose contracts list the batch among their arguments.
 static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal, int32_t code = ETLG_InvalidState) {
   if (b->pending) RC(etlg_batch_sync(c, b));
   if (!b->v.on_device || !b->dev) return lib_error(c, code, refusal);
@@ -351,6 +351,95 @@ int32_t etlg_ducklake_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_
     if (ranges_out && nb) memcpy(ranges_out, staged(lay.s_ranges), nb * 24);
     if (batches_out && nb) memcpy(batches_out, staged(lay.s_batches), nb * 104);
     if (ops_out && nk) memcpy(ops_out, staged(lay.s_ops), nk * 32);
+  }
+  return ETLG_OK;
+}
+
+// The Snowflake row-batch plan (include/etlg.h; k_sfp_* in finish.hip). Everything is sized from what the host knows — the events, the
+// passes' count, the object's n_rows and n_bytes, the caller's cap — so the launches go out in one piece and the call stops once: for
+// the header and, for a host caller, the staged outputs. The bound on the segments: two neighbouring segments of a window hold at least
+// flush_bytes (the first plus the row that closed it do), so a window has at most 2 * bytes / flush_bytes + 1 of them, and never more
+// than rows; the jump levels cover the first bound, the emit grid the sum over the windows.
+int32_t etlg_snowflake_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_outline_pass* passes, uint64_t n_passes, uint32_t passes_on_device,
+                            uint32_t has_committed, uint64_t c_commit_lsn, uint64_t c_tx_ordinal, const etlg_rowbinary* ndjson, uint64_t flush_bytes,
+                            uint64_t max_row_bytes, uint32_t flags, etlg_sf_segment* segs_out, uint64_t segs_cap, etlg_sf_window* windows_out, etlg_sf_plan_info* info) {
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  *info = etlg_sf_plan_info{};
+  info->event = info->bad_pass = ~0ull;
+  if (const int32_t rc = batch_ready(c, b, "etlg_snowflake_plan" NEEDS_DEVICE, ETLG_InvalidArgument)) return rc;
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (n_passes && !passes) return lib_error(c, ETLG_InvalidArgument, "etlg_snowflake_plan: n_passes without passes");
+  if (flush_bytes < 1 || flush_bytes > (1ull << 32) || max_row_bytes < 1) return lib_error(c, ETLG_InvalidArgument, "etlg_snowflake_plan: flush_bytes in [1, 2^32] and max_row_bytes >= 1");
+  const bool copy = b->copy.active;
+  if (copy && has_committed) return lib_error(c, ETLG_InvalidArgument, "etlg_snowflake_plan: a table-copy batch is written under the zero token, there is no committed offset to compare with");
+  const etlg_batch_view& bv = b->v;
+  const uint64_t n = bv.n_events;
+  if (n_passes > (1ull << 38) || n > (1ull << 38)) return lib_error(c, ETLG_InvalidArgument, "etlg_snowflake_plan: more passes or events than one call takes (2^38: a grid of 2^30 workgroups walks them)");
+  if (!ndjson || ndjson->nd_batch != b || ndjson->nd_serial != b->serial || ndjson->nd_slot != slot || !ndjson->v.on_device ||
+      (ndjson->v.status != ETLG_RB_OK && ndjson->v.status != ETLG_RB_NEEDS_HOST))
+    return lib_error(c, ETLG_InvalidArgument, "etlg_snowflake_plan takes the object etlg_batch_ndjson built for this batch and slot, on the device (ETLG_F_OUTPUT_ON_DEVICE)");
+  const bool rows = ndjson->v.status == ETLG_RB_OK;
+  const uint64_t R = rows ? ndjson->v.n_rows : 0, n_bytes = rows ? ndjson->v.n_bytes : 0;
+  if (R >= 0xFFFFFFF0ull) return lib_error(c, ETLG_InvalidArgument, "etlg_snowflake_plan: the object has more rows than one call plans (32-bit jump tables)");
+  static_assert(sizeof(etlg_sf_segment) == 8 * kSfpSegWords && sizeof(etlg_sf_window) == 8 * kSfpWinWords && sizeof(etlg_outline_pass) == 56,
+                "k_sfp_emit / k_sfp_windows write 13 and 7 words; the windows are words 0 and 1 of 7");
+  etlg_outline_pass all{};   // a table-copy batch without passes: one window over all rows
+  if (copy && !n_passes) { all.first_event = 0; all.data_end = n; passes = &all; n_passes = 1; passes_on_device = 0; }
+  if (!n_passes || !n) {     // no window, or no event a window could hold: no member, no segment
+    if (!rows) { info->status = ETLG_SFP_NEEDS_HOST; info->event = ndjson->v.host_event; }
+    return ETLG_OK;
+  }
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  if (!segs_out) segs_cap = 0;
+  const uint64_t per_window = std::min<uint64_t>(R, 2 * (n_bytes / flush_bytes) + 2), all_windows = std::min<uint64_t>(R, 2 * (n_bytes / flush_bytes) + 1 + n_passes);
+  uint32_t levels = 1;
+  while ((per_window >> levels) != 0) levels++;   // 2^levels > the segments of any window
+  const uint64_t E = std::min(segs_cap, all_windows);   // what can be written at the most
+  uint64_t tile = c->sfp_tile_test ? c->sfp_tile_test : 2048u;
+  while ((n + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  const uint64_t n_tiles = (n + tile - 1) / tile;
+  const SfpLayout lay = sfp_layout(n, n_tiles, n_passes, R, levels, E, windows_out != nullptr, !passes_on_device, !on_dev);
+  hipStream_t s = c->stream;
+  ScratchBlk blk{c};
+  HIPCHK(c, blk_take(c, lay.total + 64, false, &blk.p, &blk.cap));
+  uint8_t* d = (uint8_t*)blk.p;
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr, 0, 128, s));
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr + 32, 0xFF, 32, s));
+  if (!passes_on_device) HIPCHK(c, hipMemcpyAsync(d + lay.passes, passes, n_passes * 56, hipMemcpyHostToDevice, s));
+  typedef unsigned long long* W64;
+  SfpJob j{};
+  j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot; j.ev_commit = bv.ev_commit_lsn; j.ev_ord = bv.ev_tx_ordinal;
+  j.n_events = n; j.passes = passes_on_device ? (const unsigned long long*)passes : (const unsigned long long*)(d + lay.passes); j.n_passes = n_passes;
+  j.row_event = rows ? (const unsigned long long*)ndjson->v.row_event : nullptr; j.q = rows ? (const unsigned long long*)ndjson->v.row_offsets : nullptr; j.n_rows = R;
+  j.slot = (uint32_t)slot; j.has_c = has_committed ? 1u : 0u; j.zero_keys = copy ? 1u : 0u; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles; j.levels = levels;
+  j.c_lsn = c_commit_lsn; j.c_ord = c_tx_ordinal; j.flush = flush_bytes; j.max_row = max_row_bytes;
+  j.hdr = (W64)(d + lay.hdr); j.tsum = (W64)(d + lay.tsum); j.code = d + lay.code; j.pre = (W64)(d + lay.pre); j.wrow = (W64)(d + lay.wrow);
+  j.slens = (uint32_t*)(d + lay.slens); j.spre = (const int64_t*)(d + lay.spre); j.jump = (uint32_t*)(d + lay.jump);
+  j.segs_cap = E;
+  j.segs_out = !segs_out ? nullptr : on_dev ? (W64)segs_out : (W64)(d + lay.s_segs);
+  j.windows_out = !windows_out ? nullptr : on_dev ? (W64)windows_out : (W64)(d + lay.s_wins);
+  etlg_k_snowflake_plan(&j, (W64)(d + lay.sblk), E, rows, s);
+  uint64_t head[SFP_H_WORDS] = {};
+  HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> back;
+  if (!on_dev && rows && lay.total > lay.stage_at) { back.resize(lay.total - lay.stage_at); HIPCHK(c, hipMemcpyAsync(back.data(), d + lay.stage_at, back.size(), hipMemcpyDeviceToHost, s)); }
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop
+  if (head[SFP_H_BAD] != ~0ull) { info->status = ETLG_SFP_BAD_PASSES; info->bad_pass = head[SFP_H_BAD]; return ETLG_OK; }
+  if (head[SFP_H_FAILED] != ~0ull) {
+    info->status = ETLG_SFP_FAILED; info->event = head[SFP_H_FAILED] >> 2; info->reason = (uint32_t)(head[SFP_H_FAILED] & 3u);
+    if (info->reason == ETLG_SFP_R_ROW_TOO_LARGE) info->row_bytes = head[SFP_H_ROWBYTES];
+    return ETLG_OK;
+  }
+  if (head[SFP_H_NOTPREFIX] != ~0ull) { info->status = ETLG_SFP_NOT_PREFIX; info->event = head[SFP_H_NOTPREFIX]; return ETLG_OK; }
+  if (!rows) { info->status = ETLG_SFP_NEEDS_HOST; info->event = ndjson->v.host_event; return ETLG_OK; }
+  if (head[SFP_H_NEEDSHOST] != ~0ull) { info->status = ETLG_SFP_NEEDS_HOST; info->event = head[SFP_H_NEEDSHOST]; return ETLG_OK; }
+  info->n_segs = head[SFP_H_SEGS]; info->n_members = head[SFP_H_MEMBERS]; info->n_retained = head[SFP_H_RETAINED];
+  info->n_dropped = info->n_members - info->n_retained; info->n_rows = info->n_retained; info->n_bytes = head[SFP_H_BYTES];
+  if (!on_dev) {
+    const uint64_t ns = info->n_segs < E ? info->n_segs : E;
+    const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
+    if (segs_out && ns) memcpy(segs_out, staged(lay.s_segs), ns * 104);
+    if (windows_out) memcpy(windows_out, staged(lay.s_wins), n_passes * 56);
   }
   return ETLG_OK;
 }

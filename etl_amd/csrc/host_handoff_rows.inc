@@ -83,6 +83,7 @@ struct RowsBuild {
     rb->v.on_device = on_dev ? 1u : 0u; rb->v.host_event = ~0ull;
     rb->m.ctx = c; rb->m.ctx_gen = c->gen;
     if (call.format == FMT_DUCKLAKE) { rb->dl_batch = b; rb->dl_serial = b->serial; rb->dl_slot = slot; rb->dl_what = call.dl_what; }
+    if (call.format == FMT_NDJSON) { rb->nd_batch = b; rb->nd_serial = b->serial; rb->nd_slot = slot; }
   }
   const uint32_t* s_cols() const { return (const uint32_t*)(S + o_cols); }
   unsigned long long* s_cnt() const { return (unsigned long long*)(S + o_cnt); }

@@ -73,6 +73,7 @@ extern "C" void etlg_k_payload_frames(const PayJob* job, hipStream_t s);
 extern "C" void etlg_k_payload_events(const PayJob* job, hipStream_t s);
 extern "C" void etlg_k_outline(const OutlineJob* job, hipStream_t s);
 extern "C" void etlg_k_ducklake_plan(const DlpJob* job, unsigned long long* gblk, unsigned long long* oblk, hipStream_t s);
+extern "C" void etlg_k_snowflake_plan(const SfpJob* job, unsigned long long* sblk, uint64_t emit_bound, bool rows, hipStream_t s);
 extern "C" void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows, unsigned long long* rows_out, hipStream_t s);
 extern "C" void etlg_k_rowbinary(const RbJob* job, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, int step, hipStream_t s);
 extern "C" int etlg_k_cells_set_lds(void);
@@ -428,6 +429,7 @@ struct etlg_ctx {
   uint32_t cuts_tile_test = 0;       // ETLG_CUTS_TILE (tests): events per scan tile of etlg_batch_cuts instead of 2048
   uint32_t ol_tile_test = 0;         // ETLG_OL_TILE (tests): events per tile of etlg_batch_outline instead of 2048
   uint32_t dlp_tile_test = 0;        // ETLG_DLP_TILE (tests): events per tile of etlg_ducklake_plan instead of 2048
+  uint32_t sfp_tile_test = 0;        // ETLG_SFP_TILE (tests): events per tile of etlg_snowflake_plan instead of 2048
   uint32_t pay_tile_test = 0;        // ETLG_PAY_TILE (tests): frames and events per scan tile of etlg_batch_payload instead of 256 and 2048
   uint64_t dlc_offset_cap_test = 0;  // ETLG_DLC_OFFSET_CAP (tests): the bytes a Utf8 / Binary column of etlg_batch_ducklake_copy may hold, instead of 2^31 - 1
   uint8_t* h_hand = nullptr; size_t h_hand_cap = 0;   // pinned: the row formats' small uploads (initial counters + column words, one copy) and read-backs (row count; totals + counters, one copy each)
@@ -557,5 +559,7 @@ struct etlg_rowbinary {
   const uint32_t* col_ends = nullptr; // [n_rows x n_cols]: block d_c (device) or behind the bytes in the pinned block (host); null without rows
   // built by etlg_batch_duckdb: of which batch, slot and `what` (etlg_ducklake_fingerprints takes the three objects of ONE batch and slot)
   const etlg_batch* dl_batch = nullptr; uint64_t dl_serial = 0; int32_t dl_slot = -1; uint32_t dl_what = ~0u;
+  // built by etlg_batch_ndjson: of which batch and slot (etlg_snowflake_plan takes the object of ITS batch and slot)
+  const etlg_batch* nd_batch = nullptr; uint64_t nd_serial = 0; int32_t nd_slot = -1;
 };
 

@@ -74,6 +74,14 @@ class DuckLakePlan:
         return [(int(r.first_event), int(r.end_event), int(r.seed)) for r in self.ranges]
 
 
+class SnowflakePlan:
+    """What Batch.snowflake_plan returns: info (abi.SfPlanInfo) and, cut to what was written — or as the device addresses the caller
+    gave —, segments (abi.SfSegment) and windows (abi.SfWindow, one per pass)."""
+
+    def __init__(self, info, segments, windows):
+        self.info, self.segments, self.windows = info, segments, windows
+
+
 class Batch:
     """A decoded batch (etlg_batch). `host()` copies the arena into numpy arrays."""
 
@@ -395,6 +403,50 @@ class Batch:
             return DuckLakePlan(info, None, None, None)
         B, K = min(bc, int(info.n_batches)), min(oc, int(info.n_ops))
         return DuckLakePlan(info, [ranges[i] for i in range(B)], [batches[i] for i in range(B)], [ops[i] for i in range(K)])
+
+    def snowflake_plan(self, slot, passes, ndjson, n_passes=None, committed=None, flush_bytes=abi.SF_MAX_UNFLUSHED_BYTES,
+                       max_row_bytes=abi.SF_MAX_ROW_BYTES, segs_cap=None, on_device=False):
+        """The Snowflake sink's row batches of schema slot `slot`, planned on the device (etlg_snowflake_plan): which rows of `ndjson`
+        — the device-resident ndjson() result of this batch and slot — each window's RowBatchBuilder takes, and where push_row flushes.
+        `passes`: what Batch.outline gave — np.uint64[P, 7], or the address of a device array of `n_passes` etlg_outline_pass; only
+        first_event and data_end are read; None on a table-copy batch: one window over all rows. committed: None or (commit_lsn,
+        tx_ordinal), the channel's committed offset. on_device: False -> arrays; a dict of device addresses under "segments", "windows"
+        (absent: that part is skipped) -> written there, with segs_cap saying what "segments" holds. segs_cap left None on the host: one
+        call counts, a second one fills an array of exactly that size. Returns a SnowflakePlan; with info.status != abi.SFP_OK nothing
+        but info is set."""
+        if passes is None:
+            pptr, npass, pdev = None, 0, 0
+        elif isinstance(passes, (int, np.integer)):
+            pptr, npass, pdev = int(passes), int(n_passes), 1
+        else:
+            passes = np.ascontiguousarray(passes, dtype=np.uint64).reshape(-1, 7)
+            pptr, npass, pdev = (passes.ctypes.data if len(passes) else None), len(passes), 0
+        has_c, cl, co = (0, 0, 0) if committed is None else (1, int(committed[0]), int(committed[1]))
+        nwin = npass if passes is not None else 1
+
+        def call(flags, sp, scap, wp):
+            info = abi.SfPlanInfo()
+            rc = self.dec.L.etlg_snowflake_plan(self.dec.h, self.h, slot, pptr, npass, pdev, has_c, cl, co, ndjson.h if ndjson is not None else None,
+                                                int(flush_bytes), int(max_row_bytes), flags, sp, scap, wp, C.byref(info))
+            if rc != abi.OK:
+                raise self.dec.last_error()
+            return info
+
+        if on_device:
+            g = lambda k: int(on_device[k]) if on_device.get(k) else None
+            info = call(abi.F_OUTPUT_ON_DEVICE, g("segments"), int(segs_cap or 0), g("windows"))
+            return SnowflakePlan(info, g("segments"), g("windows"))
+        if segs_cap is None:
+            info = call(0, None, 0, None)
+            if info.status != abi.SFP_OK:
+                return SnowflakePlan(info, None, None)
+            segs_cap = int(info.n_segs)
+        sc = int(segs_cap)
+        segs, wins = (abi.SfSegment * max(1, sc))(), (abi.SfWindow * max(1, nwin))()
+        info = call(0, C.addressof(segs) if sc else None, sc, C.addressof(wins) if nwin else None)
+        if info.status != abi.SFP_OK:
+            return SnowflakePlan(info, None, None)
+        return SnowflakePlan(info, [segs[i] for i in range(min(sc, int(info.n_segs)))], [wins[i] for i in range(nwin)])
 
     def close(self):
         if self.h:

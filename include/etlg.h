@@ -1376,6 +1376,120 @@ int32_t etlg_ducklake_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot
                            etlg_dl_range* ranges_out, etlg_dl_batch* batches_out, uint64_t batches_cap, etlg_dl_op* ops_out,
                            uint64_t ops_cap, etlg_dl_plan_info* info);
 
+/* The Snowflake sink's row batches of ONE schema slot, planned on the device: the step between etlg_batch_ndjson and the sink's
+ * requests — what the three encode_* functions (etl-destinations snowflake/core.rs:345-438) and RowBatchBuilder::push_row
+ * (snowflake/streaming/batch.rs:150-189) decide per row — without downloading row_offsets / row_event / ev_kind / ev_flags /
+ * ev_schema_slot / ev_commit_lsn / ev_tx_ordinal. The zstd stream, the split into a new request at 3.8 MB of compressed output and
+ * the 4 MB check stay the host's; the plan tells it where to look: once per segment of about flush_bytes, not once per row.
+ * Windows: `passes` as in etlg_ducklake_plan — only [first_event, data_end) of each is read; windows ascend, do not overlap and may be
+ * empty. One window is the rows accumulate_data_events (core.rs:279-303) gives one table's fresh RowBatchBuilder before a Relation or
+ * Truncate.
+ * MEMBERS of a window: its Insert / Update / Delete events with ev_schema_slot == schema_slot.
+ * `ndjson`: the object etlg_batch_ndjson built for this batch and slot; required, device-resident (ETLG_F_OUTPUT_ON_DEVICE), of status
+ * ETLG_RB_OK or ETLG_RB_NEEDS_HOST; anything else — NULL, a host-resident object, another call's, batch's or slot's object — is
+ * ETLG_InvalidArgument.
+ * FILTER: with has_committed != 0 a member is retained iff (ev_commit_lsn, ev_tx_ordinal) > (c_commit_lsn, c_tx_ordinal),
+ * lexicographically: the channel has committed an offset iff committed_offset >= offset (streaming/channel.rs:175-177), and the tokens
+ * `{commit_lsn:016x}/{tx_ordinal:016x}` (streaming/offset_token.rs:21-23) order as the pairs do. Otherwise every member is retained.
+ * FAILING members, in the reference's order: an Update with ETLG_FLAG_PARTIAL fails whether or not it is retained
+ * (ETLG_SFP_R_PARTIAL_UPDATE: snowflake_update_row :572-588 runs before the offset test in encode_update :372-394); a RETAINED Delete
+ * with ETLG_OLD_NONE fails (ETLG_SFP_R_DELETE_NO_OLD: encode_delete :396-438 tests the offset first, then snowflake_delete_row
+ * :591-608); a retained member whose NDJSON row is longer than max_row_bytes fails (ETLG_SFP_R_ROW_TOO_LARGE: strictly longer, as
+ * batch.rs:160; info->row_bytes is its length, '\n' included, for the reference's message).
+ * SEGMENTS: per window, s = 0, and for its retained rows in order, len = the row's bytes with its '\n':
+ *     if s + len >= flush_bytes: a segment starts at this row with flush_before = 1; s = 0
+ *     (the window's first retained row starts a segment in any case; its flush_before is 1 only if the line above fired)
+ *     s += len
+ * — push_row's `input_since_flush + len >= MAX_UNFLUSHED_BYTES` (batch.rs:166-180). Per segment the host does one flush when
+ * flush_before != 0, with first_row_bytes added to compressed_size() for the split (batch.rs:175), one write_all of
+ * bytes[byte_first, byte_end) of `ndjson` — a segment's rows are consecutive rows of it — and one extend of the offset range by the
+ * two tokens. No segment spans two windows. flush_bytes must lie in [1, 2^32] and max_row_bytes be >= 1; the reference's values are
+ * the two constants below.
+ * A table-copy batch (etlg_copy_decode; core.rs:683-701 uses the same builder with the zero token): n_passes == 0 with passes == NULL
+ * means one window over all rows, has_committed must be 0 (ETLG_InvalidArgument otherwise), every key is (0, 0), and first_event /
+ * last_event are row indexes.
+ * Outputs: device memory with ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory; each may be NULL and is then skipped.
+ *   segs_out[k], k < min(n_segs, segs_cap)   the segment; nothing is written at or beyond the cap, segs_cap == 0 only counts,
+ *                                            info->n_segs is the full count.
+ *   windows_out[w], every pass               seg_first / n_segs count all segments, those beyond segs_cap included; first_row /
+ *                                            end_row are the window's retained rows in `ndjson` (a window without one has
+ *                                            first_row == end_row == the rows of `ndjson` in front of data_end).
+ * info->status, the first that applies; for every status but ETLG_SFP_OK NO output array is touched and the counts are 0:
+ *   ETLG_SFP_BAD_PASSES  as ETLG_DLP_BAD_PASSES; info->bad_pass = the lowest such index.
+ *   ETLG_SFP_FAILED      info->event = the lowest failing member inside a window, whatever its reason; info->reason = ETLG_SFP_R_*;
+ *                        info->row_bytes for ROW_TOO_LARGE. The reference fails the whole call at the first such event over all
+ *                        tables: the host takes the minimum over the slots it plans.
+ *   ETLG_SFP_NOT_PREFIX  info->event = the lowest dropped member that follows a retained member of its window (offsets ascend in a
+ *                        replication stream, so this should not occur; a segment's byte range would otherwise cover a dropped row).
+ *   ETLG_SFP_NEEDS_HOST  `ndjson` has status ETLG_RB_NEEDS_HOST: info->event = its host_event; or a retained member that does not
+ *                        fail has no row in `ndjson`: info->event = the lowest such member.
+ * ETLG_InvalidArgument also: an unknown slot, a batch that is not device-resident (an ASYNC batch is synced first; one that ended in
+ * a decode error gives that error), n_passes > 0 without passes, flush_bytes or max_row_bytes out of range, n_passes or n_events above
+ * 2^38, and an `ndjson` of 2^32 - 16 rows or more (the jump tables index rows with 32 bits, as etlg_batch_cuts' do events).
+ * A stated difference from the reference: etlg_batch_ndjson runs before any filter, so an encoding error (NaN, Infinity) fails it even
+ * in a row this call's filter would drop, where the reference never encodes that row.
+ * The call stops for the device once, at its end: the jump tables and the segment bound are sized from the object's n_rows and
+ * n_bytes, which the host holds.
+ * What is tested: the reference's tests state no flush position as a number (batch.rs:272-373 assert row counts, offsets and the
+ * oversize error); tests/snowflake_plan.py restates encode_* and push_row as one sequential loop and
+ * tests/test_gpu_snowflake_plan.py compares every field with it. */
+#define ETLG_SF_MAX_UNFLUSHED_BYTES 131072ull /* MAX_UNFLUSHED_BYTES, batch.rs:26 */
+#define ETLG_SF_MAX_ROW_BYTES 2097152ull      /* MAX_UNCOMPRESSED_ROW_BYTES, batch.rs:31 */
+#define ETLG_SFP_OK 0u
+#define ETLG_SFP_BAD_PASSES 1u
+#define ETLG_SFP_FAILED 2u
+#define ETLG_SFP_NOT_PREFIX 3u
+#define ETLG_SFP_NEEDS_HOST 4u
+#define ETLG_SFP_R_PARTIAL_UPDATE 1u
+#define ETLG_SFP_R_DELETE_NO_OLD 2u
+#define ETLG_SFP_R_ROW_TOO_LARGE 3u
+
+typedef struct etlg_sf_segment {
+  uint64_t window;            /* index into `passes` */
+  uint64_t first_row;         /* rows [first_row, end_row) of `ndjson` */
+  uint64_t end_row;
+  uint64_t first_event;       /* the first row's event */
+  uint64_t last_event;        /* the last row's event */
+  uint64_t byte_first;        /* bytes [byte_first, byte_end) of `ndjson` */
+  uint64_t byte_end;
+  uint64_t first_row_bytes;   /* what the host adds to compressed_size() at batch.rs:175 */
+  uint64_t first_commit_lsn;  /* with first_tx_ordinal the first token of OffsetRange */
+  uint64_t first_tx_ordinal;
+  uint64_t last_commit_lsn;   /* with last_tx_ordinal the last token */
+  uint64_t last_tx_ordinal;
+  uint32_t flush_before;      /* 1: the encoder is flushed (and the split decided) before this segment's first row */
+  uint32_t _pad;
+} etlg_sf_segment;
+
+typedef struct etlg_sf_window {
+  uint64_t seg_first;         /* first entry of segs_out */
+  uint64_t n_segs;
+  uint64_t first_row;         /* the retained rows [first_row, end_row) of `ndjson` */
+  uint64_t end_row;
+  uint64_t n_members;
+  uint64_t n_retained;
+  uint64_t n_bytes;           /* bytes of the retained rows */
+} etlg_sf_window;
+
+typedef struct etlg_sf_plan_info {
+  uint64_t n_segs;            /* may exceed segs_cap */
+  uint64_t n_members;
+  uint64_t n_retained;
+  uint64_t n_dropped;         /* n_members - n_retained */
+  uint64_t n_rows;            /* rows in segments (== n_retained) */
+  uint64_t n_bytes;           /* their bytes */
+  uint64_t event;             /* FAILED / NOT_PREFIX / NEEDS_HOST: the event; else ~0 */
+  uint64_t row_bytes;         /* FAILED with ETLG_SFP_R_ROW_TOO_LARGE: the row's length */
+  uint64_t bad_pass;          /* BAD_PASSES: the lowest such window; else ~0 */
+  uint32_t status;            /* ETLG_SFP_* */
+  uint32_t reason;            /* FAILED: ETLG_SFP_R_* */
+} etlg_sf_plan_info;
+
+int32_t etlg_snowflake_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const etlg_outline_pass* passes, uint64_t n_passes,
+                            uint32_t passes_on_device, uint32_t has_committed, uint64_t c_commit_lsn, uint64_t c_tx_ordinal,
+                            const etlg_rowbinary* ndjson, uint64_t flush_bytes, uint64_t max_row_bytes, uint32_t flags,
+                            etlg_sf_segment* segs_out, uint64_t segs_cap, etlg_sf_window* windows_out, etlg_sf_plan_info* info);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
