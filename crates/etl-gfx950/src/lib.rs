@@ -429,6 +429,41 @@ impl GpuDecoder {
         Ok(out) // (no passes: `windows` has one entry, the whole-batch window of a table-copy batch; all zeros for any other batch)
     }
 
+    /// The ClickHouse sink's INSERT statements of one schema slot of a device-resident batch, cut on the device (etlg_clickhouse_plan):
+    /// which events `write_events_inner` (clickhouse/core.rs:1063-1136) refuses and where `insert_rows` (clickhouse/client.rs:565-649)
+    /// opens and commits each statement, as ranges of consecutive rows of `rowbinary`, the device-resident `etlg_batch_rowbinary` object
+    /// of this batch and slot; the object's engine decides the refusals. `passes`: what `GpuDecoder::outline` returned — only
+    /// `[first_event, data_end)` is read; empty on a table-copy batch (one window over all rows). The reference's budget is
+    /// `ETLG_CH_MAX_BYTES_PER_INSERT`. At most `stmts_cap` statements come back; `info.n_stmts` is the full count — call again with a
+    /// larger cap. With `info.status != ETLG_CHP_OK` nothing but `info` is set; for `ETLG_CHP_FAILED` the reference has written the
+    /// passes in front of `info.fail_pass`: plan again with those alone. Per statement the host does one INSERT of
+    /// `bytes[byte_first..byte_end]`.
+    pub fn clickhouse_plan(
+        &mut self, batch: *mut etlg_batch, schema_slot: i32, passes: &[etlg_outline_pass], rowbinary: *const etlg_rowbinary, max_bytes_per_insert: u64, stmts_cap: usize,
+    ) -> EtlResult<ClickHousePlan> {
+        let n_windows = if passes.is_empty() { 1 } else { passes.len() };
+        let mut out = ClickHousePlan {
+            statements: vec![etlg_ch_statement { window: 0, first_row: 0, end_row: 0, first_event: 0, last_event: 0, byte_first: 0, byte_end: 0 }; stmts_cap],
+            windows: vec![etlg_ch_window { stmt_first: 0, n_stmts: 0, first_row: 0, end_row: 0, n_members: 0, n_bytes: 0 }; n_windows],
+            info: etlg_ch_plan_info { n_stmts: 0, n_members: 0, n_rows: 0, n_bytes: 0, event: 0, bad_pass: 0, fail_pass: 0, status: 0, reason: 0 },
+        };
+        let rc = unsafe {
+            etlg_clickhouse_plan(
+                self.ctx, batch, schema_slot, if passes.is_empty() { std::ptr::null() } else { passes.as_ptr() }, passes.len() as u64, 0, rowbinary, max_bytes_per_insert, 0,
+                if stmts_cap == 0 { std::ptr::null_mut() } else { out.statements.as_mut_ptr() }, stmts_cap as u64, out.windows.as_mut_ptr(), &mut out.info,
+            )
+        };
+        if rc != ETLG_OK {
+            return Err(self.last_error());
+        }
+        let ok = out.info.status == ETLG_CHP_OK;
+        out.statements.truncate(if ok { out.info.n_stmts.min(stmts_cap as u64) as usize } else { 0 });
+        if !ok {
+            out.windows.clear();
+        }
+        Ok(out) // (no passes: `windows` has one entry, the whole-batch window of a table-copy batch; all zeros for any other batch)
+    }
+
     /// Source payload accounting of a device-resident batch, on the device (etlg_batch_payload), as plain values: per event the value
     /// bytes of its message (what `StreamingPayloadMetadata::{insert,update,delete}` is built from, apply.rs:2459-2463; the kind is the
     /// event's), per range of `cuts` the merged bytes and rows per kind (what `EventBatch::push` accumulates, apply.rs:656-658; rows == 0
@@ -516,6 +551,22 @@ impl SnowflakePlan {
         let (lo, n) = (self.windows[w].seg_first as usize, self.windows[w].n_segs as usize);
         let hi = (lo + n).min(self.segments.len());
         &self.segments[lo.min(hi)..hi]
+    }
+}
+
+/// What `GpuDecoder::clickhouse_plan` returns.
+pub struct ClickHousePlan {
+    pub statements: Vec<etlg_ch_statement>,
+    pub windows: Vec<etlg_ch_window>,
+    pub info: etlg_ch_plan_info,
+}
+
+impl ClickHousePlan {
+    /// The statements of window `w` that were written (those beyond `stmts_cap` are not there to be looked at).
+    pub fn statements_of(&self, w: usize) -> &[etlg_ch_statement] {
+        let (lo, n) = (self.windows[w].stmt_first as usize, self.windows[w].n_stmts as usize);
+        let hi = (lo + n).min(self.statements.len());
+        &self.statements[lo.min(hi)..hi]
     }
 }
 

@@ -200,6 +200,19 @@ class SfPlanInfo(C.Structure):   # etlg_sf_plan_info
                 + [("status", C.c_uint32), ("reason", C.c_uint32)])
 
 
+class ChStatement(C.Structure):   # etlg_ch_statement
+    _fields_ = [(n, C.c_uint64) for n in ("window", "first_row", "end_row", "first_event", "last_event", "byte_first", "byte_end")]
+
+
+class ChWindow(C.Structure):   # etlg_ch_window
+    _fields_ = [(n, C.c_uint64) for n in ("stmt_first", "n_stmts", "first_row", "end_row", "n_members", "n_bytes")]
+
+
+class ChPlanInfo(C.Structure):   # etlg_ch_plan_info
+    _fields_ = ([(n, C.c_uint64) for n in ("n_stmts", "n_members", "n_rows", "n_bytes", "event", "bad_pass", "fail_pass")]
+                + [("status", C.c_uint32), ("reason", C.c_uint32)])
+
+
 class FinishStats(C.Structure):   # etlg_finish_stats
     _fields_ = [(n, C.c_uint64) for n in ("deferred_seen", "arrays_typed", "floats_settled", "left_deferred", "heap_bytes_added")]
 
@@ -219,6 +232,9 @@ DLP_ORIGIN_NONE, DLP_ORIGIN_DELETE, DLP_ORIGIN_UPDATE, DLP_ORIGIN_REPLACE = rang
 SF_MAX_UNFLUSHED_BYTES, SF_MAX_ROW_BYTES = 131072, 2097152
 SFP_OK, SFP_BAD_PASSES, SFP_FAILED, SFP_NOT_PREFIX, SFP_NEEDS_HOST = range(5)
 SFP_R_PARTIAL_UPDATE, SFP_R_DELETE_NO_OLD, SFP_R_ROW_TOO_LARGE = 1, 2, 3
+CH_MAX_BYTES_PER_INSERT = 67108864
+CHP_OK, CHP_BAD_PASSES, CHP_FAILED, CHP_NEEDS_HOST = range(4)
+CHP_R_PARTIAL_UPDATE, CHP_R_UPDATE_IDENTITY, CHP_R_DELETE_NO_OLD, CHP_R_KEY_WIDTH, CHP_R_KEY_IDENTITY = 1, 2, 3, 4, 5
 DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)

@@ -427,6 +427,34 @@ struct SfpJob {
   unsigned long long* segs_out; uint64_t segs_cap; unsigned long long* windows_out;
 };
 
+// The ClickHouse statement plan (etlg_clickhouse_plan: k_chp_* in finish.hip). hdr: three counts start as zeros, the three status words
+// — the lowest bad pass, the lowest failing event * 8 + its reason, the lowest member that does not fail and has no row — as all ones;
+// the two windows that hold the events of the latter two are written by k_chp_scan. No kernel behind the one that sets a status word
+// writes an output once one of them is set.
+enum : uint32_t { CHP_H_MEMBERS = 0, CHP_H_STMTS = 1, CHP_H_BYTES = 2, CHP_H_BAD = 4, CHP_H_FAILED = 5, CHP_H_NEEDSHOST = 6, CHP_H_FAILPASS = 8, CHP_H_NOROWPASS = 9,
+                  CHP_H_WORDS = 16 };
+constexpr uint32_t kChpStmtWords = 7;     // etlg_ch_statement
+constexpr uint32_t kChpWinWords = 6;      // etlg_ch_window
+struct ChpJob {
+  const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot;
+  uint64_t n_events;
+  const unsigned long long* passes; uint64_t n_passes;   // etlg_outline_pass: 7 words, the window is words 0 and 1
+  const unsigned long long* row_event; const unsigned long long* q;   // the RowBinary object: n_rows events, n_rows + 1 offsets (the prefix sums of the row lengths)
+  uint64_t n_rows;
+  uint32_t slot, tile, n_tiles, levels;
+  uint32_t rows;                      // the object has rows (status ETLG_RB_OK); 0: only the statuses in front of NEEDS_HOST are worked out
+  uint32_t replacing, ident_ok, width_ok;   // the object's engine is ReplacingMergeTree; the slot's identity is PrimaryKey or Full; it has as many identity as primary-key columns
+  uint64_t budget;                    // max_bytes_per_insert
+  unsigned long long* hdr;            // CHP_H_*
+  unsigned long long* tsum;           // per tile: members; after k_chp_scan those in front of the tile
+  uint8_t* code;                      // per event: 1 member
+  unsigned long long* pre;            // n_events + 1: members in front of the event
+  unsigned long long* wrow;           // per window: first_row, end_row
+  uint32_t* slens; const int64_t* spre;   // per window: its statements, and (n_passes + 1) the statements in front of it
+  uint32_t* jump;                     // levels x (n_rows + 2): next^(2^k) of every row; n_rows + 1 is the end
+  unsigned long long* stmts_out; uint64_t stmts_cap; unsigned long long* windows_out;
+};
+
 // Source payload accounting (etlg_batch_payload). The frame side (k_payf_* in kernels.hip) measures every row message and lists the
 // frames that take a transaction ordinal; the event side (k_paye_* in finish.hip) joins every event to its frame through that list and
 // sums the ranges. Channels: 0 Insert, 1 Update, 2 Delete; a table-copy batch has channel 0 alone and reports it as ETLG_PK_COPY.

@@ -809,6 +809,177 @@ __global__ __launch_bounds__(256) void k_sfp_emit(SfpJob j) {
   o[12] = (p || len0 >= j.flush) ? 1u : 0u;
 }
 
+// ---- the ClickHouse statement plan (etlg_clickhouse_plan, include/etlg.h: the rule is stated there). What write_events_inner refuses is
+// a test per event; what insert_rows cuts is a byte counter that restarts with every statement, and it decomposes as the two rules
+// above do: the RowBinary object's row_offsets q ARE the prefix sums of the row lengths, and the statement that STARTS at row a of a
+// window whose rows end at win_end ends at next(a) = min(win_end, the smallest e > a with q[e] - q[a] >= budget), whatever came before
+// a. A window's statements are the orbit of its first row under next, cut where it reaches win_end, and the p-th is reached through the
+// jump levels next^(2^k) named by the bits of p. With no status set every member of a window has a row and the object holds no other
+// row of the window's events, so the window's rows are the last `members` rows in front of the lower bound of data_end in row_event.
+// Launches, none of which exchanges a word between its workgroups: the windows checked (k_chp_mark), per tile the members, a code byte
+// per event and the lowest failing event and member without a row (k_chp_tiles), the scan by one workgroup and the windows of those two
+// events (k_chp_scan), the prefix per event (k_chp_write), next per row (k_chp_next), a squaring per level (k_cut_level), per window its
+// rows and the count of its statements through the levels (k_chp_pass), their scan (etlg_k_scan_lens), the windows (k_chp_windows) and
+// the statements (k_chp_emit). The host sizes the levels and the emit grid from the object's n_rows and n_bytes — every statement of a
+// window but its last holds at least `budget` bytes — so nothing is read back in between. Every loop runs to a launch parameter: tile /
+// 256 chunks, log2(n_passes) and log2(n_rows) steps of a search, `levels` jumps.
+DEV bool chp_any_status(const ChpJob& j) { return j.hdr[CHP_H_BAD] != kNone64 || j.hdr[CHP_H_FAILED] != kNone64 || j.hdr[CHP_H_NEEDSHOST] != kNone64; }
+// the window that can hold event i: the last one that starts at or in front of it (every earlier one has ended by then); ~0 none
+DEV uint64_t chp_window(const ChpJob& j, uint64_t i) {
+  uint64_t lo = 0, hi = j.n_passes;
+  while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (j.passes[7 * mid] <= i) lo = mid + 1; else hi = mid; }
+  if (!lo || i >= j.passes[7 * (lo - 1) + 1]) return kNone64;
+  return lo - 1;
+}
+// the rows of the object whose event lies in front of event i
+DEV uint64_t chp_rows_before(const ChpJob& j, uint64_t i) { return j.n_rows ? cut_lower_bound(j.row_event, 0, j.n_rows - 1, i) : 0; }
+
+__global__ __launch_bounds__(256) void k_chp_mark(ChpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes) return;
+  const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1];
+  if (fe > de || de > j.n_events || (p && fe < j.passes[7 * (p - 1) + 1])) atomicMin(&j.hdr[CHP_H_BAD], (unsigned long long)p);
+}
+
+// a code byte per event, the tile's members, and the two minima: the lowest failing event (with its reason in the low bits; the tests
+// run in the reference's order, so an event has one reason) and the lowest member that does not fail and has no row. rows == 0: the
+// object's status is NEEDS_HOST, it has no rows to look at (n_rows == 0 with rows != 0 is an object that is merely empty)
+__global__ __launch_bounds__(256) void k_chp_tiles(ChpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[CHP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t members = 0, failed = kNone64, norow = kNone64;
+  for (uint64_t i = k0 + threadIdx.x; i < k1; i += 256) {
+    const uint32_t kind = j.ev_kind[i];
+    uint32_t code = 0, why = 0;
+    if (ol_is_row(kind) && j.ev_slot[i] == j.slot && chp_window(j, i) != kNone64) {
+      const uint32_t fl = j.ev_flags[i], old = fl & 3u;
+      code = 1u;
+      if (kind == 'U') {
+        if (fl & ETLG_FLAG_PARTIAL) why = ETLG_CHP_R_PARTIAL_UPDATE;
+        else if (j.replacing && !j.ident_ok) why = ETLG_CHP_R_UPDATE_IDENTITY;
+      } else if (kind == 'D') {
+        if (old == ETLG_OLD_NONE) why = ETLG_CHP_R_DELETE_NO_OLD;
+        else if (old == ETLG_OLD_KEY) why = !j.width_ok ? ETLG_CHP_R_KEY_WIDTH : !j.ident_ok ? ETLG_CHP_R_KEY_IDENTITY : 0u;
+      }
+      if (!why && j.rows) {
+        const uint64_t r = chp_rows_before(j, i);
+        if (r >= j.n_rows || j.row_event[r] != i) { if (i < norow) norow = i; }
+      }
+    }
+    j.code[i] = (uint8_t)code;
+    members += code;
+    if (why && i * 8 + why < failed) failed = i * 8 + why;
+  }
+  members = block_sum64(members, lds); failed = block_min64(failed, lds); norow = block_min64(norow, lds);
+  if (threadIdx.x == 0) {
+    j.tsum[blockIdx.x] = members;
+    if (failed != kNone64) atomicMin(&j.hdr[CHP_H_FAILED], (unsigned long long)failed);
+    if (norow != kNone64) atomicMin(&j.hdr[CHP_H_NEEDSHOST], (unsigned long long)norow);
+  }
+}
+
+// one workgroup: the sums per tile become the sums in front of the tile; the total is the call's count; the windows that hold the
+// failing event and the member without a row, for the host that plans again with the passes in front
+__global__ __launch_bounds__(256) void k_chp_scan(ChpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[CHP_H_BAD] != kNone64) return;
+  const uint64_t members = carry_scan64(j.tsum, j.n_tiles, 1, lds);
+  if (threadIdx.x == 0) {
+    j.hdr[CHP_H_MEMBERS] = members; j.pre[j.n_events] = members;
+    const uint64_t failed = j.hdr[CHP_H_FAILED], norow = j.hdr[CHP_H_NEEDSHOST];
+    if (failed != kNone64) j.hdr[CHP_H_FAILPASS] = chp_window(j, failed >> 3);
+    if (norow != kNone64) j.hdr[CHP_H_NOROWPASS] = chp_window(j, norow);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_chp_write(ChpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[CHP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t carry = j.tsum[blockIdx.x];
+  for (uint64_t kb = k0; kb < k1; kb += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t i = kb + threadIdx.x;
+    const bool on = i < k1;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(on ? j.code[i] & 1u : 0u, lds, &tot);
+    if (on) j.pre[i] = carry + ex;
+    carry += tot;
+  }
+}
+
+// a thread per row, and two more: where the statement that starts at the row ends. Rows n_rows and n_rows + 1 are the end of every orbit.
+__global__ __launch_bounds__(256) void k_chp_next(ChpJob j) {
+  const uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (a > j.n_rows + 1) return;   // (no status test: the squarings behind this launch index with what it writes, which is a row or the end whatever the passes hold)
+  uint64_t nx = j.n_rows + 1;
+  if (a < j.n_rows) {
+    nx = a + 1;
+    const uint64_t w = chp_window(j, j.row_event[a]);
+    if (w != kNone64) {
+      const uint64_t win_end = chp_rows_before(j, j.passes[7 * w + 1]);                   // > a: the row's event lies in front of data_end
+      nx = cut_lower_bound(j.q, a + 1, j.n_rows, j.q[a] + j.budget);                      // q[nx] - q[a] >= budget first holds at nx (n_rows + 1: never); the sum stays below 2^64
+      if (win_end < nx) nx = win_end;
+    }
+  }
+  j.jump[a] = (uint32_t)nx;
+}
+
+// a thread per window: its rows and the count of its statements; a workgroup's bytes go into the call's total in one add
+__global__ __launch_bounds__(256) void k_chp_pass(ChpJob j) {
+  __shared__ uint64_t lds[4];
+  if (chp_any_status(j)) return;
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint64_t bytes = 0;
+  if (p < j.n_passes) {
+    const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1], members = j.pre[de] - j.pre[fe];
+    const uint64_t end_row = chp_rows_before(j, de), first_row = end_row - members, W = j.n_rows + 2;
+    uint64_t n = 0;
+    if (members) {
+      uint64_t pos = first_row;
+      n = 1;
+      for (uint32_t k = j.levels; k-- > 0;) { const uint64_t nx = j.jump[(uint64_t)k * W + pos]; if (nx < end_row) { pos = nx; n += 1ull << k; } }
+      bytes = j.q[end_row] - j.q[first_row];
+    }
+    j.wrow[2 * p] = first_row; j.wrow[2 * p + 1] = end_row;
+    j.slens[p] = (uint32_t)n;
+  }
+  bytes = block_sum64(bytes, lds);
+  if (threadIdx.x == 0 && bytes) atomicAdd(&j.hdr[CHP_H_BYTES], (unsigned long long)bytes);
+}
+
+// a thread per window: its entry; the grid's first thread leaves the count of all statements
+__global__ __launch_bounds__(256) void k_chp_windows(ChpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes || chp_any_status(j)) return;
+  if (p == 0) j.hdr[CHP_H_STMTS] = (uint64_t)j.spre[j.n_passes];
+  if (!j.windows_out) return;
+  const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1], first_row = j.wrow[2 * p], end_row = j.wrow[2 * p + 1];
+  unsigned long long* o = j.windows_out + kChpWinWords * p;
+  o[0] = (uint64_t)j.spre[p]; o[1] = j.slens[p]; o[2] = first_row; o[3] = end_row;
+  o[4] = j.pre[de] - j.pre[fe];
+  o[5] = end_row > first_row ? j.q[end_row] - j.q[first_row] : 0;
+}
+
+// a thread per statement that can be written: its window by a search in the windows' offsets (of equal offsets the last: the windows in
+// front of it are empty), its first row through the levels named by the bits of its index in the window
+__global__ __launch_bounds__(256) void k_chp_emit(ChpJob j) {
+  const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= j.stmts_cap || chp_any_status(j) || s >= (uint64_t)j.spre[j.n_passes]) return;
+  uint64_t lo = 0, hi = j.n_passes;
+  while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if ((uint64_t)j.spre[mid] <= s) lo = mid + 1; else hi = mid; }
+  const uint64_t w = lo - 1, p = s - (uint64_t)j.spre[w], W = j.n_rows + 2;
+  uint64_t pos = j.wrow[2 * w];
+  for (uint32_t k = 0; k < j.levels; k++) if ((p >> k) & 1u) pos = j.jump[(uint64_t)k * W + pos];
+  const uint64_t end = j.jump[pos];
+  unsigned long long* o = j.stmts_out + kChpStmtWords * s;
+  o[0] = w; o[1] = pos; o[2] = end; o[3] = j.row_event[pos]; o[4] = j.row_event[end - 1]; o[5] = j.q[pos]; o[6] = j.q[end];
+}
+
 // ---- source payload accounting, event side (etlg_batch_payload, include/etlg.h): what EventBatch::push merges for the events of one
 // write_events batch (apply.rs:656-658) and record_processed reports. The arena no longer has a message's value bytes (integers, floats
 // and temporals are decoded), so every event is joined to its frame: the frame side (kernels.hip) has listed the frames that take a
@@ -1160,6 +1331,27 @@ void etlg_k_snowflake_plan(const SfpJob* jv, unsigned long long* sblk, uint64_t 
   etlg_k_scan_lens(j.slens, j.n_passes, sblk, (int64_t*)j.spre, st);
   hipLaunchKernelGGL(k_sfp_windows, per_pass, dim3(256), 0, st, j);
   if (emit_bound) hipLaunchKernelGGL(k_sfp_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
+}
+
+// etlg_clickhouse_plan: every launch in one piece (the grids come from n_events, the tile, n_passes — all > 0 —, n_rows and the host's
+// bound on the statements that can be written; threads past the device's counts exit). j.rows == 0: the object has no rows (its
+// status is NEEDS_HOST), only the statuses in front of that one are worked out. sblk: the block sums of the offset scan
+void etlg_k_clickhouse_plan(const ChpJob* jv, unsigned long long* sblk, uint64_t emit_bound, hipStream_t st) {
+  const ChpJob j = *jv;
+  const dim3 per_pass((uint32_t)((j.n_passes + 255) / 256));
+  hipLaunchKernelGGL(k_chp_mark, per_pass, dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_chp_tiles, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_chp_scan, dim3(1), dim3(256), 0, st, j);
+  if (!j.rows) return;
+  hipLaunchKernelGGL(k_chp_write, dim3(j.n_tiles), dim3(256), 0, st, j);
+  const uint64_t W = j.n_rows + 2;
+  const uint32_t nb = (uint32_t)((W + 255) / 256);
+  hipLaunchKernelGGL(k_chp_next, dim3(nb), dim3(256), 0, st, j);
+  for (uint32_t k = 1; k < j.levels; k++) hipLaunchKernelGGL(k_cut_level, dim3(nb), dim3(256), 0, st, j.jump + (uint64_t)(k - 1) * W, j.jump + (uint64_t)k * W, W);
+  hipLaunchKernelGGL(k_chp_pass, per_pass, dim3(256), 0, st, j);
+  etlg_k_scan_lens(j.slens, j.n_passes, sblk, (int64_t*)j.spre, st);
+  hipLaunchKernelGGL(k_chp_windows, per_pass, dim3(256), 0, st, j);
+  if (emit_bound) hipLaunchKernelGGL(k_chp_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
 }
 
 // etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the

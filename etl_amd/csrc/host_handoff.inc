@@ -1,5 +1,5 @@
 // Part of host.cpp (included there, one translation unit): what the hand-off calls over a decoded, device-resident batch share, and the calls
-// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, Snowflake plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
+// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, Snowflake plan, ClickHouse plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
 // fingerprint.hip). The two builders follow in host_handoff_columns.inc and host_handoff_rows.inc.
 
 extern "C++" {
@@ -8,7 +8,7 @@ extern "C++" {
 // (fail-fast, as the reference), not a hand-off of the prefix — and a batch that is not device-resident is refused. `refusal`: the
 // entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
 #define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
-// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, etlg_ducklake_plan and etlg_snowflake_plan, whose contracts list the batch among their arguments.
+// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, etlg_ducklake_plan, etlg_snowflake_plan and etlg_clickhouse_plan, whose contracts list the batch among their arguments.
 static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal, int32_t code = ETLG_InvalidState) {
   if (b->pending) RC(etlg_batch_sync(c, b));
   if (!b->v.on_device || !b->dev) return lib_error(c, code, refusal);
@@ -440,6 +440,99 @@ int32_t etlg_snowflake_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg
     const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
     if (segs_out && ns) memcpy(segs_out, staged(lay.s_segs), ns * 104);
     if (windows_out) memcpy(windows_out, staged(lay.s_wins), n_passes * 56);
+  }
+  return ETLG_OK;
+}
+
+// The ClickHouse statement plan (include/etlg.h; k_chp_* in finish.hip). As etlg_snowflake_plan above, everything is sized from what the
+// host knows — the events, the passes' count, the object's n_rows and n_bytes, the budget, the caller's cap — so the launches go out in
+// one piece and the call stops once: for the header and, for a host caller, the staged outputs. The bound on the statements: every
+// statement of a window but its last holds at least max_bytes_per_insert bytes, so a window has at most bytes / budget + 1 of them, and
+// never more than rows; the jump levels cover the first bound, the emit grid the sum over the windows. The two slot constants of the
+// refusals — the identity type, and whether the identity columns are as many as the primary-key columns — come from SlotHost.
+int32_t etlg_clickhouse_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_outline_pass* passes, uint64_t n_passes, uint32_t passes_on_device,
+                             const etlg_rowbinary* rowbinary, uint64_t max_bytes_per_insert, uint32_t flags, etlg_ch_statement* stmts_out, uint64_t stmts_cap,
+                             etlg_ch_window* windows_out, etlg_ch_plan_info* info) {
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  *info = etlg_ch_plan_info{};
+  info->event = info->bad_pass = info->fail_pass = ~0ull;
+  if (const int32_t rc = batch_ready(c, b, "etlg_clickhouse_plan" NEEDS_DEVICE, ETLG_InvalidArgument)) return rc;
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (n_passes && !passes) return lib_error(c, ETLG_InvalidArgument, "etlg_clickhouse_plan: n_passes without passes");
+  if (max_bytes_per_insert < 1 || max_bytes_per_insert > (1ull << 63))
+    return lib_error(c, ETLG_InvalidArgument, "etlg_clickhouse_plan: max_bytes_per_insert in [1, 2^63] (with 0 the sink's loop never ends)");
+  const bool copy = b->copy.active;
+  const etlg_batch_view& bv = b->v;
+  const uint64_t n = bv.n_events;
+  if (n_passes > (1ull << 38) || n > (1ull << 38)) return lib_error(c, ETLG_InvalidArgument, "etlg_clickhouse_plan: more passes or events than one call takes (2^38: a grid of 2^30 workgroups walks them)");
+  const etlg_rowbinary* rb = rowbinary;
+  if (!rb || rb->ch_batch != b || rb->ch_serial != b->serial || rb->ch_slot != slot || !rb->v.on_device || (rb->v.status != ETLG_RB_OK && rb->v.status != ETLG_RB_NEEDS_HOST))
+    return lib_error(c, ETLG_InvalidArgument, "etlg_clickhouse_plan takes the object etlg_batch_rowbinary built for this batch and slot, on the device (ETLG_F_OUTPUT_ON_DEVICE)");
+  const bool rows = rb->v.status == ETLG_RB_OK;
+  const uint64_t R = rows ? rb->v.n_rows : 0, n_bytes = rows ? rb->v.n_bytes : 0;
+  if (R >= 0xFFFFFFF0ull) return lib_error(c, ETLG_InvalidArgument, "etlg_clickhouse_plan: the object has more rows than one call plans (32-bit jump tables)");
+  static_assert(sizeof(etlg_ch_statement) == 8 * kChpStmtWords && sizeof(etlg_ch_window) == 8 * kChpWinWords && sizeof(etlg_outline_pass) == 56,
+                "k_chp_emit / k_chp_windows write 7 and 6 words; the windows are words 0 and 1 of 7");
+  etlg_outline_pass all{};   // a table-copy batch without passes: one window over all rows
+  if (copy && !n_passes) { all.first_event = 0; all.data_end = n; passes = &all; n_passes = 1; passes_on_device = 0; }
+  if (!n_passes || !n) {     // no window, or no event a window could hold: no member, no statement
+    if (!rows) { info->status = ETLG_CHP_NEEDS_HOST; info->event = rb->v.host_event; }
+    return ETLG_OK;
+  }
+  const SlotHost& sh = *c->slots[(size_t)slot];
+  uint32_t n_pk = 0;
+  for (const uint8_t k : sh.pk) n_pk += k ? 1u : 0u;
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  if (!stmts_out) stmts_cap = 0;
+  const uint64_t full = n_bytes / max_bytes_per_insert;   // statements that reached the budget, at the most
+  const uint64_t per_window = std::min<uint64_t>(R, full + 1), all_windows = std::min<uint64_t>(R, full + n_passes);
+  uint32_t levels = 1;
+  while ((per_window >> levels) != 0) levels++;   // 2^levels > the statements of any window
+  const uint64_t E = std::min(stmts_cap, all_windows);   // what can be written at the most
+  uint64_t tile = c->chp_tile_test ? c->chp_tile_test : 2048u;
+  while ((n + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  const uint64_t n_tiles = (n + tile - 1) / tile;
+  const ChpLayout lay = chp_layout(n, n_tiles, n_passes, R, levels, E, windows_out != nullptr, !passes_on_device, !on_dev);
+  hipStream_t s = c->stream;
+  ScratchBlk blk{c};
+  HIPCHK(c, blk_take(c, lay.total + 64, false, &blk.p, &blk.cap));
+  uint8_t* d = (uint8_t*)blk.p;
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr, 0, 128, s));
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr + 32, 0xFF, 32, s));
+  if (!passes_on_device) HIPCHK(c, hipMemcpyAsync(d + lay.passes, passes, n_passes * 56, hipMemcpyHostToDevice, s));
+  typedef unsigned long long* W64;
+  ChpJob j{};
+  j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot;
+  j.n_events = n; j.passes = passes_on_device ? (const unsigned long long*)passes : (const unsigned long long*)(d + lay.passes); j.n_passes = n_passes;
+  j.row_event = rows ? (const unsigned long long*)rb->v.row_event : nullptr; j.q = rows ? (const unsigned long long*)rb->v.row_offsets : nullptr; j.n_rows = R;
+  j.slot = (uint32_t)slot; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles; j.levels = levels; j.rows = rows ? 1u : 0u;
+  j.replacing = rb->ch_engine == ETLG_CH_REPLACING_MERGE_TREE ? 1u : 0u;
+  j.ident_ok = (sh.identity_type == 1 || sh.identity_type == 2) ? 1u : 0u; j.width_ok = sh.desc.n_ident == n_pk ? 1u : 0u;
+  j.budget = max_bytes_per_insert;
+  j.hdr = (W64)(d + lay.hdr); j.tsum = (W64)(d + lay.tsum); j.code = d + lay.code; j.pre = (W64)(d + lay.pre); j.wrow = (W64)(d + lay.wrow);
+  j.slens = (uint32_t*)(d + lay.slens); j.spre = (const int64_t*)(d + lay.spre); j.jump = (uint32_t*)(d + lay.jump);
+  j.stmts_cap = E;
+  j.stmts_out = !stmts_out ? nullptr : on_dev ? (W64)stmts_out : (W64)(d + lay.s_stmts);
+  j.windows_out = !windows_out ? nullptr : on_dev ? (W64)windows_out : (W64)(d + lay.s_wins);
+  etlg_k_clickhouse_plan(&j, (W64)(d + lay.sblk), E, s);
+  uint64_t head[CHP_H_WORDS] = {};
+  HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> back;
+  if (!on_dev && rows && lay.total > lay.stage_at) { back.resize(lay.total - lay.stage_at); HIPCHK(c, hipMemcpyAsync(back.data(), d + lay.stage_at, back.size(), hipMemcpyDeviceToHost, s)); }
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop
+  if (head[CHP_H_BAD] != ~0ull) { info->status = ETLG_CHP_BAD_PASSES; info->bad_pass = head[CHP_H_BAD]; return ETLG_OK; }
+  if (head[CHP_H_FAILED] != ~0ull) {
+    info->status = ETLG_CHP_FAILED; info->event = head[CHP_H_FAILED] >> 3; info->reason = (uint32_t)(head[CHP_H_FAILED] & 7u); info->fail_pass = head[CHP_H_FAILPASS];
+    return ETLG_OK;
+  }
+  if (!rows) { info->status = ETLG_CHP_NEEDS_HOST; info->event = rb->v.host_event; return ETLG_OK; }
+  if (head[CHP_H_NEEDSHOST] != ~0ull) { info->status = ETLG_CHP_NEEDS_HOST; info->event = head[CHP_H_NEEDSHOST]; info->fail_pass = head[CHP_H_NOROWPASS]; return ETLG_OK; }
+  info->n_stmts = head[CHP_H_STMTS]; info->n_members = head[CHP_H_MEMBERS]; info->n_rows = info->n_members; info->n_bytes = head[CHP_H_BYTES];
+  if (!on_dev) {
+    const uint64_t ns = info->n_stmts < E ? info->n_stmts : E;
+    const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
+    if (stmts_out && ns) memcpy(stmts_out, staged(lay.s_stmts), ns * 56);
+    if (windows_out) memcpy(windows_out, staged(lay.s_wins), n_passes * 48);
   }
   return ETLG_OK;
 }

@@ -80,6 +80,23 @@ inline SfpLayout sfp_layout(uint64_t n, uint64_t n_tiles, uint64_t n_passes, uin
   return o;
 }
 
+// etlg_clickhouse_plan, its one block: hdr (4 words of zeros, 4 of all ones, 8 of zeros) | what is written before it is read — the tile
+// sums, a code byte and a prefix per event, two rows and the statements per window with their scan, the jump levels over the rows —
+// | a host caller's passes | the staging of a host caller's outputs in one piece ([stage_at, total): statements | windows). E: the
+// statements that can be written; a part nobody asked for takes nothing.
+struct ChpLayout { size_t hdr, tsum, code, pre, wrow, slens, sblk, spre, jump, passes, stage_at, s_stmts, s_wins, total; };
+inline ChpLayout chp_layout(uint64_t n, uint64_t n_tiles, uint64_t n_passes, uint64_t n_rows, uint32_t levels, uint64_t E, bool want_wins, bool passes_here, bool stage) {
+  ScratchLayout l; ChpLayout o{};
+  o.hdr = l.take(128); o.tsum = l.take(n_tiles * 8); o.code = l.take(n); o.pre = l.take((n + 1) * 8);
+  o.wrow = l.take(n_passes * 16); o.slens = l.take(n_passes * 4); o.sblk = l.take((n_passes / 256 + 2) * 8); o.spre = l.take((n_passes + 1) * 8);
+  o.jump = l.take((size_t)levels * (n_rows + 2) * 4);
+  o.passes = l.take(passes_here ? n_passes * 56 : 0);
+  o.stage_at = l.total();
+  o.s_stmts = l.take(stage ? E * 56 : 0); o.s_wins = l.take(stage && want_wins ? n_passes * 48 : 0);
+  o.total = l.total();
+  return o;
+}
+
 // etlg_batch_payload: hdr | hist | bounds (the three the call reads back and uploads) | the frame side | the event side. ev_bytes and sums
 // live here unless they go straight to the caller's device memory; the range sums' parts exist only when sums are asked for.
 struct PayLayout { size_t hdr, hist, bounds, fbytes, tcnt, r2f, brank, etb, evb, tsum, pb, pr, cuts, sums, total; };

@@ -82,6 +82,14 @@ class SnowflakePlan:
         self.info, self.segments, self.windows = info, segments, windows
 
 
+class ClickHousePlan:
+    """What Batch.clickhouse_plan returns: info (abi.ChPlanInfo) and, cut to what was written — or as the device addresses the caller
+    gave —, statements (abi.ChStatement) and windows (abi.ChWindow, one per pass)."""
+
+    def __init__(self, info, statements, windows):
+        self.info, self.statements, self.windows = info, statements, windows
+
+
 class Batch:
     """A decoded batch (etlg_batch). `host()` copies the arena into numpy arrays."""
 
@@ -447,6 +455,47 @@ class Batch:
         if info.status != abi.SFP_OK:
             return SnowflakePlan(info, None, None)
         return SnowflakePlan(info, [segs[i] for i in range(min(sc, int(info.n_segs)))], [wins[i] for i in range(nwin)])
+
+    def clickhouse_plan(self, slot, passes, rowbinary, n_passes=None, max_bytes_per_insert=abi.CH_MAX_BYTES_PER_INSERT, stmts_cap=None, on_device=False):
+        """The ClickHouse sink's INSERT statements of schema slot `slot`, cut on the device (etlg_clickhouse_plan): which rows of
+        `rowbinary` — the device-resident rowbinary() result of this batch and slot, whose engine decides the refusals — each statement
+        of insert_rows takes, per window. `passes`: what Batch.outline gave — np.uint64[P, 7], or the address of a device array of
+        `n_passes` etlg_outline_pass; only first_event and data_end are read; None on a table-copy batch: one window over all rows.
+        on_device: False -> arrays; a dict of device addresses under "statements", "windows" (absent: that part is skipped) -> written
+        there, with stmts_cap saying what "statements" holds. stmts_cap left None on the host: one call counts, a second one fills an
+        array of exactly that size. Returns a ClickHousePlan; with info.status != abi.CHP_OK nothing but info is set."""
+        if passes is None:
+            pptr, npass, pdev = None, 0, 0
+        elif isinstance(passes, (int, np.integer)):
+            pptr, npass, pdev = int(passes), int(n_passes), 1
+        else:
+            passes = np.ascontiguousarray(passes, dtype=np.uint64).reshape(-1, 7)
+            pptr, npass, pdev = (passes.ctypes.data if len(passes) else None), len(passes), 0
+        nwin = npass if passes is not None else 1
+
+        def call(flags, sp, scap, wp):
+            info = abi.ChPlanInfo()
+            rc = self.dec.L.etlg_clickhouse_plan(self.dec.h, self.h, slot, pptr, npass, pdev, rowbinary.h if rowbinary is not None else None,
+                                                 int(max_bytes_per_insert), flags, sp, scap, wp, C.byref(info))
+            if rc != abi.OK:
+                raise self.dec.last_error()
+            return info
+
+        if on_device:
+            g = lambda k: int(on_device[k]) if on_device.get(k) else None
+            info = call(abi.F_OUTPUT_ON_DEVICE, g("statements"), int(stmts_cap or 0), g("windows"))
+            return ClickHousePlan(info, g("statements"), g("windows"))
+        if stmts_cap is None:
+            info = call(0, None, 0, None)
+            if info.status != abi.CHP_OK:
+                return ClickHousePlan(info, None, None)
+            stmts_cap = int(info.n_stmts)
+        sc = int(stmts_cap)
+        stmts, wins = (abi.ChStatement * max(1, sc))(), (abi.ChWindow * max(1, nwin))()
+        info = call(0, C.addressof(stmts) if sc else None, sc, C.addressof(wins) if nwin else None)
+        if info.status != abi.CHP_OK:
+            return ClickHousePlan(info, None, None)
+        return ClickHousePlan(info, [stmts[i] for i in range(min(sc, int(info.n_stmts)))], [wins[i] for i in range(nwin)])
 
     def close(self):
         if self.h:

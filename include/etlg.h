@@ -1490,6 +1490,107 @@ int32_t etlg_snowflake_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slo
                             const etlg_rowbinary* ndjson, uint64_t flush_bytes, uint64_t max_row_bytes, uint32_t flags,
                             etlg_sf_segment* segs_out, uint64_t segs_cap, etlg_sf_window* windows_out, etlg_sf_plan_info* info);
 
+/* The ClickHouse sink's INSERT statements of ONE schema slot, cut on the device: the step between etlg_batch_rowbinary and the sink's
+ * requests — where write_events_inner (etl-destinations clickhouse/core.rs:1063-1225) refuses an event and where insert_rows
+ * (clickhouse/client.rs:565-649) opens and commits each statement — without downloading row_offsets / row_event / ev_kind / ev_flags /
+ * ev_schema_slot. Shaped after etlg_snowflake_plan above.
+ * Windows: `passes` as in etlg_snowflake_plan — only [first_event, data_end) of each is read; windows ascend, do not overlap and may be
+ * empty. One window is the rows one pass of write_events_inner gathers for one table until a Relation or Truncate (core.rs:1066-1136)
+ * and flush_pending_rows (:1172-1225) hands to one insert_rows call.
+ * MEMBERS of a window: its Insert / Update / Delete events with ev_schema_slot == schema_slot. The sink has no replay filter: every
+ * member is retained.
+ * `rowbinary`: the object etlg_batch_rowbinary built for this batch and slot; required, device-resident (ETLG_F_OUTPUT_ON_DEVICE), of
+ * status ETLG_RB_OK or ETLG_RB_NEEDS_HOST; anything else — NULL, a host-resident object, a protobuf, NDJSON or DuckLake object, another
+ * batch's or slot's object — is ETLG_InvalidArgument. The ENGINE is the one the object was built for; it is not an argument.
+ * FAILING members, raised at the event, in event order, before the pass is flushed; per event the reference's order of tests:
+ *   ETLG_CHP_R_PARTIAL_UPDATE   an Update with ETLG_FLAG_PARTIAL, both engines (clickhouse_update_row :1364-1375);
+ *   ETLG_CHP_R_UPDATE_IDENTITY  a full Update under ETLG_CH_REPLACING_MERGE_TREE on a slot whose replica identity is neither PrimaryKey
+ *                               nor Full (:1377-1379, ensure_clickhouse_key_identity_is_primary_key :1404-1427);
+ *   ETLG_CHP_R_DELETE_NO_OLD    a Delete with ETLG_OLD_NONE, both engines (clickhouse_delete_old_row :1385-1400);
+ *   ETLG_CHP_R_KEY_WIDTH        a Delete with ETLG_OLD_KEY on a slot whose identity column count differs from its primary-key column
+ *                               count, both engines (expand_key_row :1437-1450 tests the width first);
+ *   ETLG_CHP_R_KEY_IDENTITY     a Delete with ETLG_OLD_KEY, widths agree, identity neither PrimaryKey nor Full, both engines (:1452).
+ * STATEMENTS: per window, over its rows in order (every member has one row), insert_rows' loop (client.rs:578-600):
+ *     while rows remain: a statement opens; bytes = 0; while bytes < max_bytes_per_insert and rows remain: take a row, bytes += its
+ *     RowBinary length; the statement is committed
+ * — a statement closes behind the first row that brings its bytes to max_bytes_per_insert or more, never spans two windows, and the
+ * last one of a window may be short. Per statement the host does one INSERT of bytes[byte_first, byte_end) of `rowbinary` — its rows are
+ * consecutive rows of the object — and records end_row - first_row and byte_end - byte_first (ETL_CLICKHOUSE_INSERT_ROWS / _BYTES);
+ * per window with a statement it records n_stmts (ETL_CLICKHOUSE_STATEMENTS_PER_BATCH). max_bytes_per_insert must lie in [1, 2^63]:
+ * with 0 the reference's loop never ends. The reference's default is the constant below.
+ * A table-copy batch (etlg_copy_decode; write_table_rows_inner :739-773 calls the same insert_rows with the same budget): n_passes == 0
+ * with passes == NULL means one window over all rows, first_event / last_event are row indexes, and no reason can apply.
+ * Outputs: device memory with ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory; each may be NULL and is then skipped.
+ *   stmts_out[k], k < min(n_stmts, stmts_cap)   the statement; nothing is written at or beyond the cap, stmts_cap == 0 only counts,
+ *                                               info->n_stmts is the full count.
+ *   windows_out[w], every pass                  stmt_first / n_stmts count all statements, those beyond stmts_cap included; a window
+ *                                               without a member has first_row == end_row == the rows of `rowbinary` in front of
+ *                                               data_end.
+ * info->status, the first that applies; for every status but ETLG_CHP_OK NO output array is touched and the counts are 0:
+ *   ETLG_CHP_BAD_PASSES  as ETLG_SFP_BAD_PASSES; info->bad_pass = the lowest such index.
+ *   ETLG_CHP_FAILED      info->event = the lowest failing member inside a window, whatever its reason; info->reason = ETLG_CHP_R_*;
+ *                        info->fail_pass = the window that holds it. The reference has written the passes in front of that window
+ *                        when it raises the error: the host plans again with passes[0, fail_pass) alone. It fails the whole call at
+ *                        the first such event over all tables: the host takes the minimum over the slots it plans.
+ *   ETLG_CHP_NEEDS_HOST  `rowbinary` has status ETLG_RB_NEEDS_HOST: info->event = its host_event (fail_pass stays ~0); or a member
+ *                        that does not fail has no row in `rowbinary` — a key-only Delete of a slot whose tombstone only the host
+ *                        builds (a nullable non-key column of a type whose array-ness the host alone knows): info->event = the lowest
+ *                        such member, info->fail_pass its window.
+ * ETLG_InvalidArgument also: an unknown slot, a batch that is not device-resident (an ASYNC batch is synced first; one that ended in
+ * a decode error gives that error), n_passes > 0 without passes, max_bytes_per_insert out of range, n_passes or n_events above 2^38,
+ * and a `rowbinary` of 2^32 - 16 rows or more (the jump tables index rows with 32 bits).
+ * A stated difference from the reference: etlg_batch_rowbinary encodes the whole slot first, so its own errors (a NULL in a
+ * non-nullable column, a date out of range, ETLG_E_JSON) come before a refusal that the reference would have met earlier in event order.
+ * The call stops for the device once, at its end: the jump tables and the statement bound are sized from the object's n_rows and
+ * n_bytes and from max_bytes_per_insert, which the host holds.
+ * What is tested: the reference's tests state no statement boundary as a number; tests/clickhouse_plan.py restates the refusals and
+ * insert_rows' loop as one sequential loop and tests/test_gpu_clickhouse_plan.py compares every field with it. */
+#define ETLG_CH_MAX_BYTES_PER_INSERT 67108864ull /* DEFAULT_MAX_BYTES_PER_INSERT, core.rs:234 */
+#define ETLG_CHP_OK 0u
+#define ETLG_CHP_BAD_PASSES 1u
+#define ETLG_CHP_FAILED 2u
+#define ETLG_CHP_NEEDS_HOST 3u
+#define ETLG_CHP_R_PARTIAL_UPDATE 1u
+#define ETLG_CHP_R_UPDATE_IDENTITY 2u
+#define ETLG_CHP_R_DELETE_NO_OLD 3u
+#define ETLG_CHP_R_KEY_WIDTH 4u
+#define ETLG_CHP_R_KEY_IDENTITY 5u
+
+typedef struct etlg_ch_statement {
+  uint64_t window;            /* index into `passes` */
+  uint64_t first_row;         /* rows [first_row, end_row) of `rowbinary`: consecutive */
+  uint64_t end_row;
+  uint64_t first_event;       /* the first row's event */
+  uint64_t last_event;        /* the last row's event */
+  uint64_t byte_first;        /* bytes [byte_first, byte_end) of `rowbinary`: one write of one range */
+  uint64_t byte_end;
+} etlg_ch_statement;
+
+typedef struct etlg_ch_window {
+  uint64_t stmt_first;        /* first entry of stmts_out */
+  uint64_t n_stmts;           /* ETL_CLICKHOUSE_STATEMENTS_PER_BATCH (recorded when > 0) */
+  uint64_t first_row;         /* the member rows [first_row, end_row) of `rowbinary` */
+  uint64_t end_row;
+  uint64_t n_members;
+  uint64_t n_bytes;           /* bytes of the member rows */
+} etlg_ch_window;
+
+typedef struct etlg_ch_plan_info {
+  uint64_t n_stmts;           /* may exceed stmts_cap */
+  uint64_t n_members;
+  uint64_t n_rows;            /* rows in statements (== n_members) */
+  uint64_t n_bytes;           /* their bytes */
+  uint64_t event;             /* FAILED / NEEDS_HOST: the event; else ~0 */
+  uint64_t bad_pass;          /* BAD_PASSES: the lowest such window; else ~0 */
+  uint64_t fail_pass;         /* FAILED, NEEDS_HOST for a member without a row: the window that holds `event`; else ~0 */
+  uint32_t status;            /* ETLG_CHP_* */
+  uint32_t reason;            /* FAILED: ETLG_CHP_R_* */
+} etlg_ch_plan_info;
+
+int32_t etlg_clickhouse_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const etlg_outline_pass* passes, uint64_t n_passes,
+                             uint32_t passes_on_device, const etlg_rowbinary* rowbinary, uint64_t max_bytes_per_insert, uint32_t flags,
+                             etlg_ch_statement* stmts_out, uint64_t stmts_cap, etlg_ch_window* windows_out, etlg_ch_plan_info* info);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
