@@ -464,6 +464,42 @@ impl GpuDecoder {
         Ok(out) // (no passes: `windows` has one entry, the whole-batch window of a table-copy batch; all zeros for any other batch)
     }
 
+    /// The BigQuery sink's append requests of one schema slot of a device-resident batch, planned on the device (etlg_bigquery_plan):
+    /// which events `write_events` (bigquery/core.rs:956-1040) refuses and which rows form the `create_append_request` of each pass
+    /// (:1043-1064), as ranges of consecutive rows of `protobuf`, the device-resident `etlg_batch_protobuf` object of this batch and
+    /// slot; an Update that changed the primary key is two rows of one event. `passes`: what `GpuDecoder::outline` returned — only
+    /// `[first_event, data_end)` is read; empty on a table-copy batch, whose rows `split_table_rows` (:1790-1827) cuts by
+    /// `max_batch_bytes`, the client crate's `MAX_BATCH_SIZE_BYTES` (ignored elsewhere). At most `reqs_cap` requests come back;
+    /// `info.n_reqs` is the full count — call again with a larger cap. With `info.status != ETLG_BQP_OK` nothing but `info` is set;
+    /// for `ETLG_BQP_FAILED` the reference has written the passes in front of `info.fail_pass`: plan again with those alone.
+    pub fn bigquery_plan(
+        &mut self, batch: *mut etlg_batch, schema_slot: i32, passes: &[etlg_outline_pass], protobuf: *const etlg_rowbinary, max_batch_bytes: u64, reqs_cap: usize,
+    ) -> EtlResult<BigQueryPlan> {
+        let n_windows = if passes.is_empty() { 1 } else { passes.len() };
+        let mut out = BigQueryPlan {
+            requests: vec![etlg_bq_request { window: 0, first_row: 0, end_row: 0, first_event: 0, last_event: 0, byte_first: 0, byte_end: 0, n_members: 0 }; reqs_cap],
+            windows: vec![etlg_bq_window { req_first: 0, n_reqs: 0, first_row: 0, end_row: 0, n_members: 0, n_two_row: 0, n_bytes: 0 }; n_windows],
+            info: etlg_bq_plan_info {
+                n_reqs: 0, n_members: 0, n_rows: 0, n_two_row: 0, n_bytes: 0, est_row_bytes: 0, target_batches: 0, event: 0, bad_pass: 0, fail_pass: 0, status: 0, reason: 0,
+            },
+        };
+        let rc = unsafe {
+            etlg_bigquery_plan(
+                self.ctx, batch, schema_slot, if passes.is_empty() { std::ptr::null() } else { passes.as_ptr() }, passes.len() as u64, 0, protobuf, max_batch_bytes, 0,
+                if reqs_cap == 0 { std::ptr::null_mut() } else { out.requests.as_mut_ptr() }, reqs_cap as u64, out.windows.as_mut_ptr(), &mut out.info,
+            )
+        };
+        if rc != ETLG_OK {
+            return Err(self.last_error());
+        }
+        let ok = out.info.status == ETLG_BQP_OK;
+        out.requests.truncate(if ok { out.info.n_reqs.min(reqs_cap as u64) as usize } else { 0 });
+        if !ok {
+            out.windows.clear();
+        }
+        Ok(out) // (no passes: `windows` has one entry, the whole-batch window of a table-copy batch; all zeros for any other batch)
+    }
+
     /// Source payload accounting of a device-resident batch, on the device (etlg_batch_payload), as plain values: per event the value
     /// bytes of its message (what `StreamingPayloadMetadata::{insert,update,delete}` is built from, apply.rs:2459-2463; the kind is the
     /// event's), per range of `cuts` the merged bytes and rows per kind (what `EventBatch::push` accumulates, apply.rs:656-658; rows == 0
@@ -567,6 +603,22 @@ impl ClickHousePlan {
         let (lo, n) = (self.windows[w].stmt_first as usize, self.windows[w].n_stmts as usize);
         let hi = (lo + n).min(self.statements.len());
         &self.statements[lo.min(hi)..hi]
+    }
+}
+
+/// What `GpuDecoder::bigquery_plan` returns.
+pub struct BigQueryPlan {
+    pub requests: Vec<etlg_bq_request>,
+    pub windows: Vec<etlg_bq_window>,
+    pub info: etlg_bq_plan_info,
+}
+
+impl BigQueryPlan {
+    /// The requests of window `w` that were written (those beyond `reqs_cap` are not there to be looked at).
+    pub fn requests_of(&self, w: usize) -> &[etlg_bq_request] {
+        let (lo, n) = (self.windows[w].req_first as usize, self.windows[w].n_reqs as usize);
+        let hi = (lo + n).min(self.requests.len());
+        &self.requests[lo.min(hi)..hi]
     }
 }
 

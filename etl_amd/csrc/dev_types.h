@@ -455,6 +455,35 @@ struct ChpJob {
   unsigned long long* stmts_out; uint64_t stmts_cap; unsigned long long* windows_out;
 };
 
+// The BigQuery request plan (etlg_bigquery_plan: k_bqp_* in finish.hip). hdr as ChpJob's — counts that start as zeros, the three status
+// words (the lowest bad pass, the lowest failing event * 8 + its reason, the lowest member that does not fail and has no row) as all
+// ones, the two windows of the latter two events written by k_bqp_scan — with the counts an event of two rows adds and the two figures
+// of a table-copy batch. The words the kernels share with the ClickHouse plan (plan_* in finish.hip) keep ChpJob's names and numbers.
+enum : uint32_t { BQP_H_MEMBERS = 0, BQP_H_REQS = 1, BQP_H_BYTES = 2, BQP_H_ROWS = 3, BQP_H_BAD = 4, BQP_H_FAILED = 5, BQP_H_NEEDSHOST = 6, BQP_H_FAILPASS = 8,
+                  BQP_H_NOROWPASS = 9, BQP_H_TWOROW = 10, BQP_H_EST = 11, BQP_H_TARGET = 12, BQP_H_WORDS = 16 };
+static_assert((uint32_t)BQP_H_BAD == (uint32_t)CHP_H_BAD && (uint32_t)BQP_H_FAILED == (uint32_t)CHP_H_FAILED && (uint32_t)BQP_H_NEEDSHOST == (uint32_t)CHP_H_NEEDSHOST,
+              "chp_mark / chp_write in finish.hip serve both jobs");
+constexpr uint32_t kBqpReqWords = 8;      // etlg_bq_request
+constexpr uint32_t kBqpWinWords = 7;      // etlg_bq_window
+struct BqpJob {
+  const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot;
+  uint64_t n_events;
+  const unsigned long long* passes; uint64_t n_passes;   // etlg_outline_pass: 7 words, the window is words 0 and 1
+  const unsigned long long* row_event; const unsigned long long* q;   // the protobuf object: n_rows events (an event may own two consecutive rows), n_rows + 1 offsets
+  uint64_t n_rows;
+  uint32_t slot, tile, n_tiles;
+  uint32_t rows;                      // the object has rows (status ETLG_RB_OK); 0: only the statuses in front of NEEDS_HOST are worked out
+  uint32_t ident_pk, width_ok;        // the slot's identity is PrimaryKey; it has as many identity as primary-key columns
+  uint64_t budget;                    // max_batch_bytes (a table-copy batch only)
+  unsigned long long* hdr;            // BQP_H_*
+  unsigned long long* tsum;           // per tile: members; after k_bqp_scan those in front of the tile
+  uint8_t* code;                      // per event: 1 member
+  unsigned long long* pre;            // n_events + 1: members in front of the event
+  unsigned long long* wrow;           // per window: first_row, end_row
+  uint32_t* slens; const int64_t* spre;   // per window: 1 when it has a request, and (n_passes + 1) the requests in front of it
+  unsigned long long* reqs_out; uint64_t reqs_cap; unsigned long long* windows_out;
+};
+
 // Source payload accounting (etlg_batch_payload). The frame side (k_payf_* in kernels.hip) measures every row message and lists the
 // frames that take a transaction ordinal; the event side (k_paye_* in finish.hip) joins every event to its frame through that list and
 // sums the ranges. Channels: 0 Insert, 1 Update, 2 Delete; a table-copy batch has channel 0 alone and reports it as ETLG_PK_COPY.

@@ -825,21 +825,23 @@ __global__ __launch_bounds__(256) void k_sfp_emit(SfpJob j) {
 // 256 chunks, log2(n_passes) and log2(n_rows) steps of a search, `levels` jumps.
 DEV bool chp_any_status(const ChpJob& j) { return j.hdr[CHP_H_BAD] != kNone64 || j.hdr[CHP_H_FAILED] != kNone64 || j.hdr[CHP_H_NEEDSHOST] != kNone64; }
 // the window that can hold event i: the last one that starts at or in front of it (every earlier one has ended by then); ~0 none
-DEV uint64_t chp_window(const ChpJob& j, uint64_t i) {
+template <class J> DEV uint64_t chp_window(const J& j, uint64_t i) {   // (J: ChpJob, BqpJob)
   uint64_t lo = 0, hi = j.n_passes;
   while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (j.passes[7 * mid] <= i) lo = mid + 1; else hi = mid; }
   if (!lo || i >= j.passes[7 * (lo - 1) + 1]) return kNone64;
   return lo - 1;
 }
 // the rows of the object whose event lies in front of event i
-DEV uint64_t chp_rows_before(const ChpJob& j, uint64_t i) { return j.n_rows ? cut_lower_bound(j.row_event, 0, j.n_rows - 1, i) : 0; }
+template <class J> DEV uint64_t chp_rows_before(const J& j, uint64_t i) { return j.n_rows ? cut_lower_bound(j.row_event, 0, j.n_rows - 1, i) : 0; }
 
-__global__ __launch_bounds__(256) void k_chp_mark(ChpJob j) {
+// a thread per window: the lowest one that descends, overlaps its predecessor or ends past the events
+template <class J> DEV void chp_mark(const J& j) {
   const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= j.n_passes) return;
   const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1];
   if (fe > de || de > j.n_events || (p && fe < j.passes[7 * (p - 1) + 1])) atomicMin(&j.hdr[CHP_H_BAD], (unsigned long long)p);
 }
+__global__ __launch_bounds__(256) void k_chp_mark(ChpJob j) { chp_mark(j); }
 
 // a code byte per event, the tile's members, and the two minima: the lowest failing event (with its reason in the low bits; the tests
 // run in the reference's order, so an event has one reason) and the lowest member that does not fail and has no row. rows == 0: the
@@ -895,8 +897,8 @@ __global__ __launch_bounds__(256) void k_chp_scan(ChpJob j) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_chp_write(ChpJob j) {
-  __shared__ uint64_t lds[4];
+// the members in front of every event of a tile, from the code bytes and the tile's carry
+template <class J> DEV void chp_write(const J& j, uint64_t* lds) {
   if (j.hdr[CHP_H_BAD] != kNone64) return;
   const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
   if (k0 >= j.n_events) return;
@@ -910,6 +912,10 @@ __global__ __launch_bounds__(256) void k_chp_write(ChpJob j) {
     if (on) j.pre[i] = carry + ex;
     carry += tot;
   }
+}
+__global__ __launch_bounds__(256) void k_chp_write(ChpJob j) {
+  __shared__ uint64_t lds[4];
+  chp_write(j, lds);
 }
 
 // a thread per row, and two more: where the statement that starts at the row ends. Rows n_rows and n_rows + 1 are the end of every orbit.
@@ -978,6 +984,145 @@ __global__ __launch_bounds__(256) void k_chp_emit(ChpJob j) {
   const uint64_t end = j.jump[pos];
   unsigned long long* o = j.stmts_out + kChpStmtWords * s;
   o[0] = w; o[1] = pos; o[2] = end; o[3] = j.row_event[pos]; o[4] = j.row_event[end - 1]; o[5] = j.q[pos]; o[6] = j.q[end];
+}
+
+// ---- the BigQuery request plan (etlg_bigquery_plan, include/etlg.h: the rule is stated there). What write_events refuses is a test per
+// event; a window with a member is one append request of all its rows, so there is no byte counter to restart and no jump level. What
+// differs from the ClickHouse plan above: an Update that changes the primary key is TWO rows of one event, so a window's rows are not
+// its last `members` rows — both ends come from a lower bound in row_event (of first_event and of data_end), which takes both rows of
+// an event wherever the window begins or ends. Launches, none of which exchanges a word between its workgroups: the windows checked
+// (k_bqp_mark), per tile the members, a code byte per event and the lowest failing event and member without a row (k_bqp_tiles), the
+// scan by one workgroup and the windows of those two events (k_bqp_scan), the prefix per event (k_bqp_write), per window its rows, its
+// bytes and whether it has a request (k_bqp_pass), the scan of those 0 / 1 lengths (etlg_k_scan_lens), the windows (k_bqp_windows) and
+// the requests (k_bqp_emit). A table-copy batch is k_bqp_copy alone. Every loop runs to a launch parameter: tile / 256 chunks,
+// log2(n_passes) and log2(n_rows) steps of a search.
+DEV bool bqp_any_status(const BqpJob& j) { return j.hdr[BQP_H_BAD] != kNone64 || j.hdr[BQP_H_FAILED] != kNone64 || j.hdr[BQP_H_NEEDSHOST] != kNone64; }
+
+__global__ __launch_bounds__(256) void k_bqp_mark(BqpJob j) { chp_mark(j); }
+
+// as k_chp_tiles, with this sink's refusals: the tests of one event in the reference's order (bigquery/core.rs:997-1034), so an event
+// has one reason. rows == 0: the object's status is NEEDS_HOST, it has no rows to look at
+__global__ __launch_bounds__(256) void k_bqp_tiles(BqpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[BQP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t members = 0, failed = kNone64, norow = kNone64;
+  for (uint64_t i = k0 + threadIdx.x; i < k1; i += 256) {
+    const uint32_t kind = j.ev_kind[i];
+    uint32_t code = 0, why = 0;
+    if (ol_is_row(kind) && j.ev_slot[i] == j.slot && chp_window(j, i) != kNone64) {
+      const uint32_t fl = j.ev_flags[i], old = fl & 3u;
+      code = 1u;
+      if (kind == 'U' && (fl & ETLG_FLAG_PARTIAL)) why = ETLG_BQP_R_PARTIAL_UPDATE;                   // bigquery_update_new_row comes before the old image is looked at
+      else if (kind == 'U' && old == ETLG_OLD_NONE) why = j.ident_pk ? 0u : ETLG_BQP_R_UPDATE_NO_OLD_IDENTITY;
+      else if (kind == 'D' && old == ETLG_OLD_NONE) why = ETLG_BQP_R_DELETE_NO_OLD;
+      else if (kind != 'I' && old == ETLG_OLD_KEY) why = !j.width_ok ? ETLG_BQP_R_KEY_WIDTH : !j.ident_pk ? ETLG_BQP_R_KEY_IDENTITY : 0u;   // the width before the identity
+      if (!why && j.rows) {
+        const uint64_t r = chp_rows_before(j, i);
+        if (r >= j.n_rows || j.row_event[r] != i) { if (i < norow) norow = i; }
+      }
+    }
+    j.code[i] = (uint8_t)code;
+    members += code;
+    if (why && i * 8 + why < failed) failed = i * 8 + why;
+  }
+  members = block_sum64(members, lds); failed = block_min64(failed, lds); norow = block_min64(norow, lds);
+  if (threadIdx.x == 0) {
+    j.tsum[blockIdx.x] = members;
+    if (failed != kNone64) atomicMin(&j.hdr[BQP_H_FAILED], (unsigned long long)failed);
+    if (norow != kNone64) atomicMin(&j.hdr[BQP_H_NEEDSHOST], (unsigned long long)norow);
+  }
+}
+
+// one workgroup, as k_chp_scan: the sums in front of every tile, the total, the windows of the failing event and of the member without a row
+__global__ __launch_bounds__(256) void k_bqp_scan(BqpJob j) {
+  __shared__ uint64_t lds[4];
+  if (j.hdr[BQP_H_BAD] != kNone64) return;
+  const uint64_t members = carry_scan64(j.tsum, j.n_tiles, 1, lds);
+  if (threadIdx.x == 0) {
+    j.hdr[BQP_H_MEMBERS] = members; j.pre[j.n_events] = members;
+    const uint64_t failed = j.hdr[BQP_H_FAILED], norow = j.hdr[BQP_H_NEEDSHOST];
+    if (failed != kNone64) j.hdr[BQP_H_FAILPASS] = chp_window(j, failed >> 3);
+    if (norow != kNone64) j.hdr[BQP_H_NOROWPASS] = chp_window(j, norow);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bqp_write(BqpJob j) {
+  __shared__ uint64_t lds[4];
+  chp_write(j, lds);
+}
+
+// a thread per window: its rows by two lower bounds — never end_row - members: an event of two rows would push first_row into the window
+// in front —, a 0 / 1 length for its request; a workgroup's bytes, rows and second rows go into the call's totals in one add each
+__global__ __launch_bounds__(256) void k_bqp_pass(BqpJob j) {
+  __shared__ uint64_t lds[4];
+  if (bqp_any_status(j)) return;
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint64_t bytes = 0, rows = 0, two = 0;
+  if (p < j.n_passes) {
+    const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1], members = j.pre[de] - j.pre[fe];
+    const uint64_t first_row = chp_rows_before(j, fe), end_row = chp_rows_before(j, de);
+    if (members) { rows = end_row - first_row; two = rows - members; bytes = j.q[end_row] - j.q[first_row]; }   // (no status: every member has a row, the object no other row of these events)
+    j.wrow[2 * p] = first_row; j.wrow[2 * p + 1] = end_row;
+    j.slens[p] = members ? 1u : 0u;
+  }
+  bytes = block_sum64(bytes, lds); rows = block_sum64(rows, lds); two = block_sum64(two, lds);
+  if (threadIdx.x == 0 && rows) {
+    atomicAdd(&j.hdr[BQP_H_BYTES], (unsigned long long)bytes); atomicAdd(&j.hdr[BQP_H_ROWS], (unsigned long long)rows);
+    if (two) atomicAdd(&j.hdr[BQP_H_TWOROW], (unsigned long long)two);
+  }
+}
+
+// a thread per window: its entry; the grid's first thread leaves the count of all requests
+__global__ __launch_bounds__(256) void k_bqp_windows(BqpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes || bqp_any_status(j)) return;
+  if (p == 0) j.hdr[BQP_H_REQS] = (uint64_t)j.spre[j.n_passes];
+  if (!j.windows_out) return;
+  const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1], first_row = j.wrow[2 * p], end_row = j.wrow[2 * p + 1], members = j.pre[de] - j.pre[fe];
+  unsigned long long* o = j.windows_out + kBqpWinWords * p;
+  o[0] = (uint64_t)j.spre[p]; o[1] = j.slens[p]; o[2] = first_row; o[3] = end_row; o[4] = members;
+  o[5] = members ? end_row - first_row - members : 0;
+  o[6] = members ? j.q[end_row] - j.q[first_row] : 0;
+}
+
+// a thread per request that can be written: its window by a search in the windows' offsets (of equal offsets the last: the windows in
+// front of it have no request)
+__global__ __launch_bounds__(256) void k_bqp_emit(BqpJob j) {
+  const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= j.reqs_cap || bqp_any_status(j) || s >= (uint64_t)j.spre[j.n_passes]) return;
+  uint64_t lo = 0, hi = j.n_passes;
+  while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if ((uint64_t)j.spre[mid] <= s) lo = mid + 1; else hi = mid; }
+  const uint64_t w = lo - 1, first_row = j.wrow[2 * w], end_row = j.wrow[2 * w + 1];
+  unsigned long long* o = j.reqs_out + kBqpReqWords * s;
+  o[0] = w; o[1] = first_row; o[2] = end_row; o[3] = j.row_event[first_row]; o[4] = j.row_event[end_row - 1]; o[5] = j.q[first_row]; o[6] = j.q[end_row];
+  o[7] = j.pre[j.passes[7 * w + 1]] - j.pre[j.passes[7 * w]];
+}
+
+// a table-copy batch: calculate_target_batches_for_table_copy (bigquery/core.rs:1760-1784) and split_table_rows (:1790-1827) in closed
+// form, a thread per request that can be written; the grid's first thread leaves the counts and the one window. n_rows == 0: no request
+__global__ __launch_bounds__(256) void k_bqp_copy(BqpJob j) {
+  const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x, R = j.n_rows;
+  const uint64_t est = R ? j.q[1] - j.q[0] : 0;                       // encoded_len() of the first row alone
+  const uint64_t per = est ? j.budget / est : R;                      // MAX_BATCH_SIZE_BYTES.checked_div(estimated_row_size).unwrap_or(total_rows)
+  const uint64_t target = !R ? 0 : per ? (R + per - 1) / per : 1;
+  uint64_t nsub = R ? 1 : 0, each = R, extra = 0;
+  if (!(R <= 1 || target == 1 || R <= target)) {
+    const uint64_t opt = (R + target - 1) / target;                   // > 0: R > target > 1
+    nsub = (R + opt - 1) / opt; each = R / nsub; extra = R % nsub;
+  }
+  if (s == 0) {
+    const uint64_t bytes = R ? j.q[R] - j.q[0] : 0;
+    j.hdr[BQP_H_REQS] = nsub; j.hdr[BQP_H_MEMBERS] = R; j.hdr[BQP_H_ROWS] = R; j.hdr[BQP_H_BYTES] = bytes; j.hdr[BQP_H_EST] = est; j.hdr[BQP_H_TARGET] = target;
+    if (j.windows_out) { unsigned long long* o = j.windows_out; o[0] = 0; o[1] = nsub; o[2] = 0; o[3] = R; o[4] = R; o[5] = 0; o[6] = bytes; }
+  }
+  if (s >= j.reqs_cap || s >= nsub) return;
+  const uint64_t first_row = s * each + (s < extra ? s : extra), end_row = first_row + each + (s < extra ? 1 : 0);
+  unsigned long long* o = j.reqs_out + kBqpReqWords * s;
+  o[0] = 0; o[1] = first_row; o[2] = end_row; o[3] = j.row_event[first_row]; o[4] = j.row_event[end_row - 1]; o[5] = j.q[first_row]; o[6] = j.q[end_row];
+  o[7] = end_row - first_row;
 }
 
 // ---- source payload accounting, event side (etlg_batch_payload, include/etlg.h): what EventBatch::push merges for the events of one
@@ -1352,6 +1497,24 @@ void etlg_k_clickhouse_plan(const ChpJob* jv, unsigned long long* sblk, uint64_t
   etlg_k_scan_lens(j.slens, j.n_passes, sblk, (int64_t*)j.spre, st);
   hipLaunchKernelGGL(k_chp_windows, per_pass, dim3(256), 0, st, j);
   if (emit_bound) hipLaunchKernelGGL(k_chp_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
+}
+
+// etlg_bigquery_plan: every launch in one piece. copy: a table-copy batch, k_bqp_copy alone over max(1, emit_bound) threads (its first
+// thread leaves the counts). Else the grids come from n_events, the tile and n_passes — all > 0 — and the host's bound on the requests
+// that can be written; j.rows == 0: the object has no rows, only the statuses in front of NEEDS_HOST are worked out
+void etlg_k_bigquery_plan(const BqpJob* jv, unsigned long long* sblk, uint64_t emit_bound, bool copy, hipStream_t st) {
+  const BqpJob j = *jv;
+  if (copy) { hipLaunchKernelGGL(k_bqp_copy, dim3((uint32_t)(((emit_bound ? emit_bound : 1) + 255) / 256)), dim3(256), 0, st, j); return; }
+  const dim3 per_pass((uint32_t)((j.n_passes + 255) / 256));
+  hipLaunchKernelGGL(k_bqp_mark, per_pass, dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_bqp_tiles, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_bqp_scan, dim3(1), dim3(256), 0, st, j);
+  if (!j.rows) return;
+  hipLaunchKernelGGL(k_bqp_write, dim3(j.n_tiles), dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_bqp_pass, per_pass, dim3(256), 0, st, j);
+  etlg_k_scan_lens(j.slens, j.n_passes, sblk, (int64_t*)j.spre, st);
+  hipLaunchKernelGGL(k_bqp_windows, per_pass, dim3(256), 0, st, j);
+  if (emit_bound) hipLaunchKernelGGL(k_bqp_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
 }
 
 // etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the

@@ -1,5 +1,5 @@
 // Part of host.cpp (included there, one translation unit): what the hand-off calls over a decoded, device-resident batch share, and the calls
-// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, Snowflake plan, ClickHouse plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
+// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, Snowflake plan, ClickHouse plan, BigQuery plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
 // fingerprint.hip). The two builders follow in host_handoff_columns.inc and host_handoff_rows.inc.
 
 extern "C++" {
@@ -8,7 +8,7 @@ extern "C++" {
 // (fail-fast, as the reference), not a hand-off of the prefix — and a batch that is not device-resident is refused. `refusal`: the
 // entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
 #define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
-// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, etlg_ducklake_plan, etlg_snowflake_plan and etlg_clickhouse_plan, whose contracts list the batch among their arguments.
+// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, etlg_ducklake_plan, etlg_snowflake_plan, etlg_clickhouse_plan and etlg_bigquery_plan, whose contracts list the batch among their arguments.
 static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal, int32_t code = ETLG_InvalidState) {
   if (b->pending) RC(etlg_batch_sync(c, b));
   if (!b->v.on_device || !b->dev) return lib_error(c, code, refusal);
@@ -533,6 +533,93 @@ int32_t etlg_clickhouse_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etl
     const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
     if (stmts_out && ns) memcpy(stmts_out, staged(lay.s_stmts), ns * 56);
     if (windows_out) memcpy(windows_out, staged(lay.s_wins), n_passes * 48);
+  }
+  return ETLG_OK;
+}
+
+// The BigQuery request plan (include/etlg.h; k_bqp_* in finish.hip). As etlg_clickhouse_plan above, everything is sized from what the
+// host knows — the events, the passes' count, the object's n_rows, the caller's cap — so the launches go out in one piece and the call
+// stops once: for the header and, for a host caller, the staged outputs. A window has one request at the most, so the emit grid is
+// min(reqs_cap, n_passes); a table-copy batch has at most n_rows of them, so its one kernel runs min(reqs_cap, n_rows) threads — the
+// length of row 0, which decides the real count, stays on the device. The two slot constants of the refusals — the identity is
+// PrimaryKey, and the identity columns are as many as the primary-key columns — come from SlotHost.
+int32_t etlg_bigquery_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_outline_pass* passes, uint64_t n_passes, uint32_t passes_on_device,
+                           const etlg_rowbinary* protobuf, uint64_t max_batch_bytes, uint32_t flags, etlg_bq_request* reqs_out, uint64_t reqs_cap,
+                           etlg_bq_window* windows_out, etlg_bq_plan_info* info) {
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  *info = etlg_bq_plan_info{};
+  info->event = info->bad_pass = info->fail_pass = ~0ull;
+  if (const int32_t rc = batch_ready(c, b, "etlg_bigquery_plan" NEEDS_DEVICE, ETLG_InvalidArgument)) return rc;
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (n_passes && !passes) return lib_error(c, ETLG_InvalidArgument, "etlg_bigquery_plan: n_passes without passes");
+  const bool copy = b->copy.active;
+  if (copy && n_passes) return lib_error(c, ETLG_InvalidArgument, "etlg_bigquery_plan: a table-copy batch takes no passes (split_table_rows cuts the rows of the whole call)");
+  if (copy && (max_batch_bytes < 1 || max_batch_bytes > (1ull << 63)))
+    return lib_error(c, ETLG_InvalidArgument, "etlg_bigquery_plan: max_batch_bytes in [1, 2^63] for a table-copy batch");
+  const etlg_batch_view& bv = b->v;
+  const uint64_t n = bv.n_events;
+  if (n_passes > (1ull << 38) || n > (1ull << 38)) return lib_error(c, ETLG_InvalidArgument, "etlg_bigquery_plan: more passes or events than one call takes (2^38: a grid of 2^30 workgroups walks them)");
+  const etlg_rowbinary* pb = protobuf;
+  if (!pb || pb->pb_batch != b || pb->pb_serial != b->serial || pb->pb_slot != slot || !pb->v.on_device || (pb->v.status != ETLG_RB_OK && pb->v.status != ETLG_RB_NEEDS_HOST))
+    return lib_error(c, ETLG_InvalidArgument, "etlg_bigquery_plan takes the object etlg_batch_protobuf built for this batch and slot, on the device (ETLG_F_OUTPUT_ON_DEVICE)");
+  const bool rows = pb->v.status == ETLG_RB_OK;
+  const uint64_t R = rows ? pb->v.n_rows : 0;
+  if (R > (1ull << 39)) return lib_error(c, ETLG_InvalidArgument, "etlg_bigquery_plan: the object has more rows than one call plans (2^39)");
+  static_assert(sizeof(etlg_bq_request) == 8 * kBqpReqWords && sizeof(etlg_bq_window) == 8 * kBqpWinWords && sizeof(etlg_outline_pass) == 56,
+                "k_bqp_emit / k_bqp_copy / k_bqp_windows write 8 and 7 words; the windows are words 0 and 1 of 7");
+  if (!rows && (copy || !n_passes || !n)) { info->status = ETLG_BQP_NEEDS_HOST; info->event = pb->v.host_event; return ETLG_OK; }   // (no refusal can come first)
+  if (!copy && (!n_passes || !n)) return ETLG_OK;   // no window, or no event a window could hold: no member, no request
+  const SlotHost& sh = *c->slots[(size_t)slot];
+  uint32_t n_pk = 0;
+  for (const uint8_t k : sh.pk) n_pk += k ? 1u : 0u;
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  if (!reqs_out) reqs_cap = 0;
+  const uint64_t E = std::min(reqs_cap, copy ? R : n_passes);   // what can be written at the most
+  const uint64_t ne = copy ? 0 : n;                              // a table-copy batch walks no event
+  uint64_t tile = c->bqp_tile_test ? c->bqp_tile_test : 2048u;
+  while ((ne + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  const uint64_t n_tiles = (ne + tile - 1) / tile, n_win = copy ? 1 : n_passes;
+  const BqpLayout lay = bqp_layout(ne, n_tiles, n_passes, n_win, E, windows_out != nullptr, !copy && !passes_on_device, !on_dev);
+  hipStream_t s = c->stream;
+  ScratchBlk blk{c};
+  HIPCHK(c, blk_take(c, lay.total + 64, false, &blk.p, &blk.cap));
+  uint8_t* d = (uint8_t*)blk.p;
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr, 0, 128, s));
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr + 32, 0xFF, 32, s));
+  if (!copy && !passes_on_device) HIPCHK(c, hipMemcpyAsync(d + lay.passes, passes, n_passes * 56, hipMemcpyHostToDevice, s));
+  typedef unsigned long long* W64;
+  BqpJob j{};
+  j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot;
+  j.n_events = ne; j.passes = passes_on_device ? (const unsigned long long*)passes : (const unsigned long long*)(d + lay.passes); j.n_passes = n_passes;
+  j.row_event = rows ? (const unsigned long long*)pb->v.row_event : nullptr; j.q = rows ? (const unsigned long long*)pb->v.row_offsets : nullptr; j.n_rows = R;
+  j.slot = (uint32_t)slot; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles; j.rows = rows ? 1u : 0u;
+  j.ident_pk = sh.identity_type == 1 ? 1u : 0u; j.width_ok = sh.desc.n_ident == n_pk ? 1u : 0u;
+  j.budget = max_batch_bytes;
+  j.hdr = (W64)(d + lay.hdr); j.tsum = (W64)(d + lay.tsum); j.code = d + lay.code; j.pre = (W64)(d + lay.pre); j.wrow = (W64)(d + lay.wrow);
+  j.slens = (uint32_t*)(d + lay.slens); j.spre = (const int64_t*)(d + lay.spre);
+  j.reqs_cap = E;
+  j.reqs_out = !reqs_out ? nullptr : on_dev ? (W64)reqs_out : (W64)(d + lay.s_reqs);
+  j.windows_out = !windows_out ? nullptr : on_dev ? (W64)windows_out : (W64)(d + lay.s_wins);
+  etlg_k_bigquery_plan(&j, (W64)(d + lay.sblk), E, copy, s);
+  uint64_t head[BQP_H_WORDS] = {};
+  HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> back;
+  if (!on_dev && rows && lay.total > lay.stage_at) { back.resize(lay.total - lay.stage_at); HIPCHK(c, hipMemcpyAsync(back.data(), d + lay.stage_at, back.size(), hipMemcpyDeviceToHost, s)); }
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop
+  if (head[BQP_H_BAD] != ~0ull) { info->status = ETLG_BQP_BAD_PASSES; info->bad_pass = head[BQP_H_BAD]; return ETLG_OK; }
+  if (head[BQP_H_FAILED] != ~0ull) {
+    info->status = ETLG_BQP_FAILED; info->event = head[BQP_H_FAILED] >> 3; info->reason = (uint32_t)(head[BQP_H_FAILED] & 7u); info->fail_pass = head[BQP_H_FAILPASS];
+    return ETLG_OK;
+  }
+  if (!rows) { info->status = ETLG_BQP_NEEDS_HOST; info->event = pb->v.host_event; return ETLG_OK; }
+  if (head[BQP_H_NEEDSHOST] != ~0ull) { info->status = ETLG_BQP_NEEDS_HOST; info->event = head[BQP_H_NEEDSHOST]; info->fail_pass = head[BQP_H_NOROWPASS]; return ETLG_OK; }
+  info->n_reqs = head[BQP_H_REQS]; info->n_members = head[BQP_H_MEMBERS]; info->n_rows = head[BQP_H_ROWS]; info->n_two_row = head[BQP_H_TWOROW];
+  info->n_bytes = head[BQP_H_BYTES]; info->est_row_bytes = head[BQP_H_EST]; info->target_batches = head[BQP_H_TARGET];
+  if (!on_dev) {
+    const uint64_t nr = info->n_reqs < E ? info->n_reqs : E;
+    const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
+    if (reqs_out && nr) memcpy(reqs_out, staged(lay.s_reqs), nr * 64);
+    if (windows_out) memcpy(windows_out, staged(lay.s_wins), n_win * 56);
   }
   return ETLG_OK;
 }

@@ -84,6 +84,7 @@ struct RowsBuild {
     rb->m.ctx = c; rb->m.ctx_gen = c->gen;
     if (call.format == FMT_DUCKLAKE) { rb->dl_batch = b; rb->dl_serial = b->serial; rb->dl_slot = slot; rb->dl_what = call.dl_what; }
     if (call.format == FMT_NDJSON) { rb->nd_batch = b; rb->nd_serial = b->serial; rb->nd_slot = slot; }
+    if (call.format == FMT_PROTOBUF) { rb->pb_batch = b; rb->pb_serial = b->serial; rb->pb_slot = slot; }
     if (call.format == FMT_ROWBINARY) { rb->ch_batch = b; rb->ch_serial = b->serial; rb->ch_slot = slot; rb->ch_engine = call.engine; }
   }
   const uint32_t* s_cols() const { return (const uint32_t*)(S + o_cols); }

@@ -75,6 +75,7 @@ extern "C" void etlg_k_outline(const OutlineJob* job, hipStream_t s);
 extern "C" void etlg_k_ducklake_plan(const DlpJob* job, unsigned long long* gblk, unsigned long long* oblk, hipStream_t s);
 extern "C" void etlg_k_snowflake_plan(const SfpJob* job, unsigned long long* sblk, uint64_t emit_bound, bool rows, hipStream_t s);
 extern "C" void etlg_k_clickhouse_plan(const ChpJob* job, unsigned long long* sblk, uint64_t emit_bound, hipStream_t s);
+extern "C" void etlg_k_bigquery_plan(const BqpJob* job, unsigned long long* sblk, uint64_t emit_bound, bool copy, hipStream_t s);
 extern "C" void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows, unsigned long long* rows_out, hipStream_t s);
 extern "C" void etlg_k_rowbinary(const RbJob* job, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, int step, hipStream_t s);
 extern "C" int etlg_k_cells_set_lds(void);
@@ -432,6 +433,7 @@ struct etlg_ctx {
   uint32_t dlp_tile_test = 0;        // ETLG_DLP_TILE (tests): events per tile of etlg_ducklake_plan instead of 2048
   uint32_t sfp_tile_test = 0;        // ETLG_SFP_TILE (tests): events per tile of etlg_snowflake_plan instead of 2048
   uint32_t chp_tile_test = 0;        // ETLG_CHP_TILE (tests): events per tile of etlg_clickhouse_plan instead of 2048
+  uint32_t bqp_tile_test = 0;        // ETLG_BQP_TILE (tests): events per tile of etlg_bigquery_plan instead of 2048
   uint32_t pay_tile_test = 0;       // ETLG_PAY_TILE (tests): frames and events per scan tile of etlg_batch_payload instead of 256 and 2048
   uint64_t dlc_offset_cap_test = 0;  // ETLG_DLC_OFFSET_CAP (tests): the bytes a Utf8 / Binary column of etlg_batch_ducklake_copy may hold, instead of 2^31 - 1
   uint8_t* h_hand = nullptr; size_t h_hand_cap = 0;   // pinned: the row formats' small uploads (initial counters + column words, one copy) and read-backs (row count; totals + counters, one copy each)
@@ -565,5 +567,7 @@ struct etlg_rowbinary {
   const etlg_batch* nd_batch = nullptr; uint64_t nd_serial = 0; int32_t nd_slot = -1;
   // built by etlg_batch_rowbinary: of which batch and slot, for which engine (etlg_clickhouse_plan takes the object of ITS batch and slot; the engine decides a refusal)
   const etlg_batch* ch_batch = nullptr; uint64_t ch_serial = 0; int32_t ch_slot = -1; int32_t ch_engine = -1;
+  // built by etlg_batch_protobuf: of which batch and slot (etlg_bigquery_plan takes the object of ITS batch and slot)
+  const etlg_batch* pb_batch = nullptr; uint64_t pb_serial = 0; int32_t pb_slot = -1;
 };
 

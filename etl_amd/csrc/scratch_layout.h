@@ -97,6 +97,22 @@ inline ChpLayout chp_layout(uint64_t n, uint64_t n_tiles, uint64_t n_passes, uin
   return o;
 }
 
+// etlg_bigquery_plan, its one block, as ChpLayout without the jump levels: hdr (4 words of zeros, 4 of all ones, 8 of zeros) | the tile
+// sums, a code byte and a prefix per event, two rows and a 0 / 1 request per window with their scan | a host caller's passes | the
+// staging of a host caller's outputs in one piece ([stage_at, total): requests | windows). E: the requests that can be written; n_win:
+// the window entries (one on a table-copy batch, which takes none of the per-event parts: n == 0).
+struct BqpLayout { size_t hdr, tsum, code, pre, wrow, slens, sblk, spre, passes, stage_at, s_reqs, s_wins, total; };
+inline BqpLayout bqp_layout(uint64_t n, uint64_t n_tiles, uint64_t n_passes, uint64_t n_win, uint64_t E, bool want_wins, bool passes_here, bool stage) {
+  ScratchLayout l; BqpLayout o{};
+  o.hdr = l.take(128); o.tsum = l.take(n_tiles * 8); o.code = l.take(n); o.pre = l.take(n ? (n + 1) * 8 : 0);
+  o.wrow = l.take(n_passes * 16); o.slens = l.take(n_passes * 4); o.sblk = l.take((n_passes / 256 + 2) * 8); o.spre = l.take((n_passes + 1) * 8);
+  o.passes = l.take(passes_here ? n_passes * 56 : 0);
+  o.stage_at = l.total();
+  o.s_reqs = l.take(stage ? E * 64 : 0); o.s_wins = l.take(stage && want_wins ? n_win * 56 : 0);
+  o.total = l.total();
+  return o;
+}
+
 // etlg_batch_payload: hdr | hist | bounds (the three the call reads back and uploads) | the frame side | the event side. ev_bytes and sums
 // live here unless they go straight to the caller's device memory; the range sums' parts exist only when sums are asked for.
 struct PayLayout { size_t hdr, hist, bounds, fbytes, tcnt, r2f, brank, etb, evb, tsum, pb, pr, cuts, sums, total; };

@@ -90,6 +90,14 @@ class ClickHousePlan:
         self.info, self.statements, self.windows = info, statements, windows
 
 
+class BigQueryPlan:
+    """What Batch.bigquery_plan returns: info (abi.BqPlanInfo) and, cut to what was written — or as the device addresses the caller
+    gave —, requests (abi.BqRequest) and windows (abi.BqWindow, one per pass; one on a table-copy batch)."""
+
+    def __init__(self, info, requests, windows):
+        self.info, self.requests, self.windows = info, requests, windows
+
+
 class Batch:
     """A decoded batch (etlg_batch). `host()` copies the arena into numpy arrays."""
 
@@ -496,6 +504,48 @@ class Batch:
         if info.status != abi.CHP_OK:
             return ClickHousePlan(info, None, None)
         return ClickHousePlan(info, [stmts[i] for i in range(min(sc, int(info.n_stmts)))], [wins[i] for i in range(nwin)])
+
+    def bigquery_plan(self, slot, passes, protobuf, n_passes=None, max_batch_bytes=0, reqs_cap=None, on_device=False):
+        """The BigQuery sink's append requests of schema slot `slot`, planned on the device (etlg_bigquery_plan): which rows of
+        `protobuf` — the device-resident protobuf() result of this batch and slot — each create_append_request takes, one per window
+        with a member. `passes`: what Batch.outline gave — np.uint64[P, 7], or the address of a device array of `n_passes`
+        etlg_outline_pass; only first_event and data_end are read; None on a table-copy batch, whose rows split_table_rows cuts by
+        `max_batch_bytes` (the client crate's MAX_BATCH_SIZE_BYTES; required there, ignored elsewhere).
+        on_device: False -> arrays; a dict of device addresses under "requests", "windows" (absent: that part is skipped) -> written
+        there, with reqs_cap saying what "requests" holds. reqs_cap left None on the host: one call counts, a second one fills an
+        array of exactly that size. Returns a BigQueryPlan; with info.status != abi.BQP_OK nothing but info is set."""
+        if passes is None:
+            pptr, npass, pdev = None, 0, 0
+        elif isinstance(passes, (int, np.integer)):
+            pptr, npass, pdev = int(passes), int(n_passes), 1
+        else:
+            passes = np.ascontiguousarray(passes, dtype=np.uint64).reshape(-1, 7)
+            pptr, npass, pdev = (passes.ctypes.data if len(passes) else None), len(passes), 0
+        nwin = npass if passes is not None else 1
+
+        def call(flags, rp, rcap, wp):
+            info = abi.BqPlanInfo()
+            rc = self.dec.L.etlg_bigquery_plan(self.dec.h, self.h, slot, pptr, npass, pdev, protobuf.h if protobuf is not None else None,
+                                               int(max_batch_bytes), flags, rp, rcap, wp, C.byref(info))
+            if rc != abi.OK:
+                raise self.dec.last_error()
+            return info
+
+        if on_device:
+            g = lambda k: int(on_device[k]) if on_device.get(k) else None
+            info = call(abi.F_OUTPUT_ON_DEVICE, g("requests"), int(reqs_cap or 0), g("windows"))
+            return BigQueryPlan(info, g("requests"), g("windows"))
+        if reqs_cap is None:
+            info = call(0, None, 0, None)
+            if info.status != abi.BQP_OK:
+                return BigQueryPlan(info, None, None)
+            reqs_cap = int(info.n_reqs)
+        rc_ = int(reqs_cap)
+        reqs, wins = (abi.BqRequest * max(1, rc_))(), (abi.BqWindow * max(1, nwin))()
+        info = call(0, C.addressof(reqs) if rc_ else None, rc_, C.addressof(wins) if nwin else None)
+        if info.status != abi.BQP_OK:
+            return BigQueryPlan(info, None, None)
+        return BigQueryPlan(info, [reqs[i] for i in range(min(rc_, int(info.n_reqs)))], [wins[i] for i in range(nwin)])
 
     def close(self):
         if self.h:

@@ -1591,6 +1591,119 @@ int32_t etlg_clickhouse_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_sl
                              uint32_t passes_on_device, const etlg_rowbinary* rowbinary, uint64_t max_bytes_per_insert, uint32_t flags,
                              etlg_ch_statement* stmts_out, uint64_t stmts_cap, etlg_ch_window* windows_out, etlg_ch_plan_info* info);
 
+/* The BigQuery sink's append requests of ONE schema slot, planned on the device: the step between etlg_batch_protobuf and the sink's
+ * requests — where write_events (etl-destinations bigquery/core.rs:956-1069) refuses an event and which rows form each
+ * create_append_request — without downloading row_offsets / row_event / ev_kind / ev_flags / ev_schema_slot. Shaped after
+ * etlg_clickhouse_plan above.
+ * Windows: `passes` as in etlg_clickhouse_plan — only [first_event, data_end) of each is read; windows ascend, do not overlap and may
+ * be empty. One window is what one turn of write_events' outer loop gathers for one table until a Relation or Truncate
+ * (core.rs:959-1040).
+ * MEMBERS of a window: its Insert / Update / Delete events with ev_schema_slot == schema_slot. The sink has no replay filter: every
+ * member is retained.
+ * `protobuf`: the object etlg_batch_protobuf built for this batch and slot; required, device-resident (ETLG_F_OUTPUT_ON_DEVICE), of
+ * status ETLG_RB_OK or ETLG_RB_NEEDS_HOST; anything else — NULL, a host-resident object, a RowBinary, NDJSON or DuckLake object,
+ * another batch's or slot's object — is ETLG_InvalidArgument.
+ * FAILING members, raised at the event, in event order; per event the reference's order of tests, so an event has one reason:
+ *   ETLG_BQP_R_PARTIAL_UPDATE          an Update with ETLG_FLAG_PARTIAL (bigquery_update_new_row :1478-1494, called at :1000 before the
+ *                                      old image is looked at);
+ *   ETLG_BQP_R_UPDATE_NO_OLD_IDENTITY  a full Update with ETLG_OLD_NONE on a slot whose replica identity is not PrimaryKey (:1439-1442,
+ *                                      ensure_bigquery_update_without_old_row_can_skip_delete :1516-1534);
+ *   ETLG_BQP_R_KEY_WIDTH               an Update or Delete with ETLG_OLD_KEY on a slot whose identity column count differs from its
+ *                                      primary-key column count (:1599-1614 Update, :1680-1694 Delete: the width is tested first);
+ *   ETLG_BQP_R_KEY_IDENTITY            an Update or Delete with ETLG_OLD_KEY, widths agree, identity not PrimaryKey (:1616, :1696,
+ *                                      ensure_bigquery_key_image_matches_primary_key :1537-1554);
+ *   ETLG_BQP_R_DELETE_NO_OLD           a Delete with ETLG_OLD_NONE (bigquery_delete_old_row :1497-1512).
+ * The host picks the reference's description from reason and event kind (the two key-image errors are worded per kind).
+ * REQUESTS, a WAL batch: per window with at least one member exactly one — the create_append_request of that table in that turn
+ * (:1043-1064). Its rows are the rows of `protobuf` whose row_event lies in [first_event, data_end): consecutive rows, found by two
+ * lower bounds in row_event. An Update that changed the primary key is TWO rows of one event (:1445-1474), so end_row - first_row may
+ * exceed n_members; it is what ETL_BQ_APPEND_BATCHES_BATCH_SIZE records (:1053). The entry's index in reqs_out is the request_index.
+ * max_batch_bytes is ignored on this path. The client crate's own split of one request into gRPC messages is not in the reference,
+ * is not restated here and is out of scope.
+ * REQUESTS, a table-copy batch (etlg_copy_decode; write_table_rows :602-649): n_passes == 0 with passes == NULL, one window over all
+ * rows (passes on such a batch are ETLG_InvalidArgument: the split is of the whole call's rows). With R = n_rows of the object,
+ * calculate_target_batches_for_table_copy (:1760-1784) and split_table_rows (:1790-1827):
+ *     est = the length of row 0 — the object's rows lie back to back without framing, a row's length is encoded_len() of the row —;
+ *     rows_per_batch = est ? max_batch_bytes / est : R;   target = rows_per_batch ? ceil(R / rows_per_batch) : 1   (R == 0: 0);
+ *     one request of all rows if R <= 1, target == 1 or R <= target; otherwise opt = ceil(R / target), nsub = ceil(R / opt),
+ *     q = R / nsub, r = R % nsub, and request i < nsub holds q + (i < r) rows from row i * q + min(i, r). R == 0 gives no request.
+ * max_batch_bytes — the client crate's MAX_BATCH_SIZE_BYTES, whose value the reference does not state: an argument without a default
+ * macro — must lie in [1, 2^63] for a copy batch. est is read on the device. first_event / last_event are row indexes, n_members is
+ * the request's row count, `window` is 0, and no reason can apply.
+ * Outputs: device memory with ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory; each may be NULL and is then skipped.
+ *   reqs_out[k], k < min(n_reqs, reqs_cap)   the request; nothing is written at or beyond the cap, reqs_cap == 0 only counts,
+ *                                            info->n_reqs is the full count.
+ *   windows_out[w], every pass (one entry on a copy batch)   req_first / n_reqs count all requests, those beyond reqs_cap included; a
+ *                                            window without a member has first_row == end_row == the rows of `protobuf` in front of
+ *                                            data_end.
+ * info->status, the first that applies; for every status but ETLG_BQP_OK NO output array is touched and the counts are 0:
+ *   ETLG_BQP_BAD_PASSES  as ETLG_CHP_BAD_PASSES; info->bad_pass = the lowest such index.
+ *   ETLG_BQP_FAILED      info->event = the lowest failing member inside a window, whatever its reason; info->reason = ETLG_BQP_R_*;
+ *                        info->fail_pass = the window that holds it. The reference has written the passes in front of that window
+ *                        when it raises the error: the host plans again with passes[0, fail_pass) alone. It fails the whole call at
+ *                        the first such event over all tables: the host takes the minimum over the slots it plans.
+ *   ETLG_BQP_NEEDS_HOST  `protobuf` has status ETLG_RB_NEEDS_HOST: info->event = its host_event (fail_pass stays ~0); or a member
+ *                        that does not fail has no row in `protobuf` — an Update with an old image whose primary key the device does
+ *                        not compare (a float / numeric / timetz key class, a DEFERRED key cell): info->event = the lowest such
+ *                        member, info->fail_pass its window.
+ * ETLG_InvalidArgument also: an unknown slot, a batch that is not device-resident (an ASYNC batch is synced first; one that ended in
+ * a decode error gives that error), n_passes > 0 without passes, n_passes or n_events above 2^38.
+ * A stated difference from the reference: etlg_batch_protobuf encodes the whole slot first, so its own errors (a numeric of more than
+ * 38 decimal places, a NULL array element, ETLG_E_JSON) come before a refusal that the reference would have met earlier in event order.
+ * The call stops for the device once, at its end.
+ * What is tested: tests/golden/bigquery_split_kats.py holds the reference's split_table_rows_* and calculate_target_batches_* vectors
+ * (core.rs:2277-2419); tests/bigquery_plan.py restates the refusals, the request per window and the two copy functions, and
+ * tests/test_gpu_bigquery_plan.py compares every field with it. */
+#define ETLG_BQP_OK 0u
+#define ETLG_BQP_BAD_PASSES 1u
+#define ETLG_BQP_FAILED 2u
+#define ETLG_BQP_NEEDS_HOST 3u
+#define ETLG_BQP_R_PARTIAL_UPDATE 1u
+#define ETLG_BQP_R_UPDATE_NO_OLD_IDENTITY 2u
+#define ETLG_BQP_R_KEY_WIDTH 3u
+#define ETLG_BQP_R_KEY_IDENTITY 4u
+#define ETLG_BQP_R_DELETE_NO_OLD 5u
+
+typedef struct etlg_bq_request {
+  uint64_t window;            /* index into `passes`; 0 on a table-copy batch */
+  uint64_t first_row;         /* rows [first_row, end_row) of `protobuf`: consecutive */
+  uint64_t end_row;
+  uint64_t first_event;       /* the first row's event */
+  uint64_t last_event;        /* the last row's event */
+  uint64_t byte_first;        /* bytes [byte_first, byte_end) of `protobuf` */
+  uint64_t byte_end;
+  uint64_t n_members;         /* the window's members; end_row - first_row - n_members of them are two rows */
+} etlg_bq_request;
+
+typedef struct etlg_bq_window {
+  uint64_t req_first;         /* first entry of reqs_out */
+  uint64_t n_reqs;            /* 0 or 1; a table-copy batch: all */
+  uint64_t first_row;         /* the member rows [first_row, end_row) of `protobuf` */
+  uint64_t end_row;
+  uint64_t n_members;
+  uint64_t n_two_row;         /* members of two rows: end_row - first_row - n_members */
+  uint64_t n_bytes;           /* bytes of the member rows */
+} etlg_bq_window;
+
+typedef struct etlg_bq_plan_info {
+  uint64_t n_reqs;            /* may exceed reqs_cap */
+  uint64_t n_members;
+  uint64_t n_rows;            /* rows in requests (n_members + n_two_row) */
+  uint64_t n_two_row;
+  uint64_t n_bytes;           /* their bytes */
+  uint64_t est_row_bytes;     /* a table-copy batch: the length of row 0; else 0 */
+  uint64_t target_batches;    /* a table-copy batch: calculate_target_batches_for_table_copy; else 0 */
+  uint64_t event;             /* FAILED / NEEDS_HOST: the event; else ~0 */
+  uint64_t bad_pass;          /* BAD_PASSES: the lowest such window; else ~0 */
+  uint64_t fail_pass;         /* FAILED, NEEDS_HOST for a member without a row: the window that holds `event`; else ~0 */
+  uint32_t status;            /* ETLG_BQP_* */
+  uint32_t reason;            /* FAILED: ETLG_BQP_R_* */
+} etlg_bq_plan_info;
+
+int32_t etlg_bigquery_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const etlg_outline_pass* passes, uint64_t n_passes,
+                           uint32_t passes_on_device, const etlg_rowbinary* protobuf, uint64_t max_batch_bytes, uint32_t flags,
+                           etlg_bq_request* reqs_out, uint64_t reqs_cap, etlg_bq_window* windows_out, etlg_bq_plan_info* info);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
