@@ -507,6 +507,55 @@ pub struct etlg_bq_plan_info {
     pub reason: u32,
 }
 
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_ice_write {
+    pub window: u64,
+    pub first_row: u64,
+    pub end_row: u64,
+    pub first_event: u64,
+    pub last_event: u64,
+    pub n_members: u64,
+    pub other_slot_event: u64,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_ice_window {
+    pub write_first: u64,
+    pub n_writes: u64,
+    pub first_row: u64,
+    pub end_row: u64,
+    pub n_members: u64,
+    pub other_slot_event: u64,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_ice_slice {
+    pub null_count: u64,
+    pub deferred_count: u64,
+    pub byte_first: u64,
+    pub byte_end: u64,
+    pub child_first: u64,
+    pub child_end: u64,
+    pub child_null_count: u64,
+}
+
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct etlg_ice_plan_info {
+    pub n_writes: u64,
+    pub n_members: u64,
+    pub n_rows: u64,
+    pub n_mixed: u64,
+    pub event: u64,
+    pub bad_pass: u64,
+    pub fail_pass: u64,
+    pub status: u32,
+    pub reason: u32,
+}
+
 #[repr(C)]
 pub struct etlg_finish_stats {
     pub deferred_seen: u64,
@@ -602,6 +651,10 @@ pub const ETLG_BQP_R_UPDATE_NO_OLD_IDENTITY: u32 = 2;
 pub const ETLG_BQP_R_KEY_WIDTH: u32 = 3;
 pub const ETLG_BQP_R_KEY_IDENTITY: u32 = 4;
 pub const ETLG_BQP_R_DELETE_NO_OLD: u32 = 5;
+pub const ETLG_ICP_OK: u32 = 0;
+pub const ETLG_ICP_BAD_PASSES: u32 = 1;
+pub const ETLG_ICP_FAILED: u32 = 2;
+pub const ETLG_ICP_NEEDS_HOST: u32 = 3;
 pub const ETLG_DL_TUPLES: i32 = 0;
 pub const ETLG_DL_PREDICATES: i32 = 1;
 pub const ETLG_DL_UPDATES: i32 = 3;
@@ -897,6 +950,21 @@ extern "C" {
         reqs_cap: u64,
         windows_out: *mut etlg_bq_window,
         info: *mut etlg_bq_plan_info,
+    ) -> i32;
+    pub fn etlg_iceberg_plan(
+        ctx: *mut etlg_ctx,
+        batch: *mut etlg_batch,
+        schema_slot: i32,
+        passes: *const etlg_outline_pass,
+        n_passes: u64,
+        passes_on_device: u32,
+        changelog: *const etlg_columns,
+        flags: u32,
+        writes_out: *mut etlg_ice_write,
+        writes_cap: u64,
+        slices_out: *mut etlg_ice_slice,
+        windows_out: *mut etlg_ice_window,
+        info: *mut etlg_ice_plan_info,
     ) -> i32;
     pub fn etlg_batch_finish_cells(ctx: *mut etlg_ctx, batch: *mut etlg_batch, what: u32, stats: *mut etlg_finish_stats) -> i32;
     pub fn etlg_ctx_slots(ctx: *const etlg_ctx, n_slots: *mut u32, slots: *mut *const etlg_slot_desc) -> i32;

@@ -500,6 +500,48 @@ impl GpuDecoder {
         Ok(out) // (no passes: `windows` has one entry, the whole-batch window of a table-copy batch; all zeros for any other batch)
     }
 
+    /// The Iceberg sink's writes of one schema slot of a device-resident batch, planned on the device (etlg_iceberg_plan): which events
+    /// `write_events` (iceberg/core.rs:300-440) refuses, which rows of `changelog` — the device-resident `etlg_batch_iceberg` object of
+    /// this batch and slot — form the `insert_rows` of each pass (:395-409), and per write and column of the object the Arrow slice over
+    /// those rows. `passes`: what `GpuDecoder::outline` returned WITH `ETLG_OL_RELATIONS_INLINE` — only `[first_event, data_end)` is
+    /// read; empty on a table-copy batch. `n_cols`: the object's `etlg_columns_view.n_cols`. At most `writes_cap` writes (and
+    /// `writes_cap * n_cols` slices) come back; `info.n_writes` is the full count — call again with a larger cap. With `info.status !=
+    /// ETLG_ICP_OK` nothing but `info` is set; for `ETLG_ICP_FAILED` the reference has written the passes in front of `info.fail_pass`:
+    /// plan again with those alone.
+    pub fn iceberg_plan(
+        &mut self, batch: *mut etlg_batch, schema_slot: i32, passes: &[etlg_outline_pass], changelog: *const etlg_columns, n_cols: usize, writes_cap: usize,
+    ) -> EtlResult<IcebergPlan> {
+        let n_windows = if passes.is_empty() { 1 } else { passes.len() };
+        let mut out = IcebergPlan {
+            writes: vec![etlg_ice_write { window: 0, first_row: 0, end_row: 0, first_event: 0, last_event: 0, n_members: 0, other_slot_event: 0 }; writes_cap],
+            slices: vec![
+                etlg_ice_slice { null_count: 0, deferred_count: 0, byte_first: 0, byte_end: 0, child_first: 0, child_end: 0, child_null_count: 0 };
+                writes_cap * n_cols
+            ],
+            windows: vec![etlg_ice_window { write_first: 0, n_writes: 0, first_row: 0, end_row: 0, n_members: 0, other_slot_event: 0 }; n_windows],
+            info: etlg_ice_plan_info { n_writes: 0, n_members: 0, n_rows: 0, n_mixed: 0, event: 0, bad_pass: 0, fail_pass: 0, status: 0, reason: 0 },
+            n_cols,
+        };
+        let rc = unsafe {
+            etlg_iceberg_plan(
+                self.ctx, batch, schema_slot, if passes.is_empty() { std::ptr::null() } else { passes.as_ptr() }, passes.len() as u64, 0, changelog, 0,
+                if writes_cap == 0 { std::ptr::null_mut() } else { out.writes.as_mut_ptr() }, writes_cap as u64,
+                if writes_cap * n_cols == 0 { std::ptr::null_mut() } else { out.slices.as_mut_ptr() }, out.windows.as_mut_ptr(), &mut out.info,
+            )
+        };
+        if rc != ETLG_OK {
+            return Err(self.last_error());
+        }
+        let ok = out.info.status == ETLG_ICP_OK;
+        let n = if ok { out.info.n_writes.min(writes_cap as u64) as usize } else { 0 };
+        out.writes.truncate(n);
+        out.slices.truncate(n * n_cols);
+        if !ok {
+            out.windows.clear();
+        }
+        Ok(out) // (no passes: `windows` has one entry, the whole-batch window of a table-copy batch; all zeros for any other batch)
+    }
+
     /// Source payload accounting of a device-resident batch, on the device (etlg_batch_payload), as plain values: per event the value
     /// bytes of its message (what `StreamingPayloadMetadata::{insert,update,delete}` is built from, apply.rs:2459-2463; the kind is the
     /// event's), per range of `cuts` the merged bytes and rows per kind (what `EventBatch::push` accumulates, apply.rs:656-658; rows == 0
@@ -619,6 +661,22 @@ impl BigQueryPlan {
         let (lo, n) = (self.windows[w].req_first as usize, self.windows[w].n_reqs as usize);
         let hi = (lo + n).min(self.requests.len());
         &self.requests[lo.min(hi)..hi]
+    }
+}
+
+/// What `GpuDecoder::iceberg_plan` returns.
+pub struct IcebergPlan {
+    pub writes: Vec<etlg_ice_write>,
+    pub slices: Vec<etlg_ice_slice>,
+    pub windows: Vec<etlg_ice_window>,
+    pub info: etlg_ice_plan_info,
+    pub n_cols: usize,
+}
+
+impl IcebergPlan {
+    /// The slices of write `k`, one per column of the changelog object.
+    pub fn slices_of(&self, k: usize) -> &[etlg_ice_slice] {
+        &self.slices[k * self.n_cols..(k + 1) * self.n_cols]
     }
 }
 

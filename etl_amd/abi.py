@@ -226,6 +226,23 @@ class BqPlanInfo(C.Structure):   # etlg_bq_plan_info
                 + [("status", C.c_uint32), ("reason", C.c_uint32)])
 
 
+class IceWrite(C.Structure):   # etlg_ice_write
+    _fields_ = [(n, C.c_uint64) for n in ("window", "first_row", "end_row", "first_event", "last_event", "n_members", "other_slot_event")]
+
+
+class IceWindow(C.Structure):   # etlg_ice_window
+    _fields_ = [(n, C.c_uint64) for n in ("write_first", "n_writes", "first_row", "end_row", "n_members", "other_slot_event")]
+
+
+class IceSlice(C.Structure):   # etlg_ice_slice
+    _fields_ = [(n, C.c_uint64) for n in ("null_count", "deferred_count", "byte_first", "byte_end", "child_first", "child_end", "child_null_count")]
+
+
+class IcePlanInfo(C.Structure):   # etlg_ice_plan_info
+    _fields_ = ([(n, C.c_uint64) for n in ("n_writes", "n_members", "n_rows", "n_mixed", "event", "bad_pass", "fail_pass")]
+                + [("status", C.c_uint32), ("reason", C.c_uint32)])
+
+
 class FinishStats(C.Structure):   # etlg_finish_stats
     _fields_ = [(n, C.c_uint64) for n in ("deferred_seen", "arrays_typed", "floats_settled", "left_deferred", "heap_bytes_added")]
 
@@ -250,6 +267,7 @@ CHP_OK, CHP_BAD_PASSES, CHP_FAILED, CHP_NEEDS_HOST = range(4)
 CHP_R_PARTIAL_UPDATE, CHP_R_UPDATE_IDENTITY, CHP_R_DELETE_NO_OLD, CHP_R_KEY_WIDTH, CHP_R_KEY_IDENTITY = 1, 2, 3, 4, 5
 BQP_OK, BQP_BAD_PASSES, BQP_FAILED, BQP_NEEDS_HOST = range(4)
 BQP_R_PARTIAL_UPDATE, BQP_R_UPDATE_NO_OLD_IDENTITY, BQP_R_KEY_WIDTH, BQP_R_KEY_IDENTITY, BQP_R_DELETE_NO_OLD = 1, 2, 3, 4, 5
+ICP_OK, ICP_BAD_PASSES, ICP_FAILED, ICP_NEEDS_HOST = range(4)
 DL_TUPLES, DL_PREDICATES, DL_UPDATES = 0, 1, 3
 (AK_BOOLEAN, AK_INT32, AK_INT64, AK_FLOAT32, AK_FLOAT64, AK_DATE32, AK_TIME64_US, AK_TIMESTAMP_US, AK_TIMESTAMP_US_UTC, AK_FIXED16,
  AK_LARGE_UTF8, AK_LARGE_BINARY, AK_TEXT_FORM, AK_LIST) = range(14)

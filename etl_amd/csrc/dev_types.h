@@ -484,6 +484,52 @@ struct BqpJob {
   unsigned long long* reqs_out; uint64_t reqs_cap; unsigned long long* windows_out;
 };
 
+// The Iceberg write plan (etlg_iceberg_plan: k_icp_* in finish.hip). hdr as BqpJob's: counts that start as zeros, the three status
+// words as all ones, the two windows of the failing event and of the member without a row written by k_icp_scan. Two things are new.
+// The event side keeps a second prefix, of the events of the slot's TABLE under another slot (bit 1 of the code byte). The bitmap side
+// counts bits in row ranges of the changelog object's bitmaps: every bitmap that can hold a counted bit — a validity with nulls, a
+// `deferred` with deferred cells, a child validity with null elements — is a run of 64-bit words in ONE word space (`base`: where its
+// words start there), and bpre is the running count of set bits in front of every word of that space.
+enum : uint32_t { ICP_H_MEMBERS = 0, ICP_H_WRITES = 1, ICP_H_MIXED = 2, ICP_H_ROWS = 3, ICP_H_BAD = 4, ICP_H_FAILED = 5, ICP_H_NEEDSHOST = 6, ICP_H_FAILPASS = 8,
+                  ICP_H_NOROWPASS = 9, ICP_H_WORDS = 16 };
+static_assert((uint32_t)ICP_H_BAD == (uint32_t)CHP_H_BAD && (uint32_t)ICP_H_FAILED == (uint32_t)CHP_H_FAILED && (uint32_t)ICP_H_NEEDSHOST == (uint32_t)CHP_H_NEEDSHOST,
+              "chp_mark / chp_write in finish.hip serve this job too");
+constexpr uint32_t kIcpWriteWords = 7;    // etlg_ice_write
+constexpr uint32_t kIcpWinWords = 6;      // etlg_ice_window
+constexpr uint32_t kIcpSliceWords = 7;    // etlg_ice_slice
+constexpr uint32_t kIcpNoBitmap = ~0u;
+struct IcpBitmap { const unsigned long long* words; uint64_t base; };   // a scanned bitmap: its words (8-byte aligned) and where they start in the word space
+struct IcpCol {                       // a column of the object, as k_icp_slices reads it
+  const long long* offsets;           // var-len kinds and lists: n_rows + 1
+  const long long* child_offsets;     // a list with a var-len child: child_count + 1
+  uint64_t child_count;
+  uint32_t kind, child_kind;          // etlg_arrow_kind
+  uint32_t width, child_width;        // bytes of a fixed-width value / list element; 0: bit-packed or var-len
+  uint32_t bm_valid, bm_deferred, bm_child, pad_;   // index into `bitmaps`; kIcpNoBitmap: the count is 0 without a read
+};
+struct IcpJob {
+  const uint8_t* ev_kind; const uint8_t* ev_flags; const uint32_t* ev_slot; const uint32_t* ev_table;
+  uint64_t n_events;
+  const unsigned long long* passes; uint64_t n_passes;   // etlg_outline_pass: 7 words, the window is words 0 and 1
+  const unsigned long long* row_event;                   // the changelog object: n_rows events, one row per event
+  uint64_t n_rows;
+  uint32_t slot, table_id, tile, n_tiles;
+  uint32_t n_cols, n_bitmaps;
+  const IcpCol* cols; const IcpBitmap* bitmaps;          // n_cols; n_bitmaps, and one more whose base is the word space's end
+  uint64_t n_words; uint32_t wtile, n_wtiles;            // the word space, the words per tile of its scan, its tiles
+  unsigned long long* hdr;            // ICP_H_*
+  unsigned long long* tsum;           // per tile: members; after k_icp_scan those in front of the tile
+  unsigned long long* fsum;           // per tile: events of the table under another slot; after k_icp_scan those in front of the tile
+  unsigned long long* bsum;           // per word tile: set bits; after k_icp_scan those in front of the tile
+  uint8_t* code;                      // per event: 1 member | 2 an Insert / Update / Delete of the table under another slot
+  unsigned long long* pre;            // n_events + 1: members in front of the event
+  unsigned long long* fpre;           // n_events + 1: events of the table under another slot in front of the event
+  unsigned long long* bpre;           // n_words + 1: set bits in front of the word
+  unsigned long long* wrow;           // per window: first_row, end_row, other_slot_event
+  uint32_t* slens; const int64_t* spre;   // per window: 1 when it has a write, and (n_passes + 1) the writes in front of it
+  unsigned long long* writes_out; uint64_t writes_cap; unsigned long long* slices_out; unsigned long long* windows_out;
+};
+
 // Source payload accounting (etlg_batch_payload). The frame side (k_payf_* in kernels.hip) measures every row message and lists the
 // frames that take a transaction ordinal; the event side (k_paye_* in finish.hip) joins every event to its frame through that list and
 // sums the ranges. Channels: 0 Insert, 1 Update, 2 Delete; a table-copy batch has channel 0 alone and reports it as ETLG_PK_COPY.

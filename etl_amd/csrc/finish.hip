@@ -898,21 +898,23 @@ __global__ __launch_bounds__(256) void k_chp_scan(ChpJob j) {
 }
 
 // the members in front of every event of a tile, from the code bytes and the tile's carry
-template <class J> DEV void chp_write(const J& j, uint64_t* lds) {
+// (bit: which bit of the code byte is counted, with the tile carries `tsum` and the prefix `pre` that belong to it)
+template <class J> DEV void chp_write_bit(const J& j, uint64_t* lds, uint32_t bit, const unsigned long long* tsum, unsigned long long* pre) {
   if (j.hdr[CHP_H_BAD] != kNone64) return;
   const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
   if (k0 >= j.n_events) return;
   const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
-  uint64_t carry = j.tsum[blockIdx.x];
+  uint64_t carry = tsum[blockIdx.x];
   for (uint64_t kb = k0; kb < k1; kb += 256) {   // (uniform trip count: every lane takes part in every scan)
     const uint64_t i = kb + threadIdx.x;
     const bool on = i < k1;
     uint64_t tot;
-    const uint64_t ex = block_scan_excl64(on ? j.code[i] & 1u : 0u, lds, &tot);
-    if (on) j.pre[i] = carry + ex;
+    const uint64_t ex = block_scan_excl64(on ? (j.code[i] >> bit) & 1u : 0u, lds, &tot);
+    if (on) pre[i] = carry + ex;
     carry += tot;
   }
 }
+template <class J> DEV void chp_write(const J& j, uint64_t* lds) { chp_write_bit(j, lds, 0u, j.tsum, j.pre); }
 __global__ __launch_bounds__(256) void k_chp_write(ChpJob j) {
   __shared__ uint64_t lds[4];
   chp_write(j, lds);
@@ -1123,6 +1125,198 @@ __global__ __launch_bounds__(256) void k_bqp_copy(BqpJob j) {
   unsigned long long* o = j.reqs_out + kBqpReqWords * s;
   o[0] = 0; o[1] = first_row; o[2] = end_row; o[3] = j.row_event[first_row]; o[4] = j.row_event[end_row - 1]; o[5] = j.q[first_row]; o[6] = j.q[end_row];
   o[7] = end_row - first_row;
+}
+
+// ---- the Iceberg write plan (etlg_iceberg_plan, include/etlg.h: the rule is stated there). The event side is the BigQuery plan's with
+// this sink's three refusals (one test per event kind) and one event per row; it keeps a second prefix, of the Insert / Update / Delete
+// events of the slot's TABLE under another slot, so that a window's first such event is a lower bound in it. The bitmap side is what no
+// other plan has: every write is a slice of every column of the changelog object, and a slice wants the bits of a row range counted.
+// Windows go from one row to the whole object, so no thread walks a range: the words of every bitmap that can hold a counted bit lie in
+// one word space, bpre is the running popcount in front of every word of it, and a range's count is two reads of bpre and the two masked
+// words at its ends (icp_ones). Launches, none of which exchanges a word between its workgroups: the windows checked (k_icp_mark), per
+// event tile the members, the other-slot events, a code byte per event and the two minima, per word tile the set bits (k_icp_tiles),
+// the three scans by one workgroup and the windows of the two minima (k_icp_scan), the three prefixes (k_icp_write), per window its
+// rows, its other-slot event and whether it has a write (k_icp_pass), the scan of those 0 / 1 lengths (etlg_k_scan_lens), the windows
+// (k_icp_windows), and a thread per write and column for the slices with one more per write for its entry (k_icp_emit). A table-copy
+// batch has no event side: the word tiles, their scan and prefix, and k_icp_emit, whose first thread leaves the counts and the one
+// window. Every loop runs to a launch parameter: tile / 256 and wtile / 256 chunks, log2 steps of a search in n_passes, n_rows,
+// n_events or n_bitmaps.
+DEV bool icp_any_status(const IcpJob& j) { return j.hdr[ICP_H_BAD] != kNone64 || j.hdr[ICP_H_FAILED] != kNone64 || j.hdr[ICP_H_NEEDSHOST] != kNone64; }
+// word g of the word space: of the last bitmap that starts at or in front of it (the bases ascend strictly; g < n_words)
+DEV uint64_t icp_word(const IcpJob& j, uint64_t g) {
+  uint32_t lo = 0, hi = j.n_bitmaps;
+  while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (j.bitmaps[mid].base <= g) lo = mid; else hi = mid; }
+  return j.bitmaps[lo].words[g - j.bitmaps[lo].base];
+}
+// set bits of bitmap b in the bit range [lo, hi), lo <= hi <= its bits: whole words through bpre, the two edge words masked. A word is
+// read only where the range cuts it, so nothing at or behind the bitmap's last word is touched when hi ends on a word
+DEV uint64_t icp_ones(const IcpJob& j, uint32_t b, uint64_t lo, uint64_t hi) {
+  const IcpBitmap m = j.bitmaps[b];
+  uint64_t n = j.bpre[m.base + (hi >> 6)] - j.bpre[m.base + (lo >> 6)];
+  if (lo & 63) n -= (uint64_t)__builtin_popcountll(m.words[lo >> 6] & ((1ull << (lo & 63)) - 1));
+  if (hi & 63) n += (uint64_t)__builtin_popcountll(m.words[hi >> 6] & ((1ull << (hi & 63)) - 1));
+  return n;
+}
+
+__global__ __launch_bounds__(256) void k_icp_mark(IcpJob j) { chp_mark(j); }
+
+// the first n_tiles workgroups, as k_bqp_tiles with this sink's refusals (iceberg_update_row core.rs:636-652, iceberg_delete_row
+// :655-680: one test per event kind, so an event has one reason) and bit 1 of the code byte: an Insert / Update / Delete of the slot's
+// table under another slot, in a window or not. The workgroups behind them: the set bits of a tile of the word space
+__global__ __launch_bounds__(256) void k_icp_tiles(IcpJob j) {
+  __shared__ uint64_t lds[4];
+  if (blockIdx.x >= j.n_tiles) {
+    const uint64_t t = blockIdx.x - j.n_tiles, g0 = t * j.wtile, g1 = g0 + j.wtile < j.n_words ? g0 + j.wtile : j.n_words;
+    uint64_t ones = 0;
+    for (uint64_t g = g0 + threadIdx.x; g < g1; g += 256) ones += (uint64_t)__builtin_popcountll(icp_word(j, g));
+    ones = block_sum64(ones, lds);
+    if (threadIdx.x == 0) j.bsum[t] = ones;
+    return;
+  }
+  if (j.hdr[ICP_H_BAD] != kNone64) return;
+  const uint64_t k0 = (uint64_t)blockIdx.x * j.tile;
+  if (k0 >= j.n_events) return;
+  const uint64_t k1 = k0 + j.tile < j.n_events ? k0 + j.tile : j.n_events;
+  uint64_t members = 0, foreign = 0, failed = kNone64, norow = kNone64;
+  for (uint64_t i = k0 + threadIdx.x; i < k1; i += 256) {
+    const uint32_t kind = j.ev_kind[i];
+    uint32_t code = 0, why = 0;
+    if (ol_is_row(kind)) {
+      if (j.ev_slot[i] != j.slot) code = j.ev_table[i] == j.table_id ? 2u : 0u;
+      else if (chp_window(j, i) != kNone64) {
+        const uint32_t fl = j.ev_flags[i], old = fl & 3u;
+        code = 1u;
+        if (kind == 'U') why = (fl & ETLG_FLAG_PARTIAL) ? ETLG_ICE_PARTIAL_UPDATE : 0u;
+        else if (kind == 'D') why = old == ETLG_OLD_KEY ? ETLG_ICE_KEY_ONLY_DELETE : old == ETLG_OLD_NONE ? ETLG_ICE_DELETE_WITHOUT_OLD_ROW : 0u;
+        if (!why) {
+          const uint64_t r = chp_rows_before(j, i);
+          if (r >= j.n_rows || j.row_event[r] != i) { if (i < norow) norow = i; }
+        }
+      }
+    }
+    j.code[i] = (uint8_t)code;
+    members += code & 1u; foreign += code >> 1;
+    if (why && i * 8 + why < failed) failed = i * 8 + why;
+  }
+  members = block_sum64(members, lds); foreign = block_sum64(foreign, lds); failed = block_min64(failed, lds); norow = block_min64(norow, lds);
+  if (threadIdx.x == 0) {
+    j.tsum[blockIdx.x] = members; j.fsum[blockIdx.x] = foreign;
+    if (failed != kNone64) atomicMin(&j.hdr[ICP_H_FAILED], (unsigned long long)failed);
+    if (norow != kNone64) atomicMin(&j.hdr[ICP_H_NEEDSHOST], (unsigned long long)norow);
+  }
+}
+
+// one workgroup, as k_bqp_scan, over three rows of tile sums: the word tiles' first (it does not depend on the passes), then the members
+// and the other-slot events
+__global__ __launch_bounds__(256) void k_icp_scan(IcpJob j) {
+  __shared__ uint64_t lds[4];
+  const uint64_t ones = carry_scan64(j.bsum, j.n_wtiles, 1, lds);
+  if (threadIdx.x == 0) j.bpre[j.n_words] = ones;
+  if (!j.n_tiles || j.hdr[ICP_H_BAD] != kNone64) return;
+  const uint64_t members = carry_scan64(j.tsum, j.n_tiles, 1, lds), foreign = carry_scan64(j.fsum, j.n_tiles, 1, lds);
+  if (threadIdx.x == 0) {
+    j.hdr[ICP_H_MEMBERS] = members; j.pre[j.n_events] = members; j.fpre[j.n_events] = foreign;
+    const uint64_t failed = j.hdr[ICP_H_FAILED], norow = j.hdr[ICP_H_NEEDSHOST];
+    if (failed != kNone64) j.hdr[ICP_H_FAILPASS] = chp_window(j, failed >> 3);
+    if (norow != kNone64) j.hdr[ICP_H_NOROWPASS] = chp_window(j, norow);
+  }
+}
+
+// the first n_tiles workgroups: both prefixes per event of a tile; the workgroups behind them: the set bits in front of every word of a
+// tile of the word space
+__global__ __launch_bounds__(256) void k_icp_write(IcpJob j) {
+  __shared__ uint64_t lds[4];
+  if (blockIdx.x < j.n_tiles) { chp_write_bit(j, lds, 0u, j.tsum, j.pre); chp_write_bit(j, lds, 1u, j.fsum, j.fpre); return; }
+  const uint64_t t = blockIdx.x - j.n_tiles, g0 = t * j.wtile, g1 = g0 + j.wtile < j.n_words ? g0 + j.wtile : j.n_words;
+  uint64_t carry = j.bsum[t];
+  for (uint64_t gb = g0; gb < g1; gb += 256) {   // (uniform trip count: every lane takes part in every scan)
+    const uint64_t g = gb + threadIdx.x;
+    const bool on = g < g1;
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl64(on ? (uint64_t)__builtin_popcountll(icp_word(j, g)) : 0ull, lds, &tot);
+    if (on) j.bpre[g] = carry + ex;
+    carry += tot;
+  }
+}
+
+// a thread per window: its rows by two lower bounds in row_event, its first other-slot event by one in fpre, a 0 / 1 length for its
+// write; a workgroup's rows and mixed windows go into the call's totals in one add each
+__global__ __launch_bounds__(256) void k_icp_pass(IcpJob j) {
+  __shared__ uint64_t lds[4];
+  if (icp_any_status(j)) return;
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint64_t rows = 0, mixed = 0;
+  if (p < j.n_passes) {
+    const uint64_t fe = j.passes[7 * p], de = j.passes[7 * p + 1], members = j.pre[de] - j.pre[fe];
+    const uint64_t first_row = chp_rows_before(j, fe), end_row = chp_rows_before(j, de);
+    // a window with a member: fpre[e] > fpre[fe] first holds at e = the event + 1 (fe < e <= de: fpre[de] is such an entry)
+    const uint64_t other = members && j.fpre[de] != j.fpre[fe] ? cut_lower_bound(j.fpre, fe + 1, de, j.fpre[fe] + 1) - 1 : kNone64;
+    if (members) rows = end_row - first_row;   // (no status: every member has a row, the object no other row of these events)
+    mixed = other != kNone64 ? 1u : 0u;
+    j.wrow[3 * p] = first_row; j.wrow[3 * p + 1] = end_row; j.wrow[3 * p + 2] = other;
+    j.slens[p] = members ? 1u : 0u;
+  }
+  rows = block_sum64(rows, lds); mixed = block_sum64(mixed, lds);
+  if (threadIdx.x == 0) {
+    if (rows) atomicAdd(&j.hdr[ICP_H_ROWS], (unsigned long long)rows);
+    if (mixed) atomicAdd(&j.hdr[ICP_H_MIXED], (unsigned long long)mixed);
+  }
+}
+
+// a thread per window: its entry; the grid's first thread leaves the count of all writes
+__global__ __launch_bounds__(256) void k_icp_windows(IcpJob j) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= j.n_passes || icp_any_status(j)) return;
+  if (p == 0) j.hdr[ICP_H_WRITES] = (uint64_t)j.spre[j.n_passes];
+  if (!j.windows_out) return;
+  unsigned long long* o = j.windows_out + kIcpWinWords * p;
+  o[0] = (uint64_t)j.spre[p]; o[1] = j.slens[p]; o[2] = j.wrow[3 * p]; o[3] = j.wrow[3 * p + 1]; o[4] = j.pre[j.passes[7 * p + 1]] - j.pre[j.passes[7 * p]];
+  o[5] = j.wrow[3 * p + 2];
+}
+
+// the slice of column c over rows [r0, r1) of the object (r0 < r1 <= n_rows)
+DEV void icp_slice(const IcpJob& j, uint32_t c, uint64_t r0, uint64_t r1, unsigned long long* o) {
+  const IcpCol k = j.cols[c];
+  uint64_t b0 = 0, b1 = 0, c0 = 0, c1 = 0, cn = 0;
+  if (k.kind == ETLG_AK_LIST) {
+    c0 = (uint64_t)k.offsets[r0]; c1 = (uint64_t)k.offsets[r1];
+    if (k.child_width) { b0 = c0 * k.child_width; b1 = c1 * k.child_width; }
+    else if (k.child_kind == ETLG_AK_BOOLEAN) { b0 = c0; b1 = c1; }
+    else if (k.child_count) { b0 = (uint64_t)k.child_offsets[c0]; b1 = (uint64_t)k.child_offsets[c1]; }   // (no child elements: no child offsets to read)
+    if (k.bm_child != kIcpNoBitmap) cn = (c1 - c0) - icp_ones(j, k.bm_child, c0, c1);
+  } else if (k.width) { b0 = r0 * k.width; b1 = r1 * k.width; }
+  else if (k.kind == ETLG_AK_BOOLEAN) { b0 = r0; b1 = r1; }
+  else { b0 = (uint64_t)k.offsets[r0]; b1 = (uint64_t)k.offsets[r1]; }
+  o[0] = k.bm_valid != kIcpNoBitmap ? (r1 - r0) - icp_ones(j, k.bm_valid, r0, r1) : 0;
+  o[1] = k.bm_deferred != kIcpNoBitmap ? icp_ones(j, k.bm_deferred, r0, r1) : 0;
+  o[2] = b0; o[3] = b1; o[4] = c0; o[5] = c1; o[6] = cn;
+}
+
+// n_cols + 1 threads per write that can be written: a slice per column, and the write's entry. The write's window comes from a search
+// in the windows' offsets (of equal offsets the last: the windows in front of it have no write). A table-copy batch (n_passes == 0) has
+// one window over all rows and one write when the object has a row; the grid's first thread leaves its counts and its window
+__global__ __launch_bounds__(256) void k_icp_emit(IcpJob j) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, per = (uint64_t)j.n_cols + 1, s = t / per;
+  const uint32_t c = (uint32_t)(t % per);
+  const bool copy = j.n_passes == 0;
+  if (!copy && icp_any_status(j)) return;
+  const uint64_t n_writes = copy ? (j.n_rows ? 1u : 0u) : (uint64_t)j.spre[j.n_passes];
+  if (copy && t == 0) {
+    j.hdr[ICP_H_WRITES] = n_writes; j.hdr[ICP_H_MEMBERS] = j.n_rows; j.hdr[ICP_H_ROWS] = j.n_rows;
+    if (j.windows_out) { unsigned long long* o = j.windows_out; o[0] = 0; o[1] = n_writes; o[2] = 0; o[3] = j.n_rows; o[4] = j.n_rows; o[5] = kNone64; }
+  }
+  if (s >= j.writes_cap || s >= n_writes) return;
+  uint64_t w = 0, first_row = 0, end_row = j.n_rows, members = j.n_rows, other = kNone64;
+  if (!copy) {
+    uint64_t lo = 0, hi = j.n_passes;
+    while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if ((uint64_t)j.spre[mid] <= s) lo = mid + 1; else hi = mid; }
+    w = lo - 1; first_row = j.wrow[3 * w]; end_row = j.wrow[3 * w + 1]; other = j.wrow[3 * w + 2];
+    members = j.pre[j.passes[7 * w + 1]] - j.pre[j.passes[7 * w]];
+  }
+  if (c < j.n_cols) { if (j.slices_out) icp_slice(j, c, first_row, end_row, j.slices_out + kIcpSliceWords * (s * j.n_cols + c)); return; }
+  if (!j.writes_out) return;
+  unsigned long long* o = j.writes_out + kIcpWriteWords * s;
+  o[0] = w; o[1] = first_row; o[2] = end_row; o[3] = j.row_event[first_row]; o[4] = j.row_event[end_row - 1]; o[5] = members; o[6] = other;
 }
 
 // ---- source payload accounting, event side (etlg_batch_payload, include/etlg.h): what EventBatch::push merges for the events of one
@@ -1515,6 +1709,25 @@ void etlg_k_bigquery_plan(const BqpJob* jv, unsigned long long* sblk, uint64_t e
   etlg_k_scan_lens(j.slens, j.n_passes, sblk, (int64_t*)j.spre, st);
   hipLaunchKernelGGL(k_bqp_windows, per_pass, dim3(256), 0, st, j);
   if (emit_bound) hipLaunchKernelGGL(k_bqp_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
+}
+
+// etlg_iceberg_plan: every launch in one piece. The word tiles ride behind the event tiles in k_icp_tiles and k_icp_write (a table-copy
+// batch has no event tile: n_tiles == 0, n_passes == 0, and k_icp_emit runs max(1, emit_bound) threads, of which the first leaves the
+// counts). emit_bound: (n_cols + 1) threads per write that can be written
+void etlg_k_iceberg_plan(const IcpJob* jv, unsigned long long* sblk, uint64_t emit_bound, hipStream_t st) {
+  const IcpJob j = *jv;
+  const bool copy = j.n_passes == 0;
+  const dim3 per_pass((uint32_t)((j.n_passes + 255) / 256)), tiles(j.n_tiles + j.n_wtiles);
+  if (!copy) hipLaunchKernelGGL(k_icp_mark, per_pass, dim3(256), 0, st, j);
+  if (tiles.x) hipLaunchKernelGGL(k_icp_tiles, tiles, dim3(256), 0, st, j);
+  hipLaunchKernelGGL(k_icp_scan, dim3(1), dim3(256), 0, st, j);
+  if (tiles.x) hipLaunchKernelGGL(k_icp_write, tiles, dim3(256), 0, st, j);
+  if (!copy) {
+    hipLaunchKernelGGL(k_icp_pass, per_pass, dim3(256), 0, st, j);
+    etlg_k_scan_lens(j.slens, j.n_passes, sblk, (int64_t*)j.spre, st);
+    hipLaunchKernelGGL(k_icp_windows, per_pass, dim3(256), 0, st, j);
+  } else if (!emit_bound) emit_bound = 1;
+  if (emit_bound) hipLaunchKernelGGL(k_icp_emit, dim3((uint32_t)((emit_bound + 255) / 256)), dim3(256), 0, st, j);
 }
 
 // etlg_batch_payload, event side, behind the frame side on the same stream (hdr[PAY_H_COUNTS], r2f, brank, fbytes); tsum == null: the

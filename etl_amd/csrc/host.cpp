@@ -310,6 +310,8 @@ void read_knobs(etlg_ctx* c) {
   integer("ETLG_SFP_TILE", c->sfp_tile_test, 0);                  // tests: events per tile of etlg_snowflake_plan, so that a small batch crosses every level of its scan
   integer("ETLG_CHP_TILE", c->chp_tile_test, 0);                  // tests: events per tile of etlg_clickhouse_plan, so that a small batch crosses every level of its scan
   integer("ETLG_BQP_TILE", c->bqp_tile_test, 0);                  // tests: events per tile of etlg_bigquery_plan, so that a small batch crosses every level of its scan
+  integer("ETLG_ICP_TILE", c->icp_tile_test, 0);                  // tests: events per tile of etlg_iceberg_plan, so that a small batch crosses every level of its event scans
+  integer("ETLG_ICP_WORDS", c->icp_words_test, 0);                // tests: bitmap words per tile of etlg_iceberg_plan, so that a small object crosses every level of its popcount scan
   integer("ETLG_PAY_TILE", c->pay_tile_test, 0);                 // tests: frames / events per scan tile of etlg_batch_payload, so that a small batch crosses every level of its scans
   integer("ETLG_FUSED_DBG", c->fused_dbg, 0);                     // ablation bits, profiling only (results are wrong)
   integer("ETLG_FUSED_KERNEL", c->fused_kernel, -1);              // 0 k_fused/256, 1 k_fused/64, 2 k_cells, 3 k_plan, 4 k_rows whenever eligible
@@ -968,7 +970,7 @@ void etlg_batch_free(etlg_batch* b) {
   delete b;
 }
 
-#include "host_handoff.inc"           // hand-off: what the calls share; etlg_batch_size_hints / _cuts / _outline / _payload / _finish_cells, etlg_ducklake_plan / _fingerprints, etlg_snowflake_plan, etlg_clickhouse_plan, etlg_bigquery_plan (finish.hip, fingerprint.hip)
+#include "host_handoff.inc"           // hand-off: what the calls share; etlg_batch_size_hints / _cuts / _outline / _payload / _finish_cells, etlg_ducklake_plan / _fingerprints, etlg_snowflake_plan, etlg_clickhouse_plan, etlg_bigquery_plan, etlg_iceberg_plan (finish.hip, fingerprint.hip)
 #include "host_handoff_columns.inc"   // etlg_batch_columns / _iceberg / _ducklake_copy in named steps (columns.hip)
 #include "host_handoff_rows.inc"      // etlg_batch_rowbinary / _protobuf / _ndjson / _duckdb in named steps (rowformats.hip, rowformats_dl.hip)
 

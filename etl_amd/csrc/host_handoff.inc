@@ -1,5 +1,5 @@
 // Part of host.cpp (included there, one translation unit): what the hand-off calls over a decoded, device-resident batch share, and the calls
-// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, Snowflake plan, ClickHouse plan, BigQuery plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
+// that build neither columns nor rows — size hints, cuts, locate, outline, DuckLake plan, Snowflake plan, ClickHouse plan, BigQuery plan, Iceberg plan, payload, finish, fingerprints (kernels: finish.hip, kernels.hip,
 // fingerprint.hip). The two builders follow in host_handoff_columns.inc and host_handoff_rows.inc.
 
 extern "C++" {
@@ -8,7 +8,7 @@ extern "C++" {
 // (fail-fast, as the reference), not a hand-off of the prefix — and a batch that is not device-resident is refused. `refusal`: the
 // entry point's name + NEEDS_DEVICE (a string literal: the error keeps the pointer). Returns ETLG_OK, or what the caller returns.
 #define NEEDS_DEVICE " needs a device-resident batch (ETLG_F_OUTPUT_ON_DEVICE, not downloaded)"
-// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, etlg_ducklake_plan, etlg_snowflake_plan, etlg_clickhouse_plan and etlg_bigquery_plan, whose contracts list the batch among their arguments.
+// `code`: what the refusal returns — ETLG_InvalidState everywhere but in etlg_batch_outline, etlg_ducklake_plan, etlg_snowflake_plan, etlg_clickhouse_plan, etlg_bigquery_plan and etlg_iceberg_plan, whose contracts list the batch among their arguments.
 static int32_t batch_ready(etlg_ctx* c, etlg_batch* b, const char* refusal, int32_t code = ETLG_InvalidState) {
   if (b->pending) RC(etlg_batch_sync(c, b));
   if (!b->v.on_device || !b->dev) return lib_error(c, code, refusal);
@@ -620,6 +620,125 @@ int32_t etlg_bigquery_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_
     const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
     if (reqs_out && nr) memcpy(reqs_out, staged(lay.s_reqs), nr * 64);
     if (windows_out) memcpy(windows_out, staged(lay.s_wins), n_win * 56);
+  }
+  return ETLG_OK;
+}
+
+// The Iceberg write plan (include/etlg.h; k_icp_* in finish.hip). As etlg_bigquery_plan above, everything is sized from what the host
+// knows — the events, the passes' count, the caller's cap, and from the object's column records which bitmaps can hold a counted bit and
+// how many words each has — so the launches go out in one piece and the call stops once: for the header and, for a host caller, the
+// staged outputs. A window has one write at the most, so at most min(writes_cap, n_passes) writes and that many times n_cols slices
+// can be written. The column and bitmap records go up in one copy. The slot's table id is the context's (SlotHost.desc.table_id).
+static uint32_t icp_fixed_width(uint32_t kind) {   // bytes of a list element of a fixed-width kind; 0: bit-packed or var-len
+  switch (kind) {
+    case ETLG_AK_INT32: case ETLG_AK_FLOAT32: case ETLG_AK_DATE32: return 4;
+    case ETLG_AK_INT64: case ETLG_AK_FLOAT64: case ETLG_AK_TIME64_US: case ETLG_AK_TIMESTAMP_US: case ETLG_AK_TIMESTAMP_US_UTC: return 8;
+    case ETLG_AK_FIXED16: return 16;
+    default: return 0;
+  }
+}
+int32_t etlg_iceberg_plan(etlg_ctx* c, etlg_batch* b, int32_t slot, const etlg_outline_pass* passes, uint64_t n_passes, uint32_t passes_on_device,
+                          const etlg_columns* changelog, uint32_t flags, etlg_ice_write* writes_out, uint64_t writes_cap, etlg_ice_slice* slices_out,
+                          etlg_ice_window* windows_out, etlg_ice_plan_info* info) {
+  if (!c || !b || b->ctx != c || !info) return ETLG_InvalidArgument;
+  *info = etlg_ice_plan_info{};
+  info->event = info->bad_pass = info->fail_pass = ~0ull;
+  if (const int32_t rc = batch_ready(c, b, "etlg_iceberg_plan" NEEDS_DEVICE, ETLG_InvalidArgument)) return rc;
+  if (!slot_known(c, slot)) return lib_error(c, ETLG_InvalidArgument, "unknown schema slot");
+  if (n_passes && !passes) return lib_error(c, ETLG_InvalidArgument, "etlg_iceberg_plan: n_passes without passes");
+  const bool copy = b->copy.active;
+  if (copy && n_passes) return lib_error(c, ETLG_InvalidArgument, "etlg_iceberg_plan: a table-copy batch takes no passes (write_table_rows writes the rows of the whole call)");
+  const etlg_batch_view& bv = b->v;
+  const uint64_t n = bv.n_events;
+  if (n_passes > (1ull << 38) || n > (1ull << 38)) return lib_error(c, ETLG_InvalidArgument, "etlg_iceberg_plan: more passes or events than one call takes (2^38: a grid of 2^30 workgroups walks them)");
+  const etlg_columns* cl = changelog;
+  if (!cl || !cl->changelog || cl->of_batch != b || cl->of_serial != b->serial || cl->of_slot != slot || !cl->v.on_device)
+    return lib_error(c, ETLG_InvalidArgument, "etlg_iceberg_plan takes the object etlg_batch_iceberg built for this batch and slot, on the device (ETLG_F_OUTPUT_ON_DEVICE)");
+  const uint64_t R = cl->v.n_rows;
+  const uint32_t nc = cl->v.n_cols;
+  static_assert(sizeof(etlg_ice_write) == 8 * kIcpWriteWords && sizeof(etlg_ice_window) == 8 * kIcpWinWords && sizeof(etlg_ice_slice) == 8 * kIcpSliceWords &&
+                    sizeof(etlg_outline_pass) == 56 && sizeof(IcpCol) == 56 && sizeof(IcpBitmap) == 16,
+                "k_icp_emit / k_icp_windows write 7, 7 and 6 words; the windows are words 0 and 1 of 7; icp_layout sizes the records");
+  if (!copy && (!n_passes || !n)) return ETLG_OK;   // no window, or no event a window could hold: no member, no write
+  const bool on_dev = (flags & ETLG_F_OUTPUT_ON_DEVICE) != 0;
+  if (!writes_out && !slices_out) writes_cap = 0;
+  const uint64_t n_win = copy ? 1 : n_passes;
+  const uint64_t E = std::min(writes_cap, copy ? std::min<uint64_t>(R, 1) : n_passes);   // what can be written at the most
+  if (E > (1ull << 38) / ((uint64_t)nc + 1)) return lib_error(c, ETLG_InvalidArgument, "etlg_iceberg_plan: more slices than one call writes (2^38: lower writes_cap)");
+  const uint64_t ne = copy ? 0 : n;                                // a table-copy batch walks no event
+  uint64_t tile = c->icp_tile_test ? c->icp_tile_test : 2048u;
+  while ((ne + tile - 1) / tile > (1ull << 30)) tile *= 2;   // (a grid's width; only a test's tile gets here)
+  const uint64_t n_tiles = (ne + tile - 1) / tile;
+  // the records: a bitmap joins the word space only when its column reports a bit to count
+  std::vector<IcpCol> cols(nc);
+  std::vector<IcpBitmap> bitmaps;
+  uint64_t W = 0;
+  const auto bitmap = [&](const uint8_t* p, uint64_t count, uint64_t bits) -> uint32_t {
+    if (!count || !bits || !p) return kIcpNoBitmap;
+    bitmaps.push_back(IcpBitmap{(const unsigned long long*)p, W});
+    W += (bits + 63) / 64;
+    return (uint32_t)(bitmaps.size() - 1);
+  };
+  for (uint32_t i = 0; i < nc; i++) {
+    const etlg_column& k = cl->cols[i];
+    IcpCol& o = cols[i];
+    o.offsets = (const long long*)k.offsets; o.child_offsets = (const long long*)k.child_offsets; o.child_count = k.child_count;
+    o.kind = k.arrow_kind; o.child_kind = k.child_kind; o.width = k.value_bytes; o.child_width = k.arrow_kind == ETLG_AK_LIST ? icp_fixed_width(k.child_kind) : 0u;
+    o.bm_valid = bitmap(k.validity, k.null_count, R); o.bm_deferred = bitmap(k.deferred, k.deferred_count, R);
+    o.bm_child = k.arrow_kind == ETLG_AK_LIST ? bitmap(k.child_validity, k.child_null_count, k.child_count) : kIcpNoBitmap;
+  }
+  const uint32_t n_bitmaps = (uint32_t)bitmaps.size();
+  bitmaps.push_back(IcpBitmap{nullptr, W});   // the closing entry
+  uint64_t wtile = c->icp_words_test ? c->icp_words_test : 1024u;
+  while ((W + wtile - 1) / wtile > (1ull << 30)) wtile *= 2;
+  const uint64_t n_wtiles = (W + wtile - 1) / wtile;
+  const IcpLayout lay = icp_layout(ne, n_tiles, n_passes, n_win, E, nc, n_bitmaps, W, n_wtiles, writes_out != nullptr, slices_out != nullptr, windows_out != nullptr,
+                                   !copy && !passes_on_device, !on_dev);
+  hipStream_t s = c->stream;
+  ScratchBlk blk{c};
+  HIPCHK(c, blk_take(c, lay.total + 64, false, &blk.p, &blk.cap));
+  uint8_t* d = (uint8_t*)blk.p;
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr, 0, 128, s));
+  HIPCHK(c, hipMemsetAsync(d + lay.hdr + 32, 0xFF, 32, s));
+  std::vector<uint8_t> up(lay.passes - lay.up_at);   // the column records | the bitmap records: one copy
+  if (nc) memcpy(up.data() + (lay.cols - lay.up_at), cols.data(), (size_t)nc * sizeof(IcpCol));
+  memcpy(up.data() + (lay.bitmaps - lay.up_at), bitmaps.data(), bitmaps.size() * sizeof(IcpBitmap));
+  HIPCHK(c, hipMemcpyAsync(d + lay.up_at, up.data(), up.size(), hipMemcpyHostToDevice, s));
+  if (!copy && !passes_on_device) HIPCHK(c, hipMemcpyAsync(d + lay.passes, passes, n_passes * 56, hipMemcpyHostToDevice, s));
+  typedef unsigned long long* W64;
+  IcpJob j{};
+  j.ev_kind = bv.ev_kind; j.ev_flags = bv.ev_flags; j.ev_slot = bv.ev_schema_slot; j.ev_table = bv.ev_table_id;
+  j.n_events = ne; j.passes = passes_on_device ? (const unsigned long long*)passes : (const unsigned long long*)(d + lay.passes); j.n_passes = n_passes;
+  j.row_event = (const unsigned long long*)cl->v.row_event; j.n_rows = R;
+  j.slot = (uint32_t)slot; j.table_id = c->slots[(size_t)slot]->desc.table_id; j.tile = (uint32_t)tile; j.n_tiles = (uint32_t)n_tiles;
+  j.n_cols = nc; j.n_bitmaps = n_bitmaps; j.cols = (const IcpCol*)(d + lay.cols); j.bitmaps = (const IcpBitmap*)(d + lay.bitmaps);
+  j.n_words = W; j.wtile = (uint32_t)wtile; j.n_wtiles = (uint32_t)n_wtiles;
+  j.hdr = (W64)(d + lay.hdr); j.tsum = (W64)(d + lay.tsum); j.fsum = (W64)(d + lay.fsum); j.bsum = (W64)(d + lay.bsum); j.code = d + lay.code;
+  j.pre = (W64)(d + lay.pre); j.fpre = (W64)(d + lay.fpre); j.bpre = (W64)(d + lay.bpre); j.wrow = (W64)(d + lay.wrow);
+  j.slens = (uint32_t*)(d + lay.slens); j.spre = (const int64_t*)(d + lay.spre);
+  j.writes_cap = E;
+  j.writes_out = !writes_out ? nullptr : on_dev ? (W64)writes_out : (W64)(d + lay.s_writes);
+  j.slices_out = !slices_out ? nullptr : on_dev ? (W64)slices_out : (W64)(d + lay.s_slices);
+  j.windows_out = !windows_out ? nullptr : on_dev ? (W64)windows_out : (W64)(d + lay.s_wins);
+  etlg_k_iceberg_plan(&j, (W64)(d + lay.sblk), E * ((uint64_t)nc + 1), s);
+  uint64_t head[ICP_H_WORDS] = {};
+  HIPCHK(c, hipMemcpyAsync(head, j.hdr, sizeof head, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> back;
+  if (!on_dev && lay.total > lay.stage_at) { back.resize(lay.total - lay.stage_at); HIPCHK(c, hipMemcpyAsync(back.data(), d + lay.stage_at, back.size(), hipMemcpyDeviceToHost, s)); }
+  HIPCHK(c, hipStreamSynchronize(s));   // the one stop
+  if (head[ICP_H_BAD] != ~0ull) { info->status = ETLG_ICP_BAD_PASSES; info->bad_pass = head[ICP_H_BAD]; return ETLG_OK; }
+  if (head[ICP_H_FAILED] != ~0ull) {
+    info->status = ETLG_ICP_FAILED; info->event = head[ICP_H_FAILED] >> 3; info->reason = (uint32_t)(head[ICP_H_FAILED] & 7u); info->fail_pass = head[ICP_H_FAILPASS];
+    return ETLG_OK;
+  }
+  if (head[ICP_H_NEEDSHOST] != ~0ull) { info->status = ETLG_ICP_NEEDS_HOST; info->event = head[ICP_H_NEEDSHOST]; info->fail_pass = head[ICP_H_NOROWPASS]; return ETLG_OK; }
+  info->n_writes = head[ICP_H_WRITES]; info->n_members = head[ICP_H_MEMBERS]; info->n_rows = head[ICP_H_ROWS]; info->n_mixed = head[ICP_H_MIXED];
+  if (!on_dev) {
+    const uint64_t nw = info->n_writes < E ? info->n_writes : E;
+    const auto staged = [&](size_t at) { return back.data() + (at - lay.stage_at); };
+    if (writes_out && nw) memcpy(writes_out, staged(lay.s_writes), nw * 56);
+    if (slices_out && nw && nc) memcpy(slices_out, staged(lay.s_slices), nw * nc * 56);
+    if (windows_out) memcpy(windows_out, staged(lay.s_wins), n_win * 48);
   }
   return ETLG_OK;
 }

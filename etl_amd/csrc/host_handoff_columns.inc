@@ -59,6 +59,7 @@ struct ColumnsBuild {
     cs->m.ctx = c; cs->m.ctx_gen = c->gen;
     cs->changelog = changelog; cs->ci.host_event = ~0ull; cs->ci.n_data_cols = nc;
     cs->ducklake = dlc;
+    cs->of_batch = b; cs->of_serial = b->serial; cs->of_slot = slot;
   }
   uint8_t* a_cnt() const { return A + la.cnt; }
 

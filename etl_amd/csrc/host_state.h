@@ -76,6 +76,7 @@ extern "C" void etlg_k_ducklake_plan(const DlpJob* job, unsigned long long* gblk
 extern "C" void etlg_k_snowflake_plan(const SfpJob* job, unsigned long long* sblk, uint64_t emit_bound, bool rows, hipStream_t s);
 extern "C" void etlg_k_clickhouse_plan(const ChpJob* job, unsigned long long* sblk, uint64_t emit_bound, hipStream_t s);
 extern "C" void etlg_k_bigquery_plan(const BqpJob* job, unsigned long long* sblk, uint64_t emit_bound, bool copy, hipStream_t s);
+extern "C" void etlg_k_iceberg_plan(const IcpJob* job, unsigned long long* sblk, uint64_t emit_bound, hipStream_t s);
 extern "C" void etlg_k_cuts_locate(const unsigned long long* cuts, uint64_t n_cuts, const unsigned long long* row_event, uint64_t n_rows, unsigned long long* rows_out, hipStream_t s);
 extern "C" void etlg_k_rowbinary(const RbJob* job, unsigned long long* blk, int64_t* offsets, unsigned long long* tot, int step, hipStream_t s);
 extern "C" int etlg_k_cells_set_lds(void);
@@ -434,6 +435,8 @@ struct etlg_ctx {
   uint32_t sfp_tile_test = 0;        // ETLG_SFP_TILE (tests): events per tile of etlg_snowflake_plan instead of 2048
   uint32_t chp_tile_test = 0;        // ETLG_CHP_TILE (tests): events per tile of etlg_clickhouse_plan instead of 2048
   uint32_t bqp_tile_test = 0;        // ETLG_BQP_TILE (tests): events per tile of etlg_bigquery_plan instead of 2048
+  uint32_t icp_tile_test = 0;        // ETLG_ICP_TILE (tests): events per tile of etlg_iceberg_plan instead of 2048
+  uint32_t icp_words_test = 0;       // ETLG_ICP_WORDS (tests): bitmap words per tile of etlg_iceberg_plan's popcount scan instead of 1024
   uint32_t pay_tile_test = 0;       // ETLG_PAY_TILE (tests): frames and events per scan tile of etlg_batch_payload instead of 256 and 2048
   uint64_t dlc_offset_cap_test = 0;  // ETLG_DLC_OFFSET_CAP (tests): the bytes a Utf8 / Binary column of etlg_batch_ducklake_copy may hold, instead of 2^31 - 1
   uint8_t* h_hand = nullptr; size_t h_hand_cap = 0;   // pinned: the row formats' small uploads (initial counters + column words, one copy) and read-backs (row count; totals + counters, one copy each)
@@ -554,6 +557,8 @@ struct etlg_columns {  // etlg_batch_columns, etlg_batch_iceberg, etlg_batch_duc
   etlg_changelog_info ci{};
   bool ducklake = false;           // built by etlg_batch_ducklake_copy: `di` is valid (etlg_columns_ducklake_get)
   etlg_ducklake_copy_info di{};
+  // of which batch and slot (etlg_iceberg_plan takes the changelog object of ITS batch and slot)
+  const etlg_batch* of_batch = nullptr; uint64_t of_serial = 0; int32_t of_slot = -1;
 };
 
 struct etlg_rowbinary {

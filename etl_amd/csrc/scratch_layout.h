@@ -113,6 +113,27 @@ inline BqpLayout bqp_layout(uint64_t n, uint64_t n_tiles, uint64_t n_passes, uin
   return o;
 }
 
+// etlg_iceberg_plan, its one block, as BqpLayout with the second prefix and the bitmap side: hdr (4 words of zeros, 4 of all ones, 8 of
+// zeros) | the tile sums of members and of other-slot events, a code byte and two prefixes per event, three words and a 0 / 1 write per
+// window with their scan | the word space's tile sums and its prefix (W words: W + 1 entries) | what the host uploads in one piece
+// ([up_at, stage_at): the column records, the bitmap records with their closing entry, a host caller's passes) | the staging of a host
+// caller's outputs in one piece ([stage_at, total): writes | slices | windows). E: the writes that can be written; n_win: the window
+// entries (one on a table-copy batch, which takes none of the per-event parts: n == 0).
+struct IcpLayout { size_t hdr, tsum, fsum, code, pre, fpre, wrow, slens, sblk, spre, bsum, bpre, up_at, cols, bitmaps, passes, stage_at, s_writes, s_slices, s_wins, total; };
+inline IcpLayout icp_layout(uint64_t n, uint64_t n_tiles, uint64_t n_passes, uint64_t n_win, uint64_t E, uint64_t n_cols, uint64_t n_bitmaps, uint64_t W, uint64_t n_wtiles,
+                            bool want_writes, bool want_slices, bool want_wins, bool passes_here, bool stage) {
+  ScratchLayout l; IcpLayout o{};
+  o.hdr = l.take(128); o.tsum = l.take(n_tiles * 8); o.fsum = l.take(n_tiles * 8); o.code = l.take(n); o.pre = l.take(n ? (n + 1) * 8 : 0); o.fpre = l.take(n ? (n + 1) * 8 : 0);
+  o.wrow = l.take(n_passes * 24); o.slens = l.take(n_passes * 4); o.sblk = l.take((n_passes / 256 + 2) * 8); o.spre = l.take((n_passes + 1) * 8);
+  o.bsum = l.take(n_wtiles * 8); o.bpre = l.take((W + 1) * 8);
+  o.up_at = l.total();
+  o.cols = l.take(n_cols * 56); o.bitmaps = l.take((n_bitmaps + 1) * 16); o.passes = l.take(passes_here ? n_passes * 56 : 0);
+  o.stage_at = l.total();
+  o.s_writes = l.take(stage && want_writes ? E * 56 : 0); o.s_slices = l.take(stage && want_slices ? E * n_cols * 56 : 0); o.s_wins = l.take(stage && want_wins ? n_win * 48 : 0);
+  o.total = l.total();
+  return o;
+}
+
 // etlg_batch_payload: hdr | hist | bounds (the three the call reads back and uploads) | the frame side | the event side. ev_bytes and sums
 // live here unless they go straight to the caller's device memory; the range sums' parts exist only when sums are asked for.
 struct PayLayout { size_t hdr, hist, bounds, fbytes, tcnt, r2f, brank, etb, evb, tsum, pb, pr, cuts, sums, total; };

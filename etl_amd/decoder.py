@@ -98,6 +98,15 @@ class BigQueryPlan:
         self.info, self.requests, self.windows = info, requests, windows
 
 
+class IcebergPlan:
+    """What Batch.iceberg_plan returns: info (abi.IcePlanInfo) and, cut to what was written — or as the device addresses the caller
+    gave —, writes (abi.IceWrite), slices (per write a list of abi.IceSlice, one per column of the changelog object) and windows
+    (abi.IceWindow, one per pass; one on a table-copy batch)."""
+
+    def __init__(self, info, writes, slices, windows):
+        self.info, self.writes, self.slices, self.windows = info, writes, slices, windows
+
+
 class Batch:
     """A decoded batch (etlg_batch). `host()` copies the arena into numpy arrays."""
 
@@ -546,6 +555,51 @@ class Batch:
         if info.status != abi.BQP_OK:
             return BigQueryPlan(info, None, None)
         return BigQueryPlan(info, [reqs[i] for i in range(min(rc_, int(info.n_reqs)))], [wins[i] for i in range(nwin)])
+
+    def iceberg_plan(self, slot, passes, changelog, n_passes=None, writes_cap=None, on_device=False):
+        """The Iceberg sink's writes of schema slot `slot`, planned on the device (etlg_iceberg_plan): which rows of `changelog` — the
+        device-resident iceberg() result of this batch and slot — each insert_rows takes, one per window with a member, and per
+        write and column of the object the Arrow slice over those rows (null, deferred and child null counts, value and child
+        ranges). `passes`: what Batch.outline gave WITH abi.OL_RELATIONS_INLINE — np.uint64[P, 7], or the address of a device array
+        of `n_passes` etlg_outline_pass; only first_event and data_end are read; None on a table-copy batch.
+        on_device: False -> arrays; a dict of device addresses under "writes", "slices", "windows" (absent: that part is skipped)
+        -> written there, with writes_cap saying what "writes" holds ("slices": writes_cap * n_cols entries). writes_cap left None
+        on the host: one call counts, a second one fills arrays of exactly that size. Returns an IcebergPlan — slices[k][c] is
+        the slice of write k and column c —; with info.status != abi.ICP_OK nothing but info is set."""
+        if passes is None:
+            pptr, npass, pdev = None, 0, 0
+        elif isinstance(passes, (int, np.integer)):
+            pptr, npass, pdev = int(passes), int(n_passes), 1
+        else:
+            passes = np.ascontiguousarray(passes, dtype=np.uint64).reshape(-1, 7)
+            pptr, npass, pdev = (passes.ctypes.data if len(passes) else None), len(passes), 0
+        nwin = npass if passes is not None else 1
+        ncols = int(changelog.view.n_cols) if changelog is not None else 0
+
+        def call(flags, wp, wcap, sp, np_):
+            info = abi.IcePlanInfo()
+            rc = self.dec.L.etlg_iceberg_plan(self.dec.h, self.h, slot, pptr, npass, pdev, changelog.h if changelog is not None else None,
+                                              flags, wp, wcap, sp, np_, C.byref(info))
+            if rc != abi.OK:
+                raise self.dec.last_error()
+            return info
+
+        if on_device:
+            g = lambda k: int(on_device[k]) if on_device.get(k) else None
+            info = call(abi.F_OUTPUT_ON_DEVICE, g("writes"), int(writes_cap or 0), g("slices"), g("windows"))
+            return IcebergPlan(info, g("writes"), g("slices"), g("windows"))
+        if writes_cap is None:
+            info = call(0, None, 0, None, None)
+            if info.status != abi.ICP_OK:
+                return IcebergPlan(info, None, None, None)
+            writes_cap = int(info.n_writes)
+        wc = int(writes_cap)
+        writes, slices, wins = (abi.IceWrite * max(1, wc))(), (abi.IceSlice * max(1, wc * ncols))(), (abi.IceWindow * max(1, nwin))()
+        info = call(0, C.addressof(writes) if wc else None, wc, C.addressof(slices) if wc else None, C.addressof(wins) if nwin else None)
+        if info.status != abi.ICP_OK:
+            return IcebergPlan(info, None, None, None)
+        nw = min(wc, int(info.n_writes))
+        return IcebergPlan(info, [writes[i] for i in range(nw)], [[slices[k * ncols + c] for c in range(ncols)] for k in range(nw)], [wins[i] for i in range(nwin)])
 
     def close(self):
         if self.h:

@@ -23,7 +23,7 @@ EXPORTS = [
     "etlg_batch_columns", "etlg_columns_view_get", "etlg_columns_free", "etlg_batch_iceberg", "etlg_columns_changelog_get", "etlg_batch_ducklake_copy", "etlg_columns_ducklake_get",
     "etlg_batch_rowbinary", "etlg_batch_protobuf", "etlg_batch_ndjson", "etlg_batch_duckdb", "etlg_rowbinary_view_get", "etlg_rowbinary_col_ends_get", "etlg_rowbinary_free", "etlg_batch_size_hints",
     "etlg_batch_finish_cells", "etlg_ducklake_fingerprints", "etlg_batch_cuts", "etlg_cuts_locate", "etlg_batch_payload",
-    "etlg_batch_outline", "etlg_ducklake_plan", "etlg_snowflake_plan", "etlg_clickhouse_plan", "etlg_bigquery_plan",
+    "etlg_batch_outline", "etlg_ducklake_plan", "etlg_snowflake_plan", "etlg_clickhouse_plan", "etlg_bigquery_plan", "etlg_iceberg_plan",
 ]
 
 _LIB = None
@@ -128,6 +128,8 @@ def lib():
                                        C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(abi.ChPlanInfo)]
     L.etlg_bigquery_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
                                      C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(abi.BqPlanInfo)]
+    L.etlg_iceberg_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
+                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(abi.IcePlanInfo)]
     L.etlg_batch_finish_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.etlg_table_cache_get.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.etlg_shard_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p]

@@ -1704,6 +1704,127 @@ int32_t etlg_bigquery_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot
                            uint32_t passes_on_device, const etlg_rowbinary* protobuf, uint64_t max_batch_bytes, uint32_t flags,
                            etlg_bq_request* reqs_out, uint64_t reqs_cap, etlg_bq_window* windows_out, etlg_bq_plan_info* info);
 
+/* The Iceberg sink's writes of ONE schema slot, planned on the device: the step between etlg_batch_iceberg and the sink's insert_rows
+ * calls — where write_events (etl-destinations iceberg/core.rs:300-440) refuses an event, which rows of the changelog object form each
+ * insert_rows call, and what a slice of every Arrow column of the object over those rows needs — without downloading row_event /
+ * ev_kind / ev_flags / ev_schema_slot / ev_table_id, nor any validity bitmap or offsets array of the object. Shaped after
+ * etlg_bigquery_plan above.
+ * Windows: `passes` are the passes of etlg_batch_outline taken WITH ETLG_OL_RELATIONS_INLINE: Iceberg's inner loop breaks at Truncate
+ * only (core.rs:310-312) and meets Relation events inside the data run (:360). Only [first_event, data_end) of each is read; windows
+ * ascend, do not overlap and may be empty. The call cannot tell which option the outline was built with: passes taken without it are
+ * narrower windows (they end at every Relation), which plan more writes than the reference makes, and nothing here reports that.
+ * MEMBERS of a window: its Insert / Update / Delete events with ev_schema_slot == schema_slot.
+ * `changelog`: the object etlg_batch_iceberg built for this batch and slot; required, device-resident (ETLG_F_OUTPUT_ON_DEVICE).
+ * Anything else — NULL, a host-resident object, an object of etlg_batch_columns or etlg_batch_ducklake_copy, another batch's or slot's
+ * object — is ETLG_InvalidArgument.
+ * FAILING members, raised at the event, in event order; one test applies per event kind, so an event has one reason (the numbers of
+ * etlg_changelog_info.host_reason):
+ *   ETLG_ICE_PARTIAL_UPDATE          an Update with ETLG_FLAG_PARTIAL (iceberg_update_row, core.rs:636-652);
+ *   ETLG_ICE_KEY_ONLY_DELETE         a Delete with ETLG_OLD_KEY (iceberg_delete_row, :661);
+ *   ETLG_ICE_DELETE_WITHOUT_OLD_ROW  a Delete with ETLG_OLD_NONE (:670). pgoutput sends no Delete without an old image: this reason is
+ *                                    reachable in the model (tests/iceberg_plan.py) alone.
+ * The changelog object holds no row for a refused event, by design.
+ * WRITES, a WAL batch: per window with at least one member exactly one — the insert_rows of that table in that turn (:395-409). Its
+ * rows are the rows of `changelog` whose row_event lies in [first_event, data_end): consecutive rows, found by two lower bounds in
+ * row_event. One event is one row, so end_row - first_row == n_members.
+ * THE TABLE KEY. The loop groups rows in a HashMap<TableId, (schema, rows)> with the first schema seen for the table (:304-307,
+ * :324-327): per TABLE, not per schema slot. A window that holds Insert / Update / Delete events of this slot's table_id (the context's,
+ * as etlg_ctx_slots reports it) under ANOTHER slot is one the reference encodes under one schema, or refuses at the Relation between
+ * them (:360-382). The planner does not decide this. Every window with a member reports other_slot_event: the lowest Insert / Update /
+ * Delete event in [first_event, data_end) whose ev_table_id is the slot's table and whose ev_schema_slot is another slot, ~0 if there
+ * is none; a window without a member of this slot reports ~0 (the table's entry of that turn is the other slot's alone, and the
+ * plan of that slot covers it). info->n_mixed counts the windows that have one.
+ * SLICES. For every write k < min(n_writes, writes_cap) and every column c of the object — the data columns and the two CDC columns,
+ * n_cols = etlg_columns_view.n_cols — slices_out[k * n_cols + c] describes rows [first_row, end_row) of that column as an Arrow slice:
+ *   null_count         zero bits of `validity` in the row range;
+ *   deferred_count     set bits of `deferred` in the row range;
+ *   byte_first/_end    the range of `values` the slice owns: row * value_bytes for a fixed-width kind; the bit positions first_row,
+ *                      end_row for ETLG_AK_BOOLEAN; offsets[first_row], offsets[end_row] for LARGE_UTF8 / LARGE_BINARY / TEXT_FORM; for
+ *                      ETLG_AK_LIST the child range times the element width, the child bit positions for a BOOLEAN child, and
+ *                      child_offsets[child_first], child_offsets[child_end] for a var-len child (both 0 when the column has no child
+ *                      element: there are no child offsets then);
+ *   child_first/_end   ETLG_AK_LIST: offsets[first_row], offsets[end_row]; otherwise 0;
+ *   child_null_count   ETLG_AK_LIST: zero bits of child_validity in [child_first, child_end); otherwise 0.
+ * Over writes that cover all rows of the object the null_count / deferred_count / child_null_count of a column's slices sum to the
+ * column's own counts. A bitmap whose column reports a count of 0 is not read.
+ * A table-copy batch (etlg_copy_decode; write_table_rows, core.rs:268-291): n_passes == 0 with passes == NULL (passes on such a batch are
+ * ETLG_InvalidArgument), one window over all rows and one write when the object has a row (!table_rows.is_empty()). No refusal can
+ * apply; first_event / last_event are row indexes, n_members the row count, other_slot_event ~0.
+ * Outputs: device memory with ETLG_F_OUTPUT_ON_DEVICE in `flags`, else host memory; each may be NULL and is then skipped.
+ *   writes_out[k], k < min(n_writes, writes_cap)   the write; nothing is written at or beyond the cap (slices: writes_cap * n_cols),
+ *                                                  writes_cap == 0 only counts, info->n_writes is the full count.
+ *   windows_out[w], every pass (one entry on a copy batch)   write_first / n_writes count all writes, those beyond writes_cap
+ *                                                  included; a window without a member has first_row == end_row == the rows of
+ *                                                  `changelog` in front of data_end.
+ * info->status, the first that applies; for every status but ETLG_ICP_OK NO output array is touched and the counts are 0:
+ *   ETLG_ICP_BAD_PASSES  as ETLG_CHP_BAD_PASSES; info->bad_pass = the lowest such index.
+ *   ETLG_ICP_FAILED      info->event = the lowest failing member inside a window, whatever its reason; info->reason = ETLG_ICE_*;
+ *                        info->fail_pass = the window that holds it. The reference raises the error while it gathers that pass, so
+ *                        the passes in front of it are written: the host plans again with passes[0, fail_pass) alone. It fails the
+ *                        whole call at the first such event over all tables: the host takes the minimum over the slots it plans.
+ *   ETLG_ICP_NEEDS_HOST  a member that does not fail has no row in `changelog`: info->event = the lowest such member, info->fail_pass
+ *                        its window. etlg_batch_iceberg selects every Insert, full Update and full-old-row Delete of the slot, and the
+ *                        call takes no other object, so this status is reachable in the model alone, not through this ABI; the
+ *                        kernels keep the test so that a row is never read for an event that has none.
+ * ETLG_InvalidArgument also: an unknown slot, a batch that is not device-resident (an ASYNC batch is synced first; one that ended in
+ * a decode error gives that error), n_passes > 0 without passes, n_passes or n_events above 2^38, more than 2^38 slices to write.
+ * Stated differences from the reference: etlg_batch_iceberg builds the whole slot first, so its own errors (a malformed array literal,
+ * ETLG_E_JSON) come before a refusal that the reference would have met earlier in event order. Column names, the catalog calls, the
+ * Relation metadata check against the store and Parquet encoding are not restated here.
+ * The call stops for the device once, at its end.
+ * What is tested: tests/golden/iceberg_plan_kats.py holds the outcomes of the reference's iceberg_update_row_* / iceberg_delete_row_*
+ * unit tests (core.rs:794-840); tests/iceberg_plan.py restates the refusals, the write per window, other_slot_event and the slice
+ * arithmetic, and tests/test_gpu_iceberg_plan.py compares every field of every output with it. */
+#define ETLG_ICP_OK 0u
+#define ETLG_ICP_BAD_PASSES 1u
+#define ETLG_ICP_FAILED 2u
+#define ETLG_ICP_NEEDS_HOST 3u
+
+typedef struct etlg_ice_write {
+  uint64_t window;            /* index into `passes`; 0 on a table-copy batch */
+  uint64_t first_row;         /* rows [first_row, end_row) of `changelog`: consecutive */
+  uint64_t end_row;
+  uint64_t first_event;       /* the first row's event */
+  uint64_t last_event;        /* the last row's event */
+  uint64_t n_members;         /* == end_row - first_row */
+  uint64_t other_slot_event;  /* the window's; ~0 none */
+} etlg_ice_write;
+
+typedef struct etlg_ice_window {
+  uint64_t write_first;       /* first entry of writes_out */
+  uint64_t n_writes;          /* 0 or 1 */
+  uint64_t first_row;         /* the member rows [first_row, end_row) of `changelog` */
+  uint64_t end_row;
+  uint64_t n_members;
+  uint64_t other_slot_event;  /* the lowest Insert / Update / Delete of the slot's table under another slot in the window; ~0 none */
+} etlg_ice_window;
+
+typedef struct etlg_ice_slice {
+  uint64_t null_count;
+  uint64_t deferred_count;
+  uint64_t byte_first;        /* of `values`: bytes, or bit positions where the values are bit-packed */
+  uint64_t byte_end;
+  uint64_t child_first;       /* ETLG_AK_LIST: the child elements [child_first, child_end); else 0 */
+  uint64_t child_end;
+  uint64_t child_null_count;
+} etlg_ice_slice;
+
+typedef struct etlg_ice_plan_info {
+  uint64_t n_writes;          /* may exceed writes_cap */
+  uint64_t n_members;
+  uint64_t n_rows;            /* rows in writes (== n_members) */
+  uint64_t n_mixed;           /* windows with an other_slot_event */
+  uint64_t event;             /* FAILED / NEEDS_HOST: the event; else ~0 */
+  uint64_t bad_pass;          /* BAD_PASSES: the lowest such window; else ~0 */
+  uint64_t fail_pass;         /* FAILED / NEEDS_HOST: the window that holds `event`; else ~0 */
+  uint32_t status;            /* ETLG_ICP_* */
+  uint32_t reason;            /* FAILED: ETLG_ICE_* */
+} etlg_ice_plan_info;
+
+int32_t etlg_iceberg_plan(etlg_ctx* ctx, etlg_batch* batch, int32_t schema_slot, const etlg_outline_pass* passes, uint64_t n_passes,
+                          uint32_t passes_on_device, const etlg_columns* changelog, uint32_t flags, etlg_ice_write* writes_out,
+                          uint64_t writes_cap, etlg_ice_slice* slices_out, etlg_ice_window* windows_out, etlg_ice_plan_info* info);
+
 /* Schema slots known to the context (also reachable from every batch view). */
 int32_t etlg_ctx_slots(const etlg_ctx* ctx, uint32_t* n_slots,
                        const etlg_slot_desc** slots);
